@@ -12,7 +12,9 @@ Weak scaling: 4096 envs and 1024 minibatch rows per GPU; global batch_size = 102
 (5 120-row GEMMs), ONE unroll + 64 minibatch steps per training step, gradient all-reduce after each; on one GPU it runs one rank's share with the
 collectives issued on a one-rank RCCL group; `--gpus N --config cfg3` uses batch_size = 256*N.
 
-Usage: python bench.py [--gpus N --steps K --warmup W]
+Usage: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+K timed training steps (>= 1) after W untimed ones.  `--dump-outputs DIR`: what the last timed step computed as DIR/<name>.npy (dump_outputs); the
+inputs are seeded, so two builds run with the same arguments can be compared array for array.
 N > 1: one rank per GPU over RCCL.  Either the caller starts the ranks (`python -m torch.distributed.run --nproc-per-node N bench.py
 --gpus N ...`: RANK / WORLD_SIZE are then in the environment) or bench.py does it itself: `python bench.py --gpus N` starts that
 command as a CHILD process before anything touches the GPU and relays rank 0's JSON line (track_mjx_amd/launch.py; the reference
@@ -280,6 +282,41 @@ def parity_summary():
     return out
 
 
+DUMP_ROWS, DUMP_OBS_ROWS, DUMP_MAX_BYTES = 1024, 256, 64 << 20
+
+
+def dump_outputs(out_dir: str, learner, metrics: dict) -> dict:
+    """`--dump-outputs DIR`: what the LAST timed training step computed, one float32 DIR/<name>.npy per array, so that two builds run with the same
+    arguments (identical seeded inputs) can be compared output for output:
+      metric.<key>              the loss metrics update() returned (METRIC_KEYS), scalars
+      policy.<param> / value.<param>   every parameter after the step's SGD updates
+      normalizer.{mean,std,count}      the observation normaliser after the step's update
+      rollout.<buffer>          what collect() wrote: [unroll_length, rows] / [unroll_length, rows, width] buffers at a fixed, seeded sample of rows
+                                (DUMP_ROWS; DUMP_OBS_ROWS of them for the 696-wide observations: the whole buffer is ~1 GB)
+    Returns {name: shape}; at most DUMP_MAX_BYTES in all."""
+    import numpy as np
+    import torch
+    arrays = {f"metric.{k}": metrics[k] for k in learner.METRIC_KEYS}
+    arrays.update({f"policy.{n}": p for n, p in learner.policy.named_parameters()})
+    arrays.update({f"value.{n}": p for n, p in learner.value.named_parameters()})
+    arrays.update({f"normalizer.{k}": getattr(learner.normalizer, k) for k in ("mean", "std", "count")})
+    rows = learner.buf["reward"].shape[1]
+    pick = np.sort(np.random.default_rng(0).choice(rows, min(rows, DUMP_ROWS), replace=False))
+    idx = torch.as_tensor(pick, device=learner.dev)
+    for k, v in learner.buf.items():
+        wide = k in ("observation", "next_observation_last")
+        arrays[f"rollout.{k}"] = v.index_select(0 if k == "next_observation_last" else 1, idx[:DUMP_OBS_ROWS] if wide else idx)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for k, a in host.items():
+        np.save(d / f"{k}.npy", a)
+    return {k: list(a.shape) for k, a in host.items()}
+
+
 def dry_run_ranks(args) -> None:
     """`--dry-run-ranks`: the launcher plumbing without a GPU — every rank joins a gloo group, all-reduces a one, rank 0 prints the
     line's skeleton (tests/test_launch.py drives `bench.py --gpus 2 --dry-run-ranks` through the self-launch branch)."""
@@ -321,7 +358,11 @@ def main(argv=None, runner=None):
     ap.add_argument("--dry-run-ranks", action="store_true", help="launcher check on CPU: gloo ranks, no GPU work (tests)")
     ap.add_argument("--no-live-pmc", action="store_true", help="do not collect the HBM-traffic counters with two child rocprofv3 passes (then the stamped profiles/pmc_traffic.json is what the line carries)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the short cfg4 / cfg5 measurements the default N = 1 line carries under config.other_configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (loss metrics, parameters, "
+                    "normaliser, a seeded sample of the roll-out buffers) as DIR/<name>.npy, float32, at most 64 MB (rank 0)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     from track_mjx_amd import launch
     if launch.needs_spawn(args.gpus):
         # `python bench.py --gpus N` as the driver types it: start the N ranks as a child process (nothing has touched the GPU yet)
@@ -427,7 +468,7 @@ def main(argv=None, runner=None):
     t0 = time.perf_counter()
     for _ in range(args.steps):
         ev3 = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        ev3[0].record(); learner.collect(); ev3[1].record(); learner.update(1); ev3[2].record()
+        ev3[0].record(); learner.collect(); ev3[1].record(); last_metrics = learner.update(1); ev3[2].record()
         split_ev.append(ev3)
     sync()
     elapsed = time.perf_counter() - t0
@@ -435,6 +476,7 @@ def main(argv=None, runner=None):
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dumped = dump_outputs(args.dump_outputs, learner, last_metrics) if (args.dump_outputs and rank == 0) else None     # (before the roll-out-only leg steps the envs on)
     rollout_ms = sum(a.elapsed_time(b) for a, b, _ in split_ev) / args.steps
     sgd_ms = sum(b.elapsed_time(c) for _, b, c in split_ev) / args.steps
     env_steps = learner.env_steps_per_training_step * args.steps
@@ -566,6 +608,8 @@ def main(argv=None, runner=None):
                               "mfma_util_source": "profiles/mfma_counters.json (tools/mfma_counters.sh), not collected by this run"},
             "parity": parity_summary(),
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": len(dumped)}
         # the finished measurement is on disk before any extra runs: a hard kill (SIGKILL, a driver time-out) during the minute of extras below cannot lose it
         # (stdout still carries exactly ONE line, the enriched one, printed by emit())
         for side in (ROOT / "gpurun_out", Path("/tmp")):

@@ -186,14 +186,11 @@ def test_toy_contact_slots_and_priority_mixing(toy):
 
 
 def test_rodent_blob_scaling_against_the_xml():
-    """The committed blob (rescale_factor 0.9, torque actuators) against numbers read straight from rodent.xml with ElementTree."""
-    import xml.etree.ElementTree as ET
-    xml = Path(cm.DEFAULT_XML)
-    if not xml.exists():
-        pytest.skip("reference asset not present on this machine")
+    """The committed blob (rescale_factor 0.9, torque actuators) against numbers read straight from rodent.xml with ElementTree
+    (stored in tests/golden/rodent_xml.npz by tests/golden/make_rodent_xml_fixture.py)."""
+    X = np.load(ROOT / "tests" / "golden" / "rodent_xml.npz")
     w, _ = default_walker()
-    root = ET.parse(xml).getroot()
-    pos = {b.get("name"): np.array([float(v) for v in b.get("pos", "0 0 0").split()]) for b in root.iter("body")}
+    pos = dict(zip(X["body_name"].tolist(), X["body_pos"]))
     names = [ln.split()[2] for ln in (ROOT / "track_mjx_amd" / "assets" / "rodent_model.names.txt").read_text().splitlines() if ln.startswith("body ")]
     bp = np.asarray(w.model["body_pos"]).reshape(-1, 3)
     checked = 0
@@ -202,13 +199,13 @@ def test_rodent_blob_scaling_against_the_xml():
             np.testing.assert_allclose(bp[i], 0.9 * pos[n], rtol=1e-12, atol=1e-15, err_msg=n)
             checked += 1
     assert checked >= 60
-    acts = {a.get("name"): a for a in root.find("actuator")}
+    forcerange = dict(zip(X["actuator_name"].tolist(), X["actuator_forcerange"]))
     anames = [ln.split()[2] for ln in (ROOT / "track_mjx_amd" / "assets" / "rodent_model.names.txt").read_text().splitlines() if ln.startswith("actuator ")]
     gain = np.asarray(w.model["act_gain"])
     for i, n in enumerate(anames):
-        fr = acts[n].get("forcerange")
-        if fr is not None:
-            assert abs(gain[i] - float(fr.split()[1])) < 1e-12, n
+        fr = forcerange[n]
+        if not np.isnan(fr[1]):
+            assert abs(gain[i] - fr[1]) < 1e-12, n
 
 
 def test_plane_capsule_and_plane_ellipsoid_contacts_by_hand():
