@@ -12,7 +12,14 @@ tables, qpos0 constants body_invweight0 / dof_invweight0 / stat.meaninertia,
 static plane-vs-paw collision pair list in MJX's contact order).
 
 Output: track_mjx_amd/assets/rodent_model.tmjx  (binary blob, float64/int32)
+        track_mjx_amd/assets/rodent_model.names.txt (body / joint / actuator ids)
         track_mjx_amd/assets/rodent_model_dump.txt (human-readable review copy)
+(side files are named after the output's stem: --out .../rodent_model_pos080.tmjx.txt writes rodent_model_pos080.names.txt and
+rodent_model_pos080_dump.txt; an --out ending in .tmjx.txt writes the blob's lossless text form, track_mjx_amd/blob.py).
+
+Actuator modes: torque_actuators=True rewrites the position servos into torque motors (the reference's default walker);
+torque_actuators=False with affine_bias=True keeps them as written (biastype="affine": force = gain * act + b0 + b1 * length)
+and emits the blob entry `act_bias` [nu, 3] = biasprm[0:3].
 
 mujoco itself is not importable in the build container, so this is a
 restatement from the published MuJoCo semantics ("parity unpinned").
@@ -234,7 +241,9 @@ def geom_volume_inertia(gtype, size):
 
 
 # --------------------------------------------------------------------------- compile
-def compile_model(xml_path, torque_actuators=True, rescale_factor=0.9):
+def compile_model(xml_path, torque_actuators=True, rescale_factor=0.9, affine_bias=False):
+    """`affine_bias`: with torque_actuators=False, compile the XML's affine-bias position servos (m["act_bias"]); without it
+    that mode is refused, as before the bias path existed."""
     root = ET.parse(xml_path).getroot()
     comp = {}
     for c in root.findall("compiler"):
@@ -406,30 +415,46 @@ def compile_model(xml_path, torque_actuators=True, rescale_factor=0.9):
             coef[jnt_dofadr[jnt_name2id[j.attrib["joint"]]]] = float(j.attrib["coef"])
         tendon_names.append(a["name"])
         ten_coef.append(coef)
-    act_names, act_moment, act_gain, act_tau, act_ctrlrange = [], [], [], [], []
+    act_names, act_moment, act_gain, act_bias, act_tau, act_ctrlrange = [], [], [], [], [], []
+    free_dofs = [d for j in range(njnt) if jnt_type[j] == JNT_FREE for d in range(jnt_dofadr[j], jnt_dofadr[j] + 6)]
     for ael in root.find("actuator"):
         assert ael.tag == "general"
         a = resolve(ael, "general", classes, None)
         assert a.get("dyntype") == "filter" and a.get("forcelimited", "false") == "false"
         assert a.get("ctrllimited") == "true"
         gear = float(a.get("gear", "1").split()[0])
-        gain = float(a["gainprm"].split()[0])
-        bias = fvec(a.get("biasprm", "0 0 0"))
+        gainprm = fvec(a["gainprm"])
+        gain = float(gainprm[0])
+        bias = np.zeros(3)
+        b = fvec(a.get("biasprm", "0 0 0"))
+        bias[:min(3, len(b))] = b[:3]
         biastype = a.get("biastype", "none")
         if torque_actuators:
             # spec edit (a): gainprm[0] = forcerange[1]; biastype none; biasprm 0
             fr = fvec(a["forcerange"])
             gain, biastype, bias = fr[1], "none", np.zeros(3)
-        assert biastype == "none", "non-torque actuator mode is not compiled (reference config uses torque_actuators=True)"
+        elif affine_bias:
+            # position servo as written: force = gainprm[0] * act + biasprm[0] + biasprm[1] * length (gaintype fixed)
+            assert a.get("gaintype", "fixed") == "fixed", f"{a['name']}: only gaintype fixed is compiled"
+            assert not np.any(gainprm[1:]), f"{a['name']}: non-zero gainprm[1:] is not compiled"
+            assert biastype in ("none", "affine"), f"{a['name']}: biastype {biastype} is not compiled"
+            if biastype == "none":
+                bias = np.zeros(3)
+            assert bias[2] == 0.0, f"{a['name']}: biasprm[2] (velocity term) != 0 is not compiled"
+        assert biastype == "none" or (not torque_actuators and affine_bias), \
+            "non-torque actuator mode needs affine_bias=True (reference default config uses torque_actuators=True)"
         gear *= s * s  # dm_scale_spec: gear *= scale^2
         if "joint" in a:
             mom = np.zeros(nv)
             mom[jnt_dofadr[jnt_name2id[a["joint"]]]] = gear
         else:
             mom = gear * ten_coef[tendon_names.index(a["tendon"])]
+        if affine_bias and not torque_actuators:
+            assert not np.any(mom[free_dofs]), f"{a['name']}: a moment on a free-joint dof has no length in the bias path"
         act_names.append(a["name"])
         act_moment.append(mom)
         act_gain.append(gain)
+        act_bias.append(bias)
         act_tau.append(float(a["dynprm"].split()[0]))
         act_ctrlrange.append(fvec(a["ctrlrange"]))
     nu = len(act_names)
@@ -460,6 +485,8 @@ def compile_model(xml_path, torque_actuators=True, rescale_factor=0.9):
         act_ctrlrange=np.array(act_ctrlrange),
         gravity=gravity, geoms=geoms,
     )
+    if affine_bias and not torque_actuators:
+        m["act_bias"] = np.array(act_bias)
     # qpos0 / qpos_spring
     qpos0 = np.zeros(nq)
     qpos_spring = np.zeros(nq)
@@ -641,6 +668,8 @@ def to_blob(m):
               "qpos0", "qpos_spring", "dof_damping", "dof_armature", "dof_invweight0", "body_invweight0",
               "act_moment", "act_gain", "act_tau", "act_ctrlrange", "gravity"):
         e[k] = np.asarray(m[k], dtype=np.float64).ravel()
+    if "act_bias" in m:       # optional (affine-bias position servos); absent = no bias
+        e["act_bias"] = np.asarray(m["act_bias"], dtype=np.float64).ravel()
     e["meaninertia"] = np.array([m["meaninertia"]])
     g = m["geoms"]
     g1, g2 = m["con_geom1"], m["con_geom2"]
@@ -680,7 +709,8 @@ def dump_text(m, path):
         f.write("\n# actuators: id name gain tau nonzero-moment\n")
         for a, n in enumerate(m["act_names"]):
             nz = np.nonzero(m["act_moment"][a])[0]
-            f.write(f"{a:3d} {n:22s} gain={m['act_gain'][a]:.6g} tau={m['act_tau'][a]} moment={{" +
+            bias = f" bias={m['act_bias'][a]}" if "act_bias" in m else ""
+            f.write(f"{a:3d} {n:22s} gain={m['act_gain'][a]:.6g}{bias} tau={m['act_tau'][a]} moment={{" +
                     ", ".join(f"{d}:{m['act_moment'][a][d]:.8g}" for d in nz) + "}\n")
         f.write("\n# contact slots (MJX order): slot geom1 geom2 sub body2\n")
         for c in range(m["ncon"]):
@@ -695,17 +725,19 @@ def main():
     ap.add_argument("--out", default=str(REPO / "track_mjx_amd" / "assets" / "rodent_model.tmjx"))
     ap.add_argument("--rescale", type=float, default=0.9)
     ap.add_argument("--no-torque", action="store_true")
+    ap.add_argument("--affine-bias", action="store_true",
+                    help="with --no-torque: compile the XML's affine-bias position servos (blob entry act_bias)")
     args = ap.parse_args()
-    m = compile_model(args.xml, torque_actuators=not args.no_torque, rescale_factor=args.rescale)
+    m = compile_model(args.xml, torque_actuators=not args.no_torque, rescale_factor=args.rescale, affine_bias=args.affine_bias)
     e = to_blob(m)
     # names travel as a text side file (ids for the walker's name -> id lookups)
     blob.save(args.out, e)
-    names = Path(args.out).with_suffix(".names.txt")
+    names = Path(args.out).with_name(blob.stem(args.out) + ".names.txt")
     with open(names, "w") as f:
         for kind, lst in (("body", m["body_names"]), ("joint", m["jnt_names"]), ("actuator", m["act_names"])):
             for i, n in enumerate(lst):
                 f.write(f"{kind} {i} {n}\n")
-    dump_text(m, Path(args.out).with_name("rodent_model_dump.txt"))
+    dump_text(m, Path(args.out).with_name(blob.stem(args.out) + "_dump.txt"))
     print(f"wrote {args.out}: nbody={m['nbody']} nq={m['nq']} nv={m['nv']} nu={m['nu']} ncon={m['ncon']} "
           f"mass={m['body_mass'].sum():.6f} meaninertia={m['meaninertia']:.6g}")
 

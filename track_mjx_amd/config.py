@@ -84,8 +84,9 @@ def sps_per_actor_config() -> dict[str, Any]:
     the constructor defaults of multi_clip_tracking.py:16-32 —, 5 physics substeps per control step, `penalty_pos_distance_scale`
     [1, 1, 0.2], 512 x 3 nets, and NO `var_*` / `jerk_coeff` keys, i.e. RewardConfig's defaults (reward.py:51-53: window 50, var_coeff
     5e-2, jerk_coeff 5e-4).  That file also omits `energy_cost_weight`, which the reference's dataclass requires (reward.py:27-28): it is
-    given as 0.0 here (term off).  The walker stays the shipped blob's (torque actuators, rescale 0.9): the file's position-actuator /
-    0.8 walker needs a recompile with tools/compile_model.py and the affine-bias actuator path, which is not built."""
+    given as 0.0 here (term off).  The walker DEFAULTS to the torque-actuator / 0.9 one (the golden vectors tests/golden/task_golden_sps.npz were
+    built on it); the file's own walker (rodent-sps-per-actor.yaml:108-109: position actuators with their affine bias, rescale 0.8) is
+    selected with the overrides `walker_config.torque_actuators=false walker_config.rescale_factor=0.8` (walker.BLOBS)."""
     cfg = default_config()
     cfg["env_config"]["env_args"].update(iterations=4, ls_iterations=4, physics_steps_per_control_step=5)
     rw = cfg["env_config"]["reward_weights"]

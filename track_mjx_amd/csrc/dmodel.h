@@ -114,6 +114,12 @@ struct DModel {
   float dof_lim[TM_MAXV][12];
   float dof_act_gain[128];      // act_gain[dof_act_id[e]] next to dof_act_coef[e]: one level fewer in the dof's actuator gather
   int lds_floats;
+  // affine actuator bias (position servos, blob entry act_bias; absent: has_bias = 0 and the fields below are zero):
+  // force[u] = act_gain[u] act[u] + act_b0[u] + act_b1[u] length[u], length[u] = sum over e in act_madr[u] .. act_madr[u+1] of
+  // act_mval[e] qpos[act_mqpos[e]] (act_mqpos: the qpos address of entry e's hinge dof; free-joint dofs carry no moment on this path)
+  int has_bias;
+  float act_b0[TM_MAXU], act_b1[TM_MAXU];
+  int act_mqpos[128];
 };
 
 enum { RW_TOO_FAR, RW_BAD_POSE, RW_BAD_QUAT, RW_CTRL_W, RW_CTRL_DIFF_W, RW_ENERGY_W, RW_POS_W, RW_QUAT_W, RW_JOINT_W,

@@ -146,6 +146,25 @@ inline bool build_dmodel(const void *blob, size_t nbytes, DModel &m, std::string
     }
   }
   m.act_madr[m.nu] = ne;
+  {  // affine actuator bias: optional entry [nu, 3] = biasprm[0:3]; absent = no bias (blobs without it load unchanged)
+    const int nb = R.count("act_bias");
+    if (nb >= 0) {
+      std::vector<float> bp((size_t)m.nu * 3 + 1);
+      if (nb != m.nu * 3 || !R.floats("act_bias", bp.data(), m.nu * 3)) { err = "blob entry act_bias must be float64 [nu, 3]"; return false; }
+      for (int a = 0; a < m.nu; a++) {
+        if (bp[3 * a + 2] != 0.f) { err = "act_bias: biasprm[2] (velocity term) != 0 is not supported"; return false; }
+        m.act_b0[a] = bp[3 * a]; m.act_b1[a] = bp[3 * a + 1];
+        if (bp[3 * a] != 0.f || bp[3 * a + 1] != 0.f) m.has_bias = 1;
+      }
+    }
+    for (int e = 0; e < ne; e++) {      // qpos address of every moment entry's dof (hinge: one qpos per dof)
+      int q = -1;
+      for (int j = 0; j < m.njnt; j++)
+        if (m.jnt_type[j] == 3 && m.jnt_dofadr[j] == m.act_mdof[e]) q = m.jnt_qposadr[j];
+      if (q < 0 && m.has_bias) { err = "act_bias: an actuator with a moment on a free-joint dof has no length on this path"; return false; }
+      m.act_mqpos[e] = q < 0 ? 0 : q;
+    }
+  }
   // single moving tree
   m.root_body = -1;
   for (int b = 1; b < m.nbody; b++) {
@@ -201,6 +220,8 @@ inline bool build_dmodel(const void *blob, size_t nbytes, DModel &m, std::string
     }
     m.grp_count[m.ngroup - 1]++;
   }
+  // the wave kernel stages the actuator forces of a bias model through the paw-velocity buffer (ngroup * 6 words; wave_physics.h)
+  if (m.has_bias && m.nu > 6 * m.ngroup) { err = "act_bias: more than 6 actuators per contact group (wave kernel staging buffer)"; return false; }
   m.n_joint_idx = R.count("joint_idxs"); m.n_body_idx = R.count("body_idxs"); m.n_endeff_idx = R.count("endeff_idxs");
   if (m.n_joint_idx <= 0 || m.n_body_idx <= 0 || m.n_endeff_idx <= 0 || m.n_joint_idx > TM_MAXIDX || m.n_body_idx > TM_MAXIDX || m.n_endeff_idx > TM_MAXIDX) {
     err = "bad tracked index lists"; return false;

@@ -282,6 +282,8 @@ int tmjx_model_create(const void *blob, size_t nbytes, tmjx_model **out) {
 #ifdef TMJX_LANE_IMPL
   const char *impl = getenv("TMJX_IMPL");
   if (impl && !strcmp(impl, "lane")) m->wave = 0;
+  // the lane-per-env cross-check has no actuator-bias path: refuse a bias model rather than run it without the bias
+  if (!m->wave && m->h.has_bias) { delete m; return fail(TMJX_EINVAL, "the lane-per-env implementation (TMJX_IMPL=lane) has no affine actuator bias path"); }
 #endif
   if (m->wave) {
     size_t lds_bytes = (size_t)tmjx_host::make_wave_layout(m->h, false).lds_floats * sizeof(float);   // the larger (generic) layout

@@ -764,7 +764,21 @@ TM_DEV void tmw_velocity_inertia(WCtx &c, const WLayout &K) {
   // lean layout: the activation state lives in the env's global record, each value written and re-read by its OWN lane (tmw_euler) — a dof's
   // lane needs other lanes' values, and global memory gives no ordering between the lanes of a wave: stage it through the paw-velocity
   // buffer, which only the J products of the solver stage use (nu <= 6 ngroup: WLayout::lean)
-  if (K.lean) { TMW_FOR { for (int a = lane; a < K.nu; a += 64) L[K.l_sv + a] = WST(m.s_act, a); } }
+  // Affine actuator bias (position servos, DModel::has_bias: a model constant, so the branch is wave-uniform — a scalar load and a scalar
+  // branch): lane u < nu forms actuator u's whole force gain act + b0 + b1 length (length from this substep's starting qpos) into the same
+  // staging buffer (nu <= 6 ngroup: tmjx_host::build_dmodel), in either layout, and the dof gather below reads forces instead of activations
+  const bool has_bias = m.has_bias != 0;
+  if (has_bias) {
+    TMW_FOR {
+      for (int a = lane; a < K.nu; a += 64) {
+        const int e0 = m.act_madr[a], e1 = m.act_madr[a + 1];
+        float len = 0.f;
+        for (int e = e0; e < e1; e++) len += m.act_mval[e] * L[K.l_qpos + m.act_mqpos[e]];
+        const float act = K.lean ? WST(m.s_act, a) : L[K.l_act + a];
+        L[K.l_sv + a] = m.act_gain[a] * act + (m.act_b0[a] + m.act_b1[a] * len);
+      }
+    }
+  } else if (K.lean) { TMW_FOR { for (int a = lane; a < K.nu; a += 64) L[K.l_sv + a] = WST(m.s_act, a); } }
   TMW_SYNC();
   TMW_TICK2(23);
   // M rows, bias, passive, actuation -> qfrc_smooth; act_dot.  The bias forces first, into registers: in the lean layout the accumulated body
@@ -809,7 +823,8 @@ TM_DEV void tmw_velocity_inertia(WCtx &c, const WLayout &K) {
       }
       const float bias = i < 64 ? bias0[TMW_LI] : bias1[TMW_LI];
       float fa = 0.f;
-      for (int e = tm_f2i(rc[6]); e < tm_f2i(rc[7]); e++) { int u = m.dof_act_id[e]; fa += m.dof_act_coef[e] * (m.dof_act_gain[e] * L[(K.lean ? K.l_sv : K.l_act) + u]); }
+      if (has_bias) { for (int e = tm_f2i(rc[6]); e < tm_f2i(rc[7]); e++) fa += m.dof_act_coef[e] * L[K.l_sv + m.dof_act_id[e]]; }
+      else for (int e = tm_f2i(rc[6]); e < tm_f2i(rc[7]); e++) { int u = m.dof_act_id[e]; fa += m.dof_act_coef[e] * (m.dof_act_gain[e] * L[(K.lean ? K.l_sv : K.l_act) + u]); }
       WST(m.s_qfrc_actuator, i) = fa;
       float f = -rc[2] * L[K.l_qvel + i] - bias + fa;
       if (rc[3] != 0.f) f += -rc[3] * (L[K.l_qpos + tm_f2i(rc[4])] - rc[5]);

@@ -71,6 +71,8 @@ def main(argv=None, runner=None):
         if a.startswith("--config-name="):
             cfg_name = a.split("=", 1)[1]; del argv[i]; break
     cfg = _config.load_config(cfg_path, argv, name=cfg_name)
+    # first line of the log: which walker this run trains (actuator mode, scale, model blob)
+    print(f"[train] config={cfg_name or cfg_path or 'rodent-full-clips'} " + Rodent(**cfg["walker_config"]).describe(), flush=True)
     from . import launch
     num_gpus = int(cfg.get("num_gpus", 1))
     if launch.needs_spawn(num_gpus):        # before anything touches the GPU: the ranks are a child process, never an exec

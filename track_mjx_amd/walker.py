@@ -2,8 +2,13 @@
 
 Reference: track_mjx/environment/walker/rodent.py:16-114 (constructor arguments, name -> id
 tables) and walker/base.py:70-88 (index properties).  The MuJoCo compile step is replaced by
-the pre-compiled model blob `assets/rodent_model.tmjx` (tools/compile_model.py), which already
-contains the torque-actuator rewrite and the 0.9 rescale the reference config asks for.
+pre-compiled model blobs (tools/compile_model.py), one per (torque_actuators, rescale_factor)
+pair in `BLOBS` (binary `.tmjx`, or its lossless text form `.tmjx.txt`: blob.py):
+  - (True, 0.9)  `assets/rodent_model.tmjx`: the torque-actuator rewrite and the 0.9 rescale of
+    rodent-full-clips.yaml:116-117 (the default walker of both named configurations);
+  - (False, 0.8) `assets/rodent_model_pos080.tmjx.txt`: rodent.xml's position servos kept as written
+    (affine bias: force = gain * act + b0 + b1 * length) and the 0.8 rescale of
+    rodent-sps-per-actor.yaml:108-109.
 """
 from __future__ import annotations
 
@@ -17,21 +22,40 @@ from . import blob as _blob
 
 _ASSETS = Path(__file__).parent / "assets"
 
+# (torque_actuators, rescale_factor) -> model blob under assets/ (with <stem>.names.txt and <stem>_dump.txt beside it)
+BLOBS = {
+    (True, 0.9): "rodent_model.tmjx",
+    (False, 0.8): "rodent_model_pos080.tmjx.txt",
+}
+
+
+def blob_file(torque_actuators: bool, rescale_factor: float) -> str:
+    for (tq, s), fname in BLOBS.items():
+        if bool(torque_actuators) == tq and abs(float(rescale_factor) - s) <= 1e-12:
+            return fname
+    have = ", ".join(f"(torque_actuators={tq}, rescale_factor={s})" for tq, s in BLOBS)
+    raise NotImplementedError(
+        f"no model blob is compiled for torque_actuators={torque_actuators}, rescale_factor={rescale_factor} (shipped: {have}); "
+        f"compile one with: python tools/compile_model.py --rescale {rescale_factor}"
+        + ("" if torque_actuators else " --no-torque --affine-bias")
+        + f" --out track_mjx_amd/assets/<stem>.tmjx.txt, and add it to walker.BLOBS")
+
 
 class Rodent:
     def __init__(self, joint_names: Sequence[str], body_names: Sequence[str], end_eff_names: Sequence[str],
                  *, torque_actuators: bool = False, rescale_factor: float = 0.9):
-        if not torque_actuators or abs(rescale_factor - 0.9) > 1e-12:
-            raise NotImplementedError(
-                "the shipped model blob is compiled for torque_actuators=True, rescale_factor=0.9 "
-                "(rodent-full-clips.yaml:116-117); recompile with tools/compile_model.py for other values")
+        fname = blob_file(torque_actuators, rescale_factor)
+        self.torque_actuators = bool(torque_actuators)
+        self.rescale_factor = float(rescale_factor)
+        self.actuator_mode = "torque" if self.torque_actuators else "position"
+        self.blob_path = _ASSETS / fname
         self._torso_name = "torso"
         self._joint_names = list(joint_names)
         self._body_names = list(body_names)
         self._end_eff_names = list(end_eff_names)
-        self.model = _blob.load(_ASSETS / "rodent_model.tmjx")
+        self.model = _blob.load(self.blob_path)
         self.names = {"body": {}, "joint": {}, "actuator": {}}
-        with open(_ASSETS / "rodent_model.names.txt") as f:
+        with open(_ASSETS / f"{_blob.stem(fname)}.names.txt") as f:
             for line in f:
                 kind, idx, name = line.split()
                 self.names[kind][name] = int(idx)
@@ -44,6 +68,10 @@ class Rodent:
         self._body_idxs = np.array([self.names["body"][b] for b in self._body_names], dtype=np.int32)
         self._endeff_idxs = np.array([self.names["body"][e] for e in self._end_eff_names], dtype=np.int32)
         self._torso_idx = int(self.names["body"][self._torso_name])
+
+    def describe(self) -> str:
+        """One line naming the walker: actuator mode, scale, blob file."""
+        return f"walker: rodent, {self.actuator_mode} actuators, rescale_factor={self.rescale_factor:g}, model blob {self.blob_path.name}"
 
     joint_idxs = property(lambda self: self._joint_idxs)
     body_idxs = property(lambda self: self._body_idxs)
