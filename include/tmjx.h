@@ -491,6 +491,41 @@ int tmjx_stats_apply(const float *sums, float n_added, float *count, float *mean
  * of which joint limits] of the last substep; "efc_in" [nefc] = 1 for the original rows that entered the solver. */
 int tmjx_debug_rows(const tmjx_model *m, const char *name, int *row0, int *count);
 
+/* ---- LSTM decoder recurrence (csrc/lstm_kernels.h) of the recurrent learner (track_mjx/agent/lstm_ppo/intention_network.py: flax
+ * nn.LSTMCell, gate order i, f, g, o):  gate = x W_i^T + h W_h^T + b_h;  c' = sig(f) c + sig(i) tanh(g);  h' = sig(o) tanh(c').
+ * One launch runs T steps of ONE layer over `rows` independent sequences; the input part x W_i^T is precomputed for every step (one GEMM,
+ * tmjx_gemm_nt) and passed as xg.  reset (optional, [T][ldr >= rows] floats): non-zero at (t, row) zeroes the carry (h, c) BEFORE step t —
+ * the roll-out's done of the previous step, the loss scan's 1 - discount[t - 1].  Rows are independent: each workgroup owns 8 rows for all
+ * T steps.  H = 32, 64, 128 or 256 (tmjx_lstm_hidden_ok). */
+typedef struct {
+  const float *xg; int32_t ldx;      /* [T][rows][ldx >= 4H]: x W_i^T, gate-major columns i | f | g | o */
+  const float *Wh; int32_t ldw;      /* [4H][ldw >= H], 16-byte aligned rows (ldw % 4 == 0) */
+  const float *bh;                   /* [4H] */
+  const float *h0, *c0; int32_t ld0; /* initial carry [rows][ld0 >= H] */
+  const float *reset; int32_t ldr;   /* optional */
+  float *h, *c; int32_t ldo;         /* h_t, c_t of every step: [T][rows][ldo >= H] (step stride rows * ldo); may alias h0 / c0 when T == 1 */
+  float *gates;                      /* optional [T][rows][4H]: sig(i) | sig(f) | tanh(g) | sig(o) (what tmjx_lstm_seq_bwd needs) */
+  float *h_prev;                     /* optional [T][rows][ldo]: the carry h each step read, resets applied (the operand of dW_h) */
+  int32_t T, rows, H;
+} tmjx_lstm_fwd_t;
+/* The reverse recurrence: dh [T][rows][ldd] = d loss / d h_t from above -> dgates [T][rows][4H] = d loss / d (pre-activation gates) (the
+ * operand of dx = dgates W_i, dW_i, dW_h = dgates^T h_prev and db = colsum(dgates)) and, optionally, d loss / d (h0, c0) [rows][ld0].
+ * gates / c / c0 / reset are the forward call's; a reset stops the gradient exactly where the forward pass stopped the carry. */
+typedef struct {
+  const float *dh; int32_t ldd;
+  const float *Wh; int32_t ldw;
+  const float *gates;
+  const float *c; int32_t ldo;
+  const float *c0; int32_t ld0;
+  const float *reset; int32_t ldr;
+  float *dgates;
+  float *dh0, *dc0;                  /* optional */
+  int32_t T, rows, H;
+} tmjx_lstm_bwd_t;
+int tmjx_lstm_hidden_ok(int H);
+int tmjx_lstm_seq_fwd(const tmjx_lstm_fwd_t *args, void *stream);
+int tmjx_lstm_seq_bwd(const tmjx_lstm_bwd_t *args, void *stream);
+
 const char *tmjx_last_error(void);
 const char *tmjx_version(void);
 

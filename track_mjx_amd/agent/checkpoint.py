@@ -24,9 +24,80 @@ def _ident(p):
     return p
 
 
+LSTM_GATES = "ifgo"          # flax nn.LSTMCell gate order: rows [g H, (g + 1) H) of w_ih / w_hh / b_hh
+
+
+def _encoder_to_flax(policy, get) -> dict:
+    enc = {}
+    for i, blk in enumerate(policy.encoder):
+        enc[f"hidden_{i}"] = {"kernel": _np(get(blk.dense.weight).t()), "bias": _np(get(blk.dense.bias))}
+        enc[f"LayerNorm_{i}"] = {"scale": _np(get(blk.norm.weight)), "bias": _np(get(blk.norm.bias))}
+    Z = policy.latents
+    w, b = get(policy.fc2.weight), get(policy.fc2.bias)
+    enc["fc2_mean"] = {"kernel": _np(w[:Z].t()), "bias": _np(b[:Z])}
+    enc["fc2_logvar"] = {"kernel": _np(w[Z:].t()), "bias": _np(b[Z:])}
+    return enc
+
+
+def lstm_policy_to_flax(policy, get=_ident) -> dict:
+    """LSTMIntentionPolicy -> the reference's lstm_ppo IntentionNetwork tree: {encoder, lstm_decoder: {lstm_{k}: {ii, if, ig, io: {kernel}, hi, hf,
+    hg, ho: {kernel, bias}}, lstm_projection: {kernel, bias}}} (flax kernels are [in, out])."""
+    H = policy.hidden_state_size
+    dec = {}
+    for k in range(policy.hidden_layer_num):
+        wi, wh, bh = get(policy.w_ih[k]), get(policy.w_hh[k]), get(policy.b_hh[k])
+        cell = {}
+        for g, name in enumerate(LSTM_GATES):
+            rows = slice(g * H, (g + 1) * H)
+            cell["i" + name] = {"kernel": _np(wi[rows].t())}
+            cell["h" + name] = {"kernel": _np(wh[rows].t()), "bias": _np(bh[rows])}
+        dec[f"lstm_{k}"] = cell
+    dec["lstm_projection"] = {"kernel": _np(get(policy.projection.weight).t()), "bias": _np(get(policy.projection.bias))}
+    return {"params": {"encoder": _encoder_to_flax(policy, get), "lstm_decoder": dec}}
+
+
+@torch.no_grad()
+def lstm_policy_from_flax(policy, tree: dict, get=_ident) -> None:
+    p = tree["params"]
+    dev = policy.fc2.weight.device
+
+    def put(dst: torch.Tensor, src) -> None:
+        dst.copy_(torch.as_tensor(np.ascontiguousarray(src), dtype=dst.dtype, device=dev))
+
+    _encoder_from_flax(policy, p["encoder"], get, put)
+    H = policy.hidden_state_size
+    for k in range(policy.hidden_layer_num):
+        cell = p["lstm_decoder"][f"lstm_{k}"]
+        wi, wh, bh = get(policy.w_ih[k]), get(policy.w_hh[k]), get(policy.b_hh[k])
+        for g, name in enumerate(LSTM_GATES):
+            rows = slice(g * H, (g + 1) * H)
+            put(wi[rows], np.asarray(cell["i" + name]["kernel"]).T)
+            put(wh[rows], np.asarray(cell["h" + name]["kernel"]).T)
+            put(bh[rows], cell["h" + name]["bias"])
+    proj = p["lstm_decoder"]["lstm_projection"]
+    put(get(policy.projection.weight), np.asarray(proj["kernel"]).T)
+    put(get(policy.projection.bias), proj["bias"])
+
+
+def _encoder_from_flax(policy, enc: dict, get, put) -> None:
+    for i, blk in enumerate(policy.encoder):
+        put(get(blk.dense.weight), np.asarray(enc[f"hidden_{i}"]["kernel"]).T)
+        put(get(blk.dense.bias), enc[f"hidden_{i}"]["bias"])
+        put(get(blk.norm.weight), enc[f"LayerNorm_{i}"]["scale"])
+        put(get(blk.norm.bias), enc[f"LayerNorm_{i}"]["bias"])
+    Z = policy.latents
+    w, b = get(policy.fc2.weight), get(policy.fc2.bias)
+    put(w[:Z], np.asarray(enc["fc2_mean"]["kernel"]).T)
+    put(w[Z:], np.asarray(enc["fc2_logvar"]["kernel"]).T)
+    put(b[:Z], enc["fc2_mean"]["bias"])
+    put(b[Z:], enc["fc2_logvar"]["bias"])
+
+
 def policy_to_flax(policy: IntentionPolicy, get=_ident) -> dict:
     """`get(parameter) -> tensor of the same shape`: identity = the parameter values; the optimiser export passes the parameter's view
     of a moment buffer, so mu / nu come out as trees with the parameters' own names (optax ScaleByAdamState.mu / .nu)."""
+    if hasattr(policy, "w_hh"):
+        return lstm_policy_to_flax(policy, get)
     enc, dec = {}, {}
     for i, blk in enumerate(policy.encoder):
         enc[f"hidden_{i}"] = {"kernel": _np(get(blk.dense.weight).t()), "bias": _np(get(blk.dense.bias))}
@@ -55,6 +126,8 @@ def normalizer_to_flax(n: RunningStatistics) -> dict:
 @torch.no_grad()
 def policy_from_flax(policy: IntentionPolicy, tree: dict, get=_ident) -> None:
     """In place.  `get(parameter)` = the destination tensor (identity: the parameter; the optimiser import passes moment-buffer views)."""
+    if hasattr(policy, "w_hh"):
+        return lstm_policy_from_flax(policy, tree, get)
     p = tree["params"]
     dev = policy.fc2.weight.device
 
@@ -170,7 +243,28 @@ def learner_tree(learner) -> dict:
             "optimizer": {"count": np.asarray(opt.t, dtype=np.int64),
                           "mu": {"policy": policy_to_flax(learner.policy, mu), "value": value_to_flax(learner.value, mu)},
                           "nu": {"policy": policy_to_flax(learner.policy, nu), "value": value_to_flax(learner.value, nu)}},
-            "rng": rng_tree(learner)}
+            "rng": rng_tree(learner), **carry_tree(learner)}
+
+
+def carry_tree(learner) -> dict:
+    """The recurrent learner's roll-out carry (TrainingState.hidden_state of lstm_ppo/ppo.py), resets applied: {"hidden_state": {h, c}} [n, L, H]."""
+    if not hasattr(learner, "settle_carry"):
+        return {}
+    learner.settle_carry()
+    return {"hidden_state": {"h": _np(learner.h_carry), "c": _np(learner.c_carry)}}
+
+
+@torch.no_grad()
+def carry_from_tree(learner, tree: dict) -> None:
+    if not hasattr(learner, "settle_carry") or "hidden_state" not in tree:
+        return
+    hs = tree["hidden_state"]
+    for dst, k in ((learner.h_carry, "h"), (learner.c_carry, "c")):
+        src = np.asarray(hs[k])
+        if src.shape != tuple(dst.shape):
+            raise ValueError(f"checkpoint carry {k} has shape {src.shape}, the learner {tuple(dst.shape)}")
+        dst.copy_(torch.as_tensor(src, dtype=dst.dtype, device=dst.device))
+    learner._pending_reset.zero_()
 
 
 def _atomic_savez(path, flat: dict, overwrite: bool) -> None:
@@ -231,6 +325,8 @@ def load_npz(path, learner, load_optimizer: bool = True) -> dict:
         learner.opt.t = int(o["count"])
     if load_optimizer and "rng" in tree:
         rng_from_tree(learner, tree["rng"])
+    if load_optimizer:
+        carry_from_tree(learner, tree)
     if hasattr(learner, "_refresh_padded_weights"):
         learner._refresh_padded_weights()
     return extra
@@ -266,6 +362,8 @@ def save_step_dir(directory, step: int, learner, config: dict | None = None, env
         ts = {"optimizer_state": tree["optimizer"], "params": {"policy": tree["policy"], "value": tree["value"]},
               "normalizer_params": tree["normalizer"], "env_steps": np.asarray(0 if env_steps is None else env_steps, dtype=np.int64),
               "rng": tree["rng"], "iteration": np.asarray(int(step), dtype=np.int64)}
+        if "hidden_state" in tree:
+            ts["hidden_state"] = tree["hidden_state"]
         _atomic_savez(os.path.join(tmp, "train_state.npz"), flatten(ts), True)
         os.makedirs(os.path.join(tmp, "config"))
         with open(os.path.join(tmp, "config", "metadata"), "w") as f:
@@ -315,6 +413,7 @@ def load_step_dir(path, learner, load_optimizer: bool = True) -> dict:
         learner.opt.t = int(o["count"])
         if "rng" in ts:
             rng_from_tree(learner, ts["rng"])
+        carry_from_tree(learner, ts)
     if hasattr(learner, "_refresh_padded_weights"):
         learner._refresh_padded_weights()
     cfg = None

@@ -64,8 +64,11 @@ class Evaluator:
     def run_evaluation(self, training_metrics: dict | None = None, aggregate_episodes: bool = True, data_split: str = "") -> dict:
         t0 = time.time()
         st = self.env.reset(self.gen)
+        carried = hasattr(self.policy, "reset_carry")       # a recurrent policy (agent/lstm.py: CarriedPolicy) carries its state across steps
+        if carried:
+            self.policy.reset_carry()
         for _ in range(self.unroll_length):
-            action, _ = self.policy(st.obs)
+            action, _ = self.policy(st.obs, done=st.done) if carried else self.policy(st.obs)
             st = self.env.step(st, action)
         torch.cuda.synchronize(self.env.device) if self.env.device.type == "cuda" else None
         dt = time.time() - t0

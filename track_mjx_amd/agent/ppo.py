@@ -250,7 +250,7 @@ class PPOLearner:
         self.env_steps_per_training_step = batch_size * unroll_length * num_minibatches
         obs, ref = env.observation_size, int(env.layout.ref_obs_size)
         torch.manual_seed(seed)  # identical init on every rank (reference: device_put_replicated, ppo.py:625-627)
-        self.policy = IntentionPolicy(obs, ref, env.action_size, latents, encoder_layers, decoder_layers).to(dev)
+        self.policy = self._build_policy(obs, ref, env.action_size, latents, encoder_layers, decoder_layers).to(dev)
         self.value = ValueNet(obs, critic_layers).to(dev)
         self.params = list(self.policy.parameters()) + list(self.value.parameters())
         self.grads = FlatGrads(self.params)
@@ -334,6 +334,9 @@ class PPOLearner:
         self._obs_rm = ([torch.zeros((e.num_envs, e.observation_size), dtype=torch.float32, device=dev) for e in self.envs]
                         if (self.lds_free and env.observation_size % 4 == 0 and not os.environ.get("TMJX_NO_OBS_STAGING")) else None)
         self._streams = [torch.cuda.Stream(device=dev) for _ in self.envs] if (len(self.envs) > 1 and dev.type == "cuda") else None
+
+    def _build_policy(self, obs, ref, action_size, latents, encoder_layers, decoder_layers):
+        return IntentionPolicy(obs, ref, action_size, latents, encoder_layers, decoder_layers)
 
     @property
     def state(self):
@@ -889,7 +892,8 @@ def train(environment, num_timesteps: int, episode_length: int, ckpt_mgr=None, c
           max_training_steps: int | None = None, eval_env=None, num_eval_envs: int = 128, deterministic_eval: bool = False,
           matmul_dtype: torch.dtype | None = None, group=None, checkpoint_path: str | None = None, restore_from: str | None = None,
           shuffle_rng: str = "torch", act_rng: str = "device", action_repeat: int = 1,
-          policy_params_fn: Callable[..., None] = lambda *args, **kwargs: None, checkpoint_callback: Callable[[int], None] | None = None, **unused):
+          policy_params_fn: Callable[..., None] = lambda *args, **kwargs: None, checkpoint_callback: Callable[[int], None] | None = None,
+          use_lstm: bool = False, hidden_state_size: int = 128, hidden_layer_num: int = 2, **unused):
     """ppo.train(environment, num_timesteps, episode_length, ...) -> (make_policy, params, metrics)  (ppo.py:128-172,809).
 
     `environment` is an un-wrapped MultiClipTracking holding THIS rank's envs; it is wrapped here exactly like
@@ -904,6 +908,9 @@ def train(environment, num_timesteps: int, episode_length: int, ckpt_mgr=None, c
     noise streams — and the run continues at the iteration after the restored one (the reference leaves its iteration restart as a TODO,
     ppo.py:670-677, and would then collide with the existing steps of the same directory).
 
+    `use_lstm`: the recurrent learner (agent/lstm.py: LSTMPPOLearner, the reference's agent/lstm_ppo) with `hidden_layer_num` LSTM layers of
+    `hidden_state_size` features; the acting policies (evaluator, make_policy) then carry their own hidden state.
+
     `policy_params_fn` (ppo.py:162,220-224): called by process 0 after every eval epoch exactly as ppo.py:762-781 does — keyword arguments
     `current_step` (the eval iteration), `jit_logging_inference_fn` (the DETERMINISTIC logging policy of ppo_networks.py:103-149:
     (params, observations, key_sample) -> (action, {"latent_mean", "latent_logvar"})), `params` ((normalizer, policy) state), a fresh
@@ -913,7 +920,13 @@ def train(environment, num_timesteps: int, episode_length: int, ckpt_mgr=None, c
     # a list of environments = equal groups of this rank's envs whose roll-outs are pipelined on separate HIP streams (collect())
     env_list = [wrap(e, episode_length=int(episode_length), action_repeat=int(action_repeat)) for e in (environment if isinstance(environment, (list, tuple)) else [environment])]
     env = env_list[0]
-    learner = PPOLearner(env_list if len(env_list) > 1 else env, encoder_layers=encoder_hidden_layer_sizes, decoder_layers=decoder_hidden_layer_sizes,
+    learner_cls, lstm_kw = PPOLearner, {}
+    if use_lstm:
+        from .lstm import LSTMPPOLearner, check_lstm_config
+        check_lstm_config(hidden_state_size, hidden_layer_num, matmul_dtype)
+        learner_cls, lstm_kw = LSTMPPOLearner, dict(hidden_state_size=hidden_state_size, hidden_layer_num=hidden_layer_num)
+        use_kl_schedule = False                # lstm_ppo/losses.py: no KL schedule
+    learner = learner_cls(env_list if len(env_list) > 1 else env, **lstm_kw, encoder_layers=encoder_hidden_layer_sizes, decoder_layers=decoder_hidden_layer_sizes,
                          critic_layers=value_hidden_layer_sizes, latents=intention_latent_size, learning_rate=learning_rate,
                          entropy_cost=entropy_cost, discounting=discounting, reward_scaling=reward_scaling, gae_lambda=gae_lambda,
                          clipping_epsilon=clipping_epsilon, unroll_length=unroll_length, batch_size=batch_size,
@@ -945,6 +958,8 @@ def train(environment, num_timesteps: int, episode_length: int, ckpt_mgr=None, c
     reset_gen = torch.Generator().manual_seed(seed + 1 + learner.rank)
 
     def reset_all():
+        if use_lstm:
+            learner.settle_carry()          # the carry continues across env resets (lstm_ppo/ppo.py:629-642), with the last step's resets applied
         for k, e in enumerate(env_list):
             learner.states[k] = e.reset(reset_gen)
     reset_all()
@@ -953,8 +968,13 @@ def train(environment, num_timesteps: int, episode_length: int, ckpt_mgr=None, c
     if eval_env is not None and learner.rank == 0:
         from .evaluator import Evaluator
         eval_gen = torch.Generator(device=learner.dev).manual_seed(seed * 1000 + 991)   # not the roll-out generators (registered with hipGraphs)
+        if use_lstm:
+            from .lstm import CarriedPolicy
+            eval_policy = CarriedPolicy(learner, deterministic=deterministic_eval, gen=eval_gen)
+        else:
+            eval_policy = lambda obs: learner.act(obs, deterministic=deterministic_eval, gen=eval_gen)   # noqa: E731
         evaluator = Evaluator(wrap(eval_env, episode_length=int(episode_length), action_repeat=int(action_repeat)),
-                              lambda obs: learner.act(obs, deterministic=deterministic_eval, gen=eval_gen), episode_length=int(episode_length),
+                              eval_policy, episode_length=int(episode_length),
                               action_repeat=int(action_repeat), seed=seed + 7)
     render_interval = max(int(((config_dict or {}).get("env_config") or {}).get("render_interval", 1) or 1), 1)
     ppf_calls = [0]
@@ -984,7 +1004,8 @@ def train(environment, num_timesteps: int, episode_length: int, ckpt_mgr=None, c
         action is deterministic: `policy_network.apply(*params, observations, key_network)` is called without `deterministic=True`
         (ppo_networks.py:117-119), so the latent is still SAMPLED — `key_sample -> split -> key_network` (:116), `-> split -> encoder_rng`
         (intention_network.py:104), `eps = normal(encoder_rng, logvar.shape)` (:85-88), drawn here by the pinned threefry restatement
-        (track_mjx_amd/jax_random.py) — and the action is the mode of the distribution of the resulting logits (:124-130)."""
+        (track_mjx_amd/jax_random.py) — and the action is the mode of the distribution of the resulting logits (:124-130).  With `use_lstm` every
+        call starts from a ZERO carry (the policy's hidden state is not a parameter): z = latent_mean, the mode of the action distribution, no key used."""
         import copy
         from .. import jax_random as _jr
         norm_sd, pol_sd = params[0], params[1]
@@ -997,6 +1018,11 @@ def train(environment, num_timesteps: int, episode_length: int, ckpt_mgr=None, c
         obs = obs.reshape(-1, obs.shape[-1])
         if learner.normalize_observations:
             obs = (obs - norm_sd["mean"].to(learner.dev)) / norm_sd["std"].to(learner.dev)
+        if use_lstm:        # the recurrent policy from a zero carry: z = latent_mean, the mode of the action distribution
+            h, c = pol.zero_carry(obs.shape[0], learner.dev)
+            logits, fc2 = pol.step(obs.contiguous(), h, c)
+            mean, logvar = torch.chunk(fc2, 2, dim=-1)
+            return (NormalTanh.mode(logits.float()).reshape(*lead, -1), {"latent_mean": mean.reshape(*lead, -1), "latent_logvar": logvar.reshape(*lead, -1)})
         key_network = _jr.split(_logging_key(key_sample))[1]
         encoder_rng = _jr.split(key_network)[1]
         eps = torch.from_numpy(np.asarray(_jr.normal(encoder_rng, (*lead, pol.latents)), dtype=np.float32)).reshape(-1, pol.latents).to(learner.dev)
@@ -1055,6 +1081,9 @@ def train(environment, num_timesteps: int, episode_length: int, ckpt_mgr=None, c
                     if len(params) > 2 and params[2] is not None:
                         learner.value.load_state_dict(params[2])
                 learner._refresh_padded_weights()
+        if use_lstm:
+            from .lstm import CarriedPolicy
+            return CarriedPolicy(learner, deterministic=deterministic)       # call(obs, *, done=None): carries its own hidden state
         return lambda obs, key=None: learner.act(obs, deterministic=deterministic)
 
     params = ({k: v.clone() for k, v in learner.normalizer.state_dict().items()}, {k: v.clone() for k, v in learner.policy.state_dict().items()},

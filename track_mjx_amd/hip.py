@@ -14,7 +14,7 @@ from pathlib import Path
 _PKG = Path(__file__).resolve().parent
 SO_PATH = Path(os.environ.get("TMJX_SO", str(_PKG / "libtmjx_hip.so")))  # TMJX_SO: alternative build (profiling)
 CSRC = _PKG / "csrc"
-SOURCES = (CSRC / "tmjx_hip.hip", CSRC / "tmjx_bf16.hip", CSRC / "tmjx_wave.hip", CSRC / "tmjx_chain.hip")
+SOURCES = (CSRC / "tmjx_hip.hip", CSRC / "tmjx_bf16.hip", CSRC / "tmjx_wave.hip", CSRC / "tmjx_chain.hip", CSRC / "tmjx_lstm.hip")
 # per-source compiler flags: the physics kernel's unit is built without machine LICM (csrc/tmjx_wave.hip says why)
 SOURCE_FLAGS = {"tmjx_wave.hip": ("-mllvm", "-disable-machine-licm")}
 
@@ -38,6 +38,7 @@ EXPORTS = ("tmjx_model_create", "tmjx_model_destroy", "tmjx_layout", "tmjx_clips
            "tmjx_rollout_store", "tmjx_clips_share", "tmjx_gemm_nt_silu", "tmjx_gemm_nt_silu_ok", "tmjx_silu_fwd", "tmjx_silu_bwd", "tmjx_gemm_nn_silu_bwd_ok", "tmjx_gemm_nn_silu_bwd", "tmjx_silu_bwd_rank1", "tmjx_head_dw_scratch_floats", "tmjx_head_dw", "tmjx_head_fwd_ok", "tmjx_head_fwd", "tmjx_bf16_shadow", "tmjx_bgemm_nt", "tmjx_bgemm_dw", "tmjx_bgemm_dw_grouped", "tmjx_bgemm_dw_scratch_floats", "tmjx_bgemm_row_tile_ok", "tmjx_bf16_z_bytes", "tmjx_bgemm_partial_floats",
            "tmjx_bgemm_ln_fwd", "tmjx_bgemm_ln_bwd", "tmjx_bgemm_silu_fwd", "tmjx_bgemm_silu_bwd", "tmjx_bf_silu_bwd", "tmjx_bf_silu_bwd_rank1",
            "tmjx_chain_rows", "tmjx_chain_fwd_ok", "tmjx_chain_fwd", "tmjx_chain_bwd_ok", "tmjx_chain_bwd",
+           "tmjx_lstm_hidden_ok", "tmjx_lstm_seq_fwd", "tmjx_lstm_seq_bwd",
            "tmjx_debug_rows", "tmjx_last_error", "tmjx_version")
 
 
@@ -99,6 +100,20 @@ class ChainBwd(C.Structure):
     """tmjx_chain_bwd_t (include/tmjx.h)."""
     _fields_ = [("G", C.c_void_p), ("ldg", C.c_int32), ("Kg", C.c_int32), ("M", C.c_int32), ("n_stages", C.c_int32), ("epi", C.c_int32), ("stage", ChainBwdStage * 4),
                 ("W0", C.c_void_p), ("ldw0", C.c_int32), ("dx_cols", C.c_int32), ("dx", C.c_void_p), ("lddx", C.c_int32), ("rows_alloc", C.c_int32), ("prof", C.c_void_p)]
+
+
+class LstmFwd(C.Structure):
+    """tmjx_lstm_fwd_t (include/tmjx.h)."""
+    _fields_ = [("xg", C.c_void_p), ("ldx", C.c_int32), ("Wh", C.c_void_p), ("ldw", C.c_int32), ("bh", C.c_void_p), ("h0", C.c_void_p), ("c0", C.c_void_p),
+                ("ld0", C.c_int32), ("reset", C.c_void_p), ("ldr", C.c_int32), ("h", C.c_void_p), ("c", C.c_void_p), ("ldo", C.c_int32),
+                ("gates", C.c_void_p), ("h_prev", C.c_void_p), ("T", C.c_int32), ("rows", C.c_int32), ("H", C.c_int32)]
+
+
+class LstmBwd(C.Structure):
+    """tmjx_lstm_bwd_t (include/tmjx.h)."""
+    _fields_ = [("dh", C.c_void_p), ("ldd", C.c_int32), ("Wh", C.c_void_p), ("ldw", C.c_int32), ("gates", C.c_void_p), ("c", C.c_void_p), ("ldo", C.c_int32),
+                ("c0", C.c_void_p), ("ld0", C.c_int32), ("reset", C.c_void_p), ("ldr", C.c_int32), ("dgates", C.c_void_p), ("dh0", C.c_void_p),
+                ("dc0", C.c_void_p), ("T", C.c_int32), ("rows", C.c_int32), ("H", C.c_int32)]
 
 
 class PpoCfg(C.Structure):
@@ -299,6 +314,9 @@ def load(path: Path):
     sig.setdefault("tmjx_chain_fwd", [None, None])[0] = [C.POINTER(ChainFwd), vp]
     sig.setdefault("tmjx_chain_bwd_ok", [None, None])[0] = [C.POINTER(ChainBwd)]
     sig.setdefault("tmjx_chain_bwd", [None, None])[0] = [C.POINTER(ChainBwd), vp]
+    sig.setdefault("tmjx_lstm_hidden_ok", [None, None])[0] = [C.c_int]
+    sig.setdefault("tmjx_lstm_seq_fwd", [None, None])[0] = [C.POINTER(LstmFwd), vp]
+    sig.setdefault("tmjx_lstm_seq_bwd", [None, None])[0] = [C.POINTER(LstmBwd), vp]
     sig.setdefault("tmjx_debug_rows", [None, None])[0] = [vp, C.c_char_p, ip, ip]
     sig.setdefault("tmjx_last_error", [None, None])[1] = C.c_char_p
     sig.setdefault("tmjx_version", [None, None])[1] = C.c_char_p

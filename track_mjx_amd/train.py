@@ -58,6 +58,19 @@ def build_env(cfg: dict, num_envs_local: int, device, n_clips: int = 64, clip_se
     return env
 
 
+def learner_options(cfg: dict) -> dict:
+    """ppo.train keywords of the learner choice (train.py:229-243 of the reference): train_config.use_lstm selects the recurrent learner
+    (agent/lstm.py) with network_config.hidden_state_size / hidden_layer_num (defaults 128 / 2, the wrap() defaults; the reference yamls carry
+    neither).  Refuses what that learner does not build, before anything touches the GPU."""
+    if not bool(cfg["train_setup"]["train_config"].get("use_lstm", False)):
+        return {}
+    from .agent.lstm import check_lstm_config
+    nc = cfg["network_config"]
+    H, L = int(nc.get("hidden_state_size", 128)), int(nc.get("hidden_layer_num", 2))
+    check_lstm_config(H, L, torch.bfloat16 if str(cfg.get("mlp_gemm_inputs", "f32")).lower() in ("bf16", "bfloat16") else None)
+    return {"use_lstm": True, "hidden_state_size": H, "hidden_layer_num": L}
+
+
 def main(argv=None, runner=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     full_argv = list(argv)
@@ -73,6 +86,9 @@ def main(argv=None, runner=None):
     cfg = _config.load_config(cfg_path, argv, name=cfg_name)
     # first line of the log: which walker this run trains (actuator mode, scale, model blob)
     print(f"[train] config={cfg_name or cfg_path or 'rodent-full-clips'} " + Rodent(**cfg["walker_config"]).describe(), flush=True)
+    lopts = learner_options(cfg)
+    if lopts:
+        print(f"[train] learner=lstm_ppo hidden_state_size={lopts['hidden_state_size']} hidden_layer_num={lopts['hidden_layer_num']}", flush=True)
     from . import launch
     num_gpus = int(cfg.get("num_gpus", 1))
     if launch.needs_spawn(num_gpus):        # before anything touches the GPU: the ranks are a child process, never an exec
@@ -128,7 +144,7 @@ def main(argv=None, runner=None):
               max_training_steps=cfg.get("max_training_steps"), eval_env=eval_env, num_eval_envs=num_eval_envs,
               deterministic_eval=bool(tc.get("deterministic_eval", False)), config_dict=cfg, action_repeat=int(tc.get("action_repeat", 1)),
               checkpoint_path=cfg.get("checkpoint_path"), restore_from=cfg.get("restore_from"), shuffle_rng=str(cfg.get("shuffle_rng", "torch")), act_rng=str(cfg.get("act_rng", "device")),
-              matmul_dtype=torch.bfloat16 if str(cfg.get("mlp_gemm_inputs", "f32")).lower() in ("bf16", "bfloat16") else None)
+              matmul_dtype=torch.bfloat16 if str(cfg.get("mlp_gemm_inputs", "f32")).lower() in ("bf16", "bfloat16") else None, **lopts)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
