@@ -526,6 +526,49 @@ int tmjx_lstm_hidden_ok(int H);
 int tmjx_lstm_seq_fwd(const tmjx_lstm_fwd_t *args, void *stream);
 int tmjx_lstm_seq_bwd(const tmjx_lstm_bwd_t *args, void *stream);
 
+/* ---- Roll-out recorder (csrc/rollout_kernels.h) of checkpoint roll-outs (track_mjx/analysis/rollout.py:73-269: generate_rollout's scan
+ * stacks the state, ctrl and activations of every step).  ONE launch per control step copies K streams into clip-major records
+ * dst[env][T][w] at row t0 + t: each env's record of a stream is one contiguous block.  The copy never rounds: recorded values are the
+ * source's bits.  A stream's source is either
+ *   SoA       src[r * ld + env], r < src_extent (the env's [field][n_env] state / metrics buffers): transposed through LDS so that each env's
+ *             w floats are written as one coalesced run;
+ *   row-major src[env * ld + c], c < src_extent (the policy's layer outputs): 16-byte loads / stores when src, ld, w and dst allow.
+ * n_idx > 0 selects rows (SoA) / columns (row-major) idx[0..w) of the source instead of 0..w (e.g. metrics in METRIC_NAMES order). */
+#define TMJX_RECORD_SOA 0
+#define TMJX_RECORD_ROWMAJOR 1
+#define TMJX_RECORD_MAX_STREAMS 64
+#define TMJX_RECORD_MAX_IDX 32
+#define TMJX_RECORD_MAX_W 4096
+typedef struct tmjx_record_stream_t {
+  const float *src;
+  float *dst;                  /* [n_env][T][w], 16-byte aligned for the vector path */
+  int32_t layout;              /* TMJX_RECORD_SOA | TMJX_RECORD_ROWMAJOR */
+  int32_t ld;                  /* SoA: >= n_env; row-major: >= src_extent */
+  int32_t w;                   /* floats per env per row, 1 .. TMJX_RECORD_MAX_W */
+  int32_t src_extent;          /* rows (SoA) / columns (row-major) of the source: the bound of every index read */
+  int32_t T, t0;               /* rows per env record; the launch's t writes row t0 + t */
+  int32_t n_idx;               /* 0, or w (<= TMJX_RECORD_MAX_IDX): idx[0..w) are source rows / columns */
+  int32_t idx[TMJX_RECORD_MAX_IDX];
+  int32_t pad_;
+} tmjx_record_stream_t;
+/* Host-side validation of a stream table for launches with 0 <= t < T (no device call): null or misaligned (4-byte) pointers, w / ld /
+ * index bounds, t0 + T beyond a stream's record.  Run once before the table is copied to the device. */
+int tmjx_record_check(const tmjx_record_stream_t *table, int k, int n_env, int T);
+/* One launch: row t of every stream of `device_table` (a device copy of a table that passed tmjx_record_check with the same k, n_env, T;
+ * 16-byte aligned).  Grid (ceil(n_env / 32), k) of 256 threads, 32 envs per workgroup. */
+int tmjx_record_step(const tmjx_record_stream_t *device_table, int k, int n_env, int t, int T, void *stream);
+
+/* Deterministic policy step (make_inference_fn(..., deterministic=True), intention_network.py:102-123):
+ * tmjx_latent_concat_det: x[i] = [ fc2[i][0..Z) | (obs_i[c] - mean[c]) / std[c] for c in [ref_w, obs_w) ], written as [n][ldx] (columns
+ *   beyond Z + obs_w - ref_w are zeroed) — z = latent_mean exactly (no mean + 0 * exp(logvar / 2), which is NaN where exp overflows);
+ *   with `traj` also traj[i][c] = (obs_i[c] - mean[c]) / std[c] for c < ref_w ([n][ldt]: the normalised reference half the reference logs).
+ *   obs_i[c] at obs[i * obs_s0 + c * obs_s1]; fc2 [n][ldf >= 2Z]; mean / std may both be NULL (no normaliser).
+ * tmjx_action_mode: NormalTanh mode, a = tanh(logits[i][j]) for j < A (logits [n][ldl >= 2A]) written as ctrl [n][A] (recorded) and
+ *   action_t [A][n] (the layout tmjx_step takes). */
+int tmjx_latent_concat_det(const float *fc2, int ldf, const float *obs, int64_t obs_s0, int64_t obs_s1, const float *mean, const float *std,
+                           float *x, int ldx, float *traj, int ldt, int n, int Z, int obs_w, int ref_w, void *stream);
+int tmjx_action_mode(const float *logits, int ldl, float *ctrl, float *action_t, int n, int A, void *stream);
+
 const char *tmjx_last_error(void);
 const char *tmjx_version(void);
 

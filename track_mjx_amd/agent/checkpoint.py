@@ -427,3 +427,82 @@ def restore(path, learner, load_optimizer: bool = True) -> dict:
     """A .npz file, a step directory, or a checkpoint directory (latest step)."""
     import os
     return load_step_dir(path, learner, load_optimizer) if os.path.isdir(str(path)) else load_npz(path, learner, load_optimizer)
+
+
+# ---- the analysis side (checkpointing.py:110-218 of the reference: load_config_from_checkpoint, load_policy, load_inference_fn): a trained policy
+# for roll-outs, without a training env or a learner ---------------------------------------------------------------------------------------------
+def resolve_step_dir(path, step: int | None = None) -> str:
+    """<run dir>/<step>/ (the latest step when `step` is None) or a step directory itself."""
+    import os
+    path = str(path)
+    if step is None and os.path.exists(os.path.join(path, "policy.npz")):
+        return path
+    st = latest_step(path) if step is None else int(step)
+    if st is None or not os.path.exists(os.path.join(path, str(st), "policy.npz")):
+        raise FileNotFoundError(f"no checkpoint step {'' if step is None else step} with a policy.npz under {path}")
+    return os.path.join(path, str(st))
+
+
+def load_config_from_checkpoint(path, step: int | None = None) -> dict:
+    """The run's config saved with the checkpoint (config/metadata of the step directory)."""
+    import json
+    import os
+    d = resolve_step_dir(path, step)
+    meta = os.path.join(d, "config", "metadata")
+    if not os.path.exists(meta):
+        raise FileNotFoundError(f"{d} has no config/metadata")
+    with open(meta) as f:
+        return json.load(f)
+
+
+def load_policy(path, cfg: dict | None = None, step: int | None = None) -> tuple:
+    """(normalizer_params, policy_params) of a step's policy.npz: the normaliser tree {count, mean, summed_variance, std} and the flax policy tree."""
+    import os
+    d = resolve_step_dir(path, step)
+    with np.load(os.path.join(d, "policy.npz")) as z:
+        tree = unflatten({k: z[k] for k in z.files})
+    return tree["0"], tree["1"]
+
+
+def load_inference_fn(cfg: dict, policy: tuple, deterministic: bool = True, get_activation: bool = True, device="cuda"):
+    """The deterministic inference function of (normalizer_params, policy_params) (make_inference_fn(...)(params, deterministic=True,
+    get_activation=...)): an analysis.rollout.RolloutPolicy holding the policy module with fp32 weights on `device`.  Layer sizes come from the
+    parameter tree; train_config.use_lstm picks the LSTM-decoder policy.  A bf16-trained (mlp_gemm_inputs=bf16) policy runs in fp32."""
+    from ..analysis.rollout import RolloutPolicy
+    if not deterministic:
+        raise NotImplementedError("load_inference_fn: only the deterministic policy (the roll-out's) is built")
+    norm, ptree = policy
+    p = ptree["params"]
+    enc = p["encoder"]
+    n_enc = len([k for k in enc if k.startswith("hidden_")])
+    enc_sizes = [int(np.asarray(enc[f"hidden_{i}"]["kernel"]).shape[1]) for i in range(n_enc)]
+    ref = int(np.asarray(enc["hidden_0"]["kernel"]).shape[0])
+    Z = int(np.asarray(enc["fc2_mean"]["kernel"]).shape[1])
+    W = int(np.asarray(norm["mean"]).shape[-1])
+    dev = torch.device(device)
+    use_lstm = "lstm_decoder" in p
+    if use_lstm != bool(cfg.get("train_setup", {}).get("train_config", {}).get("use_lstm", use_lstm)):
+        raise ValueError("load_inference_fn: train_config.use_lstm does not match the checkpoint's policy tree")
+    if use_lstm:
+        from .lstm import LSTMIntentionPolicy
+        dec = p["lstm_decoder"]
+        L = len([k for k in dec if k.startswith("lstm_") and k != "lstm_projection"])
+        H = int(np.asarray(dec["lstm_0"]["hi"]["kernel"]).shape[0])
+        A2 = int(np.asarray(dec["lstm_projection"]["kernel"]).shape[1])
+        module = LSTMIntentionPolicy(W, ref, A2 // 2, Z, enc_sizes, hidden_state_size=H, hidden_layer_num=L)
+    else:
+        dec = p["decoder"]
+        n_dec = len([k for k in dec if k.startswith("hidden_")]) - 1
+        dec_sizes = [int(np.asarray(dec[f"hidden_{i}"]["kernel"]).shape[1]) for i in range(n_dec)]
+        A2 = int(np.asarray(dec[f"hidden_{n_dec}"]["kernel"]).shape[1])
+        module = IntentionPolicy(W, ref, A2 // 2, Z, enc_sizes, dec_sizes)
+    module = module.to(dev).float().eval()
+    for q in module.parameters():
+        q.requires_grad_(False)
+    policy_from_flax(module, ptree)
+    mean = std = None
+    if bool(cfg.get("train_setup", {}).get("train_config", {}).get("normalize_observations", True)):
+        mean = torch.as_tensor(np.asarray(norm["mean"], dtype=np.float32), device=dev).reshape(-1).contiguous()
+        std = torch.as_tensor(np.asarray(norm["std"], dtype=np.float32), device=dev).reshape(-1).contiguous()
+    gi = "bf16" if str(cfg.get("mlp_gemm_inputs", "f32")).lower() in ("bf16", "bfloat16") else "f32"
+    return RolloutPolicy(module, mean, std, "lstm" if use_lstm else "mlp", get_activation=get_activation, trained_gemm_inputs=gi)

@@ -1,0 +1,508 @@
+"""Checkpoint roll-outs that record the network's activations — mirror of track_mjx/analysis/rollout.py (create_environment :25-70,
+create_rollout_generator / generate_rollout :73-269) with the reset of RenderRolloutWrapperMulticlipTracking (environment/wrappers.py:251-275).
+
+generate_rollout(clip_idx, seed) tracks whole clips from frame 0 with the deterministic policy.  A batch of clips is rolled out at once, one
+env per clip (the reference notebook's jit(vmap(generate_rollout)): every clip gets the same seed, hence the same reset noise).  One control
+step is a fixed sequence of launches on preallocated buffers, with no torch operation in the loop:
+
+    staging copy of the observation (tmjx_record_step, T = 1)  ->  encoder: tmjx_linear_nolds_norm / tmjx_linear_nolds + tmjx_silu_ln_fwd  ->
+    fc2 (tmjx_linear_nolds)  ->  tmjx_latent_concat_det  ->  decoder blocks / LSTM layers (tmjx_linear_nolds [+ tmjx_lstm_seq_fwd, T = 1])  ->
+    head  ->  tmjx_action_mode  ->  tmjx_step  ->  tmjx_record_step
+
+Every dense layer is the matrix-core variant of tmjx_linear_nolds (row-major operands with 16-byte aligned rows, K padded to a multiple of 4):
+its per-row arithmetic does not depend on the number of rows, so a clip's record is the same bits alone or in any batch.  The recorder
+writes each step into device-resident records [clip][T][w]; they are copied to the host once per batch.
+
+A checkpoint trained with mlp_gemm_inputs=bf16 is rolled out on these fp32 kernels (its weights are fp32; only the training GEMMs rounded
+their inputs).
+
+CLI:  python -m track_mjx_amd.analysis.rollout checkpoint=<run dir | step dir> [data_path=...] [clips=all|a:b|i,j,k] [seed=42] [out=<dir>]
+      [log_activations=true] [log_metrics=true]    ->  <out>/clip_<idx>.h5 (save_to_h5py layout + a `meta` group)
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import sys
+from typing import Callable, Sequence
+
+import numpy as np
+import torch
+
+from .. import hip as _hip
+from .. import jax_random as _jr
+from ..environment.task import METRIC_NAMES
+
+# logging_config.rollout_metrics of rodent-full-clips.yaml:97-113 (the default when a config has no logging_config)
+ROLLOUT_METRICS = ("pos_reward", "quat_reward", "joint_reward", "angvel_reward", "bodypos_reward", "endeff_reward", "summed_pos_distance",
+                   "joint_distance", "quat_distance", "ctrl_cost", "ctrl_diff_cost", "energy_cost", "too_far", "bad_pose", "bad_quat", "fall")
+CLIPS_PER_BATCH = 1024
+
+
+def _ceil4(n: int) -> int:
+    return (int(n) + 3) // 4 * 4
+
+
+def _p(t) -> int | None:
+    return None if t is None else t.data_ptr()
+
+
+# ---------------------------------------------------------------------------------------------------------------- environment
+def create_environment(cfg: dict, num_envs: int = 1, device: str | torch.device = "cuda"):
+    """The env of the checkpoint's config on ALL clips of `data_path` (rollout.py:25-70); "synthetic" rebuilds the training run's synthetic
+    table (n_synthetic_clips, clip seed 0).  No Episode / AutoReset wrapper: the env keeps stepping after done."""
+    from .. import clips as _clips
+    from ..train import build_env
+    from ..walker import Rodent
+    path = cfg.get("data_path", "synthetic")
+    if path == "synthetic":
+        table = _clips.make_synthetic_clips(Rodent(**cfg["walker_config"]).model, int(cfg.get("n_synthetic_clips", 64)),
+                                            n_frames=cfg["reference_config"]["clip_length"], seed=0, mocap_hz=cfg["env_config"]["env_args"]["mocap_hz"])
+    else:
+        from ..io import load
+        table = load.load_data(path)
+    return build_env(cfg, int(num_envs), device, reference_clip=table)
+
+
+def _sibling_env(env, n: int):
+    """An env of `n` envs with `env`'s model and configuration that reads `env`'s resident clip table."""
+    from ..environment.task import MultiClipTracking
+    return MultiClipTracking(env._reference_clips, env.walker, env._reward_config, physics_steps_per_control_step=env._n_frames,
+                             reset_noise_scale=env._reset_noise_scale, iterations=env._opts["iterations"], ls_iterations=env._opts["ls_iterations"],
+                             mj_model_timestep=env._opts["timestep"], mocap_hz=env._mocap_hz, clip_length=env._clip_length,
+                             random_init_range=env._random_init_range, traj_length=env._ref_len, num_envs=n, device=env.device,
+                             share_clips_with=env if env._clip_owner is None else env._clip_owner)
+
+
+# ---------------------------------------------------------------------------------------------------------------- key plumbing
+def reset_inputs(seed: int, n_clips: int, nq: int, nv: int, noise_scale: float, clip_idx: int | None = None):
+    """(clip_idx, qpos_noise [nq], qvel_noise [nv]) of generate_rollout(clip_idx, seed): key = PRNGKey(seed); _, reset_rng, act_rng = split(key, 3)
+    (rollout.py:133-134); RenderRolloutWrapperMulticlipTracking.reset: _, clip_rng, rng = split(reset_rng, 3), clip_idx = randint(clip_rng, (), 0,
+    n_clips) when None, start_frame = 0 (wrappers.py:266-271); reset_from_clip: _, rng1, _ = split(rng, 3), both noises from rng1
+    (single_clip_tracking.py:134-161)."""
+    reset_rng = _jr.split(_jr.PRNGKey(int(seed)), 3)[1]
+    _, clip_rng, rng = _jr.split(reset_rng, 3)
+    if clip_idx is None:
+        clip_idx = int(_jr.randint(clip_rng, (), 0, int(n_clips)))
+    rng1 = _jr.split(rng, 3)[1]
+    s = float(noise_scale)
+    return int(clip_idx), _jr.uniform(rng1, (int(nq),), -s, s), _jr.uniform(rng1, (int(nv),), -s, s)
+
+
+# ---------------------------------------------------------------------------------------------------------------- inference fn
+class RolloutPolicy:
+    """The deterministic inference function of a checkpoint (checkpointing.load_inference_fn): the policy module with fp32 weights on the
+    device and the normaliser's mean / std.  create_rollout_generator runs it on the HIP kernels; calling it acts on a batch of observations."""
+
+    def __init__(self, policy, mean: torch.Tensor | None, std: torch.Tensor | None, model: str, get_activation: bool = True,
+                 trained_gemm_inputs: str = "f32"):
+        self.policy, self.mean, self.std, self.model = policy, mean, std, model
+        self.get_activation, self.trained_gemm_inputs = bool(get_activation), trained_gemm_inputs
+        self.device = policy.fc2.weight.device
+        self.action_size = int(policy.action_size)
+
+    @torch.no_grad()
+    def __call__(self, obs: torch.Tensor, key=None, hidden_state=None):
+        """obs [n, W] (raw) -> (ctrl [n, nu], {"activations": ...}) (+ the new (h, c) [n, L, H] for the LSTM policy, from `hidden_state` or zeros)."""
+        obs = obs.to(device=self.device, dtype=torch.float32)
+        n = obs.shape[0]
+        step = _PolicyStep(self, n, obs.t().contiguous(), record=False)
+        if self.model == "lstm" and hidden_state is not None:
+            step.h.copy_(hidden_state[0]); step.c.copy_(hidden_state[1])
+        step.launch()
+        torch.cuda.current_stream(self.device).synchronize()
+        ctrl = step.ctrl.clone()
+        extras = {"activations": {k: v.clone() for k, v in step.activation_views().items()}} if self.get_activation else {}
+        if self.model == "lstm":
+            return ctrl, extras, (step.h.clone(), step.c.clone())
+        return ctrl, extras
+
+
+class _PolicyStep:
+    """Preallocated buffers and the launch sequence of one deterministic policy step for `n` envs reading the env's raw observation
+    buffer obs_soa [W][n]."""
+
+    def __init__(self, rp: RolloutPolicy, n: int, obs_soa: torch.Tensor, record: bool = True):
+        pol, dev = rp.policy, rp.device
+        self.rp, self.n, self.obs_soa = rp, int(n), obs_soa
+        self.L = _hip.lib()
+        f32 = dict(dtype=torch.float32, device=dev)
+        W = obs_soa.shape[0]
+        ref, Z, A = pol.reference_obs_size, pol.latents, pol.action_size
+        if W % 4:
+            raise ValueError(f"roll-out: the observation width {W} must be a multiple of 4 (row-major staging with 16-byte aligned rows)")
+        self.W, self.ref, self.Z, self.A = W, ref, Z, A
+        self.stage = torch.zeros((n, W), **f32)
+        # normaliser: mean / std of the whole observation (tmjx_latent_concat_det), mean / 1 / std of the reference part padded with zeros
+        # to the first layer's padded K (tmjx_linear_nolds_norm; the pad columns of the weight are zero)
+        Kp = _ceil4(ref)
+        self.mean, self.std = (rp.mean.contiguous(), rp.std.contiguous()) if rp.mean is not None else (None, None)
+        self.fold_mean, self.fold_inv = torch.zeros(Kp, **f32), torch.zeros(Kp, **f32)
+        if self.mean is not None:
+            self.fold_mean[:ref].copy_(self.mean[:ref])
+            torch.reciprocal(self.std[:ref], out=self.fold_inv[:ref])
+        else:
+            self.fold_inv[:ref].fill_(1.0)
+        self._padded = {}
+        self.calls = []                     # (entry point, args) of the step, in launch order
+        self.acts = {"encoder": {}}         # activation name -> (buffer, column offset, width, leading dimension)
+        h, first = None, True
+        for i, blk in enumerate(pol.encoder):
+            if first:
+                y = self._block(self.stage, W, blk, norm=True)
+            else:
+                y = self._block(h, h.shape[1], blk)
+            self.acts["encoder"][f"layer_{i}"] = (y, 0, y.shape[1], y.shape[1])
+            h, first = y, False
+        self.fc2 = self._linear(h, h.shape[1], pol.fc2, bias=True)
+        self.acts["encoder"]["mean"] = (self.fc2, 0, Z, 2 * Z)
+        self.acts["encoder"]["logvar"] = (self.fc2, Z, Z, 2 * Z)
+        prop = W - ref
+        self.x = torch.zeros((n, _ceil4(Z + prop)), **f32)
+        self.traj = torch.zeros((n, Kp), **f32)
+        self.calls.append(("tmjx_latent_concat_det", (_p(self.fc2), 2 * Z, _p(self.stage), W, 1, _p(self.mean), _p(self.std), _p(self.x), self.x.shape[1],
+                                                      _p(self.traj), self.traj.shape[1], n, Z, W, ref)))
+        if rp.model == "lstm":
+            Lk, H = pol.hidden_layer_num, pol.hidden_state_size
+            self.h, self.c = torch.zeros((n, Lk, H), **f32), torch.zeros((n, Lk, H), **f32)
+            self.xg = torch.empty((n, 4 * H), **f32)
+            a, lda = self.x, self.x.shape[1]
+            for k in range(Lk):
+                wi = self._pad(pol.w_ih[k])
+                self.calls.append(("tmjx_linear_nolds", (_p(a), lda, 1, _p(wi), None, _p(self.xg), n, 4 * H, wi.shape[1])))
+                hk, ck = self.h[:, k], self.c[:, k]
+                wh = pol.w_hh[k].detach().contiguous()
+                self._keep(wh)
+                args = _hip.LstmFwd(_p(self.xg), 4 * H, _p(wh), H, _p(pol.b_hh[k]), _p(hk), _p(ck), Lk * H, None, 0, _p(hk), _p(ck), Lk * H, None, None, 1, n, H)
+                self._keep(args)
+                self.calls.append(("tmjx_lstm_seq_fwd", (C.byref(args),)))
+                a, lda = hk, Lk * H
+            self.logits = self._linear_raw(a, lda, pol.projection, bias=True)
+            self.acts["decoder"] = {"lstm_projection": (self.logits, 0, 2 * A, 2 * A)}
+        else:
+            h = self.x
+            self.acts["decoder"] = {}
+            for i, blk in enumerate(pol.decoder):
+                h = self._block(h, h.shape[1], blk)
+                self.acts["decoder"][f"layer_{i}"] = (h, 0, h.shape[1], h.shape[1])
+            self.logits = self._linear(h, h.shape[1], pol.head, bias=True)
+            self.acts["egocentric_obs"] = (self.x, Z, prop, self.x.shape[1])
+            self.acts["traj_obs"] = (self.traj, 0, ref, self.traj.shape[1])
+        self.acts["intention"] = (self.x, 0, Z, self.x.shape[1])
+        self.ctrl = torch.empty((n, A), **f32)
+        self.action_t = torch.empty((A, n), **f32)
+        self.calls.append(("tmjx_action_mode", (_p(self.logits), self.logits.shape[1], _p(self.ctrl), _p(self.action_t), n, A)))
+        # the staging copy of the observation: one SoA stream into a [n][1][W] record
+        st = _hip.RecordStream(_p(obs_soa), _p(self.stage), _hip.RECORD_SOA, n, W, W, 1, 0, 0)
+        self.stage_table = _upload_table([st], n, 1, dev)
+        self.stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+    def _keep(self, obj):
+        self.__dict__.setdefault("_keepalive", []).append(obj)
+
+    def _pad(self, w: torch.Tensor) -> torch.Tensor:
+        """A [N][ceil4(K)] fp32 copy of a weight (zero pad columns): the float4 / matrix-core variant of tmjx_linear_nolds for every layer."""
+        key = id(w)
+        if key not in self._padded:
+            N, K = w.shape
+            buf = torch.zeros((N, _ceil4(K)), dtype=torch.float32, device=w.device)
+            buf[:, :K].copy_(w.detach())
+            self._padded[key] = buf
+        return self._padded[key]
+
+    def _linear_raw(self, a, lda, lin, bias):
+        w = self._pad(lin.weight)
+        out = torch.empty((self.n, lin.out_features), dtype=torch.float32, device=w.device)
+        self._keep(out)
+        self.calls.append(("tmjx_linear_nolds", (_p(a), lda, 1, _p(w), _p(lin.bias) if bias else None, _p(out), self.n, lin.out_features, w.shape[1])))
+        return out
+
+    def _linear(self, a, lda, lin, bias):
+        return self._linear_raw(a, lda, lin, bias)
+
+    def _block(self, a, lda, blk, norm=False):
+        n, N = self.n, blk.dense.out_features
+        w = self._pad(blk.dense.weight)
+        z = torch.empty((n, N), dtype=torch.float32, device=w.device)
+        if norm:
+            self.calls.append(("tmjx_linear_nolds_norm", (_p(a), lda, 1, _p(w), None, _p(z), n, N, w.shape[1], _p(self.fold_mean), _p(self.fold_inv))))
+        else:
+            self.calls.append(("tmjx_linear_nolds", (_p(a), lda, 1, _p(w), None, _p(z), n, N, w.shape[1])))
+        y = torch.empty_like(z)
+        stats = torch.empty((n, 2), dtype=torch.float32, device=w.device)
+        self._keep(z); self._keep(y); self._keep(stats)          # the launch list holds raw pointers: every buffer it names lives as long as the step
+        self.calls.append(("tmjx_silu_ln_fwd", (_p(z), _p(blk.dense.bias), _p(blk.norm.weight), _p(blk.norm.bias), _p(y), _p(stats), n, N,
+                                                float(blk.norm.eps))))
+        return y
+
+    def launch(self) -> None:
+        """The policy step's launches on the current stream (ctypes calls only: no torch operation)."""
+        L, s = self.L, self.stream
+        _hip.check(L.tmjx_record_step(self.stage_table.data_ptr(), 1, self.n, 0, 1, s), "tmjx_record_step")
+        for name, args in self.calls:
+            _hip.check(getattr(L, name)(*args, s), name)
+
+    def activation_views(self) -> dict:
+        out = {}
+        for k, v in self.acts.items():
+            if isinstance(v, dict):
+                for k2, (buf, c0, w, _) in v.items():
+                    out[f"{k}/{k2}"] = buf[:, c0:c0 + w]
+            else:
+                buf, c0, w, _ = v
+                out[k] = buf[:, c0:c0 + w]
+        if self.rp.model == "lstm":
+            out["hidden_state/h"], out["hidden_state/c"] = self.h, self.c
+        return out
+
+
+def _upload_table(streams: Sequence, n: int, T: int, dev) -> torch.Tensor:
+    """Validate a recorder stream table on the host (tmjx_record_check) and copy it to the device once (16-byte aligned)."""
+    k = len(streams)
+    tab = (_hip.RecordStream * k)(*streams)
+    _hip.check(_hip.lib().tmjx_record_check(tab, k, int(n), int(T)), "tmjx_record_check")
+    raw = np.frombuffer(bytes(tab), dtype=np.uint8)
+    return torch.from_numpy(raw.copy()).to(dev)
+
+
+# ---------------------------------------------------------------------------------------------------------------- generator
+def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, model: str = "mlp", log_activations: bool = False,
+                             log_metrics: bool = False, log_sensor_data: bool = False, clips_per_batch: int = CLIPS_PER_BATCH):
+    """rollout.py:73-269.  Returns generate_rollout(clip_idx=None, seed=42): one clip (int / None) -> dict of arrays; a sequence of clips -> the
+    same dict with a leading [N] axis (batches larger than `clips_per_batch` run in chunks)."""
+    if log_sensor_data:
+        raise NotImplementedError("log_sensor_data: cfrc_ext and sensordata are not computed by the physics kernel (it carries only what the "
+                                  "tracking reward and observation need), so joint forces and sensor readings cannot be logged")
+    if not isinstance(inference_fn, RolloutPolicy):
+        raise TypeError("create_rollout_generator: inference_fn must be the deterministic inference function made by "
+                        "track_mjx_amd.agent.checkpoint.load_inference_fn (the roll-out runs it on the HIP kernels); got "
+                        f"{type(inference_fn).__name__}")
+    if model not in ("mlp", "lstm"):
+        raise ValueError("model must be 'mlp' or 'lstm'")
+    if model != inference_fn.model:
+        raise ValueError(f"model={model!r} but the inference function holds the {inference_fn.model} policy")
+    metrics = tuple((cfg.get("logging_config") or {}).get("rollout_metrics", ROLLOUT_METRICS))
+    bad = [m for m in metrics if m not in METRIC_NAMES]
+    if bad:
+        raise ValueError(f"logging_config.rollout_metrics: unknown metrics {bad} (known: {METRIC_NAMES})")
+    if log_metrics and len(metrics) > _hip.RECORD_MAX_IDX:
+        raise ValueError(f"at most {_hip.RECORD_MAX_IDX} rollout metrics")
+    env0 = environment
+    spf = float(env0._steps_for_cur_frame)
+    T = int(int(cfg["reference_config"]["clip_length"]) * spf)
+    if T < 2:
+        raise ValueError("a roll-out needs clip_length * steps_for_cur_frame >= 2")
+    envs: dict = {}
+
+    def env_of(n):
+        if n == env0.num_envs:
+            return env0
+        if n not in envs:
+            envs.clear()                    # (one cached sibling: the buffers of a batch size are not kept around)
+            envs[n] = _sibling_env(env0, n)
+        return envs[n]
+
+    def run_batch(clips: list, seed: int) -> dict:
+        n = len(clips)
+        env = env_of(n)
+        dev, Lay = env.device, env.layout
+        nq, nv = int(Lay.nq), int(Lay.nv)
+        qn, vn = np.empty((nq, n), np.float32), np.empty((nv, n), np.float32)
+        for j, c in enumerate(clips):
+            _, qn[:, j], vn[:, j] = reset_inputs(seed, env._n_clips, nq, nv, env._reset_noise_scale, c)
+        with torch.cuda.device(dev):
+            env.reset(None, torch.tensor(clips, dtype=torch.int32), start_frame=torch.zeros(n, dtype=torch.int32),
+                      qpos_noise=torch.from_numpy(qn), qvel_noise=torch.from_numpy(vn))
+            step = _PolicyStep(inference_fn, n, env.obs_buf)
+            f32 = dict(dtype=torch.float32, device=dev)
+            rec: dict = {}
+            state_streams, step_streams = [], []
+
+            def add(name, buf_ptr, layout, ld, w, extent, rows, t0, idx=()):
+                dst = torch.empty((n, rows, w), **f32)
+                rec[name] = dst
+                s = _hip.RecordStream(buf_ptr, _p(dst), layout, ld, w, extent, rows, t0, len(idx))
+                for i, v in enumerate(idx):
+                    s.idx[i] = v
+                return s
+
+            sb = env.state_buf
+            state = [("qposes_rollout", sb.data_ptr() + 4 * Lay.qpos * n, _hip.RECORD_SOA, n, nq, nq, ()),
+                     ("state_rewards", _p(env.reward_buf), _hip.RECORD_SOA, n, 1, 1, ())]
+            if log_metrics:
+                state.append(("rollout_metrics", _p(env.metrics_buf), _hip.RECORD_SOA, n, len(metrics), len(METRIC_NAMES),
+                              tuple(METRIC_NAMES.index(m) for m in metrics)))
+            for name, ptr, lay, ld, w, ext, idx in state:
+                state_streams.append(add(name, ptr, lay, ld, w, ext, T, 1, idx))
+            init_streams = []
+            for (name, ptr, lay, ld, w, ext, idx), s in zip(state, state_streams):
+                s0 = _hip.RecordStream.from_buffer_copy(s)
+                s0.t0 = 0
+                init_streams.append(s0)
+            step_streams.append(add("ctrl", _p(step.ctrl), _hip.RECORD_ROWMAJOR, inference_fn.action_size, inference_fn.action_size,
+                                    inference_fn.action_size, T - 1, 0))
+            if log_activations:
+                for name, v in step.acts.items():
+                    items = v.items() if isinstance(v, dict) else [(None, v)]
+                    for k2, (buf, c0, w, ld) in items:
+                        key = name if k2 is None else f"{name}/{k2}"
+                        step_streams.append(add("act:" + key, buf.data_ptr() + 4 * c0, _hip.RECORD_ROWMAJOR, ld, w, w, T - 1, 0))
+                if inference_fn.model == "lstm":
+                    LH = step.h.shape[1] * step.h.shape[2]
+                    step_streams.append(add("act:hidden_state/h", _p(step.h), _hip.RECORD_ROWMAJOR, LH, LH, LH, T - 1, 0))
+                    step_streams.append(add("act:hidden_state/c", _p(step.c), _hip.RECORD_ROWMAJOR, LH, LH, LH, T - 1, 0))
+            init_tab = _upload_table(init_streams, n, 1, dev)
+            state_tab = _upload_table(state_streams, n, T - 1, dev)
+            step_tab = _upload_table(step_streams, n, T - 1, dev)
+            L, s = _hip.lib(), step.stream
+            hdl = env._handle
+            env_args = [_p(env.state_buf), _p(env.istate_buf), _p(step.action_t), _p(env.obs_buf), _p(env.reward_buf), _p(env.done_buf),
+                        _p(env.trunc_buf), _p(env.metrics_buf), _p(env.workspace), n]
+            ks, kp = len(state_streams), len(step_streams)
+            _hip.check(L.tmjx_record_step(init_tab.data_ptr(), ks, n, 0, 1, s), "tmjx_record_step")
+            _step_loop(step, L, s, hdl, env_args, state_tab.data_ptr(), ks, step_tab.data_ptr(), kp, n, T)
+            host = {k: v.cpu().numpy() for k, v in rec.items()}          # one device-to-host copy per record, once per batch
+        out = {"qposes_rollout": host["qposes_rollout"], "ctrl": host["ctrl"], "state_rewards": host["state_rewards"][:, :, 0]}
+        ref = env._reference_clips
+        rows = [np.repeat(np.hstack([np.asarray(ref.position[c], np.float32), np.asarray(ref.quaternion[c], np.float32),
+                                     np.asarray(ref.joints[c], np.float32)]), int(spf), axis=0) for c in clips]
+        out["qposes_ref"] = np.stack(rows)
+        if log_metrics:
+            m = host["rollout_metrics"]
+            out["rollout_metrics"] = {f"{name}s": np.ascontiguousarray(m[:, :, j]) for j, name in enumerate(metrics)}
+        if log_activations:
+            acts: dict = {}
+            for k, v in host.items():
+                if not k.startswith("act:"):
+                    continue
+                parts = k[4:].split("/")
+                node = acts
+                for p_ in parts[:-1]:
+                    node = node.setdefault(p_, {})
+                node[parts[-1]] = v
+            if "hidden_state" in acts:
+                Lk, H = step.h.shape[1], step.h.shape[2]
+                hs = acts.pop("hidden_state")
+                acts["hidden_state"] = (hs["h"].reshape(n, T - 1, Lk, H), hs["c"].reshape(n, T - 1, Lk, H))
+            out["activations"] = acts
+        return out
+
+    def generate_rollout(clip_idx: int | Sequence[int] | None = None, seed: int = 42) -> dict:
+        batched = clip_idx is not None and not isinstance(clip_idx, (int, np.integer))
+        if batched:
+            clips = [int(c) for c in clip_idx]
+        else:
+            clips = [reset_inputs(seed, env0._n_clips, int(env0.layout.nq), int(env0.layout.nv), env0._reset_noise_scale,
+                                  None if clip_idx is None else int(clip_idx))[0]]
+        if not clips:
+            raise ValueError("generate_rollout: no clips")
+        bad = [c for c in clips if not 0 <= c < env0._n_clips]
+        if bad:
+            raise IndexError(f"clip indices {bad[:5]} outside the table's {env0._n_clips} clips")
+        parts = [run_batch(clips[i:i + clips_per_batch], seed) for i in range(0, len(clips), int(clips_per_batch))]
+        out = _concat(parts) if len(parts) > 1 else parts[0]
+        return out if batched else _index0(out)
+
+    generate_rollout.T = T
+    generate_rollout.metrics = metrics
+    return generate_rollout
+
+
+def _step_loop(step: _PolicyStep, L, s, hdl, env_args, state_tab: int, ks: int, step_tab: int, kp: int, n: int, T: int) -> None:
+    """The T - 1 control steps: policy launches, tmjx_action_mode (inside step.launch), tmjx_step, tmjx_record_step x 2."""
+    for t in range(T - 1):
+        step.launch()
+        _hip.check(L.tmjx_step(hdl, *env_args, s), "tmjx_step")
+        _hip.check(L.tmjx_record_step(step_tab, kp, n, t, T - 1, s), "tmjx_record_step")
+        _hip.check(L.tmjx_record_step(state_tab, ks, n, t, T - 1, s), "tmjx_record_step")
+
+
+def _concat(parts: list):
+    a = parts[0]
+    if isinstance(a, dict):
+        return {k: _concat([p[k] for p in parts]) for k in a}
+    if isinstance(a, tuple):
+        return tuple(_concat([p[i] for p in parts]) for i in range(len(a)))
+    return np.concatenate(parts, axis=0)
+
+
+def _index0(tree):
+    if isinstance(tree, dict):
+        return {k: _index0(v) for k, v in tree.items()}
+    if isinstance(tree, tuple):
+        return tuple(_index0(v) for v in tree)
+    return tree[0]
+
+
+# ---------------------------------------------------------------------------------------------------------------- CLI
+def _parse_clips(spec: str, n_clips: int) -> list:
+    spec = str(spec).strip()
+    if spec in ("", "all"):
+        return list(range(n_clips))
+    if ":" in spec:
+        a, _, b = spec.partition(":")
+        return list(range(int(a or 0), int(b) if b else n_clips))
+    return [int(c) for c in spec.split(",") if c.strip()]
+
+
+def main(argv=None) -> int:
+    from .. import config as _config
+    from ..agent import checkpoint as ckpt
+    from .utils import save_to_h5py
+    argv = list(sys.argv[1:] if argv is None else argv)
+    opts = dict(a.split("=", 1) for a in argv if "=" in a and a.split("=", 1)[0] in ("checkpoint", "clips", "seed", "out", "log_activations",
+                                                                                    "log_metrics", "step"))
+    rest = [a for a in argv if not ("=" in a and a.split("=", 1)[0] in opts)]
+    if "checkpoint" not in opts:
+        print("usage: python -m track_mjx_amd.analysis.rollout checkpoint=<run dir | step dir> [data_path=...] [clips=all|a:b|i,j,k] [seed=42] "
+              "[out=<dir>] [log_activations=true] [log_metrics=true] [key=value config overrides ...]", file=sys.stderr)
+        return 2
+    yes = lambda v: str(v).lower() in ("1", "true", "yes")     # noqa: E731
+    path = opts["checkpoint"]
+    step_no = int(opts["step"]) if "step" in opts else None
+    cfg = ckpt.load_config_from_checkpoint(path, step_no)
+    cfg = _config._deep_update(_config.default_config(), cfg or {})
+    for ov in rest:                                   # the same key=value parsing as train
+        key, _, val = ov.partition("=")
+        node = cfg
+        for part in key.split(".")[:-1]:
+            node = node.setdefault(part, {})
+        import yaml
+        node[key.split(".")[-1]] = yaml.safe_load(val)
+    step_dir = ckpt.resolve_step_dir(path, step_no)
+    policy = ckpt.load_policy(step_dir, cfg)
+    fn = ckpt.load_inference_fn(cfg, policy, deterministic=True, get_activation=True)
+    env = create_environment(cfg, 1, "cuda")
+    seed = int(opts.get("seed", 42))
+    log_act, log_met = yes(opts.get("log_activations", "true")), yes(opts.get("log_metrics", "true"))
+    gen = create_rollout_generator(cfg, env, fn, model=fn.model, log_activations=log_act, log_metrics=log_met)
+    clips = _parse_clips(opts.get("clips", "all"), env._n_clips)
+    out_dir = opts.get("out", os.path.join(step_dir, "rollouts"))
+    os.makedirs(out_dir, exist_ok=True)
+    meta_common = {"seed": np.int64(seed), "checkpoint_step": np.int64(int(os.path.basename(os.path.normpath(step_dir)))
+                                                                        if os.path.basename(os.path.normpath(step_dir)).isdigit() else -1),
+                   "checkpoint": str(step_dir), "model": fn.model, "trained_gemm_inputs": fn.trained_gemm_inputs,
+                   "rollout_gemm_inputs": "f32"}
+    for i in range(0, len(clips), CLIPS_PER_BATCH):
+        chunk = clips[i:i + CLIPS_PER_BATCH]
+        res = gen(chunk, seed=seed)
+        for j, c in enumerate(chunk):
+            one = _index_j(res, j)
+            one["meta"] = dict(meta_common, clip_idx=np.int64(c))
+            save_to_h5py(os.path.join(out_dir, f"clip_{c}.h5"), one)
+    print(f"[rollout] wrote {len(clips)} clip files to {out_dir} (T={gen.T}, seed={seed}, model={fn.model})", flush=True)
+    return 0
+
+
+def _index_j(tree, j):
+    if isinstance(tree, dict):
+        return {k: _index_j(v, j) for k, v in tree.items()}
+    if isinstance(tree, tuple):
+        return tuple(_index_j(v, j) for v in tree)
+    return tree[j]
+
+
+if __name__ == "__main__":
+    # (run as a script this file is `__main__`: use the package module, whose RolloutPolicy class load_inference_fn returns)
+    from track_mjx_amd.analysis.rollout import main as _main
+    sys.exit(_main())

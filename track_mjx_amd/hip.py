@@ -14,7 +14,8 @@ from pathlib import Path
 _PKG = Path(__file__).resolve().parent
 SO_PATH = Path(os.environ.get("TMJX_SO", str(_PKG / "libtmjx_hip.so")))  # TMJX_SO: alternative build (profiling)
 CSRC = _PKG / "csrc"
-SOURCES = (CSRC / "tmjx_hip.hip", CSRC / "tmjx_bf16.hip", CSRC / "tmjx_wave.hip", CSRC / "tmjx_chain.hip", CSRC / "tmjx_lstm.hip")
+SOURCES = (CSRC / "tmjx_hip.hip", CSRC / "tmjx_bf16.hip", CSRC / "tmjx_wave.hip", CSRC / "tmjx_chain.hip", CSRC / "tmjx_lstm.hip",
+           CSRC / "tmjx_rollout.hip")
 # per-source compiler flags: the physics kernel's unit is built without machine LICM (csrc/tmjx_wave.hip says why)
 SOURCE_FLAGS = {"tmjx_wave.hip": ("-mllvm", "-disable-machine-licm")}
 
@@ -39,6 +40,7 @@ EXPORTS = ("tmjx_model_create", "tmjx_model_destroy", "tmjx_layout", "tmjx_clips
            "tmjx_bgemm_ln_fwd", "tmjx_bgemm_ln_bwd", "tmjx_bgemm_silu_fwd", "tmjx_bgemm_silu_bwd", "tmjx_bf_silu_bwd", "tmjx_bf_silu_bwd_rank1",
            "tmjx_chain_rows", "tmjx_chain_fwd_ok", "tmjx_chain_fwd", "tmjx_chain_bwd_ok", "tmjx_chain_bwd",
            "tmjx_lstm_hidden_ok", "tmjx_lstm_seq_fwd", "tmjx_lstm_seq_bwd",
+           "tmjx_record_check", "tmjx_record_step", "tmjx_latent_concat_det", "tmjx_action_mode",
            "tmjx_debug_rows", "tmjx_last_error", "tmjx_version")
 
 
@@ -114,6 +116,15 @@ class LstmBwd(C.Structure):
     _fields_ = [("dh", C.c_void_p), ("ldd", C.c_int32), ("Wh", C.c_void_p), ("ldw", C.c_int32), ("gates", C.c_void_p), ("c", C.c_void_p), ("ldo", C.c_int32),
                 ("c0", C.c_void_p), ("ld0", C.c_int32), ("reset", C.c_void_p), ("ldr", C.c_int32), ("dgates", C.c_void_p), ("dh0", C.c_void_p),
                 ("dc0", C.c_void_p), ("T", C.c_int32), ("rows", C.c_int32), ("H", C.c_int32)]
+
+
+RECORD_SOA, RECORD_ROWMAJOR, RECORD_MAX_STREAMS, RECORD_MAX_IDX = 0, 1, 64, 32
+
+
+class RecordStream(C.Structure):
+    """tmjx_record_stream_t (include/tmjx.h)."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p)] + [(k, C.c_int32) for k in ("layout", "ld", "w", "src_extent", "T", "t0", "n_idx")] + \
+               [("idx", C.c_int32 * RECORD_MAX_IDX), ("pad_", C.c_int32)]
 
 
 class PpoCfg(C.Structure):
@@ -317,6 +328,10 @@ def load(path: Path):
     sig.setdefault("tmjx_lstm_hidden_ok", [None, None])[0] = [C.c_int]
     sig.setdefault("tmjx_lstm_seq_fwd", [None, None])[0] = [C.POINTER(LstmFwd), vp]
     sig.setdefault("tmjx_lstm_seq_bwd", [None, None])[0] = [C.POINTER(LstmBwd), vp]
+    sig.setdefault("tmjx_record_check", [None, None])[0] = [C.POINTER(RecordStream), C.c_int, C.c_int, C.c_int]
+    sig.setdefault("tmjx_record_step", [None, None])[0] = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    sig.setdefault("tmjx_latent_concat_det", [None, None])[0] = [fp, C.c_int, fp, C.c_int64, C.c_int64, fp, fp, fp, C.c_int, fp, C.c_int] + [C.c_int] * 4 + [vp]
+    sig.setdefault("tmjx_action_mode", [None, None])[0] = [fp, C.c_int, fp, fp, C.c_int, C.c_int, vp]
     sig.setdefault("tmjx_debug_rows", [None, None])[0] = [vp, C.c_char_p, ip, ip]
     sig.setdefault("tmjx_last_error", [None, None])[1] = C.c_char_p
     sig.setdefault("tmjx_version", [None, None])[1] = C.c_char_p
