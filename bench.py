@@ -12,9 +12,12 @@ Weak scaling: 4096 envs and 1024 minibatch rows per GPU; global batch_size = 102
 (5 120-row GEMMs), ONE unroll + 64 minibatch steps per training step, gradient all-reduce after each; on one GPU it runs one rank's share with the
 collectives issued on a one-rank RCCL group; `--gpus N --config cfg3` uses batch_size = 256*N.
 
-Usage: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+Usage: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
 K timed training steps (>= 1) after W untimed ones.  `--dump-outputs DIR`: what the last timed step computed as DIR/<name>.npy (dump_outputs); the
 inputs are seeded, so two builds run with the same arguments can be compared array for array.
+A plain run sets up, warms up, times the K steps, dumps (if asked) and prints the line: nothing else.  `--full` adds what takes runs of its own
+after the timed region: the roll-out-only leg (and K2 alone on an idle GPU), the CPU baselines and the MJX-on-CPU probe, and at N = 1 the child
+rocprofv3 counter passes (HBM traffic, K2 vector pipe, MFMA busy) and short child runs of cfg3 / cfg4 / cfg5 under config.other_configs.
 N > 1: one rank per GPU over RCCL.  Either the caller starts the ranks (`python -m torch.distributed.run --nproc-per-node N bench.py
 --gpus N ...`: RANK / WORLD_SIZE are then in the environment) or bench.py does it itself: `python bench.py --gpus N` starts that
 command as a CHILD process before anything touches the GPU and relays rank 0's JSON line (track_mjx_amd/launch.py; the reference
@@ -114,13 +117,13 @@ _CHILDREN: list = []        # child benches in flight (other_configs): the signa
 
 
 def other_configs(timeout_s: float = 150.0) -> dict:
-    """Short runs of `bench.py --config cfg3 / cfg4 / cfg5` as child processes (5 timed steps each); the fields of their lines that matter.
+    """Short plain runs of `bench.py --config cfg3 / cfg4 / cfg5` as child processes (5 timed steps each; --full): the fields of their lines that matter.
     Every child runs in a process group of its own so that a signal that ends this process can end it too (killpg in main's handler)."""
     import signal
     import subprocess
     res = {}
     for cfg in ("cfg3", "cfg4", "cfg5"):
-        cmd = [sys.executable, str(ROOT / "bench.py"), "--config", cfg, "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--no-rollout-only"]
+        cmd = [sys.executable, str(ROOT / "bench.py"), "--config", cfg, "--steps", "5", "--warmup", "1"]      # plain runs: no extras of their own
         try:
             p = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, start_new_session=True)
             _CHILDREN.append(p)
@@ -351,13 +354,15 @@ def main(argv=None, runner=None):
     ap.add_argument("--envs-per-gpu", type=int, default=None)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--pipeline", type=int, default=0, help="env groups per GPU whose roll-outs are pipelined on separate HIP streams (0 = ppo.default_groups: 3; 1 = off; sizes: ppo.group_sizes)")
+    ap.add_argument("--full", action="store_true", help="after the headline measurement, also run the extras: roll-out-only leg, CPU baselines, "
+                    "child rocprofv3 counter passes and cfg3 / cfg4 / cfg5 child runs (the --no-* options below drop single ones)")
     ap.add_argument("--no-rollout-only", action="store_true", help="skip the extra roll-out-only measurement (tools/profile_gpu.sh: keeps the "
                     "rocprofv3 kernel averages those of the timed training steps)")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="cfg2",
                     help="BASELINE.json configs[1] (default, the headline line) / configs[2] (cfg3: one rank's share per GPU) / configs[3] / configs[4]; the others are extra measurements")
     ap.add_argument("--dry-run-ranks", action="store_true", help="launcher check on CPU: gloo ranks, no GPU work (tests)")
     ap.add_argument("--no-live-pmc", action="store_true", help="do not collect the HBM-traffic counters with two child rocprofv3 passes (then the stamped profiles/pmc_traffic.json is what the line carries)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short cfg4 / cfg5 measurements the default N = 1 line carries under config.other_configs")
+    ap.add_argument("--no-other-configs", action="store_true", help="skip the short cfg3 / cfg4 / cfg5 measurements the --full N = 1 line carries under config.other_configs")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (loss metrics, parameters, "
                     "normaliser, a seeded sample of the roll-out buffers) as DIR/<name>.npy, float32, at most 64 MB (rank 0)")
     args = ap.parse_args(argv)
@@ -487,9 +492,9 @@ def main(argv=None, runner=None):
         e._physics_events = None
     # d1 of the measurement contract also asks for the ROLL-OUT-ONLY rate (random actions, no policy, no learner): the same env
     # groups stepped on their own streams, outside the timed region of the training metric; and the physics kernel ALONE on an
-    # otherwise idle GPU (one group's launches back to back): the isolated per-launch duration next to the shared-GPU one above
+    # otherwise idle GPU (one group's launches back to back): the isolated per-launch duration next to the shared-GPU one above (--full only)
     rollout_only = rollout_err = isolated_ms = None
-    if not args.no_rollout_only:
+    if args.full and not args.no_rollout_only:
         try:
             gen = torch.Generator(device=device).manual_seed(5)
             acts = [torch.randn((38, e.num_envs), generator=gen, device=device).clamp(-1, 1) * 0.3 for e in envs]
@@ -552,7 +557,7 @@ def main(argv=None, runner=None):
             # (bf16 mode goes beyond SURVEY a16's "bf16 only for GEMM inputs": the pre-activations the backward epilogues re-read are saved as bf16 too —
             # BASELINE configs[4] says "bf16 MLP on MFMA"; the fp32-z form is a build switch of the same sources, -DTMJX_BF16_Z_F32: 4.01 against 3.79 ms per minibatch step, profiles/r05_cfg5_z_variants.txt)
             "dtype": "f32" if bc["matmul_dtype"] is None else f"f32 (physics, reward, loss head, optimiser, master weights) + {bc['matmul_dtype']} MLP: GEMM inputs, hidden activations and saved pre-activations in {bc['matmul_dtype']}, f32 accumulate",
-            "data": "synthetic", "so_build_id": so_build_id(), "mjx_cpu": mjx_cpu_probe(),
+            "data": "synthetic", "so_build_id": so_build_id(),
             "config": {"workload": f"rodent tracking PPO training step ({args.config}): {n_local} envs/GPU, {learner.env_steps_per_training_step // (n_local * learner.T * world)}x{learner.T}-step unrolls (10 physics substeps each) + {sgd_steps} minibatch updates, {bc['label']}",
                        "n_clips": bc["n_clips"], "mlp_gemm_inputs": bc["matmul_dtype"] or "f32",
                        "envs_per_gpu": n_local, "global_batch": learner.local_batch * world, "unroll_length": learner.T,
@@ -610,17 +615,17 @@ def main(argv=None, runner=None):
         }
         if dumped is not None:
             out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": len(dumped)}
-        # the finished measurement is on disk before any extra runs: a hard kill (SIGKILL, a driver time-out) during the minute of extras below cannot lose it
-        # (stdout still carries exactly ONE line, the enriched one, printed by emit())
-        for side in (ROOT / "gpurun_out", Path("/tmp")):
+        if args.full:
+            out["mjx_cpu"] = mjx_cpu_probe()
+            # the finished measurement is on disk (<tmp>/bench_headline.json) before any extra runs: a hard kill (SIGKILL, a driver time-out) during the
+            # minute of extras below cannot lose it (stdout still carries exactly ONE line, the enriched one, printed by emit())
+            import tempfile
             try:
-                side.mkdir(exist_ok=True)
-                (side / "bench_headline.json").write_text(json.dumps(out) + "\n")
-                break
+                (Path(tempfile.gettempdir()) / "bench_headline.json").write_text(json.dumps(out) + "\n")
             except OSError:
-                continue
-        # the extras below (CPU baselines, child runs of cfg4 / cfg5) take a minute: if the caller's time-out ends this process during them
-        # (SIGTERM / SIGINT), the headline measured above is printed as it stands instead of being lost — still exactly one JSON line
+                pass
+        # the extras of --full below (counter passes, CPU baselines, child runs of cfg3 / cfg4 / cfg5) take a minute: if the caller's time-out ends this process
+        # during them (SIGTERM / SIGINT), the headline measured above is printed as it stands instead of being lost — still exactly one JSON line
         import signal
         printed = []
 
@@ -645,9 +650,9 @@ def main(argv=None, runner=None):
                 signal.pthread_sigmask(signal.SIG_SETMASK, old)
         for _s in (signal.SIGTERM, signal.SIGINT):
             signal.signal(_s, emit)
-        # the HBM-traffic counters collected by THIS run (two child rocprofv3 --pmc passes, ~40 s; only the default N = 1 line): the stamped
+        # the HBM-traffic counters collected by THIS run (two child rocprofv3 --pmc passes, ~40 s; only the --full N = 1 line): the stamped
         # profiles/pmc_traffic.json stays in the line if rocprofv3 is missing or a pass fails
-        if world == 1 and args.config == "cfg2" and not args.no_live_pmc and not args.no_cpu_baseline:
+        if args.full and world == 1 and args.config == "cfg2" and not args.no_live_pmc and not args.no_cpu_baseline:
             live = live_pmc_traffic()
             if live and live.get("sq"):      # the vector-pipe counters of K2 rode along with the FETCH_SIZE pass: they replace the stamped file's
                 out["roofline_valu"].update({"valu_pipe_busy": live["sq"]["valu_pipe_busy"], "lane_occupancy": live["sq"]["lane_occupancy"],
@@ -666,7 +671,7 @@ def main(argv=None, runner=None):
                           "traffic_source": "two child `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` passes of THIS run over tools/time_step.py (4096 envs in one launch; KB per dispatch, FETCH_SIZE doubled: the gfx950 correction), bytes per launch scaled to this launch's env count",
                           "traffic_kernels": {k: v["fetch_bytes_corrected"] + v["write_bytes"] for k, v in live["kernels"].items()}})
                 r["k2_only"].update({"traffic": k2t, "traffic_over_algorithmic": k2t / (K2_ALGO_BYTES_PER_ENV_STEP * per_launch)})
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 # same action regime as the roll-out-only leg (0.3 * N(0,1)); the full-scale regime of BASELINE config 1 beside it
                 # N_env = 4096 on every host core (the headline `value`) and N_env = 1 on one thread
@@ -676,9 +681,9 @@ def main(argv=None, runner=None):
                 out["cpu_baseline"]["mjx_cpu"] = out["mjx_cpu"]
             except Exception as e:  # the baseline is a report, never a reason to lose the measurement
                 out["cpu_baseline"] = {"value": None, "unit": "env-steps/s", "cores": os.cpu_count(), "kind": "port", "sample": f"failed: {e}"}
-        # BASELINE configs[2] (one rank's share) / configs[3] / configs[4] beside the headline line (driver-visible: the default run is the only one the driver makes): each as a
+        # BASELINE configs[2] (one rank's share) / configs[3] / configs[4] beside the headline line (--full): each as a plain run in a
         # CHILD process of this script after the timed region (own process: its failure or time-out cannot touch the headline), 5 timed steps
-        if world == 1 and args.config == "cfg2" and not args.no_other_configs and not args.no_cpu_baseline:
+        if args.full and world == 1 and args.config == "cfg2" and not args.no_other_configs and not args.no_cpu_baseline:
             out["config"]["other_configs"] = other_configs()
         emit()
     if use_dist:

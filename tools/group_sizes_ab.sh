@@ -3,7 +3,7 @@
 TAG=$1; shift
 mkdir -p gpurun_out
 for gs in "$@"; do
-  TMJX_GROUP_SIZES=$gs python bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-other-configs 2>/dev/null | python -c "
+  TMJX_GROUP_SIZES=$gs python bench.py --steps 4 --warmup 2 --full --no-cpu-baseline --no-other-configs 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); c=d['config']
 print('groups $gs: value %.0f  rollout_ms %.1f sgd_ms %.1f  rollout_only %.0f' % (d['value'], c['rollout_ms_per_step'], c['sgd_ms_per_step'], c['rollout_only_env_steps_per_s_per_gpu'] or 0))" >> gpurun_out/groups_$TAG.txt
