@@ -275,6 +275,15 @@ int tmjx_adam_clip(float *param, const float *grad, float *exp_avg, float *exp_a
 int tmjx_adam_norm_floats(void);
 int tmjx_adam_clip_norm(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, float *norm_scratch, float *norm_out, long long n, float lr,
                         float beta1, float beta2, float eps, float bias_correction1, float bias_correction2, float max_norm, void *stream);
+/* tmjx_adam_clip_norm with the parameter updates of the flat range [frozen_lo, frozen_hi) zeroed: the reference's freeze_decoder optimiser
+ * optax.chain(optax.chain(clip_by_global_norm, adam), freeze(mask)) (track_mjx/agent/mlp_ppo/ppo.py:594-617; the mask is True exactly for
+ * policy.params.decoder, agent/network_masks.py:6-19).  The global norm covers ALL n gradients and exp_avg / exp_avg_sq are updated
+ * everywhere, as there (clipping and Adam come before the freeze); only `param` inside the range is never written.  Outside the range every
+ * element is bit-identical to tmjx_adam_clip_norm.  0 <= frozen_lo <= frozen_hi <= n, both multiples of 4 (flat segments start on 16-byte
+ * boundaries); frozen_lo == frozen_hi freezes nothing.  No host synchronisation: capturable in a hipGraph. */
+int tmjx_adam_clip_norm_frozen(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, float *norm_scratch, float *norm_out, long long n,
+                               long long frozen_lo, long long frozen_hi, float lr, float beta1, float beta2, float eps, float bias_correction1,
+                               float bias_correction2, float max_norm, void *stream);
 
 /* Dense layers of the learner on the matrix cores, fp32 in / fp32 accumulate (flax nn.Dense of the intention network,
  * track_mjx/agent/mlp_ppo/intention_network.py:32-44,68-76, and brax's value MLP, ppo_networks.py:180-184; the gradients are those of
@@ -483,6 +492,12 @@ int tmjx_stats_scratch_floats(int W);
 int tmjx_stats_sums(const float *src, const float *mean, float *sums, float *scratch, long long rows, int W, void *stream);
 int tmjx_stats_apply(const float *sums, float n_added, float *count, float *mean, float *summed_variance, float *std, int W, float std_min,
                      float std_max, void *stream);
+/* tmjx_stats_apply for columns [0, pin_lo) only: columns [pin_lo, W) keep mean, summed_variance and std; count += n_added as usual.  The
+ * reference's freeze_decoder run pins the proprioceptive columns (the decoder's input) to the checkpoint's statistics and writes them back
+ * after every running_statistics.update (track_mjx/agent/mlp_ppo/ppo.py:357-377,586-593).  `sums` is the [2][W] output of tmjx_stats_sums
+ * (after the optional all-reduce), unchanged.  0 <= pin_lo <= W.  No host synchronisation: capturable in a hipGraph. */
+int tmjx_stats_apply_pinned(const float *sums, float n_added, float *count, float *mean, float *summed_variance, float *std, int W, int pin_lo,
+                            float std_min, float std_max, void *stream);
 
 /* Debug/test access: copy a named per-env workspace/intermediate array of the last tmjx_forward /
  * tmjx_physics call into `out` (device pointer, [count][n_env]); returns count or a negative code.

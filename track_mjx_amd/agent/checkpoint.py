@@ -134,21 +134,60 @@ def policy_from_flax(policy: IntentionPolicy, tree: dict, get=_ident) -> None:
     def put(dst: torch.Tensor, src) -> None:
         dst.copy_(torch.as_tensor(np.ascontiguousarray(src), dtype=dst.dtype, device=dev))
 
-    for name, blocks in (("encoder", policy.encoder), ("decoder", policy.decoder)):
-        for i, blk in enumerate(blocks):
-            put(get(blk.dense.weight), np.asarray(p[name][f"hidden_{i}"]["kernel"]).T)
-            put(get(blk.dense.bias), p[name][f"hidden_{i}"]["bias"])
-            put(get(blk.norm.weight), p[name][f"LayerNorm_{i}"]["scale"])
-            put(get(blk.norm.bias), p[name][f"LayerNorm_{i}"]["bias"])
+    for i, blk in enumerate(policy.encoder):
+        put(get(blk.dense.weight), np.asarray(p["encoder"][f"hidden_{i}"]["kernel"]).T)
+        put(get(blk.dense.bias), p["encoder"][f"hidden_{i}"]["bias"])
+        put(get(blk.norm.weight), p["encoder"][f"LayerNorm_{i}"]["scale"])
+        put(get(blk.norm.bias), p["encoder"][f"LayerNorm_{i}"]["bias"])
     Z = policy.latents
     w, b = get(policy.fc2.weight), get(policy.fc2.bias)
     put(w[:Z], np.asarray(p["encoder"]["fc2_mean"]["kernel"]).T)
     put(w[Z:], np.asarray(p["encoder"]["fc2_logvar"]["kernel"]).T)
     put(b[:Z], p["encoder"]["fc2_mean"]["bias"])
     put(b[Z:], p["encoder"]["fc2_logvar"]["bias"])
-    last = p["decoder"][f"hidden_{len(policy.decoder)}"]
-    put(get(policy.head.weight), np.asarray(last["kernel"]).T)
-    put(get(policy.head.bias), last["bias"])
+    decoder_from_flax(policy, p["decoder"], get, check=False)
+
+
+def decoder_flax_params(policy: IntentionPolicy) -> dict:
+    """{"hidden_i/kernel": parameter, ...}: the decoder's entries of the flax tree (params/decoder: every block's hidden_i and LayerNorm_i, the
+    action head as the last hidden_L) -> the parameters of `policy` they live in.  Kernels are stored [in, out], the parameters [out, in]."""
+    out = {}
+    for i, blk in enumerate(policy.decoder):
+        out[f"hidden_{i}/kernel"], out[f"hidden_{i}/bias"] = blk.dense.weight, blk.dense.bias
+        out[f"LayerNorm_{i}/scale"], out[f"LayerNorm_{i}/bias"] = blk.norm.weight, blk.norm.bias
+    L = len(policy.decoder)
+    out[f"hidden_{L}/kernel"], out[f"hidden_{L}/bias"] = policy.head.weight, policy.head.bias
+    return out
+
+
+def check_decoder_tree(policy: IntentionPolicy, dec: dict) -> None:
+    """ValueError unless the flax decoder tree `dec` (params/decoder of a checkpoint) has exactly the entries and shapes of `policy`'s decoder and
+    head — they follow from decoder_layer_sizes, intention_size, the proprioceptive observation width and the action size."""
+    want = decoder_flax_params(policy)
+    have = flatten(dec)
+    extra = sorted(set(have) - set(want))
+    if extra:
+        raise ValueError(f"checkpoint decoder has decoder/{extra[0]}, which this run's decoder ({len(policy.decoder)} blocks + head) does not")
+    for name, prm in want.items():
+        if name not in have:
+            raise ValueError(f"checkpoint decoder has no decoder/{name} (this run's decoder has {len(policy.decoder)} blocks + head)")
+        shape = tuple(prm.shape[::-1]) if name.endswith("/kernel") else tuple(prm.shape)
+        if tuple(have[name].shape) != shape:
+            raise ValueError(f"checkpoint decoder/{name} has shape {tuple(have[name].shape)}, this run's has {shape} "
+                             "(decoder_layer_sizes, intention_size, the proprioceptive observation width and the action size must match)")
+
+
+@torch.no_grad()
+def decoder_from_flax(policy: IntentionPolicy, dec: dict, get=_ident, check: bool = True) -> None:
+    """The decoder half of policy_from_flax: params/decoder (blocks and the action head hidden_L) into `policy`, in place.  `check`: the shapes
+    are verified first (check_decoder_tree), so a mismatched checkpoint is refused before anything is written."""
+    if check:
+        check_decoder_tree(policy, dec)
+    dev = policy.fc2.weight.device
+    for name, prm in decoder_flax_params(policy).items():
+        layer, leaf = name.split("/")
+        src = np.asarray(dec[layer][leaf])
+        get(prm).copy_(torch.as_tensor(np.ascontiguousarray(src.T if leaf == "kernel" else src), dtype=prm.dtype, device=dev))
 
 
 @torch.no_grad()
@@ -462,6 +501,23 @@ def load_policy(path, cfg: dict | None = None, step: int | None = None) -> tuple
     with np.load(os.path.join(d, "policy.npz")) as z:
         tree = unflatten({k: z[k] for k in z.files})
     return tree["0"], tree["1"]
+
+
+def load_freeze_source(path) -> tuple:
+    """(normalizer_params, policy_params, step) that a freeze_decoder run takes its decoder and pinned normaliser columns from
+    (checkpointing.load_policy at ppo.py:569-572 of the reference): the latest step of a checkpoint directory, a step directory, or a .npz
+    of save_npz (step: its iteration, None if it has none)."""
+    import os
+    if os.path.isdir(str(path)):
+        d = resolve_step_dir(path)
+        norm, pol = load_policy(d)
+        return norm, pol, int(os.path.basename(os.path.normpath(d)))
+    with np.load(str(path)) as z:
+        flat = {k: z[k] for k in z.files if k not in ("config_json",)}
+    step = int(flat.pop("iteration")) if "iteration" in flat else None
+    flat.pop("env_steps", None)
+    tree = unflatten(flat)
+    return tree["normalizer"], tree["policy"], step
 
 
 def load_inference_fn(cfg: dict, policy: tuple, deterministic: bool = True, get_activation: bool = True, device="cuda"):

@@ -240,6 +240,9 @@ class LSTMPPOLearner(PPOLearner):
         rows = self.unrolls * self.n_local
         self.h0_store, self.c0_store = self.policy.zero_carry(rows, self.dev)
 
+    def freeze_decoder(self, policy_tree=None, normalizer_tree=None) -> dict:
+        raise NotImplementedError("freeze_decoder: the LSTM learner has no frozen-decoder training (the reference's lstm_ppo/ppo.py has none)")
+
     def _build_policy(self, obs, ref, action_size, latents, encoder_layers, decoder_layers):
         return LSTMIntentionPolicy(obs, ref, action_size, latents, encoder_layers, self.hidden_state_size, self.hidden_layer_num)
 

@@ -1549,14 +1549,16 @@ class RunningStatistics:
         self.std_min, self.std_max = std_min, std_max
 
     @torch.no_grad()
-    def update(self, batch: torch.Tensor, group=None, distributed: bool | None = None) -> None:
+    def update(self, batch: torch.Tensor, group=None, distributed: bool | None = None, pin_lo: int | None = None) -> None:
         """One pass over the batch: per column S1 = sum(x - mean_old), S2 = sum((x - mean_old)^2); then
         mean_update = S1 / count_new and variance_update = sum((x - mean_old)(x - mean_new)) = S2 - mean_update * S1 — the
         reference's update (masked_running_statistics.py:161-214) with its second pass over the data folded into the first.
         `distributed` (default: a process group is initialised with more than one rank): S1 | S2 are summed across the ranks of
         `group` (None = the default group) in ONE all-reduce — the same totals as the reference's psums of the count, mean_update
         and variance_update (ppo.py:357-361).  On the GPU the sums and the in-place update are HIP kernels (tmjx_stats_sums /
-        tmjx_stats_apply, K6); CPU tensors (tests, gloo) take the same formulas in torch."""
+        tmjx_stats_apply, K6); CPU tensors (tests, gloo) take the same formulas in torch.
+        `pin_lo`: columns [pin_lo, W) keep their mean, summed_variance and std (the freeze_decoder run's pinned proprioceptive columns,
+        ppo.py:357-377 of the reference: there they are written back after every update); the count grows as usual (tmjx_stats_apply_pinned)."""
         import torch.distributed as dist
         if distributed is None:
             distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
@@ -1578,8 +1580,12 @@ class RunningStatistics:
                 _hip.check(L.tmjx_stats_sums(p(flat), p(self.mean), p(self._sums), p(self._scratch), rows, W, stream), "tmjx_stats_sums")
                 if distributed:
                     dist.all_reduce(self._sums, group=group)
-                _hip.check(L.tmjx_stats_apply(p(self._sums), n_added, p(self.count), p(self.mean), p(self.summed_variance), p(self.std), W,
-                                              float(self.std_min), float(self.std_max), stream), "tmjx_stats_apply")
+                if pin_lo is None:
+                    _hip.check(L.tmjx_stats_apply(p(self._sums), n_added, p(self.count), p(self.mean), p(self.summed_variance), p(self.std), W,
+                                                  float(self.std_min), float(self.std_max), stream), "tmjx_stats_apply")
+                else:
+                    _hip.check(L.tmjx_stats_apply_pinned(p(self._sums), n_added, p(self.count), p(self.mean), p(self.summed_variance), p(self.std), W,
+                                                         int(pin_lo), float(self.std_min), float(self.std_max), stream), "tmjx_stats_apply_pinned")
             return
         d = flat - self.mean
         sums = torch.cat([d.sum(0), (d * d).sum(0)])
@@ -1588,9 +1594,18 @@ class RunningStatistics:
         count = self.count + n_added
         upd = sums[:W] / count
         # in place: the SGD-loop graph (PPOLearner) holds pointers to these buffers
-        self.summed_variance.add_(sums[W:] - upd * sums[:W])
-        self.mean.add_(upd); self.count.copy_(count)
-        self.std.copy_(torch.sqrt(torch.clamp(self.summed_variance, min=0) / count).clamp(self.std_min, self.std_max))
+        if pin_lo is None:
+            self.summed_variance.add_(sums[W:] - upd * sums[:W])
+            self.mean.add_(upd); self.count.copy_(count)
+            self.std.copy_(torch.sqrt(torch.clamp(self.summed_variance, min=0) / count).clamp(self.std_min, self.std_max))
+            return
+        k = int(pin_lo)
+        if not 0 <= k <= W:
+            raise ValueError(f"pin_lo={k} outside [0, {W}]")
+        sv, mean, std = self.summed_variance[:k], self.mean[:k], self.std[:k]
+        sv.add_(sums[W:W + k] - upd[:k] * sums[:k])
+        mean.add_(upd[:k]); self.count.copy_(count)
+        std.copy_(torch.sqrt(torch.clamp(sv, min=0) / count).clamp(self.std_min, self.std_max))
 
     def normalize(self, x: torch.Tensor) -> torch.Tensor:
         return (x - self.mean) / self.std

@@ -127,10 +127,16 @@ class FlatAdam:
     """optax.chain(clip_by_global_norm(max_norm), adam(lr)) (reference: ppo.py:517-520) on the flat buffers: the parameters are
     re-seated as views of ONE contiguous fp32 buffer (same layout as the gradients of FlatGrads), so the optimiser step is a norm reduction
     plus one launch of tmjx_adam_clip instead of the clip kernels, a multi-tensor scale and a multi-tensor Adam over ~30 tensors.
-    Must be built before any hipGraph captures the parameters' addresses.  CPU tensors (tests) take the same maths in torch."""
+    Must be built before any hipGraph captures the parameters' addresses.  CPU tensors (tests) take the same maths in torch.
 
-    def __init__(self, grads: FlatGrads, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, max_norm: float = 10.0):
+    `frozen` = (lo, hi): a range of the flat buffer whose parameters are never updated — optax.chain(chain(clip, adam), freeze(mask)) of the
+    reference's freeze_decoder run (ppo.py:594-617): the global norm still covers every gradient and the moments are still updated everywhere,
+    only the parameter updates inside the range are zeroed (tmjx_adam_clip_norm_frozen)."""
+
+    def __init__(self, grads: FlatGrads, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, max_norm: float = 10.0,
+                 frozen: tuple[int, int] | None = None):
         self.grads, self.lr, self.betas, self.eps, self.max_norm = grads, lr, betas, eps, max_norm
+        self.frozen = frozen
         flat = torch.zeros_like(grads.flat)
         with torch.no_grad():
             for p, seg in zip(grads.params, grads.segs):
@@ -156,16 +162,26 @@ class FlatAdam:
                 self._norm_scratch = torch.empty(int(_hip.lib().tmjx_adam_norm_floats()), dtype=torch.float32, device=g.device)
                 self._norm = torch.zeros((), dtype=torch.float32, device=g.device)
             norm = self._norm
+            ptrs = [C.c_void_p(t.data_ptr()) for t in (self.flat, g, self.exp_avg, self.exp_avg_sq, self._norm_scratch, norm)]
+            stream = C.c_void_p(torch.cuda.current_stream(g.device).cuda_stream)
             with torch.cuda.device(g.device):
-                _hip.check(_hip.lib().tmjx_adam_clip_norm(*[C.c_void_p(t.data_ptr()) for t in (self.flat, g, self.exp_avg, self.exp_avg_sq, self._norm_scratch, norm)],
-                                                          g.numel(), self.lr, b1, b2, self.eps, bc1, bc2, self.max_norm,
-                                                          C.c_void_p(torch.cuda.current_stream(g.device).cuda_stream)), "tmjx_adam_clip_norm")
+                if self.frozen is None:
+                    _hip.check(_hip.lib().tmjx_adam_clip_norm(*ptrs, g.numel(), self.lr, b1, b2, self.eps, bc1, bc2, self.max_norm, stream), "tmjx_adam_clip_norm")
+                else:
+                    _hip.check(_hip.lib().tmjx_adam_clip_norm_frozen(*ptrs, g.numel(), int(self.frozen[0]), int(self.frozen[1]), self.lr, b1, b2, self.eps,
+                                                                     bc1, bc2, self.max_norm, stream), "tmjx_adam_clip_norm_frozen")
         else:
             norm = torch.linalg.vector_norm(g)
             gs = g * (self.max_norm / torch.clamp(norm, min=self.max_norm))
             self.exp_avg.mul_(b1).add_(gs, alpha=1 - b1)
             self.exp_avg_sq.mul_(b2).addcmul_(gs, gs, value=1 - b2)
-            self.flat.addcdiv_(self.exp_avg, self.exp_avg_sq.sqrt() / (bc2 ** 0.5) + self.eps, value=-self.lr / bc1)
+            if self.frozen is None:
+                self.flat.addcdiv_(self.exp_avg, self.exp_avg_sq.sqrt() / (bc2 ** 0.5) + self.eps, value=-self.lr / bc1)
+            else:
+                den = self.exp_avg_sq.sqrt() / (bc2 ** 0.5) + self.eps
+                lo, hi = self.frozen
+                for a, b in ((0, lo), (hi, self.flat.numel())):     # no update inside [lo, hi)
+                    self.flat[a:b].addcdiv_(self.exp_avg[a:b], den[a:b], value=-self.lr / bc1)
         return norm
 
     def state_dict(self):
@@ -272,6 +288,7 @@ class PPOLearner:
         self.overlap_c1 = self.collectives and ((big and self.world > 1) if force is None else force == "1")
         self.opt = FlatAdam(self.grads, learning_rate, betas=(0.9, 0.999), eps=1e-8, max_norm=10.0)   # optax.clip_by_global_norm(10.0) -> adam
         self.normalizer = RunningStatistics(obs, dev)
+        self._pin_lo = None                # freeze_decoder(): the normaliser's columns [_pin_lo, obs) keep their statistics
         self.gen = torch.Generator(device=dev).manual_seed(seed * 1000 + 17 + self.rank)
         self.gens = [self.gen] + [torch.Generator(device=dev).manual_seed(seed * 1000 + 17 + self.rank + 7919 * g) for g in range(1, len(self.envs))]
         rows = self.unrolls * n_local
@@ -337,6 +354,46 @@ class PPOLearner:
 
     def _build_policy(self, obs, ref, action_size, latents, encoder_layers, decoder_layers):
         return IntentionPolicy(obs, ref, action_size, latents, encoder_layers, decoder_layers)
+
+    @torch.no_grad()
+    def freeze_decoder(self, policy_tree: dict | None = None, normalizer_tree: dict | None = None) -> dict:
+        """Train a new encoder on a frozen decoder (the reference's freeze_decoder run, ppo.py:569-617,357-377).
+
+        * `policy_tree` (a checkpoint's flax policy tree): its params/decoder — every decoder block and the action head hidden_L — is copied into
+          this learner's policy; every shape is checked first (ValueError naming the parameter).  Encoder, fc2 and value net keep this run's
+          initialisation.  None: the decoder as it stands (a resumed frozen run).
+        * `normalizer_tree` (the checkpoint's normaliser): its last `obs - ref` columns (mean, summed_variance, std; not count) are copied
+          into the normaliser's proprioceptive columns [ref, obs).  Those columns are then pinned: every later update leaves them as they are.
+        * The optimiser's frozen range becomes the decoder and head's part of the flat buffer: no parameter update there, while the global
+          norm still covers their gradients and their Adam moments still move (the reference's freeze(mask) comes after clip and adam).
+        Every rank calls this with the same checkpoint, so replicas stay identical.  Returns {n_frozen, frozen_range, pinned_columns}."""
+        from . import checkpoint as _ckpt
+        obs, ref = self.normalizer.mean.numel(), int(self.policy.reference_obs_size)
+        if obs - ref <= 0:
+            raise ValueError("freeze_decoder: the proprioceptive observation size is 0 — the decoder has no observation columns to pin")
+        # the frozen parameters (decoder blocks + head) must be ONE contiguous range of the flat buffer, ending where the value bucket begins:
+        # IntentionPolicy registers encoder, fc2, decoder, head and the buffer is [policy | value]
+        frozen_ids = {id(p) for p in _ckpt.decoder_flax_params(self.policy).values()}
+        idx = [i for i, p in enumerate(self.grads.params) if id(p) in frozen_ids]
+        npol = self._n_policy_params
+        if len(idx) != len(frozen_ids) or idx != list(range(npol - len(idx), npol)):
+            raise AssertionError("freeze_decoder: the decoder and head parameters are not the last segments of the policy's flat buffer")
+        lo, hi = self.grads.segs[idx[0]][0], self._bucket_split
+        if policy_tree is not None:
+            if "decoder" not in policy_tree.get("params", {}):
+                raise ValueError("freeze_decoder: the checkpoint's policy has no params/decoder (an LSTM-decoder policy cannot be frozen into this learner)")
+            _ckpt.decoder_from_flax(self.policy, policy_tree["params"]["decoder"])
+        if normalizer_tree is not None:
+            n_p = obs - ref
+            for k in ("mean", "summed_variance", "std"):
+                src = np.asarray(normalizer_tree[k], dtype=np.float32).reshape(-1)
+                if src.size < n_p:
+                    raise ValueError(f"freeze_decoder: the checkpoint's normaliser {k} has {src.size} columns, fewer than the {n_p} proprioceptive ones")
+                getattr(self.normalizer, k)[ref:].copy_(torch.as_tensor(src[src.size - n_p:], device=self.normalizer.mean.device))
+        self._pin_lo = ref
+        self.opt.frozen = (int(lo), int(hi))
+        self._refresh_padded_weights()
+        return {"n_frozen": int(sum(self.grads.params[i].numel() for i in idx)), "frozen_range": (int(lo), int(hi)), "pinned_columns": (ref, obs)}
 
     @property
     def state(self):
@@ -807,7 +864,8 @@ class PPOLearner:
 
     def update(self, it: int = 0, kl_schedule: Callable | None = None) -> dict:
         if self.normalize_observations:
-            self.normalizer.update(self.buf["observation"], group=self.group, distributed=self.collectives)     # C2 (group None = default group)
+            self.normalizer.update(self.buf["observation"], group=self.group, distributed=self.collectives,     # C2 (group None = default group)
+                                   pin_lo=self._pin_lo)
         kl_w = kl_schedule(it) if kl_schedule is not None else self.kl_weight
         rows = self.buf["reward"].shape[1]
         use_graph = self.use_graph and self.dev.type == "cuda"
@@ -893,7 +951,8 @@ def train(environment, num_timesteps: int, episode_length: int, ckpt_mgr=None, c
           matmul_dtype: torch.dtype | None = None, group=None, checkpoint_path: str | None = None, restore_from: str | None = None,
           shuffle_rng: str = "torch", act_rng: str = "device", action_repeat: int = 1,
           policy_params_fn: Callable[..., None] = lambda *args, **kwargs: None, checkpoint_callback: Callable[[int], None] | None = None,
-          use_lstm: bool = False, hidden_state_size: int = 128, hidden_layer_num: int = 2, **unused):
+          use_lstm: bool = False, hidden_state_size: int = 128, hidden_layer_num: int = 2, checkpoint_to_restore: str | None = None,
+          freeze_decoder: bool = False, **unused):
     """ppo.train(environment, num_timesteps, episode_length, ...) -> (make_policy, params, metrics)  (ppo.py:128-172,809).
 
     `environment` is an un-wrapped MultiClipTracking holding THIS rank's envs; it is wrapped here exactly like
@@ -908,6 +967,13 @@ def train(environment, num_timesteps: int, episode_length: int, ckpt_mgr=None, c
     noise streams — and the run continues at the iteration after the restored one (the reference leaves its iteration restart as a TODO,
     ppo.py:670-677, and would then collide with the existing steps of the same directory).
 
+    `checkpoint_to_restore` (ppo.py:134,558-617): without `freeze_decoder` the same as `restore_from` (naming both is a ValueError).
+    `freeze_decoder`: train a new encoder on a frozen pretrained decoder (PPOLearner.freeze_decoder).  With `checkpoint_to_restore` (a checkpoint
+    directory — its latest step —, a step directory or a .npz) ONLY the checkpoint's params/decoder and the proprioceptive columns of its
+    normaliser are taken; encoder, fc2, value net, Adam state, env_steps and the iteration start fresh from this run's seed.  With `restore_from`
+    a frozen run resumes: the whole state comes back and the restored decoder and normaliser columns stay frozen.  Neither: ValueError.  The LSTM
+    learner has no frozen decoder (NotImplementedError).
+
     `use_lstm`: the recurrent learner (agent/lstm.py: LSTMPPOLearner, the reference's agent/lstm_ppo) with `hidden_layer_num` LSTM layers of
     `hidden_state_size` features; the acting policies (evaluator, make_policy) then carry their own hidden state.
 
@@ -916,6 +982,15 @@ def train(environment, num_timesteps: int, episode_length: int, ckpt_mgr=None, c
     (params, observations, key_sample) -> (action, {"latent_mean", "latent_logvar"})), `params` ((normalizer, policy) state), a fresh
     `policy_params_fn_key` per call, and `render_video` = `it % config_dict["env_config"]["render_interval"] == 0` (every call when the
     config names no interval).  `checkpoint_callback(it)` follows every saved checkpoint (ppo.py:171,713-715; checkpointing.save)."""
+    if checkpoint_to_restore is not None and restore_from is not None:
+        raise ValueError("checkpoint_to_restore and restore_from both set: name one checkpoint (restore_from resumes a run, checkpoint_to_restore "
+                         "with freeze_decoder takes a pretrained decoder)")
+    if freeze_decoder and checkpoint_to_restore is None and restore_from is None:
+        raise ValueError("freeze_decoder needs a checkpoint to take the decoder from: set checkpoint_to_restore (or restore_from to resume a frozen run)")
+    if freeze_decoder and use_lstm:
+        raise NotImplementedError("freeze_decoder: the LSTM learner has no frozen-decoder training (the reference's lstm_ppo/ppo.py has none)")
+    if checkpoint_to_restore is not None and not freeze_decoder:
+        restore_from = checkpoint_to_restore          # the whole training state (checkpointing.load_training_state, ppo.py:561-567)
     from ..environment import wrap
     # a list of environments = equal groups of this rank's envs whose roll-outs are pipelined on separate HIP streams (collect())
     env_list = [wrap(e, episode_length=int(episode_length), action_repeat=int(action_repeat)) for e in (environment if isinstance(environment, (list, tuple)) else [environment])]
@@ -939,6 +1014,17 @@ def train(environment, num_timesteps: int, episode_length: int, ckpt_mgr=None, c
     restored = {"env_steps": None, "iteration": None}
     if restore_from is not None:
         restored = _ckpt.restore(restore_from, learner)
+    if freeze_decoder:
+        if restore_from is None:          # a pretrained decoder and its normaliser columns into this fresh run (ppo.py:569-617)
+            norm_tree, pol_tree, src_step = _ckpt.load_freeze_source(checkpoint_to_restore)
+            info = learner.freeze_decoder(pol_tree, norm_tree)
+            src = checkpoint_to_restore
+        else:                             # a frozen run resumed: its restored decoder and normaliser columns stay as they are
+            info = learner.freeze_decoder()
+            src, src_step = restore_from, restored.get("iteration")
+        if learner.rank == 0:
+            print(f"[train] freeze_decoder checkpoint={src} step={src_step} frozen_params={info['n_frozen']} "
+                  f"pinned_obs_columns=[{info['pinned_columns'][0]}, {info['pinned_columns'][1]})", flush=True)
     start_it = int(restored.get("iteration") or 0)
 
     def save_checkpoint(it: int, env_steps: int):

@@ -1081,6 +1081,29 @@ __global__ __launch_bounds__(256) void k_adam_clip(float *__restrict__ p, const 
     p[i] -= step * mi / (sqrtf(vi) * rs + eps);
   }
 }
+// k_adam_clip<true> with the parameter updates of [lo, hi) zeroed: optax.chain(chain(clip_by_global_norm, adam), freeze(mask)) of the
+// reference's freeze_decoder run (agent/mlp_ppo/ppo.py:594-617, agent/network_masks.py:6-19).  The norm still covers all n gradients and
+// the moments are still updated everywhere (the mask comes after clip and adam); only the stores of p inside the range are dropped.  A
+// sibling instead of a flag on k_adam_clip, so the default optimiser step compiles to the code it always did
+__global__ __launch_bounds__(256) void k_adam_clip_frozen(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
+                                                          const float *__restrict__ grad_norm, long long n, long long lo, long long hi, float lr, float b1,
+                                                          float b2, float eps, float bc1, float bc2, float max_norm, float *__restrict__ norm_out) {
+  __shared__ float lds[4];
+  float s = wave_sum(grad_norm[threadIdx.x]);          // the ADAM_NORM_PARTS partials of k_grad_sumsq, added as k_adam_clip<true> adds them
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
+  __syncthreads();
+  const float nrm = sqrtf((lds[0] + lds[1]) + (lds[2] + lds[3]));
+  if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = nrm;
+  const float scale = max_norm / fmaxf(max_norm, nrm);
+  const float step = lr / bc1, rs = 1.f / sqrtf(bc2);
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    float gi = g[i] * scale;
+    float mi = b1 * m[i] + (1.f - b1) * gi;
+    float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    m[i] = mi; v[i] = vi;
+    if (i < lo || i >= hi) p[i] -= step * mi / (sqrtf(vi) * rs + eps);
+  }
+}
 
 // ---- column sums of a row-major [rows][width] matrix (bias gradients dy.sum(0) of the dense layers): stage 1 = one block per (64
 // row chunks) x (32 columns), 8 row slices per block, partial sums to [nchunk][width]; stage 2 = k_colsum over the chunks.  torch's
@@ -1183,6 +1206,21 @@ __global__ void k_stats_finalize(const float *__restrict__ sums, float n_added, 
   // written by a second tiny launch (k_stats_count) — stream order makes it safe
 }
 __global__ void k_stats_count(float *count, float n_added) { *count += n_added; }
+// k_stats_finalize for columns [0, pin_lo) only: columns [pin_lo, W) keep their mean, summed_variance and std (the reference's freeze_decoder run
+// writes the checkpoint's values back over the proprioceptive columns after every update, agent/mlp_ppo/ppo.py:357-377).  sums is still [2][W]
+__global__ void k_stats_finalize_pinned(const float *__restrict__ sums, float n_added, float *count, float *mean, float *summed_variance, float *std,
+                                        int W, int pin_lo, float std_min, float std_max) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  const float cnt = *count + n_added;
+  if (c < pin_lo) {
+    const float s1 = sums[c], s2 = sums[W + c];
+    const float upd = s1 / cnt;
+    const float sv = summed_variance[c] + (s2 - upd * s1);
+    mean[c] += upd;
+    summed_variance[c] = sv;
+    std[c] = fminf(fmaxf(sqrtf(fmaxf(sv, 0.f) / cnt), std_min), std_max);
+  }
+}
 
 // ---- Dense -> SiLU (brax value MLP: swish, no LayerNorm) element-wise halves: y = silu(z + bias) for layers the fused GEMM epilogue
 // (tmjx_gemm_nt_silu) does not take, and dz = dy silu'(z + bias) — the operand of the layer's input- and weight-gradient GEMMs

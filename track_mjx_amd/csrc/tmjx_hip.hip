@@ -806,6 +806,24 @@ int tmjx_adam_clip_norm(float *param, const float *grad, float *exp_avg, float *
                      bias_correction1, bias_correction2, max_norm, norm_out);
   return check_launch("k_adam_clip(norm)");
 }
+int tmjx_adam_clip_norm_frozen(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, float *norm_scratch, float *norm_out, long long n,
+                               long long frozen_lo, long long frozen_hi, float lr, float beta1, float beta2, float eps, float bias_correction1,
+                               float bias_correction2, float max_norm, void *stream) {
+  if (!param || !grad || !exp_avg || !exp_avg_sq || !norm_scratch) return fail(TMJX_EINVAL, "tmjx_adam_clip_norm_frozen: null argument");
+  if (n < 1 || !(bias_correction1 > 0.f) || !(bias_correction2 > 0.f) || !(max_norm > 0.f))
+    return fail(TMJX_EINVAL, "tmjx_adam_clip_norm_frozen: bad n / bias corrections / max_norm");
+  if ((uintptr_t)grad & 15) return fail(TMJX_EINVAL, "tmjx_adam_clip_norm_frozen: the gradient buffer must be 16-byte aligned");
+  if (frozen_lo < 0 || frozen_lo > frozen_hi || frozen_hi > n)
+    return fail(TMJX_EINVAL, "tmjx_adam_clip_norm_frozen: the frozen range must satisfy 0 <= lo <= hi <= n");
+  if ((frozen_lo | frozen_hi) & 3)
+    return fail(TMJX_EINVAL, "tmjx_adam_clip_norm_frozen: the frozen range's ends must be multiples of 4 (flat segments start on 16-byte boundaries)");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_grad_sumsq, dim3(ADAM_NORM_PARTS), dim3(256), 0, s, grad, n, norm_scratch);
+  int grid = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+  hipLaunchKernelGGL(k_adam_clip_frozen, dim3(grid), dim3(256), 0, s, param, grad, exp_avg, exp_avg_sq, (const float *)norm_scratch, n, frozen_lo, frozen_hi,
+                     lr, beta1, beta2, eps, bias_correction1, bias_correction2, max_norm, norm_out);
+  return check_launch("k_adam_clip_frozen");
+}
 
 int tmjx_latent_concat(const float *fc2, const float *eps, const float *obs, float *x, int n, int Z, int obs_w, int ref_w,
                        int64_t obs_s0, int64_t obs_s1, const float *mean, const float *std, int x_stride, uint64_t seed, const int64_t *rng_state,
@@ -1261,6 +1279,18 @@ int tmjx_stats_apply(const float *sums, float n_added, float *count, float *mean
   hipLaunchKernelGGL(k_stats_finalize, dim3((W + 255) / 256), dim3(256), 0, s, sums, n_added, count, mean, summed_variance, std, W, std_min, std_max);
   hipLaunchKernelGGL(k_stats_count, dim3(1), dim3(1), 0, s, count, n_added);
   return check_launch("k_stats_finalize");
+}
+
+int tmjx_stats_apply_pinned(const float *sums, float n_added, float *count, float *mean, float *summed_variance, float *std, int W, int pin_lo,
+                            float std_min, float std_max, void *stream) {
+  if (!sums || !count || !mean || !summed_variance || !std) return fail(TMJX_EINVAL, "tmjx_stats_apply_pinned: null argument");
+  if (W < 1 || !(n_added > 0.f)) return fail(TMJX_EINVAL, "tmjx_stats_apply_pinned: W must be >= 1 and n_added > 0");
+  if (pin_lo < 0 || pin_lo > W) return fail(TMJX_EINVAL, "tmjx_stats_apply_pinned: pin_lo must satisfy 0 <= pin_lo <= W");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_stats_finalize_pinned, dim3((W + 255) / 256), dim3(256), 0, s, sums, n_added, count, mean, summed_variance, std, W, pin_lo,
+                     std_min, std_max);
+  hipLaunchKernelGGL(k_stats_count, dim3(1), dim3(1), 0, s, count, n_added);
+  return check_launch("k_stats_finalize_pinned");
 }
 
 int tmjx_debug_rows(const tmjx_model *m, const char *name, int *row0, int *count) {

@@ -71,6 +71,19 @@ def learner_options(cfg: dict) -> dict:
     return {"use_lstm": True, "hidden_state_size": H, "hidden_layer_num": L}
 
 
+def restore_options(cfg: dict) -> dict:
+    """ppo.train keywords of the reference's train_setup.checkpoint_to_restore and train_setup.freeze_decoder (train.py:306-314 of the reference):
+    only the keys a config sets, so a config without them trains as before.  The reference's replacement of the whole config by the checkpoint's
+    (its train.py:117-133) is not done: the network sizes come from this config, and a decoder that does not fit is refused by its shape check."""
+    ts = cfg.get("train_setup") or {}
+    out = {}
+    if ts.get("checkpoint_to_restore") is not None:
+        out["checkpoint_to_restore"] = str(ts["checkpoint_to_restore"])
+    if bool(ts.get("freeze_decoder", False)):
+        out["freeze_decoder"] = True
+    return out
+
+
 def main(argv=None, runner=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     full_argv = list(argv)
@@ -144,7 +157,8 @@ def main(argv=None, runner=None):
               max_training_steps=cfg.get("max_training_steps"), eval_env=eval_env, num_eval_envs=num_eval_envs,
               deterministic_eval=bool(tc.get("deterministic_eval", False)), config_dict=cfg, action_repeat=int(tc.get("action_repeat", 1)),
               checkpoint_path=cfg.get("checkpoint_path"), restore_from=cfg.get("restore_from"), shuffle_rng=str(cfg.get("shuffle_rng", "torch")), act_rng=str(cfg.get("act_rng", "device")),
-              matmul_dtype=torch.bfloat16 if str(cfg.get("mlp_gemm_inputs", "f32")).lower() in ("bf16", "bfloat16") else None, **lopts)
+              matmul_dtype=torch.bfloat16 if str(cfg.get("mlp_gemm_inputs", "f32")).lower() in ("bf16", "bfloat16") else None, **lopts,
+              **restore_options(cfg))
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
