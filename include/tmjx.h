@@ -94,6 +94,23 @@ int tmjx_physics_step(tmjx_model *m, float *state, const float *action, float *w
  * (brax PipelineEnv.pipeline_step, called at task/single_clip_tracking.py:219). */
 int tmjx_physics(tmjx_model *m, float *state, const float *action, int n_substeps, float *workspace, int n_env,
                  void *stream);
+/* Sensor outputs (checkpoint roll-outs with log_sensor_data; reference: track_mjx/analysis/rollout.py), through the RECORDING physics
+ * kernel — K2 with a sensor stage between the solve and Euler of the last substep (mjx.step = forward, then euler: the values belong to the
+ * last substep's starting qpos / qvel and to its solve's qacc / efc_force, like qfrc_actuator).  Both outputs are [row][n_env], device memory:
+ *   sensordata [nsensordata][n_env]: the model's sensors in blob order (rodent: head accelerometer, velocimeter, gyro in the site frame,
+ *              torso subtreelinvel in the world frame); may be NULL when the model has no sensors;
+ *   cfrc_ext   [nbody * 6][n_env]: per body [torque(3), force(3)] of the contact forces about subtree_com[body_rootid] (mj_rnePostConstraint:
+ *              minus on geom 1's body, plus on geom 2's; row block 0, the world, stays 0).
+ * tmjx_sensor_info: sizes of the two (nsensordata = 0 for a model without sensors). */
+int tmjx_sensor_info(const tmjx_model *m, int *nsensordata, int *nbody);
+/* tmjx_physics through the recording kernel (n_substeps >= 1). */
+int tmjx_physics_sensors(tmjx_model *m, float *state, const float *action, int n_substeps, float *sensordata, float *cfrc_ext,
+                         float *workspace, int n_env, void *stream);
+/* tmjx_step through the recording kernel: the same launches and results (state, obs, reward, done, truncation, metrics bit for bit);
+ * with action_repeat R the outputs are those of the last repeat's last substep; with auto-reset on, those of the physics that ran,
+ * before K3 restores a done env. */
+int tmjx_step_sensors(tmjx_model *m, float *state, int32_t *istate, const float *action, float *obs, float *reward, float *done,
+                      float *truncation, float *metrics, float *workspace, float *sensordata, float *cfrc_ext, int n_env, void *stream);
 /* mjx.forward alone on the physics rows of `state` (pipeline_init, task/single_clip_tracking.py:163). */
 int tmjx_forward(tmjx_model *m, float *state, float *workspace, int n_env, void *stream);
 

@@ -16,6 +16,7 @@ Output: track_mjx_amd/assets/rodent_model.tmjx  (binary blob, float64/int32)
         track_mjx_amd/assets/rodent_model_dump.txt (human-readable review copy)
 (side files are named after the output's stem: --out .../rodent_model_pos080.tmjx.txt writes rodent_model_pos080.names.txt and
 rodent_model_pos080_dump.txt; an --out ending in .tmjx.txt writes the blob's lossless text form, track_mjx_amd/blob.py).
+A model with a <sensor> block also gets <stem>.sensors.tmjx.txt: the sensor entries (site_* / sensor_*: sensor_entries) in text form.
 
 Actuator modes: torque_actuators=True rewrites the position servos into torque motors (the reference's default walker);
 torque_actuators=False with affine_bias=True keeps them as written (biastype="affine": force = gain * act + b0 + b1 * length)
@@ -41,6 +42,9 @@ from track_mjx_amd import blob  # noqa: E402
 
 DEFAULT_XML = "/root/reference/track_mjx/environment/walker/assets/rodent/rodent.xml"
 
+# sensor type codes of the blob entry sensor_type (this project's own numbering, not mjtSensor) and their output widths
+SENSOR_TYPES = {"accelerometer": 0, "velocimeter": 1, "gyro": 2, "subtreelinvel": 3}
+SENSOR_DIM = {0: 3, 1: 3, 2: 3, 3: 3}
 GEOM_PLANE, GEOM_SPHERE, GEOM_CAPSULE, GEOM_ELLIPSOID, GEOM_CYLINDER, GEOM_BOX = 0, 2, 3, 4, 5, 6
 GEOM_TYPES = {"plane": 0, "hfield": 1, "sphere": 2, "capsule": 3, "ellipsoid": 4,
               "cylinder": 5, "box": 6, "mesh": 7}
@@ -187,7 +191,9 @@ def parse_body(el, parent, classes, childclass, bodies):
         elif ch.tag == "geom":
             b.geoms.append(resolve(ch, "geom", classes, cc))
         elif ch.tag == "site":
-            b.sites.append(resolve(ch, "site", classes, cc))
+            a = resolve(ch, "site", classes, cc)
+            a["_body"] = b
+            b.sites.append(a)
     for ch in el:
         if ch.tag == "body":
             b.children.append(parse_body(ch, b, classes, cc, bodies))
@@ -459,6 +465,46 @@ def compile_model(xml_path, torque_actuators=True, rescale_factor=0.9, affine_bi
         act_ctrlrange.append(fvec(a["ctrlrange"]))
     nu = len(act_names)
 
+    # ---- sensors: the ones the rodent declares (site-based accelerometer / velocimeter / gyro, body-based subtreelinvel); anything else is
+    # refused by name.  Only the sites a sensor refers to are emitted; site positions are NOT rescaled (dm_scale_spec leaves sites alone)
+    sites = {a["name"]: a for bb in bodies for a in bb.sites if "name" in a}
+    site_names, site_bodyid, site_pos, site_quat = [], [], [], []
+    sensor_names, sensor_type, sensor_objid, sensor_adr = [], [], [], []
+    nsensordata = 0
+    sens_el = root.find("sensor")
+    for sel in (sens_el if sens_el is not None else []):
+        if not isinstance(sel.tag, str):
+            continue
+        a = resolve(sel, sel.tag, classes, None)
+        name = a.get("name", f"sensor{len(sensor_names)}")
+        if sel.tag not in SENSOR_TYPES:
+            raise NotImplementedError(f"sensor {name}: type {sel.tag} is not compiled (supported: {', '.join(SENSOR_TYPES)})")
+        if float(a.get("cutoff", 0)) != 0.0:
+            raise NotImplementedError(f"sensor {name}: a non-zero cutoff is not compiled")
+        if float(a.get("noise", 0)) != 0.0:
+            raise NotImplementedError(f"sensor {name}: non-zero noise is not compiled")
+        t = SENSOR_TYPES[sel.tag]
+        if t == SENSOR_TYPES["subtreelinvel"]:
+            if "body" not in a or a["body"] not in name2body:
+                raise ValueError(f"sensor {name}: subtreelinvel needs an existing body")
+            obj = name2body[a["body"]].id
+        else:
+            sn = a.get("site")
+            if sn not in sites:
+                raise ValueError(f"sensor {name}: {sel.tag} needs an existing site")
+            if sn not in site_names:
+                st = sites[sn]
+                site_names.append(sn)
+                site_bodyid.append(st["_body"].id)
+                site_pos.append(fvec(st["pos"]) if "pos" in st else np.zeros(3))
+                site_quat.append(orientation(st))
+            obj = site_names.index(sn)
+        sensor_names.append(name)
+        sensor_type.append(t)
+        sensor_objid.append(obj)
+        sensor_adr.append(nsensordata)
+        nsensordata += SENSOR_DIM[t]
+
     # ---- options
     opt = {}
     for o in root.findall("option"):
@@ -484,7 +530,11 @@ def compile_model(xml_path, torque_actuators=True, rescale_factor=0.9, affine_bi
         act_moment=np.array(act_moment), act_gain=np.array(act_gain), act_tau=np.array(act_tau),
         act_ctrlrange=np.array(act_ctrlrange),
         gravity=gravity, geoms=geoms,
+        site_names=site_names, sensor_names=sensor_names, nsensordata=nsensordata,
     )
+    if sensor_names:
+        m["site_bodyid"], m["site_pos"], m["site_quat"] = np.array(site_bodyid), np.array(site_pos), np.array(site_quat)
+        m["sensor_type"], m["sensor_objid"], m["sensor_adr"] = np.array(sensor_type), np.array(sensor_objid), np.array(sensor_adr)
     if affine_bias and not torque_actuators:
         m["act_bias"] = np.array(act_bias)
     # qpos0 / qpos_spring
@@ -690,6 +740,21 @@ def to_blob(m):
     return e
 
 
+def sensor_entries(m):
+    """The optional sensor entries (empty for a model without sensors).  They are not part of `to_blob`'s model blob: they travel in the
+    text side file <stem>.sensors.tmjx.txt, which walker.Rodent appends to the blob it loads (the model blob keeps exactly the entries it had
+    before sensors were compiled); in the blob handed to tmjx_model_create they sit behind every other entry."""
+    e = OrderedDict()
+    if m.get("sensor_names"):
+        e["site_bodyid"] = np.asarray(m["site_bodyid"], dtype=np.int32)
+        e["site_pos"] = np.asarray(m["site_pos"], dtype=np.float64).ravel()
+        e["site_quat"] = np.asarray(m["site_quat"], dtype=np.float64).ravel()
+        e["sensor_type"] = np.asarray(m["sensor_type"], dtype=np.int32)
+        e["sensor_objid"] = np.asarray(m["sensor_objid"], dtype=np.int32)
+        e["sensor_adr"] = np.asarray(m["sensor_adr"], dtype=np.int32)
+    return e
+
+
 def dump_text(m, path):
     np.set_printoptions(precision=10, linewidth=160, suppress=False)
     with open(path, "w") as f:
@@ -712,6 +777,13 @@ def dump_text(m, path):
             bias = f" bias={m['act_bias'][a]}" if "act_bias" in m else ""
             f.write(f"{a:3d} {n:22s} gain={m['act_gain'][a]:.6g}{bias} tau={m['act_tau'][a]} moment={{" +
                     ", ".join(f"{d}:{m['act_moment'][a][d]:.8g}" for d in nz) + "}\n")
+        if m.get("sensor_names"):
+            f.write("\n# sensors: id name type object adr (types: 0 accelerometer, 1 velocimeter, 2 gyro [site]; 3 subtreelinvel [body])\n")
+            for i, n in enumerate(m["sensor_names"]):
+                f.write(f"{i:3d} {n:22s} type={m['sensor_type'][i]} obj={m['sensor_objid'][i]} adr={m['sensor_adr'][i]}\n")
+            f.write("\n# sites: id name body pos quat\n")
+            for i, n in enumerate(m["site_names"]):
+                f.write(f"{i:3d} {n:22s} body={m['site_bodyid'][i]} pos={m['site_pos'][i]} quat={m['site_quat'][i]}\n")
         f.write("\n# contact slots (MJX order): slot geom1 geom2 sub body2\n")
         for c in range(m["ncon"]):
             g2 = m["geoms"][m["con_geom2"][c]]
@@ -732,9 +804,13 @@ def main():
     e = to_blob(m)
     # names travel as a text side file (ids for the walker's name -> id lookups)
     blob.save(args.out, e)
+    se = sensor_entries(m)
+    if se:      # sensors: a text side file (blob.py's text form) named after the blob's stem
+        blob.save(Path(args.out).with_name(blob.stem(args.out) + ".sensors" + blob.TEXT_SUFFIX), se)
     names = Path(args.out).with_name(blob.stem(args.out) + ".names.txt")
     with open(names, "w") as f:
-        for kind, lst in (("body", m["body_names"]), ("joint", m["jnt_names"]), ("actuator", m["act_names"])):
+        for kind, lst in (("body", m["body_names"]), ("joint", m["jnt_names"]), ("actuator", m["act_names"]),
+                          ("site", m["site_names"]), ("sensor", m["sensor_names"])):
             for i, n in enumerate(lst):
                 f.write(f"{kind} {i} {n}\n")
     dump_text(m, Path(args.out).with_name(blob.stem(args.out) + "_dump.txt"))

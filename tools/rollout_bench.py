@@ -4,6 +4,7 @@ wall time of generate_rollout (first call = with setup, then `--repeats` timed c
 
     python tools/rollout_bench.py --clips 1024 [--config-name rodent-full-clips] [--repeats 1]
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/rollout_bench.py --clips 1024 --repeats 0    (the recorder's share of GPU time)
+    --sensors: log_sensor_data=True as well (the recording physics kernel k_physics_wave_sensors instead of k_physics_wave)
 """
 import argparse
 import json
@@ -21,6 +22,7 @@ def main():
     ap.add_argument("--clips", type=int, default=1024)
     ap.add_argument("--config-name", default="rodent-full-clips")
     ap.add_argument("--repeats", type=int, default=1)
+    ap.add_argument("--sensors", action="store_true", help="log_sensor_data=True (sensor readings and joint forces)")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -41,7 +43,7 @@ def main():
         ck.save_step_dir(d, 0, ln, config=cfg)
         fn = ck.load_inference_fn(cfg, ck.load_policy(d, cfg))
     env = create_environment(cfg, 1, "cuda")
-    gen = create_rollout_generator(cfg, env, fn, log_activations=True, log_metrics=True)
+    gen = create_rollout_generator(cfg, env, fn, log_activations=True, log_metrics=True, log_sensor_data=args.sensors)
     clips = list(range(args.clips))
     t0 = time.perf_counter()
     r = gen(clips)
@@ -57,7 +59,7 @@ def main():
         return sum(nbytes(v) for v in x.values()) if isinstance(x, dict) else (sum(nbytes(v) for v in x) if isinstance(x, tuple) else x.nbytes)
     rec = nbytes({k: v for k, v in r.items() if k != "qposes_ref"})
     steps = gen.T - 1
-    print(json.dumps({"clips": args.clips, "config": args.config_name, "T": gen.T, "first_call_s": round(first, 3),
+    print(json.dumps({"clips": args.clips, "config": args.config_name, "sensors": bool(args.sensors), "T": gen.T, "first_call_s": round(first, 3),
                       "timed_s": [round(t, 3) for t in times], "ms_per_control_step": round(1e3 * (min(times) if times else first) / steps, 3),
                       "recorded_bytes_per_env_step": int(rec / args.clips / steps)}), flush=True)
 

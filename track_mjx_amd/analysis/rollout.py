@@ -7,7 +7,7 @@ step is a fixed sequence of launches on preallocated buffers, with no torch oper
 
     staging copy of the observation (tmjx_record_step, T = 1)  ->  encoder: tmjx_linear_nolds_norm / tmjx_linear_nolds + tmjx_silu_ln_fwd  ->
     fc2 (tmjx_linear_nolds)  ->  tmjx_latent_concat_det  ->  decoder blocks / LSTM layers (tmjx_linear_nolds [+ tmjx_lstm_seq_fwd, T = 1])  ->
-    head  ->  tmjx_action_mode  ->  tmjx_step  ->  tmjx_record_step
+    head  ->  tmjx_action_mode  ->  tmjx_step (tmjx_step_sensors with log_sensor_data)  ->  tmjx_record_step
 
 Every dense layer is the matrix-core variant of tmjx_linear_nolds (row-major operands with 16-byte aligned rows, K padded to a multiple of 4):
 its per-row arithmetic does not depend on the number of rows, so a clip's record is the same bits alone or in any batch.  The recorder
@@ -16,8 +16,14 @@ writes each step into device-resident records [clip][T][w]; they are copied to t
 A checkpoint trained with mlp_gemm_inputs=bf16 is rolled out on these fp32 kernels (its weights are fp32; only the training GEMMs rounded
 their inputs).
 
+log_sensor_data (rollout.py:72-210): the env steps through the recording physics kernel (tmjx_step_sensors: K2 with a sensor stage on the
+last substep, the same state / reward bits), whose sensordata and cfrc_ext rows ([rows][n], device buffers at fixed addresses) two more
+TMJX_RECORD_SOA streams record: `sensor_readings` [T-1, nsensordata] and `joint_forces` [T-1, nbody, 6] (pipeline_state.sensordata / cfrc_ext
+of the reference; values of the last substep's forward, like the reference's).  The roll-out env has no auto-reset; on an auto-reset handle
+the values would be those of the physics that ran, before K3 restores a done env.
+
 CLI:  python -m track_mjx_amd.analysis.rollout checkpoint=<run dir | step dir> [data_path=...] [clips=all|a:b|i,j,k] [seed=42] [out=<dir>]
-      [log_activations=true] [log_metrics=true]    ->  <out>/clip_<idx>.h5 (save_to_h5py layout + a `meta` group)
+      [log_activations=true] [log_metrics=true] [log_sensor_data=false]    ->  <out>/clip_<idx>.h5 (save_to_h5py layout + a `meta` group)
 """
 from __future__ import annotations
 
@@ -270,9 +276,10 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
                              log_metrics: bool = False, log_sensor_data: bool = False, clips_per_batch: int = CLIPS_PER_BATCH):
     """rollout.py:73-269.  Returns generate_rollout(clip_idx=None, seed=42): one clip (int / None) -> dict of arrays; a sequence of clips -> the
     same dict with a leading [N] axis (batches larger than `clips_per_batch` run in chunks)."""
-    if log_sensor_data:
-        raise NotImplementedError("log_sensor_data: cfrc_ext and sensordata are not computed by the physics kernel (it carries only what the "
-                                  "tracking reward and observation need), so joint forces and sensor readings cannot be logged")
+    if log_sensor_data and not hasattr(environment, "sensor_buffers"):
+        raise NotImplementedError("log_sensor_data: cfrc_ext and sensordata are not computed by the physics kernel of this environment: they "
+                                  "come from MultiClipTracking's recording kernel (tmjx_step_sensors), and the environment given is "
+                                  f"{type(environment).__name__}")
     if not isinstance(inference_fn, RolloutPolicy):
         raise TypeError("create_rollout_generator: inference_fn must be the deterministic inference function made by "
                         "track_mjx_amd.agent.checkpoint.load_inference_fn (the roll-out runs it on the HIP kernels); got "
@@ -351,6 +358,12 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
                     LH = step.h.shape[1] * step.h.shape[2]
                     step_streams.append(add("act:hidden_state/h", _p(step.h), _hip.RECORD_ROWMAJOR, LH, LH, LH, T - 1, 0))
                     step_streams.append(add("act:hidden_state/c", _p(step.c), _hip.RECORD_ROWMAJOR, LH, LH, LH, T - 1, 0))
+            if log_sensor_data:
+                sd_buf, cf_buf = env.sensor_buffers()
+                nsd, nb6 = (0 if sd_buf is None else sd_buf.shape[0]), cf_buf.shape[0]
+                if nsd:
+                    step_streams.append(add("sensor_readings", _p(sd_buf), _hip.RECORD_SOA, n, nsd, nsd, T - 1, 0))
+                step_streams.append(add("joint_forces", _p(cf_buf), _hip.RECORD_SOA, n, nb6, nb6, T - 1, 0))
             init_tab = _upload_table(init_streams, n, 1, dev)
             state_tab = _upload_table(state_streams, n, T - 1, dev)
             step_tab = _upload_table(step_streams, n, T - 1, dev)
@@ -358,15 +371,23 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
             hdl = env._handle
             env_args = [_p(env.state_buf), _p(env.istate_buf), _p(step.action_t), _p(env.obs_buf), _p(env.reward_buf), _p(env.done_buf),
                         _p(env.trunc_buf), _p(env.metrics_buf), _p(env.workspace), n]
+            step_fn = "tmjx_step"
+            if log_sensor_data:       # tmjx_step_sensors: tmjx_step's arguments with the two output buffers in front of n_env
+                env._check_sensor_bufs(sd_buf, cf_buf)
+                env_args[-1:-1] = [_p(sd_buf), _p(cf_buf)]
+                step_fn = "tmjx_step_sensors"
             ks, kp = len(state_streams), len(step_streams)
             _hip.check(L.tmjx_record_step(init_tab.data_ptr(), ks, n, 0, 1, s), "tmjx_record_step")
-            _step_loop(step, L, s, hdl, env_args, state_tab.data_ptr(), ks, step_tab.data_ptr(), kp, n, T)
+            _step_loop(step, L, s, hdl, env_args, state_tab.data_ptr(), ks, step_tab.data_ptr(), kp, n, T, step_fn)
             host = {k: v.cpu().numpy() for k, v in rec.items()}          # one device-to-host copy per record, once per batch
         out = {"qposes_rollout": host["qposes_rollout"], "ctrl": host["ctrl"], "state_rewards": host["state_rewards"][:, :, 0]}
         ref = env._reference_clips
         rows = [np.repeat(np.hstack([np.asarray(ref.position[c], np.float32), np.asarray(ref.quaternion[c], np.float32),
                                      np.asarray(ref.joints[c], np.float32)]), int(spf), axis=0) for c in clips]
         out["qposes_ref"] = np.stack(rows)
+        if log_sensor_data:
+            out["joint_forces"] = host["joint_forces"].reshape(n, T - 1, -1, 6)
+            out["sensor_readings"] = host["sensor_readings"] if "sensor_readings" in host else np.zeros((n, T - 1, 0), np.float32)
         if log_metrics:
             m = host["rollout_metrics"]
             out["rollout_metrics"] = {f"{name}s": np.ascontiguousarray(m[:, :, j]) for j, name in enumerate(metrics)}
@@ -408,11 +429,13 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
     return generate_rollout
 
 
-def _step_loop(step: _PolicyStep, L, s, hdl, env_args, state_tab: int, ks: int, step_tab: int, kp: int, n: int, T: int) -> None:
-    """The T - 1 control steps: policy launches, tmjx_action_mode (inside step.launch), tmjx_step, tmjx_record_step x 2."""
+def _step_loop(step: _PolicyStep, L, s, hdl, env_args, state_tab: int, ks: int, step_tab: int, kp: int, n: int, T: int,
+               step_fn: str = "tmjx_step") -> None:
+    """The T - 1 control steps: policy launches, tmjx_action_mode (inside step.launch), tmjx_step (or tmjx_step_sensors), tmjx_record_step x 2."""
+    env_step = getattr(L, step_fn)
     for t in range(T - 1):
         step.launch()
-        _hip.check(L.tmjx_step(hdl, *env_args, s), "tmjx_step")
+        _hip.check(env_step(hdl, *env_args, s), step_fn)
         _hip.check(L.tmjx_record_step(step_tab, kp, n, t, T - 1, s), "tmjx_record_step")
         _hip.check(L.tmjx_record_step(state_tab, ks, n, t, T - 1, s), "tmjx_record_step")
 
@@ -451,11 +474,11 @@ def main(argv=None) -> int:
     from .utils import save_to_h5py
     argv = list(sys.argv[1:] if argv is None else argv)
     opts = dict(a.split("=", 1) for a in argv if "=" in a and a.split("=", 1)[0] in ("checkpoint", "clips", "seed", "out", "log_activations",
-                                                                                    "log_metrics", "step"))
+                                                                                    "log_metrics", "log_sensor_data", "step"))
     rest = [a for a in argv if not ("=" in a and a.split("=", 1)[0] in opts)]
     if "checkpoint" not in opts:
         print("usage: python -m track_mjx_amd.analysis.rollout checkpoint=<run dir | step dir> [data_path=...] [clips=all|a:b|i,j,k] [seed=42] "
-              "[out=<dir>] [log_activations=true] [log_metrics=true] [key=value config overrides ...]", file=sys.stderr)
+              "[out=<dir>] [log_activations=true] [log_metrics=true] [log_sensor_data=false] [key=value config overrides ...]", file=sys.stderr)
         return 2
     yes = lambda v: str(v).lower() in ("1", "true", "yes")     # noqa: E731
     path = opts["checkpoint"]
@@ -475,7 +498,8 @@ def main(argv=None) -> int:
     env = create_environment(cfg, 1, "cuda")
     seed = int(opts.get("seed", 42))
     log_act, log_met = yes(opts.get("log_activations", "true")), yes(opts.get("log_metrics", "true"))
-    gen = create_rollout_generator(cfg, env, fn, model=fn.model, log_activations=log_act, log_metrics=log_met)
+    log_sens = yes(opts.get("log_sensor_data", "false"))
+    gen = create_rollout_generator(cfg, env, fn, model=fn.model, log_activations=log_act, log_metrics=log_met, log_sensor_data=log_sens)
     clips = _parse_clips(opts.get("clips", "all"), env._n_clips)
     out_dir = opts.get("out", os.path.join(step_dir, "rollouts"))
     os.makedirs(out_dir, exist_ok=True)
@@ -483,6 +507,12 @@ def main(argv=None) -> int:
                                                                         if os.path.basename(os.path.normpath(step_dir)).isdigit() else -1),
                    "checkpoint": str(step_dir), "model": fn.model, "trained_gemm_inputs": fn.trained_gemm_inputs,
                    "rollout_gemm_inputs": "f32"}
+    if log_sens:
+        table = env.walker.sensor_table()
+        meta_common.update(sensor_names=",".join(t[0] for t in table), sensor_adr=np.array([t[1] for t in table], np.int64),
+                           sensor_dim=np.array([t[2] for t in table], np.int64),
+                           joint_forces_convention="cfrc_ext: per body [torque(3), force(3)] of the contact forces, world frame, about "
+                                                   "subtree_com[body_rootid] (mj_rnePostConstraint); values of the control step's last substep")
     for i in range(0, len(clips), CLIPS_PER_BATCH):
         chunk = clips[i:i + CLIPS_PER_BATCH]
         res = gen(chunk, seed=seed)

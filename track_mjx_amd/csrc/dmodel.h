@@ -14,6 +14,8 @@
 #define TM_MAXG 8     // contact groups (distinct paw bodies)
 #define TM_MAXIDX 40
 #define TM_NMETRIC 20
+#define TM_MAXS 8       // sensors (blob entries sensor_*)
+#define TM_MAXSITE 8    // sites a sensor refers to (blob entries site_*)
 
 struct DModel {
   int nbody, njnt, nq, nv, nu, ncon, nlim, nefc, ngroup, nnz;
@@ -120,6 +122,16 @@ struct DModel {
   int has_bias;
   float act_b0[TM_MAXU], act_b1[TM_MAXU];
   int act_mqpos[128];
+  // sensors (optional blob entries site_* / sensor_*, tools/compile_model.py; absent: nsensor = 0).  Read only by the recording kernel's sensor
+  // stage (wave_physics.h: tmw_sensor_stage); kept BEHIND every field above so that the product kernel's offsets stay what they were.
+  // sensor_type: 0 accelerometer, 1 velocimeter, 2 gyro (object = site), 3 subtreelinvel (object = body); every type is 3 wide
+  int nsensor, nsensordata, nsite;
+  int sensor_type[TM_MAXS], sensor_objid[TM_MAXS], sensor_adr[TM_MAXS];
+  int site_bodyid[TM_MAXSITE];
+  float site_pos[TM_MAXSITE][3], site_quat[TM_MAXSITE][4];
+  // subtree_com[body_rootid[b]] of the bodies OUTSIDE the moving tree (static: their roots' inertial frame origins, fixed in the world; the
+  // moving tree's is the kernel's centre of mass): the point cfrc_ext rows are taken about
+  float body_static_com[TM_MAXB][3];
 };
 
 enum { RW_TOO_FAR, RW_BAD_POSE, RW_BAD_QUAT, RW_CTRL_W, RW_CTRL_DIFF_W, RW_ENERGY_W, RW_POS_W, RW_QUAT_W, RW_JOINT_W,

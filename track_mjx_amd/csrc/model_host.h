@@ -429,6 +429,40 @@ inline bool build_dmodel(const void *blob, size_t nbytes, DModel &m, std::string
     while (r0 > 1 && m.body_parentid[r0] == r0 - 1) r0--;
     m.fix_p[m.n_fix] = p; m.fix_r0[m.n_fix] = r0; m.fix_adr[++m.n_fix] = first + nch;
   }
+  // sensors: optional entries (a blob without them has none); counts, types and ids are checked here
+  {
+    const int ns = R.count("sensor_type"), nsi = R.count("site_bodyid");
+    if (ns >= 0) {
+      if (ns < 1 || ns > TM_MAXS) { err = "sensor_type: 1 .. " + std::to_string(TM_MAXS) + " sensors are supported"; return false; }
+      if (nsi < 0 || nsi > TM_MAXSITE) { err = "site_bodyid: 0 .. " + std::to_string(TM_MAXSITE) + " sites are supported"; return false; }
+      m.nsensor = ns; m.nsite = nsi;
+      if (!R.ints("sensor_type", m.sensor_type, ns) || !R.ints("sensor_objid", m.sensor_objid, ns) || !R.ints("sensor_adr", m.sensor_adr, ns) ||
+          (nsi > 0 && (!R.ints("site_bodyid", m.site_bodyid, nsi) || !R.floats("site_pos", &m.site_pos[0][0], nsi * 3) ||
+                       !R.floats("site_quat", &m.site_quat[0][0], nsi * 4)))) { err = R.err; return false; }
+      int adr = 0;
+      for (int s = 0; s < ns; s++) {
+        const int t = m.sensor_type[s], o = m.sensor_objid[s];
+        if (t < 0 || t > 3) { err = "sensor_type: unsupported sensor type code " + std::to_string(t); return false; }
+        if (t < 3 && (o < 0 || o >= nsi)) { err = "sensor_objid: site id out of range"; return false; }
+        if (t == 3 && (o < 1 || o >= m.nbody)) { err = "sensor_objid: body id out of range"; return false; }
+        if (m.sensor_adr[s] != adr) { err = "sensor_adr: sensors must be packed in order (3 floats each)"; return false; }
+        adr += 3;
+      }
+      m.nsensordata = adr;
+      for (int i = 0; i < nsi; i++) if (m.site_bodyid[i] < 0 || m.site_bodyid[i] >= m.nbody) { err = "site_bodyid: body id out of range"; return false; }
+    } else if (nsi >= 0 || R.count("sensor_objid") >= 0 || R.count("sensor_adr") >= 0) {
+      err = "site_* / sensor_* entries without sensor_type"; return false;
+    }
+    for (int b = 1; b < m.nbody; b++) {
+      if (m.body_moving[b]) continue;
+      const int r = rootid[b];      // a static root hangs off the world: its frame is its body_pos / body_quat
+      const float *q = m.body_quat[r], *ip = m.body_ipos[r];
+      float X[9] = {q[0] * q[0] + q[1] * q[1] - q[2] * q[2] - q[3] * q[3], 2.f * (q[1] * q[2] - q[0] * q[3]), 2.f * (q[1] * q[3] + q[0] * q[2]),
+                    2.f * (q[1] * q[2] + q[0] * q[3]), q[0] * q[0] - q[1] * q[1] + q[2] * q[2] - q[3] * q[3], 2.f * (q[2] * q[3] - q[0] * q[1]),
+                    2.f * (q[1] * q[3] - q[0] * q[2]), 2.f * (q[2] * q[3] + q[0] * q[1]), q[0] * q[0] - q[1] * q[1] - q[2] * q[2] + q[3] * q[3]};
+      for (int k = 0; k < 3; k++) m.body_static_com[b][k] = m.body_pos[r][k] + X[3 * k] * ip[0] + X[3 * k + 1] * ip[1] + X[3 * k + 2] * ip[2];
+    }
+  }
   // LDS map of the wave kernel: one source of truth (wave_layout.h); only the total is kept in the model
   m.lds_floats = make_wave_layout(m).lds_floats;
   return true;

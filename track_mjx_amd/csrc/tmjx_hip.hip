@@ -40,7 +40,7 @@ struct tmjx_model {
 // workspace words in front of the record: window partials (2 nu rows) + post partials (16 rows), each n_env wide
 #define WAVE_REC_OFFSET(m, n) ((size_t)(2 * (m)->h.nu + 16) * (size_t)(n))
 static int launch_wave(const tmjx_model *m, float *state, const float *action, int nsub, int do_euler, float *ws, int n_env, hipStream_t stream,
-                       float *rec = nullptr);
+                       float *rec = nullptr, float *sensordata = nullptr, float *cfrc_ext = nullptr);
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -223,6 +223,10 @@ __global__ __launch_bounds__(64) void k_rec_out(const DModel *__restrict__ mp, f
 // flag of its own (track_mjx_amd/hip.py) — and launched through this entry
 extern "C" void tmjx_internal_launch_physics_wave(int rodent, int cnt, size_t lds, hipStream_t stream, const DModel *mp, float *st, const float *action, int nsub,
                                                   int do_euler, float *ws_dump, int n, int e0, int rs, float *spill, int spill_stride);
+// the recording kernel of checkpoint roll-outs (K2 + the sensor stage on the last substep): csrc/tmjx_wave_sensors.hip
+extern "C" void tmjx_internal_launch_physics_wave_sensors(int rodent, int cnt, size_t lds, hipStream_t stream, const DModel *mp, float *st,
+                                                          const float *action, int nsub, int do_euler, float *ws_dump, int n, int e0, int rs,
+                                                          float *spill, int spill_stride, float *sensordata, float *cfrc_ext);
 
 __global__ void k_reset_pre(const DModel *__restrict__ mp, float *st, int *is, const int *clip, const int *start, const float *qn,
                             const float *vn, float *ws, int n) {
@@ -389,9 +393,13 @@ int tmjx_clips_share(tmjx_model *m, const tmjx_model *owner) {
 }
 
 static int launch_wave(const tmjx_model *m, float *state, const float *action, int nsub, int do_euler, float *ws, int n_env, hipStream_t stream,
-                       float *rec) {
+                       float *rec, float *sensordata, float *cfrc_ext) {
   // the compile-time (rodent) kernel uses the chain layout, the run-time one the generic layout of the same dims
   size_t lds = (size_t)(m->rodent ? m->h.lds_floats : tmjx_host::make_wave_layout(m->h, false).lds_floats) * sizeof(float);
+  if (cfrc_ext) {   // recording kernel: the sensor stage's scratch behind the product image (wave_physics.h: TmwSens)
+    lds = (size_t)tmw_sens_layout(m->rodent ? tmjx_host::make_wave_layout(m->h) : tmjx_host::make_wave_layout(m->h, false)).end * sizeof(float);
+    if (lds > 64 * 1024) return fail(TMJX_EINVAL, "the sensor stage needs more than 64 KiB of LDS per env for this model");
+  }
   if (const char *pad = getenv("TMJX_LDS_PAD_KB")) lds += (size_t)atoi(pad) * 1024;  // occupancy experiments only
   const int sstride = WAVE_SPILL_STRIDE(m);
   if (m->rodent && m->mspill_envs < n_env) {
@@ -414,7 +422,9 @@ static int launch_wave(const tmjx_model *m, float *state, const float *action, i
   float *st = rec ? rec : state;
   for (int p = 0; p < parts; p++) {
     int cnt = n_env / parts, e0 = p * cnt;
-    tmjx_internal_launch_physics_wave(m->rodent ? 1 : 0, cnt, lds, stream, m->d, st, action, nsub, do_euler, ws, n_env, e0, rs, spill, sstride);
+    if (cfrc_ext) tmjx_internal_launch_physics_wave_sensors(m->rodent ? 1 : 0, cnt, lds, stream, m->d, st, action, nsub, do_euler, ws, n_env, e0, rs, spill,
+                                                            sstride, sensordata, cfrc_ext);
+    else tmjx_internal_launch_physics_wave(m->rodent ? 1 : 0, cnt, lds, stream, m->d, st, action, nsub, do_euler, ws, n_env, e0, rs, spill, sstride);
   }
   if (rec) hipLaunchKernelGGL(k_rec_out, dim3((n_env + 63) / 64, (m->h.s_prev_ctrl - m->h.s_qpos + REC_ROWS_PER_THREAD - 1) / REC_ROWS_PER_THREAD), dim3(64), 0, stream, m->d, state, (const float *)rec, n_env, rs);
   return TMJX_OK;
@@ -502,6 +512,46 @@ int tmjx_step(tmjx_model *m, float *state, int32_t *istate, const float *action,
 #else
   return fail(TMJX_EINVAL, "lane-per-env implementation not built");
 #endif
+}
+
+// ---- sensor outputs of checkpoint roll-outs (include/tmjx.h): the recording kernel in place of K2, everything else as above
+int tmjx_sensor_info(const tmjx_model *m, int *nsensordata, int *nbody) {
+  if (!m || !nsensordata || !nbody) return fail(TMJX_EINVAL, "null argument");
+  *nsensordata = m->h.nsensordata; *nbody = m->h.nbody;
+  return TMJX_OK;
+}
+
+static int check_sensor_args(const tmjx_model *m, const float *sensordata, const float *cfrc_ext) {
+  if (!m->wave) return fail(TMJX_EINVAL, "sensor outputs need the wave-per-env implementation");
+  if (!cfrc_ext) return fail(TMJX_EINVAL, "cfrc_ext is null (it is written for every model: [nbody * 6][n_env])");
+  if (!sensordata && m->h.nsensordata > 0) return fail(TMJX_EINVAL, "sensordata is null but the model has " + std::to_string(m->h.nsensordata) + " sensordata floats");
+  return TMJX_OK;
+}
+
+int tmjx_physics_sensors(tmjx_model *m, float *state, const float *action, int n_substeps, float *sensordata, float *cfrc_ext, float *workspace,
+                         int n_env, void *stream) {
+  if (!m || !state) return fail(TMJX_EINVAL, "null argument");
+  if (n_env < 1 || n_substeps < 1) return fail(TMJX_EINVAL, "bad n_env / n_substeps (the sensor stage runs on the last substep: n_substeps >= 1)");
+  if (int rc = check_sensor_args(m, sensordata, cfrc_ext)) return rc;
+  if (int rc = launch_wave(m, state, action, n_substeps, 1, workspace, n_env, (hipStream_t)stream, nullptr, sensordata, cfrc_ext)) return rc;
+  return check_launch("k_physics_wave_sensors");
+}
+
+int tmjx_step_sensors(tmjx_model *m, float *state, int32_t *istate, const float *action, float *obs, float *reward, float *done,
+                      float *truncation, float *metrics, float *workspace, float *sensordata, float *cfrc_ext, int n_env, void *stream) {
+  if (!m || !state || !istate || !action || !obs || !reward || !done || !truncation || !metrics || !workspace) return fail(TMJX_EINVAL, "null argument");
+  if (n_env < 1) return fail(TMJX_EINVAL, "n_env must be >= 1");
+  if (!m->h.clip_pos) return fail(TMJX_EINVAL, "tmjx_clips_upload has not been called");
+  if (int rc = check_sensor_args(m, sensordata, cfrc_ext)) return rc;
+  // tmjx_step's launches; every repeat's physics writes the outputs, so the last repeat's last substep is what is left in them
+  const int R = m->action_repeat;
+  for (int r = 0; r < R; r++) {
+    if (int rc = launch_wave(m, state, action, m->h.n_frames, 1, (float *)nullptr, n_env, (hipStream_t)stream, wave_record(m, workspace, n_env),
+                             sensordata, cfrc_ext)) return rc;
+    launch_k3(m, state, istate, action, obs, reward, done, truncation, metrics, workspace, n_env, (hipStream_t)stream,
+              TM_REP(R, r == 0, r == R - 1));
+  }
+  return check_launch("k_step_sensors(wave)");
 }
 
 // the physics part of tmjx_step alone (record transposes + K2 with the configured n_frames): what bench.py brackets with HIP events

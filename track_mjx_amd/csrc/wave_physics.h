@@ -2496,3 +2496,237 @@ TM_DEV void tmw_dump(WCtx &c, const WLayout &K, float *ws) {
 #undef WDUMP
   TMW_SYNC();
 }
+
+// ------------------------------------------------------------------------------------------ sensor stage (recording kernel only)
+// sensordata and cfrc_ext of one substep, for checkpoint roll-outs (csrc/tmjx_wave_sensors.hip: k_physics_wave_sensors).  Runs between the
+// solve and Euler of the control step's LAST substep (MJX: the sensors of mjx.step = forward, then euler): qpos / qvel are the substep's starting
+// state, qacc the solve's iterate, efc_force is formed from Jaref / efc_D as tmw_dump does.  Everything it needs besides those is rebuilt here —
+// body frames (pointer jumping over DModel::scan_parent), cvel, cdof_dot and cacc (prefix sums along the dof tree: tmw_chain_scan on the
+// rodent) — into LDS BEHIND the product image (TmwSens, at lds_floats rounded up): the product image is only READ, so the rest of the
+// substep runs on exactly the words it would have had.  The product kernel never calls this.
+//   cacc      = [0, -gravity] + sum over the dof path of (cdof_dot qvel + cdof qacc)              (mj_rnePostConstraint)
+//   site sensors (local frame, mj_objectVelocity / mj_objectAcceleration with flg_local): with d = site_xpos - subtree_com[root],
+//     gyro = R^T w, velocimeter = R^T (v - d x w), accelerometer = R^T (a - d x alpha) + gyro x velocimeter
+//   subtreelinvel[b] = sum over the subtree [b, b + body_nsub[b]) of m_k (v_k - (xipos_k - com) x w_k) / its mass
+//   cfrc_ext[b] = [torque, force] about subtree_com[root(b)]: per contact the pyramid rows decoded to the contact frame (normal = sum of the
+//     four rows, tangent j = (f[2j] - f[2j+1]) mu), rotated to world, taken at the contact point; minus on geom 1's body, plus on geom 2's; the
+//     world body (row 0) is skipped.  One lane per body adds up the contacts: no atomics.
+struct TmwSens { int xa, xb, xip, dsa, dsb, cvel, cacc, con, end; };
+constexpr TmwSens tmw_sens_layout(const WLayout &K) {   // (constexpr: callable on the host too)
+  TmwSens s{0, 0, 0, 0, 0, 0, 0, 0, 0};
+  int l = (K.lds_floats + 3) & ~3;
+  s.xa = l; l += K.nbody * 8; s.xb = l; l += K.nbody * 8; s.xip = l; l += K.nbody * 3;
+  s.dsa = l; l += K.nv * TMW_DS; s.dsb = l; l += K.nv * TMW_DS;
+  s.cvel = l; l += K.nbody * 6; s.cacc = l; l += K.nbody * 6; s.con = l; l += K.ncon * 6;
+  s.end = l;
+  return s;
+}
+
+// inclusive prefix sums of 6-vectors along the dof tree, result at `a` (`b`: a second buffer for the generic layout's pointer jumping; the
+// entries' word 6 holds dof_parentid there)
+TM_DEV void tmw_sens_dofscan(WCtx &c, const WLayout &K, int a, int b) {
+  float *L = c.L; TMW_LANE_DECL
+  if (K.chains) { tmw_chain_scan(c, K, a); return; }
+  int R = K.nround_dof + (K.nround_dof & 1);
+  for (int r = 0; r < R; r++) {
+    const float *cur = L + ((r & 1) ? b : a);
+    float *nxt = L + ((r & 1) ? a : b);
+    TMW_FOR {
+      for (int i = lane; i < K.nv; i += 64) {
+        const float *s = cur + i * TMW_DS;
+        float v[6] = {s[0], s[1], s[2], s[3], s[4], s[5]};
+        int an = tm_f2i(s[6]);
+        if (an >= 0) { const float *sa = cur + an * TMW_DS; for (int k = 0; k < 6; k++) v[k] += sa[k]; an = tm_f2i(sa[6]); }
+        float *o = nxt + i * TMW_DS;
+        for (int k = 0; k < 6; k++) o[k] = v[k];
+        o[6] = tm_i2f(an);
+      }
+    }
+    TMW_SYNC();
+  }
+}
+
+// `sd`: [nsensordata][n] (may be null: a model without sensors), `cf`: [nbody * 6][n]; env c.e of a launch of c.n envs
+TM_DEV void tmw_sensor_stage(WCtx &c, const WLayout &K, float *sd, float *cf) {
+  TmwModel &m = *c.mp; float *L = c.L; TMW_LANE_DECL
+  const TmwSens S = tmw_sens_layout(K);
+  const float com[3] = {L[K.l_com], L[K.l_com + 1], L[K.l_com + 2]};
+  // (1) body frames relative to their scan ancestor (absolute for the world, the static bodies' roots and the free-joint body)
+  TMW_FOR {
+    for (int b = lane; b < K.nbody; b += 64) {
+      float t[3] = {m.body_pos[b][0], m.body_pos[b][1], m.body_pos[b][2]}, q[4] = {m.body_quat[b][0], m.body_quat[b][1], m.body_quat[b][2], m.body_quat[b][3]};
+      if (b == 0) { t[0] = t[1] = t[2] = 0.f; q[0] = 1.f; q[1] = q[2] = q[3] = 0.f; }
+      for (int jj = 0; b > 0 && jj < m.body_jntnum[b]; jj++) {
+        const int j = m.body_jntadr[b] + jj, qa = m.jnt_qposadr[j];
+        if (m.jnt_type[j] == 0) {
+          for (int k = 0; k < 3; k++) t[k] = L[K.l_qpos + qa + k];
+          for (int k = 0; k < 4; k++) q[k] = L[K.l_qpos + qa + 3 + k];
+          tm_normalize4(q);
+        } else {
+          float r[3], an[3], ql[4], q2[4], jpos[3] = {m.jnt_pos[j][0], m.jnt_pos[j][1], m.jnt_pos[j][2]};
+          const float jax[3] = {m.jnt_axis[j][0], m.jnt_axis[j][1], m.jnt_axis[j][2]};
+          tm_rotate(r, jpos, q);
+          for (int k = 0; k < 3; k++) an[k] = t[k] + r[k];
+          float ang = (L[K.l_qpos + qa] - m.qpos0[qa]) * 0.5f, sn, cs;
+          sincosf(ang, &sn, &cs);
+          ql[0] = cs; ql[1] = jax[0] * sn; ql[2] = jax[1] * sn; ql[3] = jax[2] * sn;
+          tm_quat_mul(q2, q, ql);
+          for (int k = 0; k < 4; k++) q[k] = q2[k];
+          tm_rotate(r, jpos, q);
+          for (int k = 0; k < 3; k++) t[k] = an[k] - r[k];
+        }
+      }
+      float *o = L + S.xa + b * 8;
+      o[0] = t[0]; o[1] = t[1]; o[2] = t[2]; o[3] = q[0]; o[4] = q[1]; o[5] = q[2]; o[6] = q[3]; o[7] = tm_i2f(b == 0 ? -1 : m.scan_parent[b]);
+    }
+  }
+  TMW_SYNC();
+  // (2) pointer jumping (an even number of rounds: the result is back in xa)
+  const int RB = K.nround_body + (K.nround_body & 1);
+  for (int r = 0; r < RB; r++) {
+    const float *cur = L + ((r & 1) ? S.xb : S.xa);
+    float *nxt = L + ((r & 1) ? S.xa : S.xb);
+    TMW_FOR {
+      for (int b = lane; b < K.nbody; b += 64) {
+        const float *s = cur + b * 8;
+        float t[3] = {s[0], s[1], s[2]}, q[4] = {s[3], s[4], s[5], s[6]};
+        int a = tm_f2i(s[7]);
+        if (a >= 0) {
+          const float *sa = cur + a * 8;
+          float qa[4] = {sa[3], sa[4], sa[5], sa[6]}, rt[3], q2[4];
+          tm_rotate(rt, t, qa);
+          for (int k = 0; k < 3; k++) t[k] = sa[k] + rt[k];
+          tm_quat_mul(q2, qa, q);
+          for (int k = 0; k < 4; k++) q[k] = q2[k];
+          a = tm_f2i(sa[7]);
+        }
+        float *o = nxt + b * 8;
+        o[0] = t[0]; o[1] = t[1]; o[2] = t[2]; o[3] = q[0]; o[4] = q[1]; o[5] = q[2]; o[6] = q[3]; o[7] = tm_i2f(a);
+      }
+    }
+    TMW_SYNC();
+  }
+  // (3) inertial frame origins; cdof * qvel into the first scan buffer
+  TMW_FOR {
+    for (int b = lane; b < K.nbody; b += 64) {
+      const float *s = L + S.xa + b * 8;
+      float r[3], ip[3] = {m.body_ipos[b][0], m.body_ipos[b][1], m.body_ipos[b][2]};
+      tm_rotate(r, ip, s + 3);
+      for (int k = 0; k < 3; k++) L[S.xip + b * 3 + k] = s[k] + r[k];
+    }
+    for (int i = lane; i < K.nv; i += 64) {
+      const float qv = L[K.l_qvel + i];
+      float *o = L + S.dsa + i * TMW_DS;
+      for (int k = 0; k < 6; k++) o[k] = L[K.l_cdof + i * 6 + k] * qv;
+      o[6] = tm_i2f(m.dof_parentid[i]);
+    }
+  }
+  TMW_SYNC();
+  tmw_sens_dofscan(c, K, S.dsa, S.dsb);
+  // (4) cvel of every body; cdof_dot = cvel(velocity parent) x cdof (zero for the free joint's translations), and the acceleration terms
+  // cdof_dot qvel + cdof qacc into the second scan buffer
+  TMW_FOR {
+    for (int b = lane; b < K.nbody; b += 64) {
+      const int ld = m.body_lastdof[b];
+      for (int k = 0; k < 6; k++) L[S.cvel + b * 6 + k] = ld >= 0 ? L[S.dsa + ld * TMW_DS + k] : 0.f;
+    }
+    for (int i = lane; i < K.nv; i += 64) {
+      float dd[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, cd[6];
+      for (int k = 0; k < 6; k++) cd[k] = L[K.l_cdof + i * 6 + k];
+      if (!m.dof_freetrans[i]) {
+        const int vp = m.dof_vpar[i];
+        float E[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (vp >= 0) for (int k = 0; k < 6; k++) E[k] = L[S.dsa + vp * TMW_DS + k];
+        tm_motion_cross(dd, E, cd);
+      }
+      const float qv = L[K.l_qvel + i], qa = TMW_QA(i);
+      float *o = L + S.dsb + i * TMW_DS;
+      for (int k = 0; k < 6; k++) o[k] = dd[k] * qv + cd[k] * qa;
+      o[6] = tm_i2f(m.dof_parentid[i]);
+    }
+  }
+  TMW_SYNC();
+  tmw_sens_dofscan(c, K, S.dsb, S.dsa);
+  // (5) cacc of every body; the world-frame force and the point of every contact (zero force: a contact outside the solver)
+  TMW_FOR {
+    for (int b = lane; b < K.nbody; b += 64) {
+      const int ld = m.body_lastdof[b];
+      for (int k = 0; k < 6; k++) L[S.cacc + b * 6 + k] = (k < 3 ? 0.f : -m.gravity[k - 3]) + (ld >= 0 ? L[S.dsb + ld * TMW_DS + k] : 0.f);
+    }
+    for (int cc = lane; cc < K.ncon; cc += 64) {
+      float f[4] = {0.f, 0.f, 0.f, 0.f};
+      const int row = TMW_CCROW(K)[cc];
+      if (row != 255) {
+        for (int k = 0; k < 4; k++) { const int kr = row + k; const float ja = L[K.l_Jaref + kr]; f[k] = ja < 0.f ? -L[K.l_efc_D + TMW_DIDX(kr)] * ja : 0.f; }
+      }
+      const float mu = TMW_MU(cc), fn = f[0] + f[1] + f[2] + f[3], f1 = (f[0] - f[1]) * mu, f2 = (f[2] - f[3]) * mu;
+      float fr[9];
+      tmw_get_con_frame(L, K, cc, fr);
+      tm_cross(fr + 6, fr, fr + 3);
+      for (int k = 0; k < 3; k++) {
+        L[S.con + cc * 6 + k] = fr[k] * fn + fr[3 + k] * f1 + fr[6 + k] * f2;
+        L[S.con + cc * 6 + 3 + k] = L[K.l_con_off + cc * 3 + k] + com[k];
+      }
+    }
+  }
+  TMW_SYNC();
+  // (6) outputs: cfrc_ext (one lane per body) and sensordata (one lane per sensor)
+  TMW_FOR {
+    for (int b = lane; b < K.nbody; b += 64) {
+      float w[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      if (b > 0) {
+        float cb[3];
+        for (int k = 0; k < 3; k++) cb[k] = m.body_moving[b] ? com[k] : m.body_static_com[b][k];
+        for (int cc = 0; cc < K.ncon; cc++) {
+          const float sg = (m.con_body2[cc] == b ? 1.f : 0.f) - (m.con_body1[cc] == b ? 1.f : 0.f);
+          if (sg == 0.f) continue;
+          const float *F = L + S.con + cc * 6;
+          float d[3] = {F[3] - cb[0], F[4] - cb[1], F[5] - cb[2]}, tq[3];
+          tm_cross(tq, d, F);
+          for (int k = 0; k < 3; k++) { w[k] += sg * tq[k]; w[3 + k] += sg * F[k]; }
+        }
+      }
+      for (int k = 0; k < 6; k++) cf[(size_t)(b * 6 + k) * (size_t)c.n + (size_t)c.e] = w[k];
+    }
+    for (int s = lane; sd && s < m.nsensor; s += 64) {
+      const int t = m.sensor_type[s], o = m.sensor_objid[s];
+      float out[3];
+      if (t == 3) {
+        float p[3] = {0.f, 0.f, 0.f}, mass = 0.f;
+        for (int k = o; k < o + m.body_nsub[o]; k++) {
+          const float mk = m.body_mass[k], *v = L + S.cvel + k * 6, *x = L + S.xip + k * 3;
+          float d[3] = {x[0] - com[0], x[1] - com[1], x[2] - com[2]}, dw[3];
+          tm_cross(dw, d, v);
+          for (int r = 0; r < 3; r++) p[r] += mk * (v[3 + r] - dw[r]);
+          mass += mk;
+        }
+        for (int r = 0; r < 3; r++) out[r] = p[r] / fmaxf(TM_MINVAL, mass);
+      } else {
+        const int b = m.site_bodyid[o];
+        const float *s8 = L + S.xa + b * 8;
+        float sp[3] = {m.site_pos[o][0], m.site_pos[o][1], m.site_pos[o][2]}, sq[4] = {m.site_quat[o][0], m.site_quat[o][1], m.site_quat[o][2], m.site_quat[o][3]};
+        float r[3], q[4], X[9], d[3];
+        tm_rotate(r, sp, s8 + 3);
+        tm_quat_mul(q, s8 + 3, sq);
+        tm_quat_to_mat(X, q);
+        for (int k = 0; k < 3; k++) d[k] = s8[k] + r[k] - (m.body_moving[b] ? com[k] : m.body_static_com[b][k]);
+        const float *v = L + S.cvel + b * 6, *a = L + S.cacc + b * 6;
+        float dw[3], lv[3], lw[3];
+        tm_cross(dw, d, v);
+        float vl[3] = {v[3] - dw[0], v[4] - dw[1], v[5] - dw[2]};
+        for (int k = 0; k < 3; k++) { lw[k] = X[k] * v[0] + X[3 + k] * v[1] + X[6 + k] * v[2]; lv[k] = X[k] * vl[0] + X[3 + k] * vl[1] + X[6 + k] * vl[2]; }
+        if (t == 0) {
+          float da[3], corr[3];
+          tm_cross(da, d, a);
+          float al[3] = {a[3] - da[0], a[4] - da[1], a[5] - da[2]};
+          tm_cross(corr, lw, lv);
+          for (int k = 0; k < 3; k++) out[k] = X[k] * al[0] + X[3 + k] * al[1] + X[6 + k] * al[2] + corr[k];
+        } else {
+          for (int k = 0; k < 3; k++) out[k] = t == 1 ? lv[k] : lw[k];
+        }
+      }
+      for (int k = 0; k < 3; k++) sd[(size_t)(m.sensor_adr[s] + k) * (size_t)c.n + (size_t)c.e] = out[k];
+    }
+  }
+  TMW_SYNC();
+}

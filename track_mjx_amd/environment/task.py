@@ -272,6 +272,48 @@ class MultiClipTracking:
         self._keep_a = a
         return self._state()
 
+    # ---- sensor outputs (checkpoint roll-outs with log_sensor_data: include/tmjx.h tmjx_step_sensors)
+    def sensor_info(self) -> tuple[int, int]:
+        """(nsensordata, nbody) of the model: the row counts of the two sensor output buffers ([nsensordata][n], [nbody * 6][n])."""
+        nsd, nb = C.c_int32(), C.c_int32()
+        _hip.check(self._L.tmjx_sensor_info(self._handle, C.byref(nsd), C.byref(nb)), "tmjx_sensor_info")
+        return nsd.value, nb.value
+
+    def sensor_buffers(self) -> tuple[torch.Tensor | None, torch.Tensor]:
+        """Freshly allocated (sensordata [nsensordata][n] or None for a model without sensors, cfrc_ext [nbody * 6][n]) on the env's device."""
+        nsd, nb = self.sensor_info()
+        f32 = dict(dtype=torch.float32, device=self.device)
+        return (torch.zeros((nsd, self.num_envs), **f32) if nsd else None), torch.zeros((nb * 6, self.num_envs), **f32)
+
+    def _check_sensor_bufs(self, sensordata, cfrc_ext) -> None:
+        nsd, nb = self.sensor_info()
+        for name, t, rows in (("sensordata", sensordata, nsd), ("cfrc_ext", cfrc_ext, nb * 6)):
+            if rows == 0 and t is None:
+                continue
+            dev = torch.device(self.device)
+            if (t is None or t.dtype != torch.float32 or t.device.type != dev.type or (dev.index is not None and t.device.index != dev.index)
+                    or not t.is_contiguous() or t.numel() < rows * self.num_envs):
+                raise ValueError(f"{name} must be a contiguous float32 tensor of >= {rows} x {self.num_envs} floats on {self.device}")
+
+    def step_sensors(self, action_rows: torch.Tensor, sensordata: torch.Tensor | None, cfrc_ext: torch.Tensor) -> None:
+        """step() with the action as contiguous [nu][n] device rows, through the recording physics kernel: the same state / obs / reward /
+        done / metrics as step(), plus the last substep's sensordata ([nsensordata][n]) and cfrc_ext ([nbody * 6][n]) written into the given
+        preallocated buffers (sensor_buffers()).  One C-ABI call, no torch op (a roll-out calls tmjx_step_sensors itself, with raw pointers)."""
+        self._check_sensor_bufs(sensordata, cfrc_ext)
+        with torch.cuda.device(self.device):
+            _hip.check(self._L.tmjx_step_sensors(self._handle, _ptr(self.state_buf), _ptr(self.istate_buf), _ptr(action_rows), _ptr(self.obs_buf),
+                                                 _ptr(self.reward_buf), _ptr(self.done_buf), _ptr(self.trunc_buf), _ptr(self.metrics_buf),
+                                                 _ptr(self.workspace), _ptr(sensordata), _ptr(cfrc_ext), self.num_envs, self._stream()),
+                       "tmjx_step_sensors")
+        self._keep_a = action_rows
+
+    def physics_sensors(self, action_rows: torch.Tensor | None, n_substeps: int, sensordata: torch.Tensor | None, cfrc_ext: torch.Tensor) -> None:
+        """physics() through the recording kernel (tests)."""
+        self._check_sensor_bufs(sensordata, cfrc_ext)
+        with torch.cuda.device(self.device):
+            _hip.check(self._L.tmjx_physics_sensors(self._handle, _ptr(self.state_buf), _ptr(action_rows), int(n_substeps), _ptr(sensordata),
+                                                    _ptr(cfrc_ext), _ptr(self.workspace), self.num_envs, self._stream()), "tmjx_physics_sensors")
+
     # ---- K2 / K3 alone (tests, profiling)
     def physics(self, action_rows: torch.Tensor | None, n_substeps: int) -> None:
         with torch.cuda.device(self.device):

@@ -15,9 +15,10 @@ _PKG = Path(__file__).resolve().parent
 SO_PATH = Path(os.environ.get("TMJX_SO", str(_PKG / "libtmjx_hip.so")))  # TMJX_SO: alternative build (profiling)
 CSRC = _PKG / "csrc"
 SOURCES = (CSRC / "tmjx_hip.hip", CSRC / "tmjx_bf16.hip", CSRC / "tmjx_wave.hip", CSRC / "tmjx_chain.hip", CSRC / "tmjx_lstm.hip",
-           CSRC / "tmjx_rollout.hip")
+           CSRC / "tmjx_rollout.hip", CSRC / "tmjx_wave_sensors.hip")
 # per-source compiler flags: the physics kernel's unit is built without machine LICM (csrc/tmjx_wave.hip says why)
-SOURCE_FLAGS = {"tmjx_wave.hip": ("-mllvm", "-disable-machine-licm")}
+SOURCE_FLAGS = {"tmjx_wave.hip": ("-mllvm", "-disable-machine-licm"),
+                "tmjx_wave_sensors.hip": ("-mllvm", "-disable-machine-licm")}      # (the recording kernel: the same loop body)
 
 
 class TmjxError(RuntimeError):
@@ -41,6 +42,7 @@ EXPORTS = ("tmjx_model_create", "tmjx_model_destroy", "tmjx_layout", "tmjx_clips
            "tmjx_chain_rows", "tmjx_chain_fwd_ok", "tmjx_chain_fwd", "tmjx_chain_bwd_ok", "tmjx_chain_bwd",
            "tmjx_lstm_hidden_ok", "tmjx_lstm_seq_fwd", "tmjx_lstm_seq_bwd",
            "tmjx_record_check", "tmjx_record_step", "tmjx_latent_concat_det", "tmjx_action_mode",
+           "tmjx_sensor_info", "tmjx_physics_sensors", "tmjx_step_sensors",
            "tmjx_debug_rows", "tmjx_last_error", "tmjx_version")
 
 
@@ -242,6 +244,9 @@ def load(path: Path):
     sig.setdefault("tmjx_step", [None, None])[0] = [vp, fp, vp, fp, fp, fp, fp, fp, fp, fp, C.c_int, vp]
     sig.setdefault("tmjx_physics", [None, None])[0] = [vp, fp, fp, C.c_int, fp, C.c_int, vp]
     sig.setdefault("tmjx_physics_step", [None, None])[0] = [vp, fp, fp, fp, C.c_int, vp]
+    sig.setdefault("tmjx_sensor_info", [None, None])[0] = [vp, ip, ip]
+    sig.setdefault("tmjx_physics_sensors", [None, None])[0] = [vp, fp, fp, C.c_int, fp, fp, fp, C.c_int, vp]
+    sig.setdefault("tmjx_step_sensors", [None, None])[0] = [vp, fp, vp, fp, fp, fp, fp, fp, fp, fp, fp, fp, C.c_int, vp]
     sig.setdefault("tmjx_forward", [None, None])[0] = [vp, fp, fp, C.c_int, vp]
     sig.setdefault("tmjx_reward_obs", [None, None])[0] = [vp, fp, vp, fp, fp, fp, fp, fp, fp, fp, C.c_int, vp]
     sig.setdefault("tmjx_reward_frame", [None, None])[0] = [vp, fp, vp, fp] + [fp] * 5 + [fp] * 5 + [C.c_int, vp]

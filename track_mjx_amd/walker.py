@@ -3,7 +3,8 @@
 Reference: track_mjx/environment/walker/rodent.py:16-114 (constructor arguments, name -> id
 tables) and walker/base.py:70-88 (index properties).  The MuJoCo compile step is replaced by
 pre-compiled model blobs (tools/compile_model.py), one per (torque_actuators, rescale_factor)
-pair in `BLOBS` (binary `.tmjx`, or its lossless text form `.tmjx.txt`: blob.py):
+pair in `BLOBS` (binary `.tmjx`, or its lossless text form `.tmjx.txt`: blob.py; the sensor entries, when the model has sensors, in the text
+side file `<stem>.sensors.tmjx.txt`, appended to the loaded entries):
   - (True, 0.9)  `assets/rodent_model.tmjx`: the torque-actuator rewrite and the 0.9 rescale of
     rodent-full-clips.yaml:116-117 (the default walker of both named configurations);
   - (False, 0.8) `assets/rodent_model_pos080.tmjx.txt`: rodent.xml's position servos kept as written
@@ -54,7 +55,15 @@ class Rodent:
         self._body_names = list(body_names)
         self._end_eff_names = list(end_eff_names)
         self.model = _blob.load(self.blob_path)
-        self.names = {"body": {}, "joint": {}, "actuator": {}}
+        # sensors (tools/compile_model.py sensor_entries): a text side file <stem>.sensors.tmjx.txt appended behind the blob's own entries
+        sens = _ASSETS / f"{_blob.stem(fname)}.sensors{_blob.TEXT_SUFFIX}"
+        if sens.exists():
+            extra = _blob.load(sens)
+            clash = [k for k in extra if k in self.model]
+            if clash:
+                raise ValueError(f"{sens.name}: entries {clash} are already in {fname}")
+            self.model.update(extra)
+        self.names = {"body": {}, "joint": {}, "actuator": {}, "site": {}, "sensor": {}}   # site / sensor: blobs that carry sensors
         with open(_ASSETS / f"{_blob.stem(fname)}.names.txt") as f:
             for line in f:
                 kind, idx, name = line.split()
@@ -62,6 +71,20 @@ class Rodent:
         dims = self.model["dims"]
         self.nbody, self.njnt, self.nq, self.nv, self.nu, self.ncon = (int(x) for x in dims)
         self._initialize_indices()
+
+    def sensor_table(self) -> "list[tuple[str, int, int]]":
+        """(name, sensordata address, width) of every sensor of the blob in sensordata order; [] for a blob without sensors."""
+        if "sensor_adr" not in self.model:
+            return []
+        names = sorted(self.names["sensor"], key=self.names["sensor"].get)
+        adr = [int(a) for a in self.model["sensor_adr"]]
+        ends = adr[1:] + [self.nsensordata]
+        return [(n, a, e - a) for n, a, e in zip(names, adr, ends)]
+
+    @property
+    def nsensordata(self) -> int:
+        """Floats of sensordata per env (every supported sensor type is 3 wide: tools/compile_model.py SENSOR_DIM)."""
+        return 3 * len(self.model["sensor_adr"]) if "sensor_adr" in self.model else 0
 
     def _initialize_indices(self) -> None:
         self._joint_idxs = np.array([self.names["joint"][j] for j in self._joint_names], dtype=np.int32)
