@@ -59,6 +59,23 @@ int tmjx_layout(const tmjx_model *m, tmjx_layout_t *out);
  * brax EpisodeWrapper's step counter / truncation at `episode_length`, and the (LSTM)AutoResetWrapperTracking restore on done).  Only
  * the two constants change; the clip table of the handle stays resident.  Blocking; not to be called with launches in flight. */
 int tmjx_set_wrappers(tmjx_model *m, int episode_length, int auto_reset);
+/* What tmjx_step / tmjx_step_sensors do, after the last action repeat, with an env whose step ended with done set (terminated or truncated):
+ *   TMJX_DONE_NONE   nothing: the env keeps stepping from where it is (tmjx_set_wrappers(m, L, 0));
+ *   TMJX_DONE_RESET  (LSTM)AutoResetWrapperTracking: physics state, observation and prev_ctrl <- the snapshot of the last tmjx_reset
+ *                    (tmjx_set_wrappers(m, L, 1));
+ *   TMJX_DONE_ALIGN  AutoAlignWrapperTracking (track_mjx/environment/wrappers.py:328-381): qpos <- position | quaternion | joints and
+ *                    qvel <- velocity | angular_velocity | joints_velocity of the clip frame the step computed its reward against
+ *                    (floor(time * mocap_hz + start_frame), clamped to the clip's last frame), no noise; kinematics on that state (xpos, torso
+ *                    xmat); the observation rebuilt from it with the unchanged clip / start frame.  time is not rewound; act, qacc_warmstart,
+ *                    qfrc_actuator, prev_ctrl, the action buffer, reward, done, truncation and metrics stay those of the terminated step.
+ *                    The step counter is zeroed by the next step's prologue, as under the other policies.  Envs that are not done come out
+ *                    bit for bit as under TMJX_DONE_NONE.  Needs the wave-per-env implementation and tmjx_clips_upload_velocities; where K3
+ *                    runs as one kernel (tmjx_reward_frame, tmjx_reward_obs without a workspace) the policy is refused with an error.
+ * tmjx_set_wrappers sets NONE / RESET as its auto_reset argument says; call this after it.  Blocking; not with launches in flight. */
+#define TMJX_DONE_NONE 0
+#define TMJX_DONE_RESET 1
+#define TMJX_DONE_ALIGN 2
+int tmjx_set_done_policy(tmjx_model *m, int policy);
 /* `action_repeat` of wrappers.wrap (track_mjx/environment/wrappers.py:21,43 -> brax EpisodeWrapper.step [3P]): tmjx_step then runs the
  * tracking env's own step `action_repeat` times with the same action (no termination check in between), returns the SUM of the repeats'
  * rewards, advances the episode's step counter by `action_repeat`, and takes observation / done / truncation / metrics from the last
@@ -495,6 +512,9 @@ typedef struct tmjx_rollout_store_t {
   float *obs_dst2;      /* a third row-major destination (the acting policy's staging copy of the new observation), may be NULL */
 } tmjx_rollout_store_t;
 int tmjx_rollout_store(const tmjx_rollout_store_t *s, void *stream);
+/* The two ReferenceClip leaves only TMJX_DONE_ALIGN reads: velocity (C,F,3) and joints_velocity (C,F,nv-6), HOST pointers, float32, for the
+ * table already uploaded on this handle (same C, F).  A later tmjx_clips_upload drops them; tmjx_clips_share shares them when the owner has them. */
+int tmjx_clips_upload_velocities(tmjx_model *m, const float *velocity, const float *joints_velocity, int n_clips, int n_frames);
 /* `m` reads `owner`'s resident clip table instead of holding a copy of its own (the env groups of one rank: one upload per rank).  `owner`
  * must outlive every launch of `m`. */
 int tmjx_clips_share(tmjx_model *m, const tmjx_model *owner);

@@ -22,8 +22,16 @@ TMJX_RECORD_SOA streams record: `sensor_readings` [T-1, nsensordata] and `joint_
 of the reference; values of the last substep's forward, like the reference's).  The roll-out env has no auto-reset; on an auto-reset handle
 the values would be those of the physics that ran, before K3 restores a done env.
 
+align_on_fail (AutoAlignWrapperTracking, environment/wrappers.py:328-381): the env steps under the align done-policy (tmjx_set_done_policy), so
+a clip is tracked from frame 0 to its end whatever happens on the way: an env that terminates (fell, too far, bad pose, NaN) is put onto the
+reference pose of the frame it has reached, inside the same tmjx_step, and goes on.  The record gains `aligned` [T-1] (bool: step t ended with a
+re-alignment, so qposes_rollout[t + 1] is the clip's pose) and `n_alignments` (their count: the clip's failure count); the LSTM policy's carry is
+zeroed where an alignment happened (tmjx_lstm_seq_fwd's reset flags = the env's done buffer).  Off by default: without it the records are what
+they were.
+
 CLI:  python -m track_mjx_amd.analysis.rollout checkpoint=<run dir | step dir> [data_path=...] [clips=all|a:b|i,j,k] [seed=42] [out=<dir>]
-      [log_activations=true] [log_metrics=true] [log_sensor_data=false]    ->  <out>/clip_<idx>.h5 (save_to_h5py layout + a `meta` group)
+      [log_activations=true] [log_metrics=true] [log_sensor_data=false] [align_on_fail=false]
+      ->  <out>/clip_<idx>.h5 (save_to_h5py layout + a `meta` group)
 """
 from __future__ import annotations
 
@@ -128,7 +136,8 @@ class _PolicyStep:
     """Preallocated buffers and the launch sequence of one deterministic policy step for `n` envs reading the env's raw observation
     buffer obs_soa [W][n]."""
 
-    def __init__(self, rp: RolloutPolicy, n: int, obs_soa: torch.Tensor, record: bool = True):
+    def __init__(self, rp: RolloutPolicy, n: int, obs_soa: torch.Tensor, record: bool = True, carry_reset: torch.Tensor | None = None):
+        """`carry_reset` [n] float32 (LSTM policy): where it is non-zero when the step is launched, the row's (h, c) are zeroed first."""
         pol, dev = rp.policy, rp.device
         self.rp, self.n, self.obs_soa = rp, int(n), obs_soa
         self.L = _hip.lib()
@@ -179,7 +188,7 @@ class _PolicyStep:
                 hk, ck = self.h[:, k], self.c[:, k]
                 wh = pol.w_hh[k].detach().contiguous()
                 self._keep(wh)
-                args = _hip.LstmFwd(_p(self.xg), 4 * H, _p(wh), H, _p(pol.b_hh[k]), _p(hk), _p(ck), Lk * H, None, 0, _p(hk), _p(ck), Lk * H, None, None, 1, n, H)
+                args = _hip.LstmFwd(_p(self.xg), 4 * H, _p(wh), H, _p(pol.b_hh[k]), _p(hk), _p(ck), Lk * H, _p(carry_reset), n, _p(hk), _p(ck), Lk * H, None, None, 1, n, H)
                 self._keep(args)
                 self.calls.append(("tmjx_lstm_seq_fwd", (C.byref(args),)))
                 a, lda = hk, Lk * H
@@ -273,7 +282,8 @@ def _upload_table(streams: Sequence, n: int, T: int, dev) -> torch.Tensor:
 
 # ---------------------------------------------------------------------------------------------------------------- generator
 def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, model: str = "mlp", log_activations: bool = False,
-                             log_metrics: bool = False, log_sensor_data: bool = False, clips_per_batch: int = CLIPS_PER_BATCH):
+                             log_metrics: bool = False, log_sensor_data: bool = False, clips_per_batch: int = CLIPS_PER_BATCH,
+                             align_on_fail: bool = False):
     """rollout.py:73-269.  Returns generate_rollout(clip_idx=None, seed=42): one clip (int / None) -> dict of arrays; a sequence of clips -> the
     same dict with a leading [N] axis (batches larger than `clips_per_batch` run in chunks)."""
     if log_sensor_data and not hasattr(environment, "sensor_buffers"):
@@ -301,13 +311,25 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
         raise ValueError("a roll-out needs clip_length * steps_for_cur_frame >= 2")
     envs: dict = {}
 
+    policy = "align" if align_on_fail else "none"
+    if align_on_fail and not hasattr(env0, "configure_wrappers"):
+        raise NotImplementedError(f"align_on_fail: {type(env0).__name__} has no done-policy to switch (MultiClipTracking.configure_wrappers)")
+
+    def with_policy(env):
+        # align_on_fail: the handle under the align done-policy, no episode limit; otherwise the env as it was given — except one that an
+        # earlier align_on_fail generator left aligning, which goes back to stepping on after done
+        if getattr(env, "_done_policy", "none") != policy and (align_on_fail or env._done_policy == "align"):
+            env.configure_wrappers(env._episode_length if not align_on_fail else (1 << 30), auto_reset=False,
+                                   action_repeat=getattr(env, "_action_repeat", 1), done_policy=policy)
+        return env
+
     def env_of(n):
         if n == env0.num_envs:
-            return env0
+            return with_policy(env0)
         if n not in envs:
             envs.clear()                    # (one cached sibling: the buffers of a batch size are not kept around)
             envs[n] = _sibling_env(env0, n)
-        return envs[n]
+        return with_policy(envs[n])
 
     def run_batch(clips: list, seed: int) -> dict:
         n = len(clips)
@@ -320,7 +342,8 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
         with torch.cuda.device(dev):
             env.reset(None, torch.tensor(clips, dtype=torch.int32), start_frame=torch.zeros(n, dtype=torch.int32),
                       qpos_noise=torch.from_numpy(qn), qvel_noise=torch.from_numpy(vn))
-            step = _PolicyStep(inference_fn, n, env.obs_buf)
+            # align_on_fail: the LSTM carry of an env is zeroed in the policy step that follows its alignment (done_buf is 0 after reset)
+            step = _PolicyStep(inference_fn, n, env.obs_buf, carry_reset=env.done_buf if align_on_fail and inference_fn.model == "lstm" else None)
             f32 = dict(dtype=torch.float32, device=dev)
             rec: dict = {}
             state_streams, step_streams = [], []
@@ -364,6 +387,8 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
                 if nsd:
                     step_streams.append(add("sensor_readings", _p(sd_buf), _hip.RECORD_SOA, n, nsd, nsd, T - 1, 0))
                 step_streams.append(add("joint_forces", _p(cf_buf), _hip.RECORD_SOA, n, nb6, nb6, T - 1, 0))
+            if align_on_fail:
+                step_streams.append(add("aligned", _p(env.done_buf), _hip.RECORD_SOA, n, 1, 1, T - 1, 0))
             init_tab = _upload_table(init_streams, n, 1, dev)
             state_tab = _upload_table(state_streams, n, T - 1, dev)
             step_tab = _upload_table(step_streams, n, T - 1, dev)
@@ -385,6 +410,9 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
         rows = [np.repeat(np.hstack([np.asarray(ref.position[c], np.float32), np.asarray(ref.quaternion[c], np.float32),
                                      np.asarray(ref.joints[c], np.float32)]), int(spf), axis=0) for c in clips]
         out["qposes_ref"] = np.stack(rows)
+        if align_on_fail:
+            out["aligned"] = host["aligned"][:, :, 0] != 0
+            out["n_alignments"] = out["aligned"].sum(axis=1).astype(np.int64)
         if log_sensor_data:
             out["joint_forces"] = host["joint_forces"].reshape(n, T - 1, -1, 6)
             out["sensor_readings"] = host["sensor_readings"] if "sensor_readings" in host else np.zeros((n, T - 1, 0), np.float32)
@@ -426,6 +454,7 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
 
     generate_rollout.T = T
     generate_rollout.metrics = metrics
+    generate_rollout.done_policy = policy
     return generate_rollout
 
 
@@ -468,17 +497,25 @@ def _parse_clips(spec: str, n_clips: int) -> list:
     return [int(c) for c in spec.split(",") if c.strip()]
 
 
+CLI_OPTIONS = ("checkpoint", "clips", "seed", "out", "log_activations", "log_metrics", "log_sensor_data", "align_on_fail", "step")
+
+
+def _split_argv(argv) -> tuple:
+    """(the roll-out's own key=value options, everything else: config overrides in train's syntax)."""
+    opts = dict(a.split("=", 1) for a in argv if "=" in a and a.split("=", 1)[0] in CLI_OPTIONS)
+    rest = [a for a in argv if not ("=" in a and a.split("=", 1)[0] in opts)]
+    return opts, rest
+
+
 def main(argv=None) -> int:
     from .. import config as _config
     from ..agent import checkpoint as ckpt
     from .utils import save_to_h5py
     argv = list(sys.argv[1:] if argv is None else argv)
-    opts = dict(a.split("=", 1) for a in argv if "=" in a and a.split("=", 1)[0] in ("checkpoint", "clips", "seed", "out", "log_activations",
-                                                                                    "log_metrics", "log_sensor_data", "step"))
-    rest = [a for a in argv if not ("=" in a and a.split("=", 1)[0] in opts)]
+    opts, rest = _split_argv(argv)
     if "checkpoint" not in opts:
         print("usage: python -m track_mjx_amd.analysis.rollout checkpoint=<run dir | step dir> [data_path=...] [clips=all|a:b|i,j,k] [seed=42] "
-              "[out=<dir>] [log_activations=true] [log_metrics=true] [log_sensor_data=false] [key=value config overrides ...]", file=sys.stderr)
+              "[out=<dir>] [log_activations=true] [log_metrics=true] [log_sensor_data=false] [align_on_fail=false] [key=value config overrides ...]", file=sys.stderr)
         return 2
     yes = lambda v: str(v).lower() in ("1", "true", "yes")     # noqa: E731
     path = opts["checkpoint"]
@@ -499,7 +536,11 @@ def main(argv=None) -> int:
     seed = int(opts.get("seed", 42))
     log_act, log_met = yes(opts.get("log_activations", "true")), yes(opts.get("log_metrics", "true"))
     log_sens = yes(opts.get("log_sensor_data", "false"))
-    gen = create_rollout_generator(cfg, env, fn, model=fn.model, log_activations=log_act, log_metrics=log_met, log_sensor_data=log_sens)
+    align = yes(opts.get("align_on_fail", "false"))
+    gen = create_rollout_generator(cfg, env, fn, model=fn.model, log_activations=log_act, log_metrics=log_met, log_sensor_data=log_sens,
+                                   align_on_fail=align)
+    print(f"[rollout] done-policy: {gen.done_policy}" + (" (a done env is re-aligned to the clip frame it has reached; `aligned` / `n_alignments` "
+                                                        "are recorded)" if align else " (the env keeps stepping after done)"), flush=True)
     clips = _parse_clips(opts.get("clips", "all"), env._n_clips)
     out_dir = opts.get("out", os.path.join(step_dir, "rollouts"))
     os.makedirs(out_dir, exist_ok=True)
@@ -507,6 +548,8 @@ def main(argv=None) -> int:
                                                                         if os.path.basename(os.path.normpath(step_dir)).isdigit() else -1),
                    "checkpoint": str(step_dir), "model": fn.model, "trained_gemm_inputs": fn.trained_gemm_inputs,
                    "rollout_gemm_inputs": "f32"}
+    if align:
+        meta_common["done_policy"] = "align"
     if log_sens:
         table = env.walker.sensor_table()
         meta_common.update(sensor_names=",".join(t[0] for t in table), sensor_adr=np.array([t[1] for t in table], np.int64),

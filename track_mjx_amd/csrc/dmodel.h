@@ -132,7 +132,13 @@ struct DModel {
   // subtree_com[body_rootid[b]] of the bodies OUTSIDE the moving tree (static: their roots' inertial frame origins, fixed in the world; the
   // moving tree's is the kernel's centre of mass): the point cfrc_ext rows are taken about
   float body_static_com[TM_MAXB][3];
+  // what happens to an env that is done (TM_DONE_*, include/tmjx.h: tmjx_set_done_policy; `auto_reset` above stays 1 exactly for TM_DONE_RESET)
+  // and the two clip leaves only the align policy reads (tmjx_clips_upload_velocities; null until uploaded).  Behind everything else, as the
+  // sensor fields are.
+  int done_policy;
+  const float *clip_vel, *clip_jvel;   // (C, F, 3) root linear velocity, (C, F, nv - 6) joint velocities
 };
+enum { TM_DONE_NONE = 0, TM_DONE_RESET = 1, TM_DONE_ALIGN = 2 };
 
 enum { RW_TOO_FAR, RW_BAD_POSE, RW_BAD_QUAT, RW_CTRL_W, RW_CTRL_DIFF_W, RW_ENERGY_W, RW_POS_W, RW_QUAT_W, RW_JOINT_W,
        RW_ANGVEL_W, RW_BODYPOS_W, RW_ENDEFF_W, RW_ZLO, RW_ZHI, RW_POS_S, RW_QUAT_S, RW_JOINT_S, RW_ANGVEL_S,

@@ -312,6 +312,9 @@ TM_DEV void tm_step_post(const DModel &m, EnvRef r, int *r_is, const float *acti
   ST(m.s_done, 0) = done;
   reward[r.e] = rew; done_out[r.e] = done; trunc_out[r.e] = trunc;
   // auto-reset: pipeline_state, obs, prev_ctrl <- snapshot taken at reset
+  // (the third done-policy, align — TM_DONE_ALIGN: done envs go onto the clip pose of this `frame` — needs kinematics, which this lane-per-env
+  // function does not have: it is csrc/wave_align.h, one wavefront per done env, launched behind K3's split form; the C-ABI refuses the policy
+  // wherever K3 runs in this inline form, so nothing is skipped silently)
   if (done != 0.f && m.auto_reset && !split) {
     for (int i = 0; i < m.nphys; i++) ST(m.s_qpos, i) = ST(m.s_first_phys, i);
     for (int i = 0; i < m.obs_size; i++) OUTROW(obs, i) = ST(m.s_first_obs, i);

@@ -200,6 +200,7 @@ inline bool build_dmodel(const void *blob, size_t nbytes, DModel &m, std::string
   m.timestep = optf[0]; m.tolerance = optf[1]; m.ls_tolerance = optf[2]; m.impratio = optf[3];
   m.iterations = opti[0]; m.ls_iterations = opti[1]; m.n_frames = opti[2];
   m.mocap_hz = envi[0]; m.clip_length = envi[1]; m.traj_length = envi[2]; m.window = envi[3]; m.torso_idx = envi[4]; m.episode_length = envi[5]; m.auto_reset = envi[6];
+  m.done_policy = m.auto_reset ? TM_DONE_RESET : TM_DONE_NONE;
   m.ngroup = 0;
   for (int c = 0; c < m.ncon; c++) {
     if (m.body_moving[m.con_body1[c]] || !m.body_moving[m.con_body2[c]]) { err = "contact slots must be (static geom, moving geom)"; return false; }

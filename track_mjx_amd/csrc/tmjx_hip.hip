@@ -22,7 +22,7 @@
 struct tmjx_model {
   DModel h;           // host copy (clip pointers are device pointers)
   DModel *d = nullptr;  // device copy
-  float *clips[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  float *clips[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // [5], [6]: velocity, joints_velocity (tmjx_clips_upload_velocities)
   int block = 64;     // lanes per workgroup for the lane-per-env kernels (K1/K3 and the v1 physics)
   int wave = 1;       // 1: wave-per-env LDS physics kernel (default); 0: lane-per-env reference implementation
   bool rodent = false;  // dims match the compile-time specialisation of the wave kernel
@@ -223,6 +223,9 @@ __global__ __launch_bounds__(64) void k_rec_out(const DModel *__restrict__ mp, f
 // flag of its own (track_mjx_amd/hip.py) — and launched through this entry
 extern "C" void tmjx_internal_launch_physics_wave(int rodent, int cnt, size_t lds, hipStream_t stream, const DModel *mp, float *st, const float *action, int nsub,
                                                   int do_euler, float *ws_dump, int n, int e0, int rs, float *spill, int spill_stride);
+// the ALIGN done-policy's epilogue kernel (csrc/tmjx_wave_align.hip)
+extern "C" void tmjx_internal_launch_align_wave(int rodent, size_t lds, hipStream_t stream, const DModel *mp, float *st, const int *is, float *obs,
+                                                const float *done, int n);
 // the recording kernel of checkpoint roll-outs (K2 + the sensor stage on the last substep): csrc/tmjx_wave_sensors.hip
 extern "C" void tmjx_internal_launch_physics_wave_sensors(int rodent, int cnt, size_t lds, hipStream_t stream, const DModel *mp, float *st,
                                                           const float *action, int nsub, int do_euler, float *ws_dump, int n, int e0, int rs,
@@ -310,7 +313,7 @@ int tmjx_model_create(const void *blob, size_t nbytes, tmjx_model **out) {
 
 void tmjx_model_destroy(tmjx_model *m) {
   if (!m) return;
-  for (int i = 0; i < 5; i++) if (m->clips[i] && m->clips_owned) hipFree(m->clips[i]);
+  for (int i = 0; i < 7; i++) if (m->clips[i] && m->clips_owned) hipFree(m->clips[i]);
   if (m->d) hipFree(m->d);
   if (m->mspill) hipFree(m->mspill);
   delete m;
@@ -336,9 +339,34 @@ int tmjx_set_wrappers(tmjx_model *m, int episode_length, int auto_reset) {
   if (episode_length < 1) return fail(TMJX_EINVAL, "episode_length must be >= 1");
   m->h.episode_length = episode_length;
   m->h.auto_reset = auto_reset ? 1 : 0;
+  m->h.done_policy = auto_reset ? TM_DONE_RESET : TM_DONE_NONE;
   // a blocking copy of the constants: called between roll-outs (wrappers.wrap, before the first reset), never while launches of this
   // handle are in flight; the clip table stays where it is (re-creating the handle re-uploaded it: 631 MB at 1024 clips)
   HIP_TRY(hipMemcpy(m->d, &m->h, sizeof(DModel), hipMemcpyHostToDevice));
+  return TMJX_OK;
+}
+
+static_assert(TMJX_DONE_NONE == TM_DONE_NONE && TMJX_DONE_RESET == TM_DONE_RESET && TMJX_DONE_ALIGN == TM_DONE_ALIGN, "include/tmjx.h and csrc/dmodel.h disagree");
+int tmjx_set_done_policy(tmjx_model *m, int policy) {
+  if (policy != TMJX_DONE_NONE && policy != TMJX_DONE_RESET && policy != TMJX_DONE_ALIGN)
+    return fail(TMJX_EINVAL, "unknown done policy " + std::to_string(policy) + " (TMJX_DONE_NONE, TMJX_DONE_RESET or TMJX_DONE_ALIGN)");
+  if (!m) return fail(TMJX_EINVAL, "null argument");
+  if (policy == TMJX_DONE_ALIGN) {
+    if (!m->wave) return fail(TMJX_EINVAL, "the align done-policy needs the wave-per-env implementation (its kinematics are the physics kernel's position stage)");
+    if (!m->h.clip_pos) return fail(TMJX_EINVAL, "the align done-policy needs a clip table: tmjx_clips_upload has not been called");
+    if (!m->h.clip_vel || !m->h.clip_jvel)
+      return fail(TMJX_EINVAL, "the align done-policy needs the clips' velocity and joints_velocity: tmjx_clips_upload_velocities has not been called "
+                               "(or the handle shares the table of an owner that has none)");
+  }
+  m->h.done_policy = policy;
+  m->h.auto_reset = policy == TMJX_DONE_RESET ? 1 : 0;
+  HIP_TRY(hipMemcpy(m->d, &m->h, sizeof(DModel), hipMemcpyHostToDevice));      // blocking, between roll-outs: as tmjx_set_wrappers
+  return TMJX_OK;
+}
+// an aligning handle whose velocities have gone (a new tmjx_clips_upload / tmjx_clips_share since): an error, never a read of a null pointer
+static int check_done_policy(const tmjx_model *m) {
+  if (m->h.done_policy == TM_DONE_ALIGN && (!m->h.clip_vel || !m->h.clip_jvel))
+    return fail(TMJX_EINVAL, "the align done-policy is selected but the handle's clip table has no velocities (tmjx_clips_upload_velocities)");
   return TMJX_OK;
 }
 
@@ -357,10 +385,11 @@ int tmjx_clips_upload(tmjx_model *m, const float *position, const float *quatern
   size_t cf = (size_t)n_clips * n_frames;
   size_t widths[5] = {3, 4, (size_t)(m->h.nq - 7), (size_t)(m->h.nbody - 1) * 3, 3};
   const float *src[5] = {position, quaternion, joints, body_positions, angular_velocity};
-  for (int i = 0; i < 5; i++) {
+  for (int i = 0; i < 7; i++) {      // (a new table drops the old one's velocities with it)
     if (m->clips[i] && m->clips_owned) hipFree(m->clips[i]);
     m->clips[i] = nullptr;
   }
+  m->h.clip_vel = m->h.clip_jvel = nullptr;
   m->clips_owned = true;
   for (int i = 0; i < 5; i++) {
     HIP_TRY(hipMalloc((void **)&m->clips[i], cf * widths[i] * sizeof(float)));
@@ -373,18 +402,44 @@ int tmjx_clips_upload(tmjx_model *m, const float *position, const float *quatern
   return TMJX_OK;
 }
 
+// The two clip leaves that only the align done-policy reads, for the table tmjx_clips_upload put on this handle (same n_clips, n_frames)
+int tmjx_clips_upload_velocities(tmjx_model *m, const float *velocity, const float *joints_velocity, int n_clips, int n_frames) {
+  if (!m || !velocity || !joints_velocity) return fail(TMJX_EINVAL, "null argument");
+  if (!m->clips[0]) return fail(TMJX_EINVAL, "tmjx_clips_upload has not been called");
+  if (!m->clips_owned) return fail(TMJX_EINVAL, "this handle shares another handle's clip table: upload the velocities on the owner, then share again");
+  if (n_clips != m->h.n_clips || n_frames != m->h.n_frames_clip)
+    return fail(TMJX_EINVAL, "velocities of " + std::to_string(n_clips) + " x " + std::to_string(n_frames) + " frames for a clip table of " +
+                                 std::to_string(m->h.n_clips) + " x " + std::to_string(m->h.n_frames_clip));
+  size_t cf = (size_t)n_clips * n_frames;
+  size_t widths[2] = {3, (size_t)(m->h.nv - 6)};
+  const float *src[2] = {velocity, joints_velocity};
+  for (int i = 0; i < 2; i++) {
+    if (m->clips[5 + i]) hipFree(m->clips[5 + i]);
+    m->clips[5 + i] = nullptr;
+  }
+  m->h.clip_vel = m->h.clip_jvel = nullptr;
+  for (int i = 0; i < 2; i++) {
+    HIP_TRY(hipMalloc((void **)&m->clips[5 + i], cf * widths[i] * sizeof(float)));
+    HIP_TRY(hipMemcpy(m->clips[5 + i], src[i], cf * widths[i] * sizeof(float), hipMemcpyHostToDevice));
+  }
+  m->h.clip_vel = m->clips[5]; m->h.clip_jvel = m->clips[6];
+  HIP_TRY(hipMemcpy(m->d, &m->h, sizeof(DModel), hipMemcpyHostToDevice));
+  return TMJX_OK;
+}
+
 // The env groups of one rank (pipelined roll-outs: one handle each) read ONE resident clip table: `m` takes over `owner`'s device
 // arrays (631 MB at 1024 clips) without owning them.  `owner` must outlive `m`'s launches and be of the same model dimensions.
 int tmjx_clips_share(tmjx_model *m, const tmjx_model *owner) {
   if (!m || !owner) return fail(TMJX_EINVAL, "null argument");
   if (m == owner) return TMJX_OK;
   if (!owner->clips[0]) return fail(TMJX_EINVAL, "the owner has no clip table");
-  if (m->h.nq != owner->h.nq || m->h.nbody != owner->h.nbody || m->h.traj_length > owner->h.n_frames_clip) return fail(TMJX_EINVAL, "handles of different models cannot share a clip table");
-  for (int i = 0; i < 5; i++) {
+  if (m->h.nq != owner->h.nq || m->h.nv != owner->h.nv || m->h.nbody != owner->h.nbody || m->h.traj_length > owner->h.n_frames_clip) return fail(TMJX_EINVAL, "handles of different models cannot share a clip table");
+  for (int i = 0; i < 7; i++) {      // (the velocities too, when the owner has them: null otherwise)
     if (m->clips[i] && m->clips_owned) hipFree(m->clips[i]);
     m->clips[i] = owner->clips[i];
   }
   m->clips_owned = false;
+  m->h.clip_vel = m->clips[5]; m->h.clip_jvel = m->clips[6];
   m->h.clip_pos = m->clips[0]; m->h.clip_quat = m->clips[1]; m->h.clip_joints = m->clips[2];
   m->h.clip_bodypos = m->clips[3]; m->h.clip_angvel = m->clips[4];
   m->h.n_clips = owner->h.n_clips; m->h.n_frames_clip = owner->h.n_frames_clip;
@@ -487,6 +542,11 @@ static void launch_k3(tmjx_model *m, float *state, int32_t *istate, const float 
     int total = h.nphys + h.obs_size + h.nu;
     hipLaunchKernelGGL(k_autoreset, dim3((n_env + 63) / 64, (total + 15) / 16), dim3(64), 0, stream, m->d, state, obs, done, n_env);
   }
+  // align: the done envs onto the clip pose of their current frame, kinematics, observation (csrc/wave_align.h) — the launch in k_autoreset's place
+  if (h.done_policy == TM_DONE_ALIGN && (rep & TM_REP_LAST)) {
+    const size_t lds = (size_t)(m->rodent ? h.lds_floats : tmjx_host::make_wave_layout(h, false).lds_floats) * sizeof(float);
+    tmjx_internal_launch_align_wave(m->rodent ? 1 : 0, lds, stream, m->d, state, istate, obs, done, n_env);
+  }
 }
 
 int tmjx_step(tmjx_model *m, float *state, int32_t *istate, const float *action, float *obs, float *reward, float *done,
@@ -494,6 +554,7 @@ int tmjx_step(tmjx_model *m, float *state, int32_t *istate, const float *action,
   if (!m || !state || !istate || !action || !obs || !reward || !done || !truncation || !metrics || !workspace) return fail(TMJX_EINVAL, "null argument");
   if (n_env < 1) return fail(TMJX_EINVAL, "n_env must be >= 1");
   if (!m->h.clip_pos) return fail(TMJX_EINVAL, "tmjx_clips_upload has not been called");
+  if (int rc = check_done_policy(m)) return rc;
   if (m->wave) {
     // action_repeat (brax EpisodeWrapper): the env's own step R times with the same action; K3 sums the rewards and applies the episode
     // counter / truncation / auto-reset after the last repeat only (env_core.h: tm_step_post, TM_REP_*)
@@ -543,6 +604,7 @@ int tmjx_step_sensors(tmjx_model *m, float *state, int32_t *istate, const float 
   if (n_env < 1) return fail(TMJX_EINVAL, "n_env must be >= 1");
   if (!m->h.clip_pos) return fail(TMJX_EINVAL, "tmjx_clips_upload has not been called");
   if (int rc = check_sensor_args(m, sensordata, cfrc_ext)) return rc;
+  if (int rc = check_done_policy(m)) return rc;
   // tmjx_step's launches; every repeat's physics writes the outputs, so the last repeat's last substep is what is left in them
   const int R = m->action_repeat;
   for (int r = 0; r < R; r++) {
@@ -603,6 +665,9 @@ int tmjx_reward_obs(tmjx_model *m, float *state, int32_t *istate, const float *a
   if (!m || !state || !istate || !action || !obs || !reward || !done || !truncation || !metrics) return fail(TMJX_EINVAL, "null argument");
   if (n_env < 1) return fail(TMJX_EINVAL, "n_env must be >= 1");
   if (!m->h.clip_pos) return fail(TMJX_EINVAL, "tmjx_clips_upload has not been called");
+  if (int rc = check_done_policy(m)) return rc;
+  // (the inline, lane-per-env form of K3 has no kinematics of its own: the align policy exists in the split form only, and is refused here)
+  if (!workspace && m->h.done_policy == TM_DONE_ALIGN) return fail(TMJX_EINVAL, "tmjx_reward_obs without a workspace (K3 in one kernel) cannot apply the align done-policy: pass the workspace");
   if (workspace) launch_k3(m, state, istate, action, obs, reward, done, truncation, metrics, workspace, n_env, (hipStream_t)stream);
   else hipLaunchKernelGGL(k_post, GRID(m, n_env), 0, (hipStream_t)stream, m->d, state, istate, action, obs, reward, done, truncation,
                           metrics, (const float *)nullptr, 0, TM_REP_ONE, n_env);
@@ -616,6 +681,7 @@ int tmjx_reward_frame(tmjx_model *m, float *state, int32_t *istate, const float 
   if (!frame_pos || !frame_quat || !frame_joints || !frame_bodypos || !frame_angvel) return fail(TMJX_EINVAL, "null reference-frame leaf");
   if (n_env < 1) return fail(TMJX_EINVAL, "n_env must be >= 1");
   if (!m->h.clip_pos) return fail(TMJX_EINVAL, "tmjx_clips_upload has not been called");      // (the observation's trajectory part still reads the table)
+  if (m->h.done_policy == TM_DONE_ALIGN) return fail(TMJX_EINVAL, "tmjx_reward_frame (K3 in one kernel, the caller's frame) cannot apply the align done-policy");
   TmFrame fo{frame_pos, frame_quat, frame_joints, frame_bodypos, frame_angvel};
   hipLaunchKernelGGL(k_post_frame, GRID(m, n_env), 0, (hipStream_t)stream, m->d, state, istate, action, obs, reward, done, truncation, metrics, fo, n_env);
   return check_launch("k_post_frame");

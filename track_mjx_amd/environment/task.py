@@ -28,6 +28,8 @@ from .. import hip as _hip
 from ..clips import ReferenceClip
 from ..walker import Rodent, build_blob
 
+DONE_POLICIES = {"none": _hip.DONE_NONE, "reset": _hip.DONE_RESET, "align": _hip.DONE_ALIGN}      # tmjx_set_done_policy (include/tmjx.h)
+
 METRIC_NAMES = ("pos_reward", "quat_reward", "joint_reward", "angvel_reward", "bodypos_reward", "endeff_reward",
                 "ctrl_cost", "ctrl_diff_cost", "energy_cost", "done", "too_far", "bad_pose", "bad_quat", "fall", "nan",
                 "joint_distance", "summed_pos_distance", "quat_distance", "var_cost", "jerk_cost")
@@ -106,6 +108,7 @@ class MultiClipTracking:
         self._physics_events = None   # list => step() records (start, end) HIP events around the physics kernel
         self._episode_length = int(episode_length) if episode_length is not None else (1 << 30)
         self._auto_reset = bool(auto_reset)
+        self._done_policy = "reset" if self._auto_reset else "none"
         # the env groups of one rank read ONE resident clip table (tmjx_clips_share): this env uses `share_clips_with`'s device arrays
         self._clip_owner = share_clips_with
         self._create_handle()
@@ -136,6 +139,14 @@ class MultiClipTracking:
                 n_clips, n_frames = arrs[0].shape[:2]
                 _hip.check(self._L.tmjx_clips_upload(self._handle, *[a.ctypes.data_as(C.c_void_p) for a in arrs], n_clips, n_frames),
                            "tmjx_clips_upload")
+                # velocity / joints_velocity: read by the align done-policy only (AutoAlignWrapperTracking); uploaded when the clip set has them
+                vel = [getattr(c, k, None) for k in ("velocity", "joints_velocity")]
+                if all(v is not None for v in vel):
+                    vel = [np.ascontiguousarray(v, dtype=np.float32) for v in vel]
+                    if vel[0].shape != (n_clips, n_frames, 3) or vel[1].shape != (n_clips, n_frames, self.walker.nv - 6):
+                        raise ValueError("clip velocity must be (C, F, 3) and joints_velocity (C, F, nv - 6)")
+                    _hip.check(self._L.tmjx_clips_upload_velocities(self._handle, *[a.ctypes.data_as(C.c_void_p) for a in vel], n_clips, n_frames),
+                               "tmjx_clips_upload_velocities")
 
     def _alloc(self) -> None:
         n, L, dev = self.num_envs, self.layout, self.device
@@ -347,16 +358,27 @@ class MultiClipTracking:
         t = self.state_buf[L.time] * float(self._mocap_hz)
         return torch.floor(t + self.istate_buf[L.i_start_frame].float()).to(torch.int32)
 
-    def configure_wrappers(self, episode_length: int, auto_reset: bool, action_repeat: int = 1) -> None:
+    def configure_wrappers(self, episode_length: int, auto_reset: bool, action_repeat: int = 1, done_policy: str | None = None) -> None:
         """Switch the Episode / AutoReset wrapper semantics of the handle (wrappers.wrap): two constants of the device model change,
-        the clip table stays resident (tmjx_set_wrappers); `action_repeat` is brax EpisodeWrapper's (tmjx_set_action_repeat)."""
+        the clip table stays resident (tmjx_set_wrappers); `action_repeat` is brax EpisodeWrapper's (tmjx_set_action_repeat).
+        `done_policy`: None = what `auto_reset` says ("reset" / "none"); "align" = AutoAlignWrapperTracking (tmjx_set_done_policy: a done env
+        goes onto the clip pose of the frame it has reached), which needs the clip set's velocity / joints_velocity and auto_reset=False."""
         if int(action_repeat) < 1:
             raise ValueError("action_repeat must be >= 1")
+        if done_policy is None:
+            done_policy = "reset" if auto_reset else "none"
+        if done_policy not in DONE_POLICIES:
+            raise ValueError(f"done_policy must be one of {sorted(DONE_POLICIES)}, not {done_policy!r}")
+        if bool(auto_reset) != (done_policy == "reset"):
+            raise ValueError(f"done_policy={done_policy!r} contradicts auto_reset={bool(auto_reset)}")
         self._episode_length, self._auto_reset, self._action_repeat = int(episode_length), bool(auto_reset), int(action_repeat)
         with torch.cuda.device(self.device):
             torch.cuda.synchronize(self.device)        # no launch of this handle may be in flight while its constants change
             _hip.check(self._L.tmjx_set_wrappers(self._handle, self._episode_length, int(self._auto_reset)), "tmjx_set_wrappers")
             _hip.check(self._L.tmjx_set_action_repeat(self._handle, self._action_repeat), "tmjx_set_action_repeat")
+            if done_policy == "align":       # (tmjx_set_wrappers has set "reset" / "none")
+                _hip.check(self._L.tmjx_set_done_policy(self._handle, DONE_POLICIES[done_policy]), "tmjx_set_done_policy")
+        self._done_policy = done_policy
         self._blob = build_blob(self.walker, n_frames=self._n_frames, mocap_hz=self._mocap_hz, clip_length=self._clip_length,
                                 traj_length=self._ref_len, window=int(self._reward_config.var_window_size),
                                 episode_length=self._episode_length, reward_f=self._reward_config.vector(),
