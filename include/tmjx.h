@@ -621,6 +621,35 @@ int tmjx_latent_concat_det(const float *fc2, int ldf, const float *obs, int64_t 
                            float *x, int ldx, float *traj, int ldt, int n, int Z, int obs_w, int ref_w, void *stream);
 int tmjx_action_mode(const float *logits, int ldl, float *ctrl, float *action_t, int n, int A, void *stream);
 
+/* ---- Decoder policy of a high-level env (make_decoder_policy, intention_network.py:194-222; HighLevelWrapper, environment/wrappers.py:384-412):
+ * the env is stepped with an intention vector per env, the pretrained decoder turns it into controls.
+ * tmjx_decoder_input: tmjx_latent_concat_det's launch (the same kernel, the same bits) for latents that are NOT the front of an fc2 buffer:
+ *   x[i] = [ latents[i][0..Z) | (obs_i[c] - mean[c]) / std[c] for c in [ref_w, obs_w) | 0 .. ], latents [n][ldz >= Z], x [n][ldx]. */
+int tmjx_decoder_input(const float *latents, int ldz, const float *obs, int64_t obs_s0, int64_t obs_s1, const float *mean, const float *std,
+                       float *x, int ldx, int n, int Z, int obs_w, int ref_w, void *stream);
+/* tmjx_decoder_act (csrc/decoder_act.h): the whole decoder policy as ONE launch —
+ *   [latents | normalised proprioception] -> n_blocks Dense -> SiLU -> LayerNorm blocks, 256 wide -> action head (2A <= 128 columns) -> tanh.
+ * latents [n][ldz >= Z]; obs_i[c] at obs[i * obs_s0 + c * obs_s1]: the env's raw [obs][n_env] buffer as tmjx_step leaves it goes in as
+ * (obs_s0, obs_s1) = (1, n_env), no staging copy; mean / std of the whole observation [obs_w], or both NULL (no normaliser); Z + obs_w - ref_w <= 320.
+ * block[0].W [256][ldw >= Z + obs_w - ref_w rounded up to 4], block[l > 0].W [256][ldw >= 256], Wf [2A][ldwf >= 256]: rows 16-byte aligned;
+ * bias / gamma / beta 16-byte aligned [256]; bf [2A] or NULL.
+ * Outputs: action_t [A][n] (the layout tmjx_step takes); optionally ctrl [n][A] and logits [n][ldl >= 2A] (NULL: not written).  Nothing else
+ * reaches global memory.  logits are bit-identical to tmjx_latent_concat_det -> tmjx_chain_fwd (epi 1) on the same inputs, action_t / ctrl to
+ * tmjx_action_mode of those logits.  Any n >= 1.  tmjx_decoder_act_ok says whether a descriptor qualifies (no error recorded, no device call). */
+typedef struct { const float *W, *bias, *gamma, *beta; int32_t width, ldw; } tmjx_decoder_block_t;
+typedef struct {
+  const float *latents; int32_t ldz;
+  const float *obs; int64_t obs_s0, obs_s1;
+  const float *mean, *std;
+  int32_t n, Z, obs_w, ref_w, n_blocks;
+  tmjx_decoder_block_t block[TMJX_CHAIN_MAX_HIDDEN];
+  const float *Wf, *bf; int32_t ldwf, A;
+  float eps;
+  float *action_t, *ctrl, *logits; int32_t ldl;
+} tmjx_decoder_act_t;
+int tmjx_decoder_act_ok(const tmjx_decoder_act_t *a);
+int tmjx_decoder_act(const tmjx_decoder_act_t *a, void *stream);
+
 const char *tmjx_last_error(void);
 const char *tmjx_version(void);
 

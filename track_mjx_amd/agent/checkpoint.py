@@ -13,7 +13,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .networks import IntentionPolicy, RunningStatistics, ValueNet
+from .networks import DecoderNet, IntentionPolicy, RunningStatistics, ValueNet
 
 
 def _np(t: torch.Tensor) -> np.ndarray:
@@ -183,7 +183,7 @@ def decoder_from_flax(policy: IntentionPolicy, dec: dict, get=_ident, check: boo
     are verified first (check_decoder_tree), so a mismatched checkpoint is refused before anything is written."""
     if check:
         check_decoder_tree(policy, dec)
-    dev = policy.fc2.weight.device
+    dev = policy.head.weight.device
     for name, prm in decoder_flax_params(policy).items():
         layer, leaf = name.split("/")
         src = np.asarray(dec[layer][leaf])
@@ -562,3 +562,106 @@ def load_inference_fn(cfg: dict, policy: tuple, deterministic: bool = True, get_
         std = torch.as_tensor(np.asarray(norm["std"], dtype=np.float32), device=dev).reshape(-1).contiguous()
     gi = "bf16" if str(cfg.get("mlp_gemm_inputs", "f32")).lower() in ("bf16", "bfloat16") else "f32"
     return RolloutPolicy(module, mean, std, "lstm" if use_lstm else "mlp", get_activation=get_activation, trained_gemm_inputs=gi)
+
+
+# ---- the decoder-only policy (ppo_networks.py:193-238 make_decoder_policy_fn, intention_network.py:194-222 make_decoder_policy): the pretrained
+# motor module on its own, driven with latents — what environment.wrappers.HighLevelWrapper puts inside an env ---------------------------------------
+class DecoderPolicy:
+    """policy(x) with x [n, Z + prop] = [latents | RAW proprioceptive observation] -> (action [n, A] = tanh(loc), extras): only the trailing
+    `prop` columns are normalised (intention_network.py:206-214), with the normaliser's columns [reference_obs_size:] — the only ones kept
+    (ppo_networks.py:225-234).  Plain torch on a CPU tensor; on the GPU the blocks' modules run their HIP kernels, and HighLevelWrapper runs the
+    whole policy as a launch list on the env's buffers.  A bf16-trained policy runs in fp32."""
+
+    def __init__(self, net: DecoderNet, mean: torch.Tensor | None, std: torch.Tensor | None, latent_size: int, reference_obs_size: int,
+                 trained_gemm_inputs: str = "f32"):
+        if (mean is None) != (std is None):
+            raise ValueError("DecoderPolicy: mean and std together")
+        self.net, self.mean, self.std = net, mean, std
+        self.latent_size, self.reference_obs_size, self.action_size = int(latent_size), int(reference_obs_size), int(net.action_size)
+        first = net.decoder[0].dense if len(net.decoder) else net.head
+        self.proprioceptive_obs_size = int(first.in_features) - self.latent_size
+        self.decoder_layer_sizes = tuple(int(b.dense.out_features) for b in net.decoder)
+        self.device = net.head.weight.device
+        self.trained_gemm_inputs = trained_gemm_inputs
+        if mean is not None and (mean.shape != (self.proprioceptive_obs_size,) or std.shape != mean.shape):
+            raise ValueError(f"DecoderPolicy: mean / std must hold the {self.proprioceptive_obs_size} proprioceptive columns")
+
+    @torch.no_grad()
+    def logits(self, x: torch.Tensor) -> torch.Tensor:
+        Z, P = self.latent_size, self.proprioceptive_obs_size
+        if x.shape[-1] != Z + P:
+            raise ValueError(f"DecoderPolicy: the input has {x.shape[-1]} columns, not latents + proprioception = {Z} + {P}")
+        x = x.to(device=self.device, dtype=torch.float32)
+        prop = x[..., Z:]
+        if self.mean is not None:
+            prop = (prop - self.mean) / self.std
+        return self.net(torch.cat([x[..., :Z], prop], dim=-1))
+
+    def __call__(self, x: torch.Tensor, key=None):
+        return torch.tanh(self.logits(x)[..., :self.action_size]), {}
+
+
+def decoder_policy_from_trees(norm: dict | None, ptree: dict, normalize_observations: bool = True, device="cuda",
+                              trained_gemm_inputs: str = "f32") -> DecoderPolicy:
+    """DecoderPolicy of (normalizer_params, policy_params): sizes from the parameter tree (Z = fc2_mean's width, proprioceptive width = the first
+    decoder layer's input - Z, reference_obs_size = the normaliser's width - that), params/decoder only, mean / std columns [reference_obs_size:] only."""
+    p = ptree.get("params", {})
+    if "lstm_decoder" in p:
+        raise NotImplementedError("make_decoder_policy_fn: the checkpoint holds an LSTM decoder (params/lstm_decoder); the decoder-only policy is built "
+                                  "for the MLP decoder only")
+    if "decoder" not in p:
+        raise ValueError("make_decoder_policy_fn: the checkpoint's policy tree has no params/decoder")
+    dec = p["decoder"]
+    n_dec = len([k for k in dec if k.startswith("hidden_")]) - 1
+    if n_dec < 0:
+        raise ValueError("make_decoder_policy_fn: params/decoder has no hidden_<i> layer")
+    if "encoder" not in p or "fc2_mean" not in p["encoder"]:
+        raise ValueError("make_decoder_policy_fn: the intention size is read from params/encoder/fc2_mean, which the checkpoint does not have")
+    Z = int(np.asarray(p["encoder"]["fc2_mean"]["kernel"]).shape[1])
+    sizes = [int(np.asarray(dec[f"hidden_{i}"]["kernel"]).shape[1]) for i in range(n_dec)]
+    A2 = int(np.asarray(dec[f"hidden_{n_dec}"]["kernel"]).shape[1])
+    in0 = int(np.asarray(dec["hidden_0"]["kernel"]).shape[0])
+    prop = in0 - Z
+    if prop < 0 or A2 % 2:
+        raise ValueError(f"make_decoder_policy_fn: decoder input width {in0} < intention size {Z}, or an odd head width {A2}")
+    if norm is None or "mean" not in norm:
+        raise ValueError("make_decoder_policy_fn: the checkpoint has no normaliser (its width gives reference_obs_size)")
+    W = int(np.asarray(norm["mean"]).shape[-1])
+    ref = W - prop
+    if ref < 0:
+        raise ValueError(f"make_decoder_policy_fn: the normaliser has {W} columns, fewer than the decoder's {prop} proprioceptive inputs")
+    dev = torch.device(device)
+    net = DecoderNet(in0, A2 // 2, sizes).to(dev).float().eval()
+    for q in net.parameters():
+        q.requires_grad_(False)
+    decoder_from_flax(net, dec)
+    mean = std = None
+    if normalize_observations:
+        mean = torch.as_tensor(np.asarray(norm["mean"], dtype=np.float32).reshape(-1)[ref:].copy(), device=dev).contiguous()
+        std = torch.as_tensor(np.asarray(norm["std"], dtype=np.float32).reshape(-1)[ref:].copy(), device=dev).contiguous()
+    return DecoderPolicy(net, mean, std, Z, ref, trained_gemm_inputs)
+
+
+def make_decoder_policy_fn(ckpt_path, step: int | None = None, device="cuda") -> DecoderPolicy:
+    """The decoder-only inference function of a checkpoint (ppo_networks.py:193-238): a run directory (latest step, or `step`), a step directory, or
+    a .npz of save_npz.  normalize_observations=false in the saved config means no normaliser."""
+    import json
+    import os
+    path = str(ckpt_path)
+    if os.path.isdir(path):
+        d = resolve_step_dir(path, step)
+        norm, ptree = load_policy(d)
+        meta = os.path.join(d, "config", "metadata")
+        cfg = {}
+        if os.path.exists(meta):
+            with open(meta) as f:
+                cfg = json.load(f) or {}
+    else:
+        if step is not None:
+            raise ValueError("make_decoder_policy_fn: `step` selects a step of a checkpoint directory; a .npz file holds one policy")
+        norm, ptree, _ = load_freeze_source(path)
+        with np.load(path) as z:
+            cfg = json.loads(bytes(z["config_json"]).decode()) if "config_json" in z.files else {}
+    tc = (cfg.get("train_setup") or {}).get("train_config") or {}
+    gi = "bf16" if str(cfg.get("mlp_gemm_inputs", "f32")).lower() in ("bf16", "bfloat16") else "f32"
+    return decoder_policy_from_trees(norm, ptree, bool(tc.get("normalize_observations", True)), device, gi)

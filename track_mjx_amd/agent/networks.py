@@ -1440,6 +1440,24 @@ class IntentionPolicy(nn.Module):
         return logits, mean, logvar
 
 
+class DecoderNet(nn.Module):
+    """The decoder half of IntentionPolicy alone (intention_network.py:194-222 make_decoder_policy: Decoder.apply on [latent | proprioception]):
+    the same blocks and head modules, so the same torch / HIP ops as the full policy's decoder."""
+
+    def __init__(self, input_size: int, action_size: int, decoder_layers: Sequence[int] = (1024, 1024)):
+        super().__init__()
+        self.action_size = action_size
+        dec, d = [], input_size
+        for h in decoder_layers:
+            dec.append(_Block(d, h)); d = h
+        self.decoder = nn.Sequential(*dec)
+        self.head = _dense(d, 2 * action_size)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """x = [latent | normalised proprioception] -> logits [.., 2 * action_size]."""
+        return self.head(self.decoder(x))
+
+
 class _NoCtx:
     """Stand-in for an autograd context when a Function's forward is run outside autograd (inference)."""
     def save_for_backward(self, *a):

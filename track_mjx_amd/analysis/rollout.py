@@ -32,6 +32,9 @@ they were.
 CLI:  python -m track_mjx_amd.analysis.rollout checkpoint=<run dir | step dir> [data_path=...] [clips=all|a:b|i,j,k] [seed=42] [out=<dir>]
       [log_activations=true] [log_metrics=true] [log_sensor_data=false] [align_on_fail=false]
       ->  <out>/clip_<idx>.h5 (save_to_h5py layout + a `meta` group)
+      replay_latents=<dir of clip_<i>.h5> [latent_scale=1.0] [path=auto|fused|layers]: instead of running the encoder, re-run the clips of those files
+      through a HighLevelWrapper env (environment/wrappers.py: the checkpoint's decoder inside the env) fed their recorded activations/intention
+      (times latent_scale), and write the same clip_<i>.h5 layout (activations: the intention that was fed).
 """
 from __future__ import annotations
 
@@ -497,7 +500,80 @@ def _parse_clips(spec: str, n_clips: int) -> list:
     return [int(c) for c in spec.split(",") if c.strip()]
 
 
-CLI_OPTIONS = ("checkpoint", "clips", "seed", "out", "log_activations", "log_metrics", "log_sensor_data", "align_on_fail", "step")
+CLI_OPTIONS = ("checkpoint", "clips", "seed", "out", "log_activations", "log_metrics", "log_sensor_data", "align_on_fail", "step",
+               "replay_latents", "latent_scale", "path")
+
+
+def replay_latents(cfg: dict, decoder_policy, clips: Sequence[int], latents: np.ndarray, seed: int = 42, path: str = "auto", metrics=ROLLOUT_METRICS) -> dict:
+    """Step a HighLevelWrapper env (the decoder inside the env) from generate_rollout's reset of `clips` with latents [n, T - 1, Z]: the roll-out
+    dict ([n] leading axis) with qposes_rollout, ctrl, state_rewards, qposes_ref, rollout_metrics and activations/intention (what was fed)."""
+    from ..environment.wrappers import HighLevelWrapper
+    n, T = len(clips), latents.shape[1] + 1
+    env = create_environment(cfg, n, decoder_policy.device)
+    hl = HighLevelWrapper(env, decoder_policy, decoder_policy.reference_obs_size, path=path)
+    nq, nv = int(env.layout.nq), int(env.layout.nv)
+    qn, vn = np.empty((nq, n), np.float32), np.empty((nv, n), np.float32)
+    for j, c in enumerate(clips):
+        _, qn[:, j], vn[:, j] = reset_inputs(seed, env._n_clips, nq, nv, env._reset_noise_scale, int(c))
+    with torch.cuda.device(env.device):
+        st = hl.reset(None, torch.tensor([int(c) for c in clips], dtype=torch.int32), start_frame=torch.zeros(n, dtype=torch.int32),
+                      qpos_noise=torch.from_numpy(qn), qvel_noise=torch.from_numpy(vn))
+        lat = torch.from_numpy(np.ascontiguousarray(latents, dtype=np.float32)).to(env.device)
+        f32 = dict(dtype=torch.float32, device=env.device)
+        qpos, rew = torch.empty((T, n, nq), **f32), torch.empty((T, n), **f32)
+        met, ctrl = torch.empty((T, len(METRIC_NAMES), n), **f32), torch.empty((T - 1, n, decoder_policy.action_size), **f32)
+        qpos[0].copy_(st.pipeline_state["qpos"]); rew[0].copy_(st.reward); met[0].copy_(env.metrics_buf)
+        for t in range(T - 1):
+            st = hl.step(st, lat[:, t])
+            qpos[t + 1].copy_(st.pipeline_state["qpos"]); rew[t + 1].copy_(st.reward); met[t + 1].copy_(env.metrics_buf); ctrl[t].copy_(hl.last_ctrl)
+        qpos, rew, met, ctrl = (v.cpu().numpy() for v in (qpos, rew, met, ctrl))
+    spf = int(env._steps_for_cur_frame)
+    ref = env._reference_clips
+    rows = [np.repeat(np.hstack([np.asarray(ref.position[c], np.float32), np.asarray(ref.quaternion[c], np.float32),
+                                 np.asarray(ref.joints[c], np.float32)]), spf, axis=0) for c in clips]
+    return {"qposes_rollout": np.ascontiguousarray(qpos.transpose(1, 0, 2)), "ctrl": np.ascontiguousarray(ctrl.transpose(1, 0, 2)),
+            "state_rewards": np.ascontiguousarray(rew.T), "qposes_ref": np.stack(rows),
+            "rollout_metrics": {f"{m}s": np.ascontiguousarray(met[:, METRIC_NAMES.index(m)].T) for m in metrics},
+            "activations": {"intention": np.ascontiguousarray(latents, dtype=np.float32)}, "path": hl.path}
+
+
+def _main_replay(opts: dict, cfg: dict, step_dir: str) -> int:
+    import re
+    from ..agent import checkpoint as ckpt
+    from .utils import load_from_h5py, save_to_h5py
+    src = opts["replay_latents"]
+    found = sorted(int(m.group(1)) for m in (re.fullmatch(r"clip_(\d+)\.h5", f) for f in os.listdir(src)) if m)
+    if "clips" in opts and opts["clips"] not in ("", "all"):
+        want = set(_parse_clips(opts["clips"], max(found, default=-1) + 1))
+        found = [c for c in found if c in want]
+    if not found:
+        print(f"[rollout] replay_latents: no clip_<i>.h5 in {src}", file=sys.stderr)
+        return 2
+    scale = float(opts.get("latent_scale", 1.0))
+    dp = ckpt.make_decoder_policy_fn(step_dir, device="cuda")
+    metrics = tuple((cfg.get("logging_config") or {}).get("rollout_metrics", ROLLOUT_METRICS))
+    out_dir = opts.get("out", os.path.join(step_dir, "replays"))
+    os.makedirs(out_dir, exist_ok=True)
+    for i in range(0, len(found), CLIPS_PER_BATCH):
+        chunk = found[i:i + CLIPS_PER_BATCH]
+        recs = [load_from_h5py(os.path.join(src, f"clip_{c}.h5")) for c in chunk]
+        for c, r in zip(chunk, recs):
+            if "activations" not in r or "intention" not in r["activations"]:
+                raise ValueError(f"replay_latents: {src}/clip_{c}.h5 has no activations/intention (roll it out with log_activations=true)")
+        seed = int(opts["seed"]) if "seed" in opts else int(recs[0]["meta"]["seed"])
+        lat = np.stack([np.asarray(r["activations"]["intention"], np.float32) for r in recs])
+        if scale != 1.0:
+            lat = lat * np.float32(scale)
+        res = replay_latents(cfg, dp, chunk, lat, seed=seed, path=opts.get("path", "auto"), metrics=metrics)
+        used = res.pop("path")
+        for j, c in enumerate(chunk):
+            one = _index_j(res, j)
+            one["meta"] = {"seed": np.int64(seed), "clip_idx": np.int64(c), "checkpoint": str(step_dir), "model": "mlp", "replay_latents": str(src),
+                           "latent_scale": np.float64(scale), "decoder_path": used, "rollout_gemm_inputs": "f32",
+                           "trained_gemm_inputs": dp.trained_gemm_inputs}
+            save_to_h5py(os.path.join(out_dir, f"clip_{c}.h5"), one)
+    print(f"[rollout] replayed the recorded intentions of {len(found)} clips (x {scale}) through the {used} decoder path; wrote {out_dir}", flush=True)
+    return 0
 
 
 def _split_argv(argv) -> tuple:
@@ -515,7 +591,8 @@ def main(argv=None) -> int:
     opts, rest = _split_argv(argv)
     if "checkpoint" not in opts:
         print("usage: python -m track_mjx_amd.analysis.rollout checkpoint=<run dir | step dir> [data_path=...] [clips=all|a:b|i,j,k] [seed=42] "
-              "[out=<dir>] [log_activations=true] [log_metrics=true] [log_sensor_data=false] [align_on_fail=false] [key=value config overrides ...]", file=sys.stderr)
+              "[out=<dir>] [log_activations=true] [log_metrics=true] [log_sensor_data=false] [align_on_fail=false] "
+              "[replay_latents=<dir of clip_<i>.h5> [latent_scale=1.0] [path=auto|fused|layers]] [key=value config overrides ...]", file=sys.stderr)
         return 2
     yes = lambda v: str(v).lower() in ("1", "true", "yes")     # noqa: E731
     path = opts["checkpoint"]
@@ -530,6 +607,11 @@ def main(argv=None) -> int:
         import yaml
         node[key.split(".")[-1]] = yaml.safe_load(val)
     step_dir = ckpt.resolve_step_dir(path, step_no)
+    if "replay_latents" in opts:
+        return _main_replay(opts, cfg, step_dir)
+    if "latent_scale" in opts or "path" in opts:
+        print("[rollout] latent_scale / path go with replay_latents=<dir>", file=sys.stderr)
+        return 2
     policy = ckpt.load_policy(step_dir, cfg)
     fn = ckpt.load_inference_fn(cfg, policy, deterministic=True, get_activation=True)
     env = create_environment(cfg, 1, "cuda")

@@ -33,7 +33,8 @@ template <int MT> struct ChainLds {
 // One GEMM of a chain on the workgroup's row tile: acc[MT][NI] (+)= A[BM rows][K] . op(W), 8 waves side by side along N (16 NI columns each).
 //   BT     W is [N][K] (forward: y = x W^T), LDS image [n][32] swizzled;  !BT W is [K][N] (input gradient: dx = dy W), LDS image [k][BN + 4]
 //   A_LDS  the A operand is the Y image (K == 256); otherwise A is read from global memory and staged like k_gemm_act's
-template <int MT, int NI, bool BT, bool A_LDS>
+//   YLD    floats per row of the LDS image the A fragments come from (256: the Y image; decoder_act.h reads a wider image of the same swizzle)
+template <int MT, int NI, bool BT, bool A_LDS, int YLD = 256>
 struct ChainGemm {
   static constexpr int BM = 16 * MT, BN = 128 * NI, A_ROWS = BM + 8;
   static constexpr int A_PASS = A_LDS ? 0 : (BM * 8 + CH_NT - 1) / CH_NT, B_PASS = BN / 64, NPASS = A_PASS + B_PASS;
@@ -120,7 +121,7 @@ struct ChainGemm {
     const float *sb = wst + stage * CH_WSTAGE;
     if (A_LDS) {
 #pragma unroll
-      for (int a = 0; a < MT; a++) F.a[a] = *reinterpret_cast<const gf4 *>(yimg + (16 * a + li) * 256 + (((8 * kt + 4 * c + kq) ^ li) << 2));
+      for (int a = 0; a < MT; a++) F.a[a] = *reinterpret_cast<const gf4 *>(yimg + (16 * a + li) * YLD + (((8 * kt + 4 * c + kq) ^ li) << 2));
     } else {
       const float *sa = ast + stage * A_STAGE;
 #pragma unroll

@@ -73,6 +73,20 @@ int tmjx_latent_concat_det(const float *fc2, int ldf, const float *obs, int64_t 
   return check_launch("k_latent_concat_det");
 }
 
+int tmjx_decoder_input(const float *latents, int ldz, const float *obs, int64_t obs_s0, int64_t obs_s1, const float *mean, const float *std,
+                       float *x, int ldx, int n, int Z, int obs_w, int ref_w, void *stream) {
+  if (!latents || !obs || !x) return fail(TMJX_EINVAL, "tmjx_decoder_input: null latents / obs / x");
+  if (!mean != !std) return fail(TMJX_EINVAL, "tmjx_decoder_input: mean and std together");
+  if (n < 1 || Z < 1 || ref_w < 0 || obs_w <= ref_w || ldz < Z || ldx < Z + obs_w - ref_w || obs_s0 < 0 || obs_s1 < 0)
+    return fail(TMJX_EINVAL, "tmjx_decoder_input: bad sizes (n >= 1, ldz >= Z >= 1, obs_w > ref_w >= 0, ldx >= Z + obs_w - ref_w)");
+  for (const void *p : {(const void *)latents, (const void *)obs, (const void *)mean, (const void *)std, (const void *)x})
+    if (!al4(p)) return fail(TMJX_EINVAL, "tmjx_decoder_input: misaligned float pointer");
+  // k_latent_concat_det reads columns [0, Z) of its first operand only: the latents go where fc2 = [mean | logvar] goes in the policy step
+  hipLaunchKernelGGL(k_latent_concat_det, dim3(grid_of((long long)n * ldx)), dim3(256), 0, (hipStream_t)stream, latents, ldz, obs, (long long)obs_s0,
+                     (long long)obs_s1, mean, std, x, ldx, (float *)nullptr, 0, n, Z, obs_w, ref_w);
+  return check_launch("k_latent_concat_det");
+}
+
 int tmjx_action_mode(const float *logits, int ldl, float *ctrl, float *action_t, int n, int A, void *stream) {
   if (!logits || !ctrl || !action_t) return fail(TMJX_EINVAL, "tmjx_action_mode: null logits / ctrl / action_t");
   if (n < 1 || A < 1 || ldl < 2 * A) return fail(TMJX_EINVAL, "tmjx_action_mode: n >= 1, A >= 1, ldl >= 2A");

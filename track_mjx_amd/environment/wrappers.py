@@ -9,8 +9,14 @@ runs that many times per `step` with the same action, rewards summed, the step c
 
 AutoAlignWrapperTracking (wrappers.py:328-381) and EvalClipWrapperTracking (wrappers.py:313-325) are the evaluation-side wrappers: the first
 switches the handle to the align done-policy (include/tmjx.h: tmjx_set_done_policy; csrc/wave_align.h), the second pins reset to a clip's frame 0.
+
+HighLevelWrapper (wrappers.py:384-412) puts a pretrained decoder INSIDE the env: step(state, latents) takes an intention vector per env instead of
+joint controls.  With a DecoderPolicy (agent/checkpoint.py: make_decoder_policy_fn) the decoder runs as launches on the env's own device buffers —
+one fused launch (include/tmjx.h: tmjx_decoder_act) where the decoder qualifies, else the roll-out policy step's decoder half, layer by layer.
 """
 from __future__ import annotations
+
+import ctypes as C
 
 from .task import MultiClipTracking
 
@@ -72,3 +78,229 @@ class EvalClipWrapperTracking:
         if int(ci.min()) < 0 or int(ci.max()) >= max(e._n_clips, 1):
             raise IndexError(f"clip_idx outside the table's {e._n_clips} clips")
         return e.reset(rng, ci, start_frame=torch.zeros(n, dtype=torch.int32), qvel_noise=torch.zeros((int(e.layout.nv), n)))
+
+
+def _ceil4(n: int) -> int:
+    return (int(n) + 3) // 4 * 4
+
+
+def _same_device(a, b) -> bool:
+    import torch
+    a, b = torch.device(a), torch.device(b)
+    if a.type != b.type:
+        return False
+    if a.type != "cuda":
+        return True
+    cur = torch.cuda.current_device() if (a.index is None or b.index is None) else 0
+    return (cur if a.index is None else a.index) == (cur if b.index is None else b.index)
+
+
+class _DecoderStep:
+    """Preallocated buffers and the launch list of the decoder policy for `n` envs reading the env's raw observation buffer obs_soa [W][n] and
+    writing the action as [nu][n] rows (what tmjx_step takes) — the decoder half of analysis.rollout._PolicyStep, fed with latents.
+
+    path "layers": tmjx_decoder_input (tmjx_latent_concat_det's kernel, for latents [n][ldz >= Z]) -> per block tmjx_linear_nolds + tmjx_silu_ln_fwd ->
+    head (tmjx_linear_nolds) -> tmjx_action_mode: the kernels, operand layouts and therefore the bits of the roll-out's policy step.
+    path "fused": one tmjx_decoder_act launch."""
+
+    def __init__(self, dp, n: int, obs_soa, path: str):
+        import torch
+        from .. import hip as _hip
+        self._hip, self.L = _hip, _hip.lib()
+        net, dev = dp.net, dp.device
+        self.n, self.path = int(n), path
+        Z, prop, A, ref = dp.latent_size, dp.proprioceptive_obs_size, dp.action_size, dp.reference_obs_size
+        W = int(obs_soa.shape[0])
+        self.Z, self.A = Z, A
+        f32 = dict(dtype=torch.float32, device=dev)
+        p = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+        # the normaliser as tmjx_latent_concat_det / tmjx_decoder_act index it: by observation column (the reference columns are never read)
+        self.mean = self.std = None
+        if dp.mean is not None:
+            self.mean, self.std = torch.zeros(W, **f32), torch.ones(W, **f32)
+            self.mean[ref:].copy_(dp.mean); self.std[ref:].copy_(dp.std)
+        self.ctrl = torch.empty((n, A), **f32)
+        self.action_t = torch.empty((A, n), **f32)
+        self.keep = []
+
+        def pad(w):          # [N][ceil4(K)] fp32 copy with zero pad columns: 16-byte aligned rows for the matrix-core kernels
+            N, K = w.shape
+            buf = torch.zeros((N, _ceil4(K)), **f32)
+            buf[:, :K].copy_(w.detach())
+            self.keep.append(buf)
+            return buf
+
+        self.calls = []              # (entry point, argument tuple with `None` where the latents' pointer / row stride go)
+        if path == "fused":
+            d = self.desc = _hip.DecoderAct()
+            d.obs, d.obs_s0, d.obs_s1, d.mean, d.std = p(obs_soa), 1, n, p(self.mean), p(self.std)
+            d.n, d.Z, d.obs_w, d.ref_w, d.n_blocks = n, Z, W, ref, len(net.decoder)
+            for i, blk in enumerate(net.decoder):
+                w = pad(blk.dense.weight)
+                b = d.block[i]
+                b.W, b.bias, b.gamma, b.beta, b.width, b.ldw = p(w), p(blk.dense.bias), p(blk.norm.weight), p(blk.norm.bias), blk.dense.out_features, w.shape[1]
+            wf = pad(net.head.weight)
+            d.Wf, d.bf, d.ldwf, d.A = p(wf), p(net.head.bias), wf.shape[1], A
+            d.eps = float(net.decoder[0].norm.eps)
+            d.action_t, d.ctrl, d.logits, d.ldl = p(self.action_t), p(self.ctrl), None, 0
+        else:
+            self.x = torch.zeros((n, _ceil4(Z + prop)), **f32)
+            self.calls.append(["tmjx_decoder_input", [None, None, p(obs_soa), 1, n, p(self.mean), p(self.std), p(self.x), self.x.shape[1], n, Z, W, ref]])
+            h = self.x
+            for blk in net.decoder:
+                N = blk.dense.out_features
+                w = pad(blk.dense.weight)
+                z, y, stats = torch.empty((n, N), **f32), torch.empty((n, N), **f32), torch.empty((n, 2), **f32)
+                self.keep += [z, y, stats]
+                self.calls.append(["tmjx_linear_nolds", [p(h), h.shape[1], 1, p(w), None, p(z), n, N, w.shape[1]]])
+                self.calls.append(["tmjx_silu_ln_fwd", [p(z), p(blk.dense.bias), p(blk.norm.weight), p(blk.norm.bias), p(y), p(stats), n, N, float(blk.norm.eps)]])
+                h = y
+            wf = pad(net.head.weight)
+            self.logits = torch.empty((n, 2 * A), **f32)
+            self.calls.append(["tmjx_linear_nolds", [p(h), h.shape[1], 1, p(wf), p(net.head.bias), p(self.logits), n, 2 * A, wf.shape[1]]])
+            self.calls.append(["tmjx_action_mode", [p(self.logits), 2 * A, p(self.ctrl), p(self.action_t), n, A]])
+
+    def launch(self, lat_ptr: int, ldz: int, stream) -> None:
+        """The decoder's launches on `stream` (ctypes calls only: no torch operation)."""
+        L, check = self.L, self._hip.check
+        if self.path == "fused":
+            self.desc.latents, self.desc.ldz = lat_ptr, ldz
+            check(L.tmjx_decoder_act(C.byref(self.desc), stream), "tmjx_decoder_act")
+            return
+        first = self.calls[0][1]
+        first[0], first[1] = lat_ptr, ldz
+        for name, args in self.calls:
+            check(getattr(L, name)(*args, stream), name)
+
+
+def decoder_act_why_not(dp, obs_w: int, n: int = 1) -> str | None:
+    """None if the fused launch (tmjx_decoder_act) runs this decoder, else the library's reason (tmjx_decoder_act_ok on a descriptor of its shapes)."""
+    from .. import hip as _hip
+    a = 1 << 20                  # a non-null, 16-byte aligned dummy address: the check reads shapes and alignments, never memory
+    d = _hip.DecoderAct()
+    d.latents, d.ldz, d.obs, d.obs_s0, d.obs_s1 = a, dp.latent_size, a, 1, n
+    d.n, d.Z, d.obs_w, d.ref_w, d.n_blocks = n, dp.latent_size, int(obs_w), dp.reference_obs_size, len(dp.decoder_layer_sizes)
+    k = dp.latent_size + dp.proprioceptive_obs_size
+    for i, wd in enumerate(dp.decoder_layer_sizes[:_hip.CHAIN_MAX_HIDDEN]):
+        b = d.block[i]
+        b.W, b.bias, b.gamma, b.beta, b.width, b.ldw = a, a, a, a, wd, _ceil4(k)
+        k = wd
+    d.Wf, d.bf, d.ldwf, d.A, d.eps, d.action_t = a, a, _ceil4(k), dp.action_size, 1e-6, a
+    L = _hip.lib()
+    if L.tmjx_decoder_act_ok(C.byref(d)) == 1:
+        return None
+    L.tmjx_decoder_act(C.byref(d), None)          # (refused before any device call: records the reason)
+    return L.tmjx_last_error().decode()
+
+
+class HighLevelWrapper:
+    """step(state, latents): the decoder's action on concat([latents, state.obs[..., reference_obs_size:]]) drives the wrapped env
+    (wrappers.py:384-412); reset and everything else are the wrapped env's, so it composes with wrap / AutoAlignWrapperTracking /
+    EvalClipWrapperTracking.  action_size is the latent width.
+
+    decoder_inference_fn: a DecoderPolicy on the env's device runs as launches on the env's buffers — after the first call `step` issues ctypes
+    calls only (no torch op, no allocation, no host synchronisation) and returns the same State object, whose tensors are views of the buffers
+    the kernels update in place.  `path`: "fused" (one tmjx_decoder_act launch; ValueError if the decoder does not qualify), "layers" (the
+    roll-out policy step's decoder half, any decoder shape), "auto" (fused where tmjx_decoder_act_ok says so AND AUTO_PREFERS_FUSED, else layers).
+    Any other callable fn(x) -> (action, extras) is called on the torch concat, as the reference does."""
+
+    # "auto" takes the fused launch only once tools/decoder_act_bench.py has shown it faster than the layer-by-layer list at 4 096 AND 8 192 envs by
+    # more than the spread of the alternating repeats (DESIGN.md §7).  That measurement has not been taken yet: "auto" means "layers", the fused
+    # launch is selected with path="fused"
+    AUTO_PREFERS_FUSED = False
+
+    def __init__(self, env, decoder_inference_fn, reference_obs_size: int, path: str = "auto"):
+        from ..agent.checkpoint import DecoderPolicy
+        if path not in ("auto", "fused", "layers"):
+            raise ValueError(f"HighLevelWrapper: path must be 'auto', 'fused' or 'layers', not {path!r}")
+        if not callable(decoder_inference_fn):
+            raise TypeError("HighLevelWrapper: decoder_inference_fn must be a DecoderPolicy or a callable fn(x) -> (action, extras)")
+        self.env, self._fn, self._ref = env, decoder_inference_fn, int(reference_obs_size)
+        W = int(env.observation_size)
+        if not 0 <= self._ref <= W:
+            raise ValueError(f"HighLevelWrapper: reference_obs_size {self._ref} outside the observation's {W} columns")
+        self._step = self._state = None
+        self.path = "callable"
+        if isinstance(decoder_inference_fn, DecoderPolicy):
+            dp = decoder_inference_fn
+            if dp.reference_obs_size != self._ref:
+                raise ValueError(f"HighLevelWrapper: reference_obs_size={self._ref}, but the decoder policy was built for {dp.reference_obs_size}")
+            if dp.proprioceptive_obs_size != W - self._ref:
+                raise ValueError(f"HighLevelWrapper: the env has {W - self._ref} proprioceptive columns, the decoder policy takes {dp.proprioceptive_obs_size}")
+            if dp.action_size != int(env.action_size):
+                raise ValueError(f"HighLevelWrapper: the decoder policy acts on {dp.action_size} controls, the env takes {int(env.action_size)}")
+            self._Z = dp.latent_size
+            import torch
+            if hasattr(env, "obs_buf") and dp.device.type == "cuda" and _same_device(env.device, dp.device):
+                why = decoder_act_why_not(dp, W, int(env.num_envs))
+                if path == "fused" and why is not None:
+                    raise ValueError(f"HighLevelWrapper: path='fused' does not run this decoder {list(dp.decoder_layer_sizes)}: {why}")
+                self.path = "fused" if path == "fused" or (path == "auto" and why is None and self.AUTO_PREFERS_FUSED) else "layers"
+            elif path != "auto":
+                raise ValueError(f"HighLevelWrapper: path={path!r} needs the decoder policy on the env's device ({getattr(env, 'device', None)}), it is on {dp.device}")
+        else:
+            if path != "auto":
+                raise ValueError(f"HighLevelWrapper: path={path!r} needs a DecoderPolicy (agent.checkpoint.make_decoder_policy_fn); a generic callable runs "
+                                 "through torch")
+            self._Z = None
+
+    def __getattr__(self, name):
+        return getattr(self.env, name)
+
+    @property
+    def action_size(self) -> int:
+        if self._Z is None:
+            raise AttributeError("HighLevelWrapper.action_size: a generic callable does not say its latent width")
+        return self._Z
+
+    @property
+    def observation_size(self) -> int:
+        return int(self.env.observation_size)
+
+    def reset(self, *a, **kw):
+        self._state = None
+        return self.env.reset(*a, **kw)
+
+    def _check_latents(self, latents):
+        n = int(self.env.num_envs)
+        if latents.dim() != 2 or latents.shape[0] != n:
+            raise ValueError(f"HighLevelWrapper.step: latents must be [{n}, Z] (one row per env), got {tuple(latents.shape)}")
+        if self._Z is not None and latents.shape[1] != self._Z:
+            raise ValueError(f"HighLevelWrapper.step: latents have {latents.shape[1]} columns, the decoder's intention size is {self._Z}")
+
+    def step(self, state, latents):
+        self._check_latents(latents)
+        env = self.env
+        if self.path == "callable":
+            import torch
+            x = torch.cat([latents.to(state.obs.device), state.obs[..., self._ref:]], dim=-1)
+            action, _ = self._fn(x)
+            return env.step(state, action)
+        import torch
+        if latents.device.type != "cuda" or (latents.device.index is not None and self._fn.device.index is not None
+                                             and latents.device.index != self._fn.device.index):
+            raise ValueError(f"HighLevelWrapper.step: latents are on {latents.device}, the env and its decoder on {self._fn.device}")
+        if latents.dtype != torch.float32 or latents.stride(1) != 1 or latents.stride(0) < latents.shape[1] or latents.data_ptr() % 4:
+            latents = latents.to(torch.float32).contiguous()
+        n = int(env.num_envs)
+        if self._step is None:
+            with torch.cuda.device(env.device):
+                self._step = _DecoderStep(self._fn, n, env.obs_buf, self.path)
+            p = lambda t: t.data_ptr()      # noqa: E731
+            self._env_args = (env._handle, p(env.state_buf), p(env.istate_buf), p(self._step.action_t), p(env.obs_buf), p(env.reward_buf), p(env.done_buf),
+                              p(env.trunc_buf), p(env.metrics_buf), p(env.workspace), n)
+        if self._state is None:
+            self._state = env._state()
+        if getattr(env, "_physics_events", None) is not None:
+            raise RuntimeError("HighLevelWrapper: the K2-bracketing measurement mode steps the plain env")
+        with torch.cuda.device(env.device):
+            stream = C.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)
+            self._step.launch(latents.data_ptr(), latents.stride(0), stream)
+            self._step._hip.check(self._step.L.tmjx_step(*self._env_args, stream), "tmjx_step")
+        self._keep_lat = latents
+        return self._state
+
+    @property
+    def last_ctrl(self):
+        """[n, A] view of the controls the decoder produced in the last device-path step (None before it)."""
+        return None if self._step is None else self._step.ctrl

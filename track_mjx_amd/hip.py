@@ -42,6 +42,7 @@ EXPORTS = ("tmjx_model_create", "tmjx_model_destroy", "tmjx_layout", "tmjx_clips
            "tmjx_chain_rows", "tmjx_chain_fwd_ok", "tmjx_chain_fwd", "tmjx_chain_bwd_ok", "tmjx_chain_bwd",
            "tmjx_lstm_hidden_ok", "tmjx_lstm_seq_fwd", "tmjx_lstm_seq_bwd",
            "tmjx_record_check", "tmjx_record_step", "tmjx_latent_concat_det", "tmjx_action_mode",
+           "tmjx_decoder_input", "tmjx_decoder_act_ok", "tmjx_decoder_act",
            "tmjx_sensor_info", "tmjx_physics_sensors", "tmjx_step_sensors",
            "tmjx_set_done_policy", "tmjx_clips_upload_velocities",
            "tmjx_debug_rows", "tmjx_last_error", "tmjx_version")
@@ -94,6 +95,22 @@ class ChainFwd(C.Structure):
                 ("Wf", C.c_void_p), ("bf", C.c_void_p), ("outf", C.c_void_p), ("Nf", C.c_int32), ("ldwf", C.c_int32), ("ldof", C.c_int32), ("eps", C.c_float), ("rows_alloc", C.c_int32),
                 ("lat_eps", C.c_void_p), ("lat_out", C.c_void_p), ("prop", C.c_void_p), ("lat_Z", C.c_int32), ("lat_ld", C.c_int32), ("prop_w", C.c_int32), ("prop_ld", C.c_int32),
                 ("prof", C.c_void_p)]
+
+
+CHAIN_MAX_HIDDEN = 4         # TMJX_CHAIN_MAX_HIDDEN (include/tmjx.h)
+
+
+class DecoderBlock(C.Structure):
+    """tmjx_decoder_block_t (include/tmjx.h)."""
+    _fields_ = [(k, C.c_void_p) for k in ("W", "bias", "gamma", "beta")] + [("width", C.c_int32), ("ldw", C.c_int32)]
+
+
+class DecoderAct(C.Structure):
+    """tmjx_decoder_act_t (include/tmjx.h)."""
+    _fields_ = [("latents", C.c_void_p), ("ldz", C.c_int32), ("obs", C.c_void_p), ("obs_s0", C.c_int64), ("obs_s1", C.c_int64), ("mean", C.c_void_p),
+                ("std", C.c_void_p), ("n", C.c_int32), ("Z", C.c_int32), ("obs_w", C.c_int32), ("ref_w", C.c_int32), ("n_blocks", C.c_int32),
+                ("block", DecoderBlock * CHAIN_MAX_HIDDEN), ("Wf", C.c_void_p), ("bf", C.c_void_p), ("ldwf", C.c_int32), ("A", C.c_int32), ("eps", C.c_float),
+                ("action_t", C.c_void_p), ("ctrl", C.c_void_p), ("logits", C.c_void_p), ("ldl", C.c_int32)]
 
 
 class ChainBwdStage(C.Structure):
@@ -343,6 +360,9 @@ def load(path: Path):
     sig.setdefault("tmjx_record_step", [None, None])[0] = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     sig.setdefault("tmjx_latent_concat_det", [None, None])[0] = [fp, C.c_int, fp, C.c_int64, C.c_int64, fp, fp, fp, C.c_int, fp, C.c_int] + [C.c_int] * 4 + [vp]
     sig.setdefault("tmjx_action_mode", [None, None])[0] = [fp, C.c_int, fp, fp, C.c_int, C.c_int, vp]
+    sig.setdefault("tmjx_decoder_input", [None, None])[0] = [fp, C.c_int, fp, C.c_int64, C.c_int64, fp, fp, fp, C.c_int] + [C.c_int] * 4 + [vp]
+    sig.setdefault("tmjx_decoder_act_ok", [None, None])[0] = [C.POINTER(DecoderAct)]
+    sig.setdefault("tmjx_decoder_act", [None, None])[0] = [C.POINTER(DecoderAct), vp]
     sig.setdefault("tmjx_debug_rows", [None, None])[0] = [vp, C.c_char_p, ip, ip]
     sig.setdefault("tmjx_last_error", [None, None])[1] = C.c_char_p
     sig.setdefault("tmjx_version", [None, None])[1] = C.c_char_p
