@@ -76,6 +76,19 @@ int tmjx_set_wrappers(tmjx_model *m, int episode_length, int auto_reset);
 #define TMJX_DONE_RESET 1
 #define TMJX_DONE_ALIGN 2
 int tmjx_set_done_policy(tmjx_model *m, int policy);
+/* Per-env domain randomisation: brax's DomainRandomizationVmapWrapper (track_mjx/environment/wrappers.py:44-47), restricted to three SCALARS per
+ * env.  `scales_dev` is DEVICE memory, float32 [3][n_env]: row 0 scales every contact's sliding friction, row 1 the actuators' force (gain and
+ * the affine bias pair; ctrlrange and the activation time constant are not scaled), row 2 the dofs' damping (passive force and the
+ * timestep * damping diagonal of the implicit Euler step).  Env e of a launch reads column e.  The scale multiplies the MODEL CONSTANT before it
+ * is used, so a power-of-two scale reproduces bit for bit a handle whose blob was scaled on the host.  The handle stores the pointer and the
+ * count; the caller owns the memory and keeps it alive and unchanged while launches read it.  Nothing on the device is validated.  NULL clears
+ * the scales: the handle then launches exactly what it launched before (the product kernel; the RAND kernel, csrc/tmjx_wave_rand.hip, runs only
+ * while scales are set).  Honoured by every launch of the physics kernel: tmjx_step (each action repeat, under all three done-policies),
+ * tmjx_physics, tmjx_physics_step, and the forward pass of tmjx_forward / tmjx_reset; a launch of more envs than `n_env` fails with
+ * TMJX_EINVAL.  The reward / observation kernels and the align policy's epilogue read no scaled constant and are unchanged.
+ * tmjx_physics_sensors / tmjx_step_sensors refuse a handle with scales (the recording kernel has no RAND build), as does a handle of the
+ * lane-per-env cross-check implementation.  Per-env models, masses and per-geom / per-dof / per-actuator vectors are not supported. */
+int tmjx_set_env_scales(tmjx_model *m, const float *scales_dev, int n_env);
 /* `action_repeat` of wrappers.wrap (track_mjx/environment/wrappers.py:21,43 -> brax EpisodeWrapper.step [3P]): tmjx_step then runs the
  * tracking env's own step `action_repeat` times with the same action (no termination check in between), returns the SUM of the repeats'
  * rewards, advances the episode's step counter by `action_repeat`, and takes observation / done / truncation / metrics from the last

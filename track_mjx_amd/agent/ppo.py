@@ -952,7 +952,7 @@ def train(environment, num_timesteps: int, episode_length: int, ckpt_mgr=None, c
           shuffle_rng: str = "torch", act_rng: str = "device", action_repeat: int = 1,
           policy_params_fn: Callable[..., None] = lambda *args, **kwargs: None, checkpoint_callback: Callable[[int], None] | None = None,
           use_lstm: bool = False, hidden_state_size: int = 128, hidden_layer_num: int = 2, checkpoint_to_restore: str | None = None,
-          freeze_decoder: bool = False, **unused):
+          freeze_decoder: bool = False, randomization_fn=None, **unused):
     """ppo.train(environment, num_timesteps, episode_length, ...) -> (make_policy, params, metrics)  (ppo.py:128-172,809).
 
     `environment` is an un-wrapped MultiClipTracking holding THIS rank's envs; it is wrapped here exactly like
@@ -977,6 +977,12 @@ def train(environment, num_timesteps: int, episode_length: int, ckpt_mgr=None, c
     `use_lstm`: the recurrent learner (agent/lstm.py: LSTMPPOLearner, the reference's agent/lstm_ppo) with `hidden_layer_num` LSTM layers of
     `hidden_state_size` features; the acting policies (evaluator, make_policy) then carry their own hidden state.
 
+    `randomization_fn` (ppo.py:147,455-473,631-659): per-env domain randomisation, restricted to three scales per env.  fn(model, rng) ->
+    environment.DomainRandomization for model["num_envs"] envs (environment.uniform_randomization_fn builds one from ranges).  The training envs'
+    scales are ONE global draw from key_env over all ranks' envs — every rank evaluates the same key and takes its shard, every env group of the
+    pipelined roll-out its slice of that —, the evaluator's a draw of `num_eval_envs` from eval_key; both keys come from `seed` alone
+    (environment/randomization.py: randomization_keys), so a resumed run has the same scales.
+
     `policy_params_fn` (ppo.py:162,220-224): called by process 0 after every eval epoch exactly as ppo.py:762-781 does — keyword arguments
     `current_step` (the eval iteration), `jit_logging_inference_fn` (the DETERMINISTIC logging policy of ppo_networks.py:103-149:
     (params, observations, key_sample) -> (action, {"latent_mean", "latent_logvar"})), `params` ((normalizer, policy) state), a fresh
@@ -993,7 +999,22 @@ def train(environment, num_timesteps: int, episode_length: int, ckpt_mgr=None, c
         restore_from = checkpoint_to_restore          # the whole training state (checkpointing.load_training_state, ppo.py:561-567)
     from ..environment import wrap
     # a list of environments = equal groups of this rank's envs whose roll-outs are pipelined on separate HIP streams (collect())
-    env_list = [wrap(e, episode_length=int(episode_length), action_repeat=int(action_repeat)) for e in (environment if isinstance(environment, (list, tuple)) else [environment])]
+    raw_envs = list(environment) if isinstance(environment, (list, tuple)) else [environment]
+    group_dr = [None] * len(raw_envs)
+    eval_key = None
+    if randomization_fn is not None:
+        from ..environment import randomization as _rand
+        key_env, eval_key = _rand.randomization_keys(seed)
+        world_ = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
+        rank_ = dist.get_rank(group) if world_ > 1 else 0
+        n_local = sum(int(e.num_envs) for e in raw_envs)
+        local_dr = _rand.shard_scales(_rand.draw_for_training(randomization_fn, raw_envs[0], key_env, n_local * world_), rank_, world_)
+        lo_ = 0
+        for k, e in enumerate(raw_envs):
+            group_dr[k] = local_dr.shard(lo_, lo_ + int(e.num_envs))
+            lo_ += int(e.num_envs)
+    env_list = [wrap(e, episode_length=int(episode_length), action_repeat=int(action_repeat),
+                     randomization_fn=None if d is None else (lambda m, d=d: d)) for e, d in zip(raw_envs, group_dr)]
     env = env_list[0]
     learner_cls, lstm_kw = PPOLearner, {}
     if use_lstm:
@@ -1059,7 +1080,9 @@ def train(environment, num_timesteps: int, episode_length: int, ckpt_mgr=None, c
             eval_policy = CarriedPolicy(learner, deterministic=deterministic_eval, gen=eval_gen)
         else:
             eval_policy = lambda obs: learner.act(obs, deterministic=deterministic_eval, gen=eval_gen)   # noqa: E731
-        evaluator = Evaluator(wrap(eval_env, episode_length=int(episode_length), action_repeat=int(action_repeat)),
+        eval_dr = None if randomization_fn is None else _rand.draw_for_training(randomization_fn, eval_env, eval_key, int(eval_env.num_envs))
+        evaluator = Evaluator(wrap(eval_env, episode_length=int(episode_length), action_repeat=int(action_repeat),
+                                   randomization_fn=None if eval_dr is None else (lambda m: eval_dr)),
                               eval_policy, episode_length=int(episode_length),
                               action_repeat=int(action_repeat), seed=seed + 7)
     render_interval = max(int(((config_dict or {}).get("env_config") or {}).get("render_interval", 1) or 1), 1)

@@ -286,9 +286,21 @@ def _upload_table(streams: Sequence, n: int, T: int, dev) -> torch.Tensor:
 # ---------------------------------------------------------------------------------------------------------------- generator
 def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, model: str = "mlp", log_activations: bool = False,
                              log_metrics: bool = False, log_sensor_data: bool = False, clips_per_batch: int = CLIPS_PER_BATCH,
-                             align_on_fail: bool = False):
+                             align_on_fail: bool = False, friction_scale=None, actuator_scale=None, damping_scale=None):
     """rollout.py:73-269.  Returns generate_rollout(clip_idx=None, seed=42): one clip (int / None) -> dict of arrays; a sequence of clips -> the
-    same dict with a leading [N] axis (batches larger than `clips_per_batch` run in chunks)."""
+    same dict with a leading [N] axis (batches larger than `clips_per_batch` run in chunks).
+
+    `friction_scale` / `actuator_scale` / `damping_scale` (the perturbation experiment): one float for every clip, or one per clip of a
+    generate_rollout call — each roll-out env then runs with its clip's scales of the model's sliding friction, actuator force and dof damping
+    (environment.DomainRandomization), and the result carries them as `domain_scales` [3].  All None: the env as it was given."""
+    given_scales = {k: v for k, v in (("friction", friction_scale), ("actuator", actuator_scale), ("damping", damping_scale)) if v is not None}
+    if given_scales and not hasattr(environment, "set_domain_randomization"):
+        raise NotImplementedError(f"friction_scale / actuator_scale / damping_scale: {type(environment).__name__} has no per-env scales "
+                                  "(MultiClipTracking.set_domain_randomization)")
+    if given_scales and log_sensor_data:
+        raise NotImplementedError("log_sensor_data cannot be combined with friction_scale / actuator_scale / damping_scale: the recording physics "
+                                  "kernel that produces sensor_readings and joint_forces has no domain-randomisation build; run the perturbed "
+                                  "roll-out without log_sensor_data, or the sensor roll-out without scales")
     if log_sensor_data and not hasattr(environment, "sensor_buffers"):
         raise NotImplementedError("log_sensor_data: cfrc_ext and sensordata are not computed by the physics kernel of this environment: they "
                                   "come from MultiClipTracking's recording kernel (tmjx_step_sensors), and the environment given is "
@@ -334,9 +346,26 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
             envs[n] = _sibling_env(env0, n)
         return with_policy(envs[n])
 
-    def run_batch(clips: list, seed: int) -> dict:
+    def scales_of(n: int, offset: int, total: int):
+        """[3][n] scales of clips offset .. offset + n of a call of `total` clips, or None."""
+        if not given_scales:
+            return None
+        tab = np.ones((3, n), np.float32)
+        for r, name in enumerate(("friction", "actuator", "damping")):
+            if name not in given_scales:
+                continue
+            v = np.atleast_1d(np.asarray(given_scales[name], dtype=np.float64)).ravel()
+            if v.size not in (1, total):
+                raise ValueError(f"{name}_scale: {v.size} values for {total} clips (one value, or one per clip)")
+            tab[r] = v[0] if v.size == 1 else v[offset:offset + n]
+        return tab
+
+    def run_batch(clips: list, seed: int, scales=None) -> dict:
         n = len(clips)
         env = env_of(n)
+        if scales is not None:
+            from ..environment import DomainRandomization
+            env.set_domain_randomization(DomainRandomization(scales[0], scales[1], scales[2]))
         dev, Lay = env.device, env.layout
         nq, nv = int(Lay.nq), int(Lay.nv)
         qn, vn = np.empty((nq, n), np.float32), np.empty((nv, n), np.float32)
@@ -413,6 +442,8 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
         rows = [np.repeat(np.hstack([np.asarray(ref.position[c], np.float32), np.asarray(ref.quaternion[c], np.float32),
                                      np.asarray(ref.joints[c], np.float32)]), int(spf), axis=0) for c in clips]
         out["qposes_ref"] = np.stack(rows)
+        if scales is not None:
+            out["domain_scales"] = np.ascontiguousarray(scales.T)          # [n, 3]: friction, actuator, damping of each clip's env
         if align_on_fail:
             out["aligned"] = host["aligned"][:, :, 0] != 0
             out["n_alignments"] = out["aligned"].sum(axis=1).astype(np.int64)
@@ -439,7 +470,13 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
             out["activations"] = acts
         return out
 
-    def generate_rollout(clip_idx: int | Sequence[int] | None = None, seed: int = 42) -> dict:
+    def generate_rollout(clip_idx: int | Sequence[int] | None = None, seed: int = 42, scales: dict | None = None) -> dict:
+        """`scales`: {"friction" | "actuator" | "damping": float or one per clip} for THIS call, in place of the generator's own (a generator made
+        without scales takes none: its sensor / env checks were made for the plain env)."""
+        if scales is not None:
+            if not given_scales:
+                raise ValueError("generate_rollout(scales=...): the generator was created without friction_scale / actuator_scale / damping_scale")
+            given_scales.clear(); given_scales.update({k: v for k, v in scales.items() if v is not None})
         batched = clip_idx is not None and not isinstance(clip_idx, (int, np.integer))
         if batched:
             clips = [int(c) for c in clip_idx]
@@ -451,7 +488,8 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
         bad = [c for c in clips if not 0 <= c < env0._n_clips]
         if bad:
             raise IndexError(f"clip indices {bad[:5]} outside the table's {env0._n_clips} clips")
-        parts = [run_batch(clips[i:i + clips_per_batch], seed) for i in range(0, len(clips), int(clips_per_batch))]
+        parts = [run_batch(clips[i:i + clips_per_batch], seed, scales_of(len(clips[i:i + clips_per_batch]), i, len(clips)))
+                 for i in range(0, len(clips), int(clips_per_batch))]
         out = _concat(parts) if len(parts) > 1 else parts[0]
         return out if batched else _index0(out)
 
@@ -501,7 +539,7 @@ def _parse_clips(spec: str, n_clips: int) -> list:
 
 
 CLI_OPTIONS = ("checkpoint", "clips", "seed", "out", "log_activations", "log_metrics", "log_sensor_data", "align_on_fail", "step",
-               "replay_latents", "latent_scale", "path")
+               "replay_latents", "latent_scale", "path", "friction_scale", "actuator_scale", "damping_scale")
 
 
 def replay_latents(cfg: dict, decoder_policy, clips: Sequence[int], latents: np.ndarray, seed: int = 42, path: str = "auto", metrics=ROLLOUT_METRICS) -> dict:
@@ -592,6 +630,7 @@ def main(argv=None) -> int:
     if "checkpoint" not in opts:
         print("usage: python -m track_mjx_amd.analysis.rollout checkpoint=<run dir | step dir> [data_path=...] [clips=all|a:b|i,j,k] [seed=42] "
               "[out=<dir>] [log_activations=true] [log_metrics=true] [log_sensor_data=false] [align_on_fail=false] "
+              "[friction_scale=<s | s0,s1,..>] [actuator_scale=..] [damping_scale=..] "
               "[replay_latents=<dir of clip_<i>.h5> [latent_scale=1.0] [path=auto|fused|layers]] [key=value config overrides ...]", file=sys.stderr)
         return 2
     yes = lambda v: str(v).lower() in ("1", "true", "yes")     # noqa: E731
@@ -619,11 +658,20 @@ def main(argv=None) -> int:
     log_act, log_met = yes(opts.get("log_activations", "true")), yes(opts.get("log_metrics", "true"))
     log_sens = yes(opts.get("log_sensor_data", "false"))
     align = yes(opts.get("align_on_fail", "false"))
+    clips = _parse_clips(opts.get("clips", "all"), env._n_clips)
+
+    def scale_opt(name):          # one float, or a comma list with one value per clip
+        if name not in opts:
+            return None
+        v = [float(x) for x in str(opts[name]).split(",") if x.strip() != ""]
+        if len(v) not in (1, len(clips)):
+            raise ValueError(f"{name}: {len(v)} values for {len(clips)} clips (one value, or one per clip)")
+        return v
+    scale_lists = {k: scale_opt(k) for k in ("friction_scale", "actuator_scale", "damping_scale")}
     gen = create_rollout_generator(cfg, env, fn, model=fn.model, log_activations=log_act, log_metrics=log_met, log_sensor_data=log_sens,
-                                   align_on_fail=align)
+                                   align_on_fail=align, **{k: (None if v is None else 1.0) for k, v in scale_lists.items()})
     print(f"[rollout] done-policy: {gen.done_policy}" + (" (a done env is re-aligned to the clip frame it has reached; `aligned` / `n_alignments` "
                                                         "are recorded)" if align else " (the env keeps stepping after done)"), flush=True)
-    clips = _parse_clips(opts.get("clips", "all"), env._n_clips)
     out_dir = opts.get("out", os.path.join(step_dir, "rollouts"))
     os.makedirs(out_dir, exist_ok=True)
     meta_common = {"seed": np.int64(seed), "checkpoint_step": np.int64(int(os.path.basename(os.path.normpath(step_dir)))
@@ -640,7 +688,8 @@ def main(argv=None) -> int:
                                                    "subtree_com[body_rootid] (mj_rnePostConstraint); values of the control step's last substep")
     for i in range(0, len(clips), CLIPS_PER_BATCH):
         chunk = clips[i:i + CLIPS_PER_BATCH]
-        res = gen(chunk, seed=seed)
+        sc = {k.split("_")[0]: (v[0] if len(v) == 1 else v[i:i + len(chunk)]) for k, v in scale_lists.items() if v is not None}
+        res = gen(chunk, seed=seed, **({"scales": sc} if sc else {}))
         for j, c in enumerate(chunk):
             one = _index_j(res, j)
             one["meta"] = dict(meta_common, clip_idx=np.int64(c))

@@ -137,6 +137,9 @@ struct DModel {
   // sensor fields are.
   int done_policy;
   const float *clip_vel, *clip_jvel;   // (C, F, 3) root linear velocity, (C, F, nv - 6) joint velocities
+  // t of con_invweight = (t + mu^2 t) 2 mu^2 / impratio (the two bodies' invweight0 summed): read only by the RAND physics kernel (per-env
+  // friction scales, csrc/tmjx_wave_rand.hip), which forms the weight from its own env's mu.  Behind everything else, as the fields above.
+  float con_tw[TM_MAXC];
 };
 enum { TM_DONE_NONE = 0, TM_DONE_RESET = 1, TM_DONE_ALIGN = 2 };
 

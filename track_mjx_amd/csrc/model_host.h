@@ -207,6 +207,7 @@ inline bool build_dmodel(const void *blob, size_t nbytes, DModel &m, std::string
     float mu = fr[c * 3];
     m.con_mu[c] = mu;
     float t = binv[m.con_body1[c] * 2] + binv[m.con_body2[c] * 2];
+    m.con_tw[c] = t;
     m.con_invweight[c] = (t + mu * mu * t) * 2.f * mu * mu / m.impratio;  // pyramidal edge, condim 3
     int b = m.con_body2[c];
     if (m.ngroup == 0 || m.grp_body[m.ngroup - 1] != b) {

@@ -71,6 +71,32 @@ typedef const __attribute__((address_space(4))) DModel TmwModel;
 #endif
 // a small model array as a local (the vector helpers of tm_common.h take plain pointers)
 #define TMW_LOCAL(name, n, src) float name[n]; { _Pragma("unroll") for (int k_ = 0; k_ < (n); k_++) name[k_] = (src)[k_]; }
+// ---- per-env domain randomisation (tmjx_set_env_scales): the RAND build of this body.  csrc/tmjx_wave_rand.hip (and tests/hostemu/rand_emu.cpp)
+// define TMW_RAND in front of this header; no other unit does, and without it the two macros below expand to NOTHING / to their first argument:
+// every other unit compiles the tokens it compiled before the switch existed.  One env = one wavefront, so the three scales are wave-uniform
+// scalars.  A scale is applied to the MODEL CONSTANT, before the constant is used (mu = con_mu s_f, gain s_a, b0 s_a, b1 s_a, damping s_d) and the
+// product is made opaque to the optimiser (tmw_scaled), so that it cannot be contracted into the expression that uses it: with a power-of-two
+// scale the product is exact and the run reproduces, bit for bit, the plain kernel on a model whose constants were scaled on the host.
+#ifdef TMW_RAND
+#define TMW_RAND_ONLY(...) __VA_ARGS__
+#define TMW_SCALE(x, s) tmw_scaled((x), c.s)
+#ifdef TM_HOST_EMU
+TM_DEV float tmw_scaled(float x, float s) { volatile float r = x * s; return r; }
+#else
+TM_DEV float tmw_scaled(float x, float s) { float r = x * s; asm volatile("" : "+v"(r)); return r; }
+#endif
+// R's weight of a contact's pyramid rows: model_host.h's expression (t + mu^2 t) 2 mu^2 / impratio with the scaled mu, rounded operation by
+// operation as the host rounds it (every product opaque: no FMA contraction)
+TM_DEV float tmw_rand_invweight(float t, float mu, float impratio) {
+  const float mm = tmw_scaled(mu, mu), a = tmw_scaled(mm, t), b = tmw_scaled(t + a, 2.f), d = tmw_scaled(b, mu), e = tmw_scaled(d, mu);
+  return e / impratio;
+}
+#define TMW_CON_IW(cc) tmw_rand_invweight(m.con_tw[cc], TMW_MU(cc), m.impratio)
+#else
+#define TMW_RAND_ONLY(...)
+#define TMW_SCALE(x, s) x
+#define TMW_CON_IW(cc) m.con_invweight[cc]
+#endif
 #define TMW_EMU_HAS_QA 1      // (tests/hostemu: WCtx carries the qa* / ma* registers)
 struct WCtx {
   TmwModel *mp;
@@ -94,6 +120,7 @@ struct WCtx {
   float ma0[TMW_NL], ma1[TMW_NL];     // lean layout, CG: ut = y - y_s (first M qacc; parked in / staged through l_Ma = l_Mgrad)
   int tp0[TMW_NL], tp1[TMW_NL];       // lean layout: packed index word of dof lane / lane + 64 (DModel::tpack; round 5: the table left LDS)
   float *mspill;              // chain layout (WLayout::m_spilled): this env's copy of M in global memory (nnz words, 64 readable words in front)
+  TMW_RAND_ONLY(float s_f, s_a, s_d;)   // RAND build: this env's friction / actuator / damping scale (wave-uniform: one scalar load each per launch)
 };
 // solver statistics of the last substep, kept in the spare LDS word behind the centre of mass (registers are what this kernel has none
 // left of): 64 * CG iterations (MJX data.solver_niter) + line-search iterations summed over them; tmw_dump unpacks it for the tests
@@ -141,7 +168,7 @@ struct WCtx {
 #define TMW_WP(i) ((i) < 64 ? c.wp0[TMW_LI] : c.wp1[TMW_LI])
 #define TMW_WP_SET(i, v) do { if ((i) < 64) c.wp0[TMW_LI] = (v); else c.wp1[TMW_LI] = (v); } while (0)
 // friction coefficient of contact slot cc: lean layout = ONE coefficient for all slots (a uniform model read; tmjx_host::rodent_chains_match)
-#define TMW_MU(cc) (K.lean ? m.con_mu[0] : L[K.l_con_mu + (cc)])
+#define TMW_MU(cc) (K.lean ? TMW_SCALE(m.con_mu[0], s_f) : L[K.l_con_mu + (cc)])
 // efc_D of compact row kr: the four pyramid rows of a contact share ONE value (same penetration, impedance and weight), so the lean layout keeps
 // it per contact — limits first (row = index), then one word per active contact (nlim + ncon words instead of nlim + 4 ncon; round 5)
 #ifdef TMW_NO_EFCD_PACK
@@ -253,7 +280,7 @@ TM_DEV float tmw_load_state(WCtx &c, const WLayout &K, const float *action) {
       }
       for (int g = lane; g < K.ngroup; g += 64) ((signed char *)(L + K.l_tgrp))[g] = (signed char)m.grp_lastdof[g];
     }
-    for (int cc = lane; cc < K.ncon; cc += 64) { if (!K.lean) L[K.l_con_mu + cc] = m.con_mu[cc]; TMW_CONGRP(K)[cc] = (unsigned char)m.con_grp[cc]; }
+    for (int cc = lane; cc < K.ncon; cc += 64) { if (!K.lean) L[K.l_con_mu + cc] = TMW_SCALE(m.con_mu[cc], s_f); TMW_CONGRP(K)[cc] = (unsigned char)m.con_grp[cc]; }
     {
       int su = lane / 6;
       bool ok = lane < m.n_wsub * 6;
@@ -775,7 +802,7 @@ TM_DEV void tmw_velocity_inertia(WCtx &c, const WLayout &K) {
         float len = 0.f;
         for (int e = e0; e < e1; e++) len += m.act_mval[e] * L[K.l_qpos + m.act_mqpos[e]];
         const float act = K.lean ? WST(m.s_act, a) : L[K.l_act + a];
-        L[K.l_sv + a] = m.act_gain[a] * act + (m.act_b0[a] + m.act_b1[a] * len);
+        L[K.l_sv + a] = TMW_SCALE(m.act_gain[a], s_a) * act + (TMW_SCALE(m.act_b0[a], s_a) + TMW_SCALE(m.act_b1[a], s_a) * len);
       }
     }
   } else if (K.lean) { TMW_FOR { for (int a = lane; a < K.nu; a += 64) L[K.l_sv + a] = WST(m.s_act, a); } }
@@ -800,6 +827,7 @@ TM_DEV void tmw_velocity_inertia(WCtx &c, const WLayout &K) {
       const int i = lane + 64 * slot < K.nv ? lane + 64 * slot : K.nv - 1;
 #pragma unroll
       for (int k = 0; k < 8; k++) dd[slot][k] = m.dof_dyn[i][k];
+      TMW_RAND_ONLY(dd[slot][2] = tmw_scaled(dd[slot][2], c.s_d);)
     }
 #pragma unroll
     for (int slot = 0; slot < 2; slot++) {
@@ -824,7 +852,7 @@ TM_DEV void tmw_velocity_inertia(WCtx &c, const WLayout &K) {
       const float bias = i < 64 ? bias0[TMW_LI] : bias1[TMW_LI];
       float fa = 0.f;
       if (has_bias) { for (int e = tm_f2i(rc[6]); e < tm_f2i(rc[7]); e++) fa += m.dof_act_coef[e] * L[K.l_sv + m.dof_act_id[e]]; }
-      else for (int e = tm_f2i(rc[6]); e < tm_f2i(rc[7]); e++) { int u = m.dof_act_id[e]; fa += m.dof_act_coef[e] * (m.dof_act_gain[e] * L[(K.lean ? K.l_sv : K.l_act) + u]); }
+      else for (int e = tm_f2i(rc[6]); e < tm_f2i(rc[7]); e++) { int u = m.dof_act_id[e]; fa += m.dof_act_coef[e] * (TMW_SCALE(m.dof_act_gain[e], s_a) * L[(K.lean ? K.l_sv : K.l_act) + u]); }
       WST(m.s_qfrc_actuator, i) = fa;
       float f = -rc[2] * L[K.l_qvel + i] - bias + fa;
       if (rc[3] != 0.f) f += -rc[3] * (L[K.l_qpos + tm_f2i(rc[4])] - rc[5]);
@@ -850,7 +878,7 @@ TM_DEV void tmw_factor(WCtx &c, const WLayout &K, float hdamp, int rhs = -1) {
   }
   TMW_SYNC();
   if (hdamp != 0.f) {
-    TMW_FOR { for (int i = lane; i < K.nv; i += 64) L[K.l_LD + m.dof_Madr[i]] += hdamp * m.dof_damping[i]; }
+    TMW_FOR { for (int i = lane; i < K.nv; i += 64) L[K.l_LD + m.dof_Madr[i]] += hdamp * TMW_SCALE(m.dof_damping[i], s_d); }
     TMW_SYNC();
   }
   TMW_REG(float, a0); TMW_REG(float, a1); TMW_REG(float, b0); TMW_REG(float, b1); TMW_REG(float, acc); TMW_REG(float, pr);
@@ -1883,7 +1911,7 @@ TM_DEV void tmw_make_constraint(WCtx &c, const WLayout &K) {
         pos = L[K.l_con_dist + cc];
         for (int t = 0; t < 2; t++) solref[t] = m.con_solref[cc][t];
         for (int t = 0; t < 5; t++) solimp[t] = m.con_solimp[cc][t];
-        iw = m.con_invweight[cc];
+        iw = TMW_CON_IW(cc);
       }
       tm_kbi(m.timestep, solref, solimp, pos, k, b, imp);
       float Rr = fmaxf(iw * (1.f - imp) / imp, TM_MINVAL);
@@ -1908,7 +1936,7 @@ TM_DEV void tmw_make_constraint(WCtx &c, const WLayout &K) {
           int cc = (r - K.nlim) >> 2;
           pos = L[K.l_con_dist + cc];
           { TMW_LOCAL(sr_, 2, m.con_solref[cc]); TMW_LOCAL(si_, 5, m.con_solimp[cc]); tm_kbi(m.timestep, sr_, si_, pos, k, b, imp); }
-          iw = m.con_invweight[cc];
+          iw = TMW_CON_IW(cc);
           if (TMW_CCROW(K)[cc] != 255) kr = TMW_CCROW(K)[cc] + ((r - K.nlim) & 3);
         }
         float Rr = fmaxf(iw * (1.f - imp) / imp, TM_MINVAL);
@@ -2411,7 +2439,7 @@ TM_DEV float tmw_euler(WCtx &c, const WLayout &K, float time) {
   // timestep * damping (the diagonal Euler adds to M) into the dead search vector; the activation state is advanced here already — nothing
   // reads act between tmw_velocity_inertia and the end of the substep — so that ctrl's global load sits next to the loads above
   TMW_FOR {
-    { const int i1 = TMW_I1(K); const float dm0 = m.dof_damping[lane], dm1 = m.dof_damping[i1]; L[K.l_hdamp + lane] = m.timestep * dm0; if (TMW_OK1(K)) L[K.l_hdamp + i1] = m.timestep * dm1; }
+    { const int i1 = TMW_I1(K); const float dm0 = TMW_SCALE(m.dof_damping[lane], s_d), dm1 = TMW_SCALE(m.dof_damping[i1], s_d); L[K.l_hdamp + lane] = m.timestep * dm0; if (TMW_OK1(K)) L[K.l_hdamp + i1] = m.timestep * dm1; }
     for (int a = lane; a < K.nu; a += 64) {
       // (record mode: the action rows were transposed in behind the state + output rows)
       float ctrl = c.rs ? c.st[(size_t)c.e * (size_t)c.rs + (size_t)(m.s_prev_ctrl + a)] : (c.action ? c.action[(size_t)a * c.n + c.e] : 0.f);

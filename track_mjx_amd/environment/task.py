@@ -111,6 +111,8 @@ class MultiClipTracking:
         self._done_policy = "reset" if self._auto_reset else "none"
         # the env groups of one rank read ONE resident clip table (tmjx_clips_share): this env uses `share_clips_with`'s device arrays
         self._clip_owner = share_clips_with
+        self._domain_randomization = None     # set_domain_randomization: the current per-env scales
+        self._scales_dev = None               # ... and their [3][n] device tensor, which the handle reads by pointer
         self._create_handle()
         self._alloc()
 
@@ -357,6 +359,33 @@ class MultiClipTracking:
         L = self.layout
         t = self.state_buf[L.time] * float(self._mocap_hz)
         return torch.floor(t + self.istate_buf[L.i_start_frame].float()).to(torch.int32)
+
+    # ---- per-env domain randomisation (include/tmjx.h: tmjx_set_env_scales; environment/randomization.py)
+    @property
+    def domain_randomization(self):
+        """The DomainRandomization in force (None: not randomised)."""
+        return self._domain_randomization
+
+    def set_domain_randomization(self, dr) -> None:
+        """Per-env friction / actuator / damping scales for every later physics launch of this env (None clears them: the handle then launches
+        the plain kernel again).  Uploads the [3][num_envs] table, keeps it alive and hands its pointer to the handle.  The sensor-recording step
+        (step_sensors) refuses an env with scales."""
+        from .randomization import DomainRandomization
+        if dr is not None and not isinstance(dr, DomainRandomization):
+            raise TypeError(f"set_domain_randomization takes a DomainRandomization or None, not {type(dr).__name__}")
+        if dr is not None and dr.num_envs != self.num_envs:
+            raise ValueError(f"DomainRandomization for {dr.num_envs} envs on an env of {self.num_envs}")
+        with torch.cuda.device(self.device):
+            torch.cuda.synchronize(self.device)        # no launch of this handle may still read the old table
+            if dr is None:
+                _hip.check(self._L.tmjx_set_env_scales(self._handle, None, 0), "tmjx_set_env_scales")
+                self._scales_dev = None
+            else:
+                t = torch.from_numpy(dr.table()).to(self.device).contiguous()
+                torch.cuda.synchronize(self.device)
+                _hip.check(self._L.tmjx_set_env_scales(self._handle, _ptr(t), self.num_envs), "tmjx_set_env_scales")
+                self._scales_dev = t
+        self._domain_randomization = dr
 
     def configure_wrappers(self, episode_length: int, auto_reset: bool, action_repeat: int = 1, done_policy: str | None = None) -> None:
         """Switch the Episode / AutoReset wrapper semantics of the handle (wrappers.wrap): two constants of the device model change,

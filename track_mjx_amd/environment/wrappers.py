@@ -28,21 +28,23 @@ def wrap(env: MultiClipTracking, episode_length: int = 1000, action_repeat: int 
     `use_lstm`, `hidden_state_dim`, `hidden_layer_num` are accepted for signature parity: the LSTM
     auto-reset wrapper differs from the plain one only by an unused `info["hidden_state"]`
     (wrappers.py:59-144 vs 278-310), which is not materialised."""
-    if randomization_fn is not None:
-        # brax's DomainRandomizationVmapWrapper steps every env with its own copy of the mjx.Model; the physics kernel reads ONE model
-        # from constant memory (csrc/dmodel.h), and no reference config or call site passes a randomization_fn (ppo.py:466-474)
-        raise NotImplementedError("domain randomisation (a per-env model) is not supported: the device model is one constant per handle")
     env.configure_wrappers(int(episode_length), auto_reset=True, action_repeat=int(action_repeat))
+    if randomization_fn is not None:
+        # brax's DomainRandomizationVmapWrapper (wrappers.py:44-47) steps every env with its own copy of the mjx.Model; the physics kernel reads
+        # ONE model from constant memory (csrc/dmodel.h) plus three per-env SCALARS (csrc/tmjx_wave_rand.hip): randomization_fn(model) returns a
+        # DomainRandomization (environment/randomization.py); a per-env model raises NotImplementedError
+        from .randomization import apply_randomization_fn
+        apply_randomization_fn(env, randomization_fn)
     return env
 
 
-def AutoAlignWrapperTracking(env: MultiClipTracking, episode_length: int = 1000, action_repeat: int = 1) -> MultiClipTracking:
+def AutoAlignWrapperTracking(env: MultiClipTracking, episode_length: int = 1000, action_repeat: int = 1, randomization_fn=None) -> MultiClipTracking:
     """Align-on-failure tracking (wrappers.py:328-381) with brax EpisodeWrapper's step counter / truncation underneath it, in the style of `wrap`:
     the handle is switched to the align done-policy and the env itself is returned.  An env whose step ends with done set (terminated or truncated
     at `episode_length`) is put onto the reference pose and velocities of the clip frame it has reached — kinematics and a fresh observation
     included, inside the same `step` — and tracking goes on; `state.done` of that step counts one re-alignment.  time is not rewound and
     prev_ctrl is not restored.  With `action_repeat` > 1 the alignment follows the last inner step.  Needs the clip set's velocity and
-    joints_velocity (a ValueError / TmjxError otherwise)."""
+    joints_velocity (a ValueError / TmjxError otherwise).  `randomization_fn`: as in `wrap` (per-env scales; the alignment itself is kinematics and reads none)."""
     if not isinstance(env, MultiClipTracking):
         raise TypeError(f"AutoAlignWrapperTracking wraps a MultiClipTracking env, not {type(env).__name__}")
     if int(episode_length) < 1:
@@ -50,6 +52,9 @@ def AutoAlignWrapperTracking(env: MultiClipTracking, episode_length: int = 1000,
     if int(action_repeat) < 1:
         raise ValueError("action_repeat must be >= 1")
     env.configure_wrappers(int(episode_length), auto_reset=False, action_repeat=int(action_repeat), done_policy="align")
+    if randomization_fn is not None:
+        from .randomization import apply_randomization_fn
+        apply_randomization_fn(env, randomization_fn)
     return env
 
 

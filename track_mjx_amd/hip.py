@@ -15,10 +15,11 @@ _PKG = Path(__file__).resolve().parent
 SO_PATH = Path(os.environ.get("TMJX_SO", str(_PKG / "libtmjx_hip.so")))  # TMJX_SO: alternative build (profiling)
 CSRC = _PKG / "csrc"
 SOURCES = (CSRC / "tmjx_hip.hip", CSRC / "tmjx_bf16.hip", CSRC / "tmjx_wave.hip", CSRC / "tmjx_chain.hip", CSRC / "tmjx_lstm.hip",
-           CSRC / "tmjx_rollout.hip", CSRC / "tmjx_wave_sensors.hip", CSRC / "tmjx_wave_align.hip")
+           CSRC / "tmjx_rollout.hip", CSRC / "tmjx_wave_sensors.hip", CSRC / "tmjx_wave_align.hip", CSRC / "tmjx_wave_rand.hip")
 # per-source compiler flags: the physics kernel's unit is built without machine LICM (csrc/tmjx_wave.hip says why)
 SOURCE_FLAGS = {"tmjx_wave.hip": ("-mllvm", "-disable-machine-licm"),
-                "tmjx_wave_sensors.hip": ("-mllvm", "-disable-machine-licm")}      # (the recording kernel: the same loop body)
+                "tmjx_wave_sensors.hip": ("-mllvm", "-disable-machine-licm"),      # (the recording kernel: the same loop body)
+                "tmjx_wave_rand.hip": ("-mllvm", "-disable-machine-licm")}         # (the domain-randomisation kernel: likewise)
 
 
 class TmjxError(RuntimeError):
@@ -44,7 +45,7 @@ EXPORTS = ("tmjx_model_create", "tmjx_model_destroy", "tmjx_layout", "tmjx_clips
            "tmjx_record_check", "tmjx_record_step", "tmjx_latent_concat_det", "tmjx_action_mode",
            "tmjx_decoder_input", "tmjx_decoder_act_ok", "tmjx_decoder_act",
            "tmjx_sensor_info", "tmjx_physics_sensors", "tmjx_step_sensors",
-           "tmjx_set_done_policy", "tmjx_clips_upload_velocities",
+           "tmjx_set_done_policy", "tmjx_clips_upload_velocities", "tmjx_set_env_scales",
            "tmjx_debug_rows", "tmjx_last_error", "tmjx_version")
 
 
@@ -343,6 +344,7 @@ def load(path: Path):
     sig.setdefault("tmjx_set_wrappers", [None, None])[0] = [vp, C.c_int, C.c_int]
     sig.setdefault("tmjx_set_action_repeat", [None, None])[0] = [vp, C.c_int]
     sig.setdefault("tmjx_set_done_policy", [None, None])[0] = [vp, C.c_int]
+    sig.setdefault("tmjx_set_env_scales", [None, None])[0] = [vp, fp, C.c_int]
     sig.setdefault("tmjx_clips_upload_velocities", [None, None])[0] = [vp, vp, vp, C.c_int, C.c_int]
     sig.setdefault("tmjx_stats_scratch_floats", [None, None])[0] = [C.c_int]
     sig.setdefault("tmjx_stats_sums", [None, None])[0] = [fp, fp, fp, fp, C.c_longlong, C.c_int, vp]

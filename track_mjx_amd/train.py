@@ -84,6 +84,18 @@ def restore_options(cfg: dict) -> dict:
     return out
 
 
+def randomization_options(cfg: dict) -> dict:
+    """ppo.train keywords of env_config.domain_randomization {friction_range, actuator_range, damping_range}: each (lo, hi) or null; all null
+    (the default) = no randomisation and no keyword.  A bad range is a ValueError here, before anything touches the GPU."""
+    from .environment import uniform_randomization_fn
+    dr = (cfg.get("env_config") or {}).get("domain_randomization") or {}
+    unknown = set(dr) - {"friction_range", "actuator_range", "damping_range"}
+    if unknown:
+        raise ValueError(f"env_config.domain_randomization: unknown keys {sorted(unknown)} (friction_range, actuator_range, damping_range)")
+    fn = uniform_randomization_fn(friction=dr.get("friction_range"), actuator=dr.get("actuator_range"), damping=dr.get("damping_range"))
+    return {} if fn is None else {"randomization_fn": fn}
+
+
 def main(argv=None, runner=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     full_argv = list(argv)
@@ -98,7 +110,10 @@ def main(argv=None, runner=None):
             cfg_name = a.split("=", 1)[1]; del argv[i]; break
     cfg = _config.load_config(cfg_path, argv, name=cfg_name)
     # first line of the log: which walker this run trains (actuator mode, scale, model blob)
-    print(f"[train] config={cfg_name or cfg_path or 'rodent-full-clips'} " + Rodent(**cfg["walker_config"]).describe(), flush=True)
+    ropts = randomization_options(cfg)
+    print(f"[train] config={cfg_name or cfg_path or 'rodent-full-clips'} " + Rodent(**cfg["walker_config"]).describe() +
+          ("" if not ropts else " domain_randomization " + " ".join(f"{k}={'off' if v is None else list(v)}" for k, v in ropts["randomization_fn"].ranges.items())),
+          flush=True)
     lopts = learner_options(cfg)
     if lopts:
         print(f"[train] learner=lstm_ppo hidden_state_size={lopts['hidden_state_size']} hidden_layer_num={lopts['hidden_layer_num']}", flush=True)
@@ -158,7 +173,7 @@ def main(argv=None, runner=None):
               deterministic_eval=bool(tc.get("deterministic_eval", False)), config_dict=cfg, action_repeat=int(tc.get("action_repeat", 1)),
               checkpoint_path=cfg.get("checkpoint_path"), restore_from=cfg.get("restore_from"), shuffle_rng=str(cfg.get("shuffle_rng", "torch")), act_rng=str(cfg.get("act_rng", "device")),
               matmul_dtype=torch.bfloat16 if str(cfg.get("mlp_gemm_inputs", "f32")).lower() in ("bf16", "bfloat16") else None, **lopts,
-              **restore_options(cfg))
+              **restore_options(cfg), **ropts)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
