@@ -142,7 +142,7 @@ def test_argument_validation_of_the_chain_entry_points_without_gpu():
     assert L.tmjx_chain_rows(0) == 0
     assert L.tmjx_chain_fwd_ok(ctypes.byref(fwd())) == 1
     for bad, word in ((fwd(Nf=130), b"128"), (fwd(lda=695), b"aligned"), (fwd(rows=20479), b"rows_alloc"), (fwd(n=5), b"hidden"), (fwd(n=0), b"hidden"), (fwd(A=None), b"null"),
-                      (fwd(epi=2), b"epi"), (fwd(M=0), b"M >= 1"), (fwd(lat_out=a, lat_Z=60, lat_ld=288, prop_w=226, prop_ld=696), b"latent")):
+                      (fwd(epi=2), b"epi"), (fwd(M=0), b"M >= 1")):
         assert L.tmjx_chain_fwd_ok(ctypes.byref(bad)) == 0
         assert L.tmjx_chain_fwd(ctypes.byref(bad), None) == -22 and word in L.tmjx_last_error(), (word, L.tmjx_last_error())
     wide = fwd()

@@ -9,8 +9,6 @@ from __future__ import annotations
 
 import ctypes as C
 
-import os
-
 import torch
 
 from .. import hip as _hip
@@ -150,8 +148,8 @@ def ppo_loss_and_output_grads(policy, value, normalizer, data: dict, *, entropy_
     L = _hip.lib()
     # the loss head in phases (tmjx_ppo_loss_phases) when the networks run on two streams: B — GAE, advantage statistics, value loss: the value network's
     # outputs only — goes onto the value network's stream, D (the eight scalars, which the backward pass does not wait for) leaves the main stream
-    # too: the main stream runs policy forward, A, C, backward.  TMJX_PPO_PHASES=0: the one-call form
-    phased = side_stream is not None and T <= 24 and os.environ.get("TMJX_PPO_PHASES", "1") != "0"
+    # too: the main stream runs policy forward, A, C, backward
+    phased = side_stream is not None and T <= 24
     cfg_of = lambda A_, Z_: _hip.PpoCfg(T, B, A_, Z_, reward_scaling, discounting, gae_lambda, clipping_epsilon, entropy_cost, kl_weight,  # noqa: E731
                                         int(normalize_advantage), int(acc_out is not None))
     f32 = lambda a: a.detach().contiguous().float()  # noqa: E731
@@ -170,12 +168,10 @@ def ppo_loss_and_output_grads(policy, value, normalizer, data: dict, *, entropy_
             # the DECODER's pass at the end of the forward phase and held 32 CUs back from it (decoder chain 100 us against 78 alone); in front, it hides
             # under the two large passes' first round
             with torch.no_grad():
-                bootstrap = value(nxt) if os.environ.get("TMJX_BOOTSTRAP_LAST") != "1" else None
+                bootstrap = value(nxt)
             baseline = value(obs)
-            with torch.no_grad():
-                if bootstrap is None:
-                    bootstrap = value(nxt)
-                if phased:
+            if phased:
+                with torch.no_grad():
                     bl, bs = f32(baseline), f32(bootstrap)
         logits, fc2 = policy(obs, eps=data.get("latent_eps"), return_fc2=True)
         if not phased:

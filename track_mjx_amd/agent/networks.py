@@ -113,17 +113,13 @@ def gemm_nt(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None) 
     M, K = x.shape
     N = w.shape[0]
     y = torch.empty((M, N), dtype=torch.float32, device=x.device)
-    if N == 1 and _head_kernels() and K % 4 == 0 and x.data_ptr() % 16 == 0 and x.stride(0) % 4 == 0 and w.data_ptr() % 16 == 0:
+    if N == 1 and K % 4 == 0 and x.data_ptr() % 16 == 0 and x.stride(0) % 4 == 0 and w.data_ptr() % 16 == 0:
         # a 1-wide layer (the value MLP's head) is a matrix-vector product: a wave per row instead of a 16 x 64 MFMA tile at 1 / 64 of its width — in EVERY
         # pass that computes it (learner, bootstrap value, evaluation), so that they agree to the bit
         _launch("tmjx_head_fwd", x.device, _p(x), x.stride(0), _p(w), _p(bias), _p(y), M, K)
         return y
     _launch("tmjx_gemm_nt", x.device, _p(x), x.stride(0), _p(w), w.stride(0), _p(bias), _p(y), N, M, N, K)
     return y
-
-
-def _head_kernels() -> bool:
-    return os.environ.get("TMJX_HEAD_KERNELS", "1") != "0"
 
 
 def gemm_nn(dy: torch.Tensor, w: torch.Tensor, cols: int | None = None) -> torch.Tensor:
@@ -146,7 +142,7 @@ def gemm_dw(dy: torch.Tensor, x: torch.Tensor, with_bias: bool):
     K = x.shape[1]
     dw = torch.empty((N, K), dtype=torch.float32, device=dy.device)
     db = torch.empty(N, dtype=torch.float32, device=dy.device) if with_bias else None
-    if N == 1 and _head_kernels() and dy.stride(0) == 1:
+    if N == 1 and dy.stride(0) == 1:
         # a 1-wide layer's gradients: a matrix-vector product (tmjx_head_dw) instead of a 128 x 128 tile at 1 / 128 of its width
         scratch = torch.empty(int(_hip.lib().tmjx_head_dw_scratch_floats(M, K)), dtype=torch.float32, device=dy.device)
         _launch("tmjx_head_dw", dy.device, _p(dy), _p(x), x.stride(0), _p(dw), _p(db), _p(scratch), M, K)
@@ -186,7 +182,7 @@ def bgemm_dw(dy: torch.Tensor, x: torch.Tensor, with_bias: bool, out: torch.Tens
     dw = torch.empty((N, K), dtype=torch.float32, device=dy.device) if out is None else out
     db = (torch.empty(N, dtype=torch.float32, device=dy.device) if out_bias is None else out_bias) if with_bias else None
     d = deferred_weight_grads.active
-    if d is not None and d.group_bf16 and N > 1 and out is not None:
+    if d is not None and N > 1 and out is not None:
         # inside the learner's backward pass, into a flat-buffer view (the parameter's FIRST use in this pass: `dest` / deferred_weight_grads.seen — a second
         # use's gradient is added to the first by autograd DURING the pass and must exist by then): recorded, computed with every other layer's by ONE
         # grouped launch behind the pass (deferred_weight_grads.launch)
@@ -301,15 +297,11 @@ def _colsum(dy: torch.Tensor) -> torch.Tensor:
     needs 10-25 us for the tall, narrow bias-gradient inputs); anything else goes to torch."""
     if not (dy.is_cuda and dy.dtype == torch.float32 and dy.dim() == 2 and dy.is_contiguous() and dy.shape[0] >= 1024):
         return dy.sum(0)
-    import ctypes as C
     from .. import hip as _hip
-    L = _hip.lib()
     rows, width = dy.shape
     out = torch.empty(width, dtype=torch.float32, device=dy.device)
-    scratch = torch.empty(L.tmjx_colsum_scratch_floats(width), dtype=torch.float32, device=dy.device)
-    with torch.cuda.device(dy.device):
-        _hip.check(L.tmjx_colsum(C.c_void_p(dy.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(scratch.data_ptr()), rows, width,
-                                 C.c_void_p(torch.cuda.current_stream(dy.device).cuda_stream)), "tmjx_colsum")
+    scratch = torch.empty(_hip.lib().tmjx_colsum_scratch_floats(width), dtype=torch.float32, device=dy.device)
+    _launch("tmjx_colsum", dy.device, _p(dy), _p(out), _p(scratch), rows, width)
     return out
 
 
@@ -323,8 +315,8 @@ class deferred_weight_grads:
 
     def __enter__(self):
         self.problems, self.keep, self.colsums = [], [], []
-        # bf16 GEMM-input mode: the layers' weight gradients (networks.bgemm_dw) as one grouped launch too (tmjx_bgemm_dw_grouped; TMJX_BDW_GROUPED=0: layer by layer)
-        self.bproblems, self.group_bf16 = [], os.environ.get("TMJX_BDW_GROUPED", "1") != "0"
+        # bf16 GEMM-input mode: the layers' weight gradients (networks.bgemm_dw) as one grouped launch too (tmjx_bgemm_dw_grouped)
+        self.bproblems = []
         self.seen: set = set()       # ids of the parameters whose gradient views have been handed to autograd in this block
         deferred_weight_grads.active = self
         return self
@@ -355,23 +347,12 @@ class deferred_weight_grads:
         self.problems.append((dy2, x2, gw, gb))
         return gw, gb
 
-    def launch_subset(self, pick, target_wgs: int = 0):
-        """The recorded problems whose gradient view `pick(gw)` selects, NOW (stream-ordered on the current stream), as a group of their own with
-        a workgroup budget of `target_wgs` (0: the default); the others stay recorded for launch().  PPOLearner uses it to run the value network's
-        weight gradients on the side stream right behind that network's backward pass, next to the policy's backward pass on the main stream."""
-        mine = [q for q in self.problems if pick(q[2])]
-        self.problems = [q for q in self.problems if not pick(q[2])]
-        self._launch_problems(mine, target_wgs)
-
     def launch(self):
-        import ctypes as C
         from .. import hip as _hip
-        L = _hip.lib()
         if self.colsums:      # the LayerNorm blocks' (d gamma | d beta | d bias) partials (networks._dx_through_block)
             dev = self.colsums[0][0].device
             arr = (_hip.ColsumProblem * len(self.colsums))(*[_hip.ColsumProblem(pt.data_ptr(), g.data_ptr(), nb, wd) for pt, g, nb, wd in self.colsums])
-            with torch.cuda.device(dev):
-                _hip.check(L.tmjx_colsum_grouped(arr, len(self.colsums), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "tmjx_colsum_grouped")
+            _launch("tmjx_colsum_grouped", dev, arr, len(self.colsums))
             self.keep += [t for c in self.colsums for t in c[:2]]
             self.colsums = []
         self._launch_problems(self.problems)
@@ -379,7 +360,6 @@ class deferred_weight_grads:
         self._launch_bproblems()
 
     def _launch_bproblems(self):
-        import ctypes as C
         from .. import hip as _hip
         probs, self.bproblems = self.bproblems, []
         if not probs:
@@ -398,12 +378,10 @@ class deferred_weight_grads:
                                          int(dy.dtype == torch.float32), int(x.dtype == torch.float32), _ld(dy), _ld(x), dw.stride(0) if N > 1 else max(dw.stride(0), K),
                                          dy.shape[0], N, K)
                 off += (sizes[i] + 3) // 4 * 4
-            with torch.cuda.device(dev):
-                _hip.check(L.tmjx_bgemm_dw_grouped(arr, len(grp), 0, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "tmjx_bgemm_dw_grouped")
+            _launch("tmjx_bgemm_dw_grouped", dev, arr, len(grp), 0)
             self.keep += [scratch] + [t for q in grp for t in q[:2]]
 
-    def _launch_problems(self, problems, target_wgs: int = 0):
-        import ctypes as C
+    def _launch_problems(self, problems):
         from .. import hip as _hip
         if not problems:
             return
@@ -417,13 +395,12 @@ class deferred_weight_grads:
             arr[i] = _hip.DwProblem(dy.data_ptr(), x.data_ptr(), gw.data_ptr(), gb.data_ptr() if gb is not None else None,
                                     scratch.data_ptr() + 4 * off, dy.stride(0), x.stride(0), gw.stride(0), dy.shape[0], dy.shape[1], x.shape[1])
             off += (sizes[i] + 3) // 4 * 4
-        with torch.cuda.device(dev):
-            _hip.check(L.tmjx_gemm_dw_grouped_wgs(arr, len(problems), int(target_wgs), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "tmjx_gemm_dw_grouped")
+        _launch("tmjx_gemm_dw_grouped", dev, arr, len(problems))
         self.keep += [scratch] + [t for q in problems for t in q[:2]]
 
 
 # ---- whole-chain fp32 kernels (csrc/mlp_chain.h): nets whose hidden layers are exactly 256 wide -----------------------------------------
-def chain_fwd_desc(x2, hidden, final=None, kind="ln", eps=1e-6, out=None, latent=None):
+def chain_fwd_desc(x2, hidden, final=None, kind="ln", eps=1e-6, out=None):
     """The tmjx_chain_fwd_t of one forward chain and the tensors it writes.  x2: [M, >= K0] fp32 rows (a column prefix of a wider buffer is
     fine); hidden: [(weight [256, K], bias, gamma, beta)] ("ln") or [(weight, bias)] ("silu"); final: (weight [Nf, 256], bias) or None.
     Returns (desc, saved = [(z, y, stats)] per hidden layer, out [M, Nf] / [M] for a 1-wide head / None, keep-alive list)."""
@@ -449,18 +426,13 @@ def chain_fwd_desc(x2, hidden, final=None, kind="ln", eps=1e-6, out=None, latent
         if out is None:
             out = torch.empty((M,) if Nf == 1 else (M, Nf), dtype=torch.float32, device=dev)
         d.Wf, d.bf, d.outf, d.Nf, d.ldwf, d.ldof = wf.data_ptr(), (bf.data_ptr() if bf is not None else None), out.data_ptr(), Nf, wf.stride(0), (1 if Nf == 1 else out.stride(0))
-    if latent is not None:
-        # the encoder chain's latent tail: (eps [M, Z], dec_in [M, ld] to write, prop = the proprioceptive columns [M, W] as a view with its own row stride)
-        leps, dec_in, prop = latent
-        d.lat_eps, d.lat_out, d.prop = leps.data_ptr(), dec_in.data_ptr(), prop.data_ptr()
-        d.lat_Z, d.lat_ld, d.prop_w, d.prop_ld = leps.shape[1], dec_in.stride(0), prop.shape[1], prop.stride(0)
     return d, saved, out
 
 
-def chain_fwd(x2, hidden, final=None, kind="ln", eps=1e-6, latent=None):
+def chain_fwd(x2, hidden, final=None, kind="ln", eps=1e-6):
     """One launch: the whole chain forward (tmjx_chain_fwd).  Raises TmjxError (EINVAL) when the chain does not qualify: ask chain_fwd_ok first."""
     import ctypes as C
-    d, saved, out = chain_fwd_desc(x2, hidden, final, kind, eps, latent=latent)
+    d, saved, out = chain_fwd_desc(x2, hidden, final, kind, eps)
     _launch("tmjx_chain_fwd", x2.device, C.byref(d))
     return saved, out
 
@@ -702,7 +674,7 @@ def bf16_chain(x, layers, dx_cols=None, last_y_f32=False):
 
 def _bf16_chain_ok(x) -> bool:
     sh = gemm_inputs.shadows
-    return gemm_inputs.dtype == torch.bfloat16 and sh is not None and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and not os.environ.get("TMJX_NO_BF16_CHAIN")
+    return gemm_inputs.dtype == torch.bfloat16 and sh is not None and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16)
 
 
 
@@ -715,33 +687,20 @@ class _F32ChainFn(torch.autograd.Function):
     hidden layers ("ln" or "silu", all of one kind) then the last layer ("dense" / "head"); `dx_cols`: the input's leading columns that need a gradient."""
 
     @staticmethod
-    def forward(ctx, x, layers, dx_cols, latent, *params):
+    def forward(ctx, x, layers, dx_cols, *params):
         x2 = _rows2d(x)
         hid, last = layers[:-1], layers[-1]
         kind = hid[0].kind
         hidden = [(L.lin.weight, L.lin.bias, L.norm.weight, L.norm.bias) if kind == "ln" else (L.lin.weight, L.lin.bias) for L in hid]
         eps = float(hid[0].norm.eps) if kind == "ln" else 0.0
-        dec_in = None
-        if latent is not None:
-            # the encoder: the launch also writes the decoder's input [latent sample | proprioception] (the kernel's latent tail); handed out as a second,
-            # non-differentiable output — _LatentViewFn ties it to fc2 for the backward pass
-            leps, prop = latent
-            wd = leps.shape[1] + prop.shape[1]
-            dec_in = torch.empty((x2.shape[0], (wd + 3) // 4 * 4), dtype=torch.float32, device=x2.device)
-            latent = (leps, dec_in, prop)
-        saved, out = chain_fwd(x2, hidden, (last.lin.weight, last.lin.bias), kind, eps, latent=latent)
+        saved, out = chain_fwd(x2, hidden, (last.lin.weight, last.lin.bias), kind, eps)
         flat = [t for z, y, st in saved for t in ((z, y, st) if kind == "ln" else (z, y))]
         ctx.save_for_backward(x2, *flat, *params)
         ctx.layers, ctx.dx_cols, ctx.x_shape, ctx.kind, ctx.nflat = layers, dx_cols, x.shape, kind, len(flat)
-        res = out.view(*x.shape[:-1], last.lin.out_features) if last.kind == "dense" else out.view(*x.shape[:-1], 1)
-        if dec_in is None:
-            return res
-        xd = dec_in[:, :wd]
-        ctx.mark_non_differentiable(xd)
-        return res, xd
+        return out.view(*x.shape[:-1], last.lin.out_features) if last.kind == "dense" else out.view(*x.shape[:-1], 1)
 
     @staticmethod
-    def backward(ctx, dout, *_unused):
+    def backward(ctx, dout):
         from .. import hip as _hip
         layers, kind = ctx.layers, ctx.kind
         hid, last = layers[:-1], layers[-1]
@@ -801,12 +760,12 @@ class _F32ChainFn(torch.autograd.Function):
                 got = d.try_add(dz, xin, L.lin.weight, L.lin.bias) if d is not None else None
                 grads[(l, 0)], grads[(l, 1)] = got if got is not None else gemm_dw(dz, xin, True)
         out = [grads.get((l, j)) for l, L in enumerate(layers) for j in range(len(L.params()))]
-        return (dx.view(ctx.x_shape) if dx is not None else None, None, None, None, *out)
+        return (dx.view(ctx.x_shape) if dx is not None else None, None, None, *out)
 
 
-def f32_chain(x, layers, dx_cols=None, latent=None):
+def f32_chain(x, layers, dx_cols=None):
     params = [p for L in layers for p in L.params()]
-    return _F32ChainFn.apply(x, layers, dx_cols, latent, *params)
+    return _F32ChainFn.apply(x, layers, dx_cols, *params)
 
 
 def _f32_chain_ok(x, layers, dx_cols=None) -> bool:
@@ -860,27 +819,21 @@ class ln_bwd_links:
 
 def _dx_through_block(dy2, w, link):
     """d loss / d z of the producing block from this layer's output gradient dy2 [M, N] and weight w [N, 256]: one launch."""
-    import ctypes as C
     from .. import hip as _hip
-    L = _hip.lib()
     x2, wp, z, b, gamma, stats = link.ctx.saved_tensors
     M, H = z.shape
     dz = torch.empty_like(z)
-    nfl = int(L.tmjx_gemm_nn_ln_bwd_partial_floats(M, H))
+    nfl = int(_hip.lib().tmjx_gemm_nn_ln_bwd_partial_floats(M, H))
     nblk = nfl // (3 * H)          # one partial row per workgroup of the launch: 80- or 32-row tiles by M (csrc/tmjx_hip.hip: gemm_mt)
     partial = torch.empty(nfl, dtype=torch.float32, device=z.device)
     grads = torch.empty((3, H), dtype=torch.float32, device=z.device)
-    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-    with torch.cuda.device(z.device):
-        stream = C.c_void_p(torch.cuda.current_stream(z.device).cuda_stream)
-        _hip.check(L.tmjx_gemm_nn_ln_bwd(p(dy2), dy2.stride(0), p(w), w.stride(0), p(z), p(b), p(gamma), p(stats), p(dz), p(partial), M, H, dy2.shape[1], stream),
-                   "tmjx_gemm_nn_ln_bwd")
-        d = deferred_weight_grads.active
-        if d is not None and len(d.colsums) < 16:
-            d.colsums.append((partial, grads, nblk, 3 * H))      # reduced with the others in ONE launch behind the backward pass (launch())
-        else:
-            one = (_hip.ColsumProblem * 1)(_hip.ColsumProblem(partial.data_ptr(), grads.data_ptr(), nblk, 3 * H))
-            _hip.check(L.tmjx_colsum_grouped(one, 1, stream), "tmjx_colsum_grouped")
+    _launch("tmjx_gemm_nn_ln_bwd", z.device, _p(dy2), dy2.stride(0), _p(w), w.stride(0), _p(z), _p(b), _p(gamma), _p(stats), _p(dz), _p(partial), M, H, dy2.shape[1])
+    d = deferred_weight_grads.active
+    if d is not None and len(d.colsums) < 16:
+        d.colsums.append((partial, grads, nblk, 3 * H))      # reduced with the others in ONE launch behind the backward pass (launch())
+    else:
+        one = (_hip.ColsumProblem * 1)(_hip.ColsumProblem(partial.data_ptr(), grads.data_ptr(), nblk, 3 * H))
+        _launch("tmjx_colsum_grouped", z.device, one, 1)
     link.dz_given, link.grads = True, grads
     return dz
 
@@ -1122,24 +1075,17 @@ class _SiluLayerNormFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, bias, gamma, beta, eps):
-        import ctypes as C
-        from .. import hip as _hip
         H = z.shape[-1]
         rows = z.numel() // H
         z = z.contiguous()
         y = torch.empty_like(z)
         stats = torch.empty((rows, 2), dtype=torch.float32, device=z.device)
-        L = _hip.lib()
-        with torch.cuda.device(z.device):
-            stream = C.c_void_p(torch.cuda.current_stream(z.device).cuda_stream)
-            _hip.check(L.tmjx_silu_ln_fwd(*[C.c_void_p(t.data_ptr()) for t in (z, bias, gamma, beta, y, stats)], rows, H, float(eps), stream),
-                       "tmjx_silu_ln_fwd")
+        _launch("tmjx_silu_ln_fwd", z.device, *[_p(t) for t in (z, bias, gamma, beta, y, stats)], rows, H, float(eps))
         ctx.save_for_backward(z, bias, gamma, stats)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        import ctypes as C
         from .. import hip as _hip
         z, bias, gamma, stats = ctx.saved_tensors
         H = z.shape[-1]
@@ -1147,12 +1093,8 @@ class _SiluLayerNormFn(torch.autograd.Function):
         dy = dy.contiguous()
         dz = torch.empty_like(z)
         grads = torch.empty((3, H), dtype=torch.float32, device=z.device)
-        L = _hip.lib()
-        partial = torch.empty(L.tmjx_silu_ln_partial_floats(rows, H), dtype=torch.float32, device=z.device)
-        with torch.cuda.device(z.device):
-            stream = C.c_void_p(torch.cuda.current_stream(z.device).cuda_stream)
-            _hip.check(L.tmjx_silu_ln_bwd(*[C.c_void_p(t.data_ptr()) for t in (dy, z, bias, gamma, stats, dz, grads, partial)], rows, H, stream),
-                       "tmjx_silu_ln_bwd")
+        partial = torch.empty(_hip.lib().tmjx_silu_ln_partial_floats(rows, H), dtype=torch.float32, device=z.device)
+        _launch("tmjx_silu_ln_bwd", z.device, *[_p(t) for t in (dy, z, bias, gamma, stats, dz, grads, partial)], rows, H)
         return dz, grads[2], grads[0], grads[1], None
 
 
@@ -1175,17 +1117,12 @@ class _HipBlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x2, w, b, gamma, beta, eps, dx_cols):
-        import ctypes as C
-        from .. import hip as _hip
         M, K = x2.shape
         N = w.shape[0]
         z = torch.empty((M, N), dtype=torch.float32, device=x2.device)
         y = torch.empty_like(z)
         stats = torch.empty((M, 2), dtype=torch.float32, device=x2.device)
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        with torch.cuda.device(x2.device):
-            _hip.check(_hip.lib().tmjx_gemm_nt_silu_ln(p(x2), x2.stride(0), p(w), w.stride(0), p(b), p(gamma), p(beta), p(z), p(y), N, p(stats), M, N, K,
-                                                       float(eps), C.c_void_p(torch.cuda.current_stream(x2.device).cuda_stream)), "tmjx_gemm_nt_silu_ln")
+        _launch("tmjx_gemm_nt_silu_ln", x2.device, _p(x2), x2.stride(0), _p(w), w.stride(0), _p(b), _p(gamma), _p(beta), _p(z), _p(y), N, _p(stats), M, N, K, float(eps))
         ctx.save_for_backward(x2, w, z, b, gamma, stats)
         ctx.dx_cols, ctx.param = dx_cols, w
         ctx.producer = ln_bwd_links.producer_of(x2)
@@ -1198,7 +1135,6 @@ class _HipBlockFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        import ctypes as C
         from .. import hip as _hip
         x2, w, z, b, gamma, stats = ctx.saved_tensors
         M, N = z.shape
@@ -1213,11 +1149,8 @@ class _HipBlockFn(torch.autograd.Function):
         else:
             dz = torch.empty_like(z)
             grads = torch.empty((3, N), dtype=torch.float32, device=z.device)
-            L = _hip.lib()
-            partial = torch.empty(L.tmjx_silu_ln_partial_floats(M, N), dtype=torch.float32, device=z.device)
-            with torch.cuda.device(z.device):
-                _hip.check(L.tmjx_silu_ln_bwd(*[C.c_void_p(t.data_ptr()) for t in (dy, z, b, gamma, stats, dz, grads, partial)], M, N,
-                                              C.c_void_p(torch.cuda.current_stream(z.device).cuda_stream)), "tmjx_silu_ln_bwd")
+            partial = torch.empty(_hip.lib().tmjx_silu_ln_partial_floats(M, N), dtype=torch.float32, device=z.device)
+            _launch("tmjx_silu_ln_bwd", z.device, *[_p(t) for t in (dy, z, b, gamma, stats, dz, grads, partial)], M, N)
         if ctx.needs_input_grad[0] and _fusable_dx(dz, w, ctx.producer, ctx.dx_cols):
             dx = _dx_through_block(dz, w, ctx.producer)
         else:
@@ -1265,8 +1198,6 @@ class _LatentConcatFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, fc2, eps, obs, ref, handle=None):
-        import ctypes as C
-        from .. import hip as _hip
         ctx.handle = handle
         n, Z = eps.shape
         W = obs.shape[1]
@@ -1274,50 +1205,27 @@ class _LatentConcatFn(torch.autograd.Function):
         wd = Z + W - ref
         # rows padded to a multiple of 4 floats (286 -> 288): the decoder's first GEMM reads this buffer with 16-byte row loads
         x = torch.empty((n, (wd + 3) // 4 * 4), dtype=torch.float32, device=fc2.device)     # (the pad columns are never read: the GEMM masks k >= K)
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        with torch.cuda.device(fc2.device):
-            _hip.check(_hip.lib().tmjx_latent_concat(p(fc2), p(eps), p(obs), p(x), n, Z, W, ref, obs.stride(0), obs.stride(1), None, None, x.shape[1], 0, None,
-                                                     C.c_void_p(torch.cuda.current_stream(fc2.device).cuda_stream)), "tmjx_latent_concat")
+        _launch("tmjx_latent_concat", fc2.device, _p(fc2), _p(eps), _p(obs), _p(x), n, Z, W, ref, obs.stride(0), obs.stride(1), None, None, x.shape[1], 0, None)
         ctx.save_for_backward(fc2, eps)
         return x[:, :wd]
 
     @staticmethod
     def backward(ctx, dx):
-        import ctypes as C
-        from .. import hip as _hip
         fc2, eps = ctx.saved_tensors
         n, Z = eps.shape
         dx = dx.contiguous()
         dfc2 = torch.empty_like(fc2)
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
         # a second gradient of this fc2 that the caller wants summed into the one computed here instead of seeding autograd with it
         # (losses.ppo_loss_and_output_grads: the KL term's, from the loss head) — autograd would add the two with a launch of its own.  It
         # travels on THIS forward pass's handle (LatentGradHandle), not in process-wide state
         add = ctx.handle.take() if ctx.handle is not None else None
         if add is not None and (add.shape != fc2.shape or not add.is_contiguous()):
             raise RuntimeError("_LatentConcatFn: the pending fc2 gradient does not fit this forward pass")
-        with torch.cuda.device(fc2.device):
-            stream = C.c_void_p(torch.cuda.current_stream(fc2.device).cuda_stream)
-            if add is None:
-                _hip.check(_hip.lib().tmjx_latent_concat_bwd(p(dx), p(eps), p(fc2), p(dfc2), n, Z, dx.shape[1], stream), "tmjx_latent_concat_bwd")
-            else:
-                _hip.check(_hip.lib().tmjx_latent_concat_bwd_add(p(dx), p(eps), p(fc2), p(add), p(dfc2), n, Z, dx.shape[1], stream), "tmjx_latent_concat_bwd_add")
+        if add is None:
+            _launch("tmjx_latent_concat_bwd", fc2.device, _p(dx), _p(eps), _p(fc2), _p(dfc2), n, Z, dx.shape[1])
+        else:
+            _launch("tmjx_latent_concat_bwd_add", fc2.device, _p(dx), _p(eps), _p(fc2), _p(add), _p(dfc2), n, Z, dx.shape[1])
         return dfc2, None, None, None, None
-
-
-class _LatentViewFn(torch.autograd.Function):
-    """The decoder input x = [mean + eps * exp(logvar / 2) | proprioception] when the encoder chain's launch has ALREADY written it (tmjx_chain_fwd's latent
-    tail): forward hands x on (no launch), backward is _LatentConcatFn's — d fc2 from d x through tmjx_latent_concat_bwd(_add)."""
-
-    @staticmethod
-    def forward(ctx, fc2, eps, x, handle=None):
-        ctx.handle = handle
-        ctx.save_for_backward(fc2.contiguous(), eps.contiguous())
-        return x.view_as(x)
-
-    @staticmethod
-    def backward(ctx, dx):
-        return (_LatentConcatFn.backward(ctx, dx)[0], None, None, None)
 
 
 class LatentGradHandle:
@@ -1383,22 +1291,9 @@ class IntentionPolicy(nn.Module):
             if getattr(self, "_enc_f32", None) is None and obs.is_cuda:
                 self._enc_f32 = [_Layer("ln", b.dense, b.norm) for b in self.encoder] + [_Layer("dense", self.fc2)]
                 self._dec_f32 = [_Layer("ln", b.dense, b.norm) for b in self.decoder] + [_Layer("dense", self.head)]
-            xlat = None
             if obs.is_cuda and _f32_chain_ok(traj, self._enc_f32):
-                # 2 x 256 nets: the encoder + fc2 as ONE launch forward, one backward (csrc/mlp_chain.h).  The same launch CAN also sample the latent and write
-                # the decoder's input (its latent tail, TMJX_CHAIN_LATENT=1; bit-identical) — measured 13 us per minibatch step SLOWER than the separate
-                # tmjx_latent_concat launch (0.887 against 0.874 ms, two alternating pairs): that 25 us kernel runs next to the critic's chain on the other
-                # stream, whereas the tail lengthens a kernel that holds every CU.  Off by default
-                obs2 = obs.reshape(-1, obs.shape[-1])
-                if (not deterministic and obs.dtype == torch.float32 and obs2.shape[0] * 2 * self.latents >= 2 * self.latents * 1024 and self.latents % 4 == 0
-                        and (obs.shape[-1] - self.reference_obs_size) % 2 == 0 and obs2.stride(1) == 1 and obs2.stride(0) % 2 == 0 and self.reference_obs_size % 2 == 0
-                        and os.environ.get("TMJX_CHAIN_LATENT") == "1"):
-                    if eps is None:
-                        eps = torch.randn(obs.shape[:-1] + (self.latents,), dtype=torch.float32, device=obs.device)
-                    eps2 = eps.reshape(-1, self.latents).contiguous()
-                    fc2, xlat = f32_chain(traj, self._enc_f32, latent=(eps2, obs2[:, self.reference_obs_size:]))
-                else:
-                    fc2 = f32_chain(traj, self._enc_f32)
+                # 2 x 256 nets: the encoder + fc2 as ONE launch forward, one backward (csrc/mlp_chain.h)
+                fc2 = f32_chain(traj, self._enc_f32)
             else:
                 with ln_bwd_links():       # encoder and decoder are chains: each block's output feeds exactly one dense layer
                     h = self.encoder(traj)
@@ -1411,10 +1306,7 @@ class IntentionPolicy(nn.Module):
             if eps is None:
                 eps = torch.randn_like(mean)
             handle = LatentGradHandle(fc2.reshape(-1, fc2.shape[-1])) if (fc2.requires_grad and fc2.is_contiguous()) else None
-            if not chains and xlat is not None:
-                x = _LatentViewFn.apply(fc2.reshape(-1, fc2.shape[-1]), eps.reshape(-1, self.latents), xlat, handle)
-            else:
-                x = _LatentConcatFn.apply(fc2.reshape(-1, fc2.shape[-1]), eps.reshape(-1, self.latents), obs.reshape(-1, obs.shape[-1]), self.reference_obs_size, handle)
+            x = _LatentConcatFn.apply(fc2.reshape(-1, fc2.shape[-1]), eps.reshape(-1, self.latents), obs.reshape(-1, obs.shape[-1]), self.reference_obs_size, handle)
             self.latent_grad_handle = handle
             x = x.view(*lead, x.shape[-1])
             if chains:

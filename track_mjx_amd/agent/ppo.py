@@ -35,7 +35,7 @@ def _flat_layout(params):
     columns stay exactly zero (zero gradient, zero moments).  Returns [(offset, rows, cols, padded_cols)], total floats."""
     segs, off = [], 0
     for p in params:
-        if p.dim() == 2 and p.shape[1] % 4 and not os.environ.get("TMJX_NO_PAD"):
+        if p.dim() == 2 and p.shape[1] % 4:
             rows, cols, pc = p.shape[0], p.shape[1], (p.shape[1] + 3) // 4 * 4
         else:
             rows, cols, pc = 1, p.numel(), p.numel()
@@ -274,11 +274,6 @@ class PPOLearner:
         # C1 in TWO buckets (the flat buffer is [policy | value]): the value network's gradients are reduced while the policy's backward pass
         # still runs (update()).  The reference's pmean sits inside the jitted step where XLA overlaps it (ppo.py:621-623)
         self._bucket_split = self.grads.segs[self._n_policy_params][0]
-        # (the value network's gradient views, and the workgroup budget of an EARLY weight-gradient group for them on the side stream, behind that
-        # network's backward pass and next to the policy's: TMJX_VALUE_DW_WGS.  Default 0 = one group at the end of the step: measured in round 5 at
-        # budgets 256 / 384 / 512 / 768 — 0.99 – 1.02 ms per config-2 minibatch step against 0.97 – 1.00 for the single group; the chip is busy either way)
-        self._value_grad_ptrs = {p.grad.data_ptr() for p in self.grads.params[self._n_policy_params:]}
-        self._value_dw_wgs = int(os.environ.get("TMJX_VALUE_DW_WGS", "0"))
         # Used when the gradient buffer is large (>= 8 MB: the rodent-mc-intention nets' 17.2 MB, ~ 0.2 ms on a ring) — cutting the captured
         # step into three graphs and issuing two collectives costs ~ 0.15 ms per minibatch step (measured with a one-rank RCCL group,
         # profiles/r04_bench_selflaunch_one_rank_bucketed.json), more than the 2.49 MB buffer of the 2x256 nets takes to reduce.  TMJX_BUCKET_OVERLAP=1 / 0 forces it
@@ -311,7 +306,7 @@ class PPOLearner:
         self._obs16 = None
         if self.shadows is not None and obs % 4 == 0 and not os.environ.get("TMJX_NO_BF16_TWIN"):
             self._obs16 = torch.zeros((T * self.local_batch, (obs + 63) // 64 * 64), dtype=torch.bfloat16, device=dev)
-        self._sgd_side = torch.cuda.Stream(device=dev) if (dev.type == "cuda" and os.environ.get("TMJX_SGD_TWO_STREAMS", "1") != "0") else None
+        self._sgd_side = torch.cuda.Stream(device=dev) if dev.type == "cuda" else None
         if self._sgd_side is not None and hasattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch"):
             torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)    # intentional: the value net's gradients arrive from the side stream
         self._metric_index = torch.tensor([0, 1, 2, 4, 3], dtype=torch.long, device=dev)    # METRIC_KEYS -> slots of tmjx_ppo_loss's output
@@ -349,7 +344,7 @@ class PPOLearner:
         # LDS-free acting path: a ROW-major staging copy of every group's newest observation (third destination of the roll-out store): the acting
         # policy's first layer then reads 16 bytes along K per lane instead of four strided words from the env's [obs][n_env] buffer
         self._obs_rm = ([torch.zeros((e.num_envs, e.observation_size), dtype=torch.float32, device=dev) for e in self.envs]
-                        if (self.lds_free and env.observation_size % 4 == 0 and not os.environ.get("TMJX_NO_OBS_STAGING")) else None)
+                        if (self.lds_free and env.observation_size % 4 == 0) else None)
         self._streams = [torch.cuda.Stream(device=dev) for _ in self.envs] if (len(self.envs) > 1 and dev.type == "cuda") else None
 
     def _build_policy(self, obs, ref, action_size, latents, encoder_layers, decoder_layers):
@@ -481,12 +476,11 @@ class PPOLearner:
                 return out
 
             # round 5: the layer through a 20 KB LDS tile (tmjx_linear_act) where the operands allow — the physics kernel's env image leaves that
-            # much LDS free on every CU next to twelve resident envs; TMJX_ACT_LDS=0 keeps the LDS-free kernels (A/B runs)
-            act_lds = os.environ.get("TMJX_ACT_LDS", "1") != "0"
+            # much LDS free on every CU next to twelve resident envs
 
             def linear_lds(a, sa_row, sa_k, w, bias_t, out, mean=None, inv_std=None):
                 """True if the layer went through tmjx_linear_act (row-major a with aligned rows, K % 4 == 0)."""
-                if not act_lds or sa_k != 1 or not L.tmjx_linear_act_ok(p(a), sa_row, p(w), w.stride(0), w.shape[1]):
+                if sa_k != 1 or not L.tmjx_linear_act_ok(p(a), sa_row, p(w), w.stride(0), w.shape[1]):
                     return False
                 _hip.check(L.tmjx_linear_act(p(a), sa_row, p(w), w.stride(0), p(bias_t), p(out), n, out.shape[1], w.shape[1], p(mean), p(inv_std), stream),
                            "tmjx_linear_act")
@@ -612,7 +606,7 @@ class PPOLearner:
         """act() replayed as one hipGraph per env group.  Valid while `obs` is the group's persistent observation buffer (same
         pointer every step); falls back to eager launches otherwise."""
         gen = self.gens[g]
-        if not (self.use_graph and self.dev.type == "cuda") or os.environ.get("TMJX_NO_ACT_GRAPH"):
+        if not (self.use_graph and self.dev.type == "cuda"):
             return self.act(obs, gen=gen)
         key = (obs.data_ptr(), tuple(obs.shape), tuple(obs.stride()))
         ent = self._act_graphs.get(g)
@@ -695,7 +689,7 @@ class PPOLearner:
     def _self_advancing(self) -> bool:
         """The SGD step draws its rows and its noise on the device (tmjx_minibatch_begin): needs the fused gather's layout."""
         return (self.dev.type == "cuda" and self.normalize_observations and self.buf["observation"].shape[-1] % 4 == 0
-                and all(v.is_contiguous() for v in self.buf.values()) and not os.environ.get("TMJX_NO_SELF_ADVANCE"))
+                and all(v.is_contiguous() for v in self.buf.values()))
 
     def _mb_data(self, idx):
         fused_gather = self.dev.type == "cuda" and self.normalize_observations and self.buf["observation"].shape[-1] % 4 == 0
@@ -739,14 +733,8 @@ class PPOLearner:
             with deferred_weight_grads() as dwg:
                 grads = torch.autograd.grad(o, params, grad_outputs=g)
             if which != "policy" and self._sgd_side is not None:
-                if which == "all" and self._value_dw_wgs > 0:
-                    # the value network's weight gradients as a group of their own on the side stream, right behind that network's backward pass (autograd
-                    # has queued it there): they run NEXT TO the policy's backward pass instead of behind it in the one launch at the end of the step
-                    vptr = self._value_grad_ptrs
-                    with torch.cuda.stream(self._sgd_side):
-                        dwg.launch_subset(lambda gw: gw.data_ptr() in vptr, self._value_dw_wgs)
                 torch.cuda.current_stream(self.dev).wait_stream(self._sgd_side)     # the value net's backward ran there
-            dwg.launch()             # every (remaining) layer's (dW, db) in one grouped launch, straight into the flat gradient buffer
+            dwg.launch()             # every layer's (dW, db) in one grouped launch, straight into the flat gradient buffer
         setattr(self, "_dwg_" + which, dwg)          # (keeps the slab scratch alive until the next step)
         if which == "all":
             self.grads.assign(grads)

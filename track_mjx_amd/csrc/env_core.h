@@ -42,7 +42,7 @@ TM_DEV float tm_nan_to_num(float x) {
 }
 
 // _get_obs -> obs[obs_size][n]; applies nan_to_num when `sanitize`.  `part` < 0: everything.  Otherwise one of the
-// TM_OBS_PARTS(T) = 3 T + 3 pieces the split kernel k_obs runs in parallel (one per blockIdx.y): 3 t + {0: root position +
+// TM_OBS_PARTS(T) = 3 T + 3 pieces the split kernel k_step_parts runs in parallel (one per blockIdx.y): 3 t + {0: root position +
 // quaternion, 1: joints, 2: bodies} of trajectory frame t, then 3 T + {0: qpos, 1: qvel, 2: actuator forces + torso + end effectors}.
 #define TM_OBS_PARTS(T) (3 * (T) + 3)
 // (`obs` is restrict: the observation rows overlap nothing this function reads — without that every PUT orders the loads behind it, and the
@@ -140,7 +140,7 @@ TM_DEV void tm_window_dim(const DModel &m, EnvRef r, int i, int bi, float a, flo
   }
   var_i = var / (float)W; jerk_i = jerk;
 }
-// The four long sums of tm_step_post as separately launchable parts (k_post_parts, one lane per (env, part)); results go to
+// The four long sums of tm_step_post as separately launchable parts (k_step_parts, one lane per (env, part)); results go to
 // rows 0..TM_NPOST-1 of `P` ([row][n]).  Same expressions and the same summation order as the inline code below.
 #define TM_NPOST 7   // joint distance | body-position sum | end-effector sum | energy sum | NaN flags of three state thirds
 TM_DEV void tm_post_part(const DModel &m, EnvRef r, const int *r_is, int part, float *P) {
@@ -197,7 +197,7 @@ TM_DEV void tm_post_part(const DModel &m, EnvRef r, const int *r_is, int part, f
 #define TM_REP_ONE TM_REP(1, 1, 1)
 // `win`: per-(dim, env) partials [2*nu][n] produced by the (env x action-dim)-parallel window kernel, or nullptr to
 // compute the window terms inline (lane-per-env path).
-// `split`: the observation was written by k_obs and the auto-reset copies are left to k_autoreset (tmjx_hip.hip).
+// `split`: the observation was written by k_step_parts and the auto-reset copies are left to k_autoreset (tmjx_hip.hip).
 // `fo`: the CALLER's reference frame per env (row-major [n][3 | 4 | nq - 7 | (nbody - 1) * 3 | 3]) in place of the kernel's own gather from the
 // resident clip table — compute_tracking_rewards(data, reference_frame, ...) as the reference calls it (reward.py:359-366 with the frame of
 // single_clip_tracking.py:223-225); only the inline (lane-per-env) form takes it.

@@ -34,10 +34,9 @@ static int launch_bgemm2(const void *A, int lda, const bf16_t *B, int ldb, const
 }
 template <int MI, int NI, int EPI, bool AF32>
 static int launch_bgemm(const void *A, int lda, const bf16_t *B, int ldb, const float *bias, float *C, int ldc, int M, int N, int K, const BgEpi &epi, hipStream_t s) {
-  // bf16 activations with a contraction length that is a whole number of K tiles: A by LDS-DMA, two tiles ahead (TMJX_BG_NO_DMA_A=1: A/B switch)
-  static const bool no_dma = getenv("TMJX_BG_NO_DMA_A") != nullptr;
+  // bf16 activations with a contraction length that is a whole number of K tiles: A by LDS-DMA, two tiles ahead
   if constexpr (!AF32) {
-    if (!(K % BG_BK) && !no_dma) return launch_bgemm2<MI, NI, EPI, false, true>(A, lda, B, ldb, bias, C, ldc, M, N, K, epi, s);
+    if (!(K % BG_BK)) return launch_bgemm2<MI, NI, EPI, false, true>(A, lda, B, ldb, bias, C, ldc, M, N, K, epi, s);
   }
   return launch_bgemm2<MI, NI, EPI, AF32, false>(A, lda, B, ldb, bias, C, ldc, M, N, K, epi, s);
 }
@@ -49,10 +48,10 @@ static int bgemm_by_width(const void *A, int lda, const bf16_t *B, int ldb, cons
 }
 
 // rows of M per slab and number of slabs: about two workgroups (four waves each) per CU
+constexpr int BDW_WGS = 512;
 static void bdw_split(int M, int N, int K, int *rows_per_split, int *S, int *ld_slab, int max_slabs = 0) {
   const int tiles = ((N + BGDW_BT - 1) / BGDW_BT) * ((K + BGDW_BT - 1) / BGDW_BT);
-  static const int target = getenv("TMJX_BDW_WGS") ? atoi(getenv("TMJX_BDW_WGS")) : 512;      // tuning knob
-  int want = (target + tiles - 1) / tiles;
+  int want = (BDW_WGS + tiles - 1) / tiles;
   if (max_slabs > 0 && want > max_slabs) want = max_slabs;      // (a problem of a group: the group fills the chip, not the problem)
   if (want < 1) want = 1;
   int rps = (((M + want - 1) / want) + BGDW_BM - 1) / BGDW_BM * BGDW_BM;
@@ -205,12 +204,12 @@ int tmjx_bgemm_dw(const void *dY, int y_is_f32, int ldy, const void *X, int x_is
 }
 
 // Every weight gradient of a backward pass in one launch + one reduction launch (k_bgemm_dw_grouped): problems as tmjx_bgemm_dw takes them, each with a
-// scratch of tmjx_bgemm_dw_scratch_floats(M, N, K) floats.  target_wgs: workgroups the GROUP should bring (0: TMJX_BDW_GROUP_WGS, default 2048).
+// scratch of tmjx_bgemm_dw_scratch_floats(M, N, K) floats.  target_wgs: workgroups the GROUP should bring (0: BDW_GROUP_WGS).
+constexpr int BDW_GROUP_WGS = 2048;
 int tmjx_bgemm_dw_grouped(const tmjx_bdw_problem_t *probs, int n, int target_wgs, void *stream) {
   if (!probs) return fail(TMJX_EINVAL, "null argument");
   if (n < 1 || n > BDW_GROUP_MAX) return fail(TMJX_EINVAL, "1 .. 24 problems per group");
-  static const int group_default = getenv("TMJX_BDW_GROUP_WGS") ? atoi(getenv("TMJX_BDW_GROUP_WGS")) : 2048;
-  const int group_target = target_wgs > 0 ? target_wgs : group_default;
+  const int group_target = target_wgs > 0 ? target_wgs : BDW_GROUP_WGS;
   int all_tiles = 0;
   for (int i = 0; i < n; i++) all_tiles += ((probs[i].N + BGDW_BT - 1) / BGDW_BT) * ((probs[i].K + BGDW_BT - 1) / BGDW_BT);
   // slabs in EIGHTS: a problem's slab s runs on XCD s % 8 (k_bgemm_dw's order: the tiles of one row slab share an L2), so 6 slabs leave two XCDs without

@@ -93,17 +93,6 @@ __global__ void k_physics(const DModel *__restrict__ mp, float *st, const float 
 
 #endif  // TMJX_LANE_IMPL
 
-// window statistics, one lane per (action dim, env): 38x more parallelism than lane-per-env for the 50x38 ring buffer
-__global__ void k_window(const DModel *__restrict__ mp, float *st, const int *is, const float *action, float *win, int n) {
-  int e = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
-  if (e >= n) return;
-  const DModel &m = *mp;
-  EnvRef r{st, nullptr, n, e};
-  float vi, ji;
-  tm_window_dim(m, r, i, is[(size_t)m.i_buffer_index * n + e], action[(size_t)i * n + e], vi, ji);
-  win[(size_t)i * n + e] = vi;
-  win[(size_t)(m.nu + i) * n + e] = ji;
-}
 __global__ void k_post(const DModel *__restrict__ mp, float *st, int *is, const float *action, float *obs, float *reward,
                        float *done, float *trunc, float *metrics, const float *win, int split, int rep, int n) {
   TM_PRIO_ACTING();
@@ -112,7 +101,7 @@ __global__ void k_post(const DModel *__restrict__ mp, float *st, int *is, const 
   const DModel &m = *mp;
   EnvRef r{st, nullptr, n, e};
   if (rep & TM_REP_FIRST) tm_step_prologue(m, r);
-  // split: the long sums were computed by k_post_parts into the workspace rows behind the 2 nu window partials
+  // split: the long sums were computed by k_step_parts into the workspace rows behind the 2 nu window partials
   tm_step_post(m, r, is, action, obs, reward, done, trunc, metrics, win, split != 0, split ? win + (size_t)2 * m.nu * n : nullptr, rep);
 }
 // k_post's inline form with the CALLER's reference frame per env (tmjx_reward_frame; env_core.h: TmFrame)
@@ -125,25 +114,10 @@ __global__ void k_post_frame(const DModel *__restrict__ mp, float *st, int *is, 
   tm_step_prologue(m, r);
   tm_step_post(m, r, is, action, obs, reward, done, trunc, metrics, nullptr, false, nullptr, TM_REP_ONE, &fo);
 }
-// the long reductions of the reward / termination step, one lane per (env, part) (env_core.h: tm_post_part)
-__global__ void k_post_parts(const DModel *__restrict__ mp, float *st, const int *is, float *P, int n) {
-  int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n) return;
-  EnvRef r{st, nullptr, n, e};
-  tm_post_part(*mp, r, is, blockIdx.y, P);
-}
-// observation, one lane per (env, part): TM_OBS_PARTS(T) = 18 pieces (env_core.h: tm_get_obs); rows of obs stay coalesced over envs
-__global__ void k_obs(const DModel *__restrict__ mp, float *st, const int *is, float *__restrict__ obs, int n) {
-  int e = blockIdx.x * blockDim.x + threadIdx.x, part = blockIdx.y;
-  if (e >= n) return;
-  const DModel &m = *mp;
-  EnvRef r{st, nullptr, n, e};
-  int clip = is[(size_t)m.i_clip_idx * n + e], start = is[(size_t)m.i_start_frame * n + e];
-  tm_get_obs(m, r, clip, tm_cur_frame(m, ST(m.s_time, 0), start), obs, true, part);
-}
-// k_window, k_obs and k_post_parts in ONE launch (blockIdx.y picks the piece): the three read the post-physics state and write disjoint
-// outputs, so a group's serial phase between two physics launches is one launch latency shorter twice over.  (Measured in round 1, when
-// such launches mostly waited for wave slots: no gain; re-measured in round 3 with three env groups and one-wave blocks everywhere.)
+// ONE launch, blockIdx.y picks the piece: the window statistics, one lane per (action dim, env) (38x more parallelism than lane-per-env for the
+// 50x38 ring buffer); the observation, one lane per (env, part) (TM_OBS_PARTS(T) = 18 pieces, env_core.h: tm_get_obs; rows of obs stay coalesced
+// over envs); the long reductions of the reward / termination step, one lane per (env, part) (env_core.h: tm_post_part).  The three read the
+// post-physics state and write disjoint outputs, so a group's serial phase between two physics launches is one launch latency shorter twice over
 __global__ __launch_bounds__(64) void k_step_parts(const DModel *__restrict__ mp, float *st, const int *is, const float *action, float *win,
                                                    float *__restrict__ obs, float *P, int n, int n_obs_parts) {
   TM_PRIO_ACTING();
@@ -479,7 +453,6 @@ static int launch_wave(const tmjx_model *m, float *state, const float *action, i
     lds = (size_t)tmw_sens_layout(m->rodent ? tmjx_host::make_wave_layout(m->h) : tmjx_host::make_wave_layout(m->h, false)).end * sizeof(float);
     if (lds > 64 * 1024) return fail(TMJX_EINVAL, "the sensor stage needs more than 64 KiB of LDS per env for this model");
   }
-  if (const char *pad = getenv("TMJX_LDS_PAD_KB")) lds += (size_t)atoi(pad) * 1024;  // occupancy experiments only
   const int sstride = WAVE_SPILL_STRIDE(m);
   if (m->rodent && m->mspill_envs < n_env) {
     if (m->mspill) hipFree(m->mspill);            // (hipFree waits for the launches that may still read the old block)
@@ -511,9 +484,9 @@ static int launch_wave(const tmjx_model *m, float *state, const float *action, i
   return TMJX_OK;
 }
 // env-major physics record inside the caller's workspace (behind the K3 partial rows), or nullptr = direct [row][n_env] access
-// (TMJX_NO_RECORD=1, or a workspace too small for it)
+// (no workspace, or one too small for it)
 static float *wave_record(const tmjx_model *m, float *workspace, int n_env) {
-  if (!workspace || getenv("TMJX_NO_RECORD")) return nullptr;
+  if (!workspace) return nullptr;
   if ((size_t)m->h.w_rows * (size_t)n_env < WAVE_REC_OFFSET(m, n_env) + (size_t)WAVE_REC_STRIDE(m) * (size_t)n_env) return nullptr;
   return workspace + WAVE_REC_OFFSET(m, n_env);
 }
@@ -546,22 +519,15 @@ int tmjx_reset(tmjx_model *m, float *state, int32_t *istate, const int32_t *clip
 #endif
 }
 
-// K3 behind the physics launch: window statistics + observation parts + reward partial sums (ONE launch, k_step_parts; TMJX_K3_SEPARATE=1:
-// three), reward / termination, auto-reset copies.  64-lane workgroups throughout: next to the other env groups' physics kernel (up to 3 waves
+// K3 behind the physics launch: window statistics + observation parts + reward partial sums (ONE launch, k_step_parts),
+// reward / termination, auto-reset copies.  64-lane workgroups throughout: next to the other env groups' physics kernel (up to 3 waves
 // of 168 VGPRs per SIMD) a 256-lane workgroup had to wait for four wave slots WITH registers on one CU — 245 us on average instead of 30
 static void launch_k3(tmjx_model *m, float *state, int32_t *istate, const float *action, float *obs, float *reward, float *done,
                       float *truncation, float *metrics, float *workspace, int n_env, hipStream_t stream, int rep = TM_REP_ONE) {
   const DModel &h = m->h;
-  static const bool merged = !getenv("TMJX_K3_SEPARATE");
   const int nobs = TM_OBS_PARTS(h.traj_length);
   float *parts = workspace + (size_t)2 * h.nu * n_env;
-  if (merged) {
-    hipLaunchKernelGGL(k_step_parts, dim3((n_env + 63) / 64, h.nu + nobs + TM_NPOST), dim3(64), 0, stream, m->d, state, istate, action, workspace, obs, parts, n_env, nobs);
-  } else {
-    hipLaunchKernelGGL(k_window, dim3((n_env + 63) / 64, h.nu), dim3(64), 0, stream, m->d, state, istate, action, workspace, n_env);
-    hipLaunchKernelGGL(k_obs, dim3((n_env + 63) / 64, nobs), dim3(64), 0, stream, m->d, state, istate, obs, n_env);
-    hipLaunchKernelGGL(k_post_parts, dim3((n_env + 63) / 64, TM_NPOST), dim3(64), 0, stream, m->d, state, istate, parts, n_env);
-  }
+  hipLaunchKernelGGL(k_step_parts, dim3((n_env + 63) / 64, h.nu + nobs + TM_NPOST), dim3(64), 0, stream, m->d, state, istate, action, workspace, obs, parts, n_env, nobs);
   hipLaunchKernelGGL(k_post, dim3((n_env + 63) / 64), dim3(64), 0, stream, m->d, state, istate, action, obs, reward, done, truncation, metrics,
                      (const float *)workspace, 1, rep, n_env);
   if (h.auto_reset && (rep & TM_REP_LAST)) {
@@ -736,8 +702,7 @@ int tmjx_ppo_loss(const tmjx_ppo_cfg_t *cfg, const float *logits, const float *r
   const int N = c.T * c.B, nblk = (N * PPO_G + PPO_BLOCK - 1) / PPO_BLOCK;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_ppo_a, dim3(nblk), dim3(PPO_BLOCK), 0, s, c, logits, raw_action, noise, fc2, scratch, nblk);
-  static const bool one_block_b = getenv("TMJX_PPO_ONE_BLOCK_B") != nullptr;
-  if (c.T <= PPO_TMAX && !one_block_b) {
+  if (c.T <= PPO_TMAX) {
     // GAE / advantage statistics by one 64-thread block per 64 columns, combined by the consumers (csrc/ppo_kernels.h: k_ppo_b2)
     const int nrec = (c.B + 63) / 64;
     float *rec = scratch + 4 * (size_t)N + (size_t)4 * nblk + 16;
@@ -772,9 +737,8 @@ int tmjx_ppo_loss_phases(const tmjx_ppo_cfg_t *cfg, const float *logits, const f
   const int N = c.T * c.B, nblk = (N * PPO_G + PPO_BLOCK - 1) / PPO_BLOCK, nrec = (c.B + 63) / 64;
   float *rec = scratch + 4 * (size_t)N + (size_t)4 * nblk + 16;
   hipStream_t s = (hipStream_t)stream;
-  // A and C in the same call: one launch (k_ppo_ac; TMJX_PPO_AC=0: two)
-  static const bool no_ac = getenv("TMJX_PPO_AC") && atoi(getenv("TMJX_PPO_AC")) == 0;
-  if ((phases & TMJX_PPO_PHASE_A) && (phases & TMJX_PPO_PHASE_C) && !no_ac) {
+  // A and C in the same call: one launch (k_ppo_ac)
+  if ((phases & TMJX_PPO_PHASE_A) && (phases & TMJX_PPO_PHASE_C)) {
     if (phases & TMJX_PPO_PHASE_B) {       // (B's records first: C's half reads them; A's half does not depend on B)
       hipLaunchKernelGGL(k_ppo_b2, dim3(nrec), dim3(64), 0, s, c, baseline, bootstrap, reward, discount, truncation, scratch, 0, rec);
       phases &= ~TMJX_PPO_PHASE_B;
@@ -1036,10 +1000,9 @@ int tmjx_linear_act(const float *A, int64_t lda, const float *W, int ldw, const 
   if (!tmjx_linear_act_ok(A, lda, W, ldw, K)) return fail(TMJX_EINVAL, "tmjx_linear_act: K % 4 == 0, row-major operands with 16-byte aligned rows");
   if ((mean || inv_std) && (!mean || !inv_std || (((uintptr_t)mean | (uintptr_t)inv_std) & 15))) return fail(TMJX_EINVAL, "tmjx_linear_act: mean and inv_std together, 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  // 32-row tiles while 64-row ones would leave CUs without a workgroup (the acting policy's 1 365 rows: 88 -> 172 workgroups); TMJX_ACT_ROWS=64 / 32 forces one
-  static const int force = getenv("TMJX_ACT_ROWS") ? atoi(getenv("TMJX_ACT_ROWS")) : 0;
+  // 32-row tiles while 64-row ones would leave CUs without a workgroup (the acting policy's 1 365 rows: 88 -> 172 workgroups)
   const int ncol = (N + ACT_BM - 1) / ACT_BM;
-  const bool small = force ? force == 32 : ((M + 63) / 64) * ncol < 128;
+  const bool small = ((M + 63) / 64) * ncol < 128;
   if (small) {
     dim3 grid((M + 31) / 32, ncol);
     if (mean) hipLaunchKernelGGL((k_linear_act<true, 32>), grid, dim3(256), 0, s, A, (long long)lda, W, ldw, bias, C, M, N, K, mean, inv_std);
@@ -1085,10 +1048,8 @@ static bool aligned16(const void *p, long long ld) { return !((uintptr_t)p & 15)
 // Rows per workgroup tile (16 MT): 80 where that fills the chip (20 480 rows = 256 workgroups, one per CU), 32 where 80-row tiles would leave most
 // CUs idle — 5 120 rows (one rank's share of the 8-GPU configuration: batch_size 2048 / 8 x unroll_length 20) are 64 workgroups of 80 rows but
 // 160 of 32.  Cost model: rounds of 256 workgroups x the tile's MFMA time (a 32-row tile streams the same weight tile per K step as an 80-row one,
-// ~ 10 % over its 2 / 5 share).  TMJX_GEMM_MT=5 / 2 forces either (tuning, tests).
+// ~ 10 % over its 2 / 5 share).
 static int gemm_mt(int M, int col_tiles) {
-  static const int forced = getenv("TMJX_GEMM_MT") ? atoi(getenv("TMJX_GEMM_MT")) : 0;
-  if (forced == 5 || forced == 2) return forced;
   const long long w5 = (long long)((M + 79) / 80) * col_tiles, w2 = (long long)((M + 31) / 32) * col_tiles;
   const double c5 = (double)((w5 + 255) / 256) * 5.0, c2 = (double)((w2 + 255) / 256) * 2.2;
   return c2 < c5 ? 2 : 5;
@@ -1303,10 +1264,10 @@ int tmjx_gemm_nn(const float *A, int lda, const float *W, int ldw, float *C, int
 }
 // rows of M per slab and number of slabs so that tiles x slabs is about the number of CUs (256); `max_slabs` > 0 caps the slab count (the
 // grouped launch shares the chip between its problems: tmjx_gemm_dw_grouped)
+constexpr int DW_WGS = 256;
 static void dw_split(int M, int N, int K, int *rows_per_split, int *S, int *ld_slab, int max_slabs = 0) {
   const int tiles = ((N + DW_BT - 1) / DW_BT) * ((K + DW_BT - 1) / DW_BT);
-  static const int target = getenv("TMJX_DW_WGS") ? atoi(getenv("TMJX_DW_WGS")) : 256;      // tuning knob
-  int want = (target + tiles - 1) / tiles;      // one workgroup per CU: twice as many slabs (two per CU) ran the kernel no faster and doubled the reduction's traffic
+  int want = (DW_WGS + tiles - 1) / tiles;      // one workgroup per CU: twice as many slabs (two per CU) ran the kernel no faster and doubled the reduction's traffic
   if (max_slabs > 0 && want > max_slabs) want = max_slabs;
   if (want < 1) want = 1;
   int rps = (((M + want - 1) / want) + DW_BM - 1) / DW_BM * DW_BM;
@@ -1339,19 +1300,16 @@ int tmjx_gemm_dw(const float *dY, int ldy, const float *X, int ldx, float *dW, f
   return check_launch("k_gemm_dw");
 }
 
-int tmjx_gemm_dw_grouped(const tmjx_dw_problem_t *probs, int n, void *stream) { return tmjx_gemm_dw_grouped_wgs(probs, n, 0, stream); }
-int tmjx_gemm_dw_grouped_wgs(const tmjx_dw_problem_t *probs, int n, int target_wgs, void *stream) {
+int tmjx_gemm_dw_grouped(const tmjx_dw_problem_t *probs, int n, void *stream) {
   if (!probs) return fail(TMJX_EINVAL, "null argument");
   if (n < 1 || n > DW_GROUP_MAX) return fail(TMJX_EINVAL, "1 .. 16 problems per group");
   DwGroup G;
   G.n = n;
   int wg = 0, red = 0;
-  // The problems of a group run side by side in ONE launch: together they should fill the chip about four times (TMJX_DW_GROUP_WGS = 1024 workgroups: two
+  // The problems of a group run side by side in ONE launch: together they should fill the chip about four times (1024 workgroups: two
   // 74 KB workgroups fit a CU), not once EACH — nine problems split for 256 workgroups apiece were 2 300 workgroups writing and re-reading
   // 64 slabs per weight matrix (160 MB per backward pass at 20 480 rows, 130 MB at 5 120).  Never more slabs than the problem's own split
   // (the caller sized the scratch by tmjx_gemm_dw_scratch_floats).
-  static const int group_env = getenv("TMJX_DW_GROUP_WGS") ? atoi(getenv("TMJX_DW_GROUP_WGS")) : 0;
-  const int group_target = target_wgs > 0 ? target_wgs : group_env;           // (a group that runs NEXT TO other kernels asks for fewer workgroups)
   int all_tiles = 0;
   for (int i = 0; i < n; i++) all_tiles += ((probs[i].N + DW_BT - 1) / DW_BT) * ((probs[i].K + DW_BT - 1) / DW_BT);
   if (all_tiles < 1) all_tiles = 1;
@@ -1360,8 +1318,8 @@ int tmjx_gemm_dw_grouped_wgs(const tmjx_dw_problem_t *probs, int n, int target_w
   // 25 = 1 050 (the old "about 1 024") 0.865 / 0.408 — a count like 336 puts a second workgroup on 80 of the CUs, which then run both at half speed while
   // the rest wait; 1 050 is two full rounds of two per CU plus 26 stragglers.  So: as many slabs as keep tiles x slabs within ONE workgroup per CU (fewest
   // slabs = least slab traffic and reduction work among the good counts).  Groups of more than 256 tiles (the rodent-mc-intention nets) are flat in
-  // this knob (5.06 - 5.09 ms): about 1 024 workgroups as before.  TMJX_DW_GROUP_WGS / target_wgs: an explicit workgroup budget instead.
-  const int max_slabs = group_target > 0 ? (group_target + all_tiles - 1) / all_tiles : (all_tiles <= 256 ? 256 / all_tiles : (1024 + all_tiles - 1) / all_tiles);
+  // this knob (5.06 - 5.09 ms): about 1 024 workgroups as before.
+  const int max_slabs = all_tiles <= 256 ? 256 / all_tiles : (1024 + all_tiles - 1) / all_tiles;
   for (int i = 0; i < n; i++) {
     const tmjx_dw_problem_t &q = probs[i];
     if (!q.dY || !q.X || !q.dW || !q.scratch) return fail(TMJX_EINVAL, "null pointer in a problem");
