@@ -655,6 +655,34 @@ typedef struct {
 int tmjx_decoder_act_ok(const tmjx_decoder_act_t *a);
 int tmjx_decoder_act(const tmjx_decoder_act_t *a, void *stream);
 
+/* tmjx_lstm_decoder_act (csrc/lstm_decoder_act.h): the LSTM decoder policy as ONE launch —
+ *   x_0 = [latents | normalised proprioception] (tmjx_decoder_input's expression);  per layer k < L: (h_k, c_k) zeroed where reset != 0,
+ *   gates = x_k W_i,k^T + h_k W_h,k^T + b_h,k (i | f | g | o), c_k' = sig(f) c_k + sig(i) tanh(g), h_k' = sig(o) tanh(c_k'), x_{k+1} = h_k';
+ *   logits = x_L W_p^T + b_p;  action = tanh(logits[0..A)).
+ * latents, obs, obs_s0 / obs_s1, mean / std, Z, obs_w, ref_w: as tmjx_decoder_act.  reset [n] or NULL: non-zero zeroes that row's carry of EVERY
+ * layer before the step (tmjx_lstm_fwd_t.reset at T = 1).  layer[k].Wi [4H][ldwi >= the layer's input width rounded up to 4], layer[k].Wh
+ * [4H][ldwh >= H], Wp [2A][ldwp >= H]: rows 16-byte aligned (ld % 4 == 0); bh [4H], bp [2A] or NULL.
+ * The carry h, c [n][ld >= L H] (layer k in columns [k H, (k + 1) H): the [n, L, H] layout) is read and overwritten in place.
+ * Outputs: action_t [A][n]; optionally ctrl [n][A] and logits [n][ldl >= 2A] (NULL: not written).  Nothing else reaches global memory; pad columns
+ * of h / c / logits and rows >= n are never touched.
+ * Qualifying shapes: H == 128, 1 <= L <= 4, Z + obs_w - ref_w <= 320, 2A <= 128, any n >= 1.  tmjx_lstm_decoder_act_ok says whether a descriptor
+ * qualifies (no error recorded, no device call); the entry point returns TMJX_EINVAL with the reason before any device call. */
+#define TMJX_LSTM_DECODER_MAX_LAYERS 4
+typedef struct { const float *Wi, *Wh, *bh; int32_t ldwi, ldwh; } tmjx_lstm_decoder_layer_t;
+typedef struct {
+  const float *latents; int32_t ldz;
+  const float *obs; int64_t obs_s0, obs_s1;
+  const float *mean, *std;
+  const float *reset;
+  int32_t n, Z, obs_w, ref_w, L, H;
+  tmjx_lstm_decoder_layer_t layer[TMJX_LSTM_DECODER_MAX_LAYERS];
+  const float *Wp, *bp; int32_t ldwp, A;
+  float *h, *c; int32_t ld;
+  float *action_t, *ctrl, *logits; int32_t ldl;
+} tmjx_lstm_decoder_act_t;
+int tmjx_lstm_decoder_act_ok(const tmjx_lstm_decoder_act_t *a);
+int tmjx_lstm_decoder_act(const tmjx_lstm_decoder_act_t *a, void *stream);
+
 const char *tmjx_last_error(void);
 const char *tmjx_version(void);
 

@@ -665,3 +665,150 @@ def make_decoder_policy_fn(ckpt_path, step: int | None = None, device="cuda") ->
     tc = (cfg.get("train_setup") or {}).get("train_config") or {}
     gi = "bf16" if str(cfg.get("mlp_gemm_inputs", "f32")).lower() in ("bf16", "bfloat16") else "f32"
     return decoder_policy_from_trees(norm, ptree, bool(tc.get("normalize_observations", True)), device, gi)
+
+
+# ---- the decoder-only policy of an LSTM checkpoint (the lstm_ppo counterpart of the above: params/lstm_decoder driven with latents and a carried
+# (h, c); the reference's lstm_ppo/ppo_networks.py:240 names such a function but its module defines no make_decoder_policy and has no place for the
+# carry — this follows the LSTM roll-out step, agent/lstm.py LSTMIntentionPolicy.step, without its encoder) ------------------------------------------
+class LSTMDecoderPolicy:
+    """policy(x, hidden_state=None, reset=None) with x [n, Z + prop] = [latents | RAW proprioceptive observation] -> (action [n, A] = tanh(loc),
+    extras, (h, c) [n, L, H]): only the trailing `prop` columns are normalised, with the normaliser's columns [reference_obs_size:].
+    hidden_state None = a zero carry; reset [n]: non-zero rows start from a zero carry.  The carry passed in is not modified.  Plain torch (CPU
+    tensors: agent.lstm._torch_lstm_layer); on the GPU, HighLevelWrapper runs the policy as a launch list on the env's buffers.  Weights of layer k:
+    w_ih[k] [4H, in_k], w_hh[k] [4H, H], b_hh[k] [4H] (gate rows i | f | g | o), projection w_p [2A, H], b_p [2A]."""
+
+    def __init__(self, w_ih, w_hh, b_hh, w_p: torch.Tensor, b_p: torch.Tensor, mean: torch.Tensor | None, std: torch.Tensor | None, latent_size: int,
+                 reference_obs_size: int, trained_gemm_inputs: str = "f32"):
+        if (mean is None) != (std is None):
+            raise ValueError("LSTMDecoderPolicy: mean and std together")
+        if not (len(w_ih) == len(w_hh) == len(b_hh) >= 1):
+            raise ValueError("LSTMDecoderPolicy: one (w_ih, w_hh, b_hh) per layer, at least one layer")
+        self.w_ih, self.w_hh, self.b_hh, self.w_p, self.b_p = list(w_ih), list(w_hh), list(b_hh), w_p, b_p
+        self.mean, self.std = mean, std
+        self.hidden_layer_num, self.hidden_state_size = len(self.w_ih), int(self.w_hh[0].shape[1])
+        self.latent_size, self.reference_obs_size, self.action_size = int(latent_size), int(reference_obs_size), int(w_p.shape[0]) // 2
+        self.proprioceptive_obs_size = int(self.w_ih[0].shape[1]) - self.latent_size
+        self.device = w_p.device
+        self.trained_gemm_inputs = trained_gemm_inputs
+        if mean is not None and (mean.shape != (self.proprioceptive_obs_size,) or std.shape != mean.shape):
+            raise ValueError(f"LSTMDecoderPolicy: mean / std must hold the {self.proprioceptive_obs_size} proprioceptive columns")
+
+    def zero_carry(self, n: int, device=None, dtype=torch.float32) -> tuple:
+        shape = (int(n), self.hidden_layer_num, self.hidden_state_size)
+        dev = self.device if device is None else device
+        return torch.zeros(shape, dtype=dtype, device=dev), torch.zeros(shape, dtype=dtype, device=dev)
+
+    @torch.no_grad()
+    def logits(self, x: torch.Tensor, hidden_state=None, reset=None, dtype=torch.float32):
+        """(logits [n, 2A], (h, c)) of one step; `dtype`: the precision it is evaluated in (float64: the restatement the kernels are held to)."""
+        from .lstm import _torch_lstm_layer
+        Z, P = self.latent_size, self.proprioceptive_obs_size
+        if x.dim() != 2 or x.shape[-1] != Z + P:
+            raise ValueError(f"LSTMDecoderPolicy: the input is {tuple(x.shape)}, not [n, latents + proprioception = {Z} + {P}]")
+        cv = lambda t: t.detach().to(device="cpu", dtype=dtype)      # noqa: E731
+        x = cv(x)
+        prop = x[:, Z:]
+        if self.mean is not None:
+            prop = (prop - cv(self.mean)) / cv(self.std)
+        a = torch.cat([x[:, :Z], prop], dim=-1)
+        n = x.shape[0]
+        if hidden_state is None:
+            h, c = self.zero_carry(n, "cpu", dtype)
+        else:
+            h, c = cv(hidden_state[0]).clone(), cv(hidden_state[1]).clone()
+            if h.shape != (n, self.hidden_layer_num, self.hidden_state_size) or c.shape != h.shape:
+                raise ValueError(f"LSTMDecoderPolicy: hidden_state must be (h, c) of shape [{n}, {self.hidden_layer_num}, {self.hidden_state_size}]")
+        rs = None if reset is None else cv(reset).reshape(1, n)
+        for k in range(self.hidden_layer_num):
+            hn, cn = _torch_lstm_layer((a @ cv(self.w_ih[k]).t()).unsqueeze(0), cv(self.w_hh[k]), cv(self.b_hh[k]), h[:, k], c[:, k], rs)
+            h[:, k], c[:, k] = hn[0], cn[0]
+            a = hn[0]
+        return torch.nn.functional.linear(a, cv(self.w_p), cv(self.b_p)), (h, c)      # (nn.Linear's expression: LSTMIntentionPolicy.projection)
+
+    def __call__(self, x: torch.Tensor, hidden_state=None, reset=None, key=None):
+        lg, (h, c) = self.logits(x, hidden_state, reset)
+        dev = x.device
+        return torch.tanh(lg[:, :self.action_size]).to(dev), {}, (h.to(dev), c.to(dev))
+
+
+def lstm_decoder_policy_from_trees(norm: dict | None, ptree: dict, normalize_observations: bool = True, device="cuda",
+                                   trained_gemm_inputs: str = "f32") -> LSTMDecoderPolicy:
+    """LSTMDecoderPolicy of (normalizer_params, policy_params): Z = fc2_mean's width, H and L from params/lstm_decoder/lstm_<k>, A from lstm_projection,
+    proprioceptive width = lstm_0's input - Z, reference_obs_size = the normaliser's width - that; weights converted as lstm_policy_from_flax does."""
+    who = "make_lstm_decoder_policy_fn"
+    p = ptree.get("params", {})
+    if "lstm_decoder" not in p:
+        if "decoder" in p:
+            raise ValueError(f"{who}: the checkpoint holds an MLP decoder (params/decoder): use make_decoder_policy_fn")
+        raise ValueError(f"{who}: the checkpoint's policy tree has no params/lstm_decoder")
+    dec = p["lstm_decoder"]
+    L = len([k for k in dec if k.startswith("lstm_") and k != "lstm_projection"])
+    if L < 1 or any(f"lstm_{k}" not in dec for k in range(L)):
+        raise ValueError(f"{who}: params/lstm_decoder has no lstm_<k> layers 0 .. L-1")
+    if "lstm_projection" not in dec:
+        raise ValueError(f"{who}: params/lstm_decoder has no lstm_projection")
+    if "encoder" not in p or "fc2_mean" not in p["encoder"]:
+        raise ValueError(f"{who}: the intention size is read from params/encoder/fc2_mean, which the checkpoint does not have")
+    Z = int(np.asarray(p["encoder"]["fc2_mean"]["kernel"]).shape[1])
+    H = int(np.asarray(dec["lstm_0"]["hi"]["kernel"]).shape[0])
+    in0 = int(np.asarray(dec["lstm_0"]["ii"]["kernel"]).shape[0])
+    A2 = int(np.asarray(dec["lstm_projection"]["kernel"]).shape[1])
+    prop = in0 - Z
+    if prop < 0 or A2 % 2:
+        raise ValueError(f"{who}: decoder input width {in0} < intention size {Z}, or an odd head width {A2}")
+    if norm is None or "mean" not in norm:
+        raise ValueError(f"{who}: the checkpoint has no normaliser (its width gives reference_obs_size)")
+    W = int(np.asarray(norm["mean"]).shape[-1])
+    ref = W - prop
+    if ref < 0:
+        raise ValueError(f"{who}: the normaliser has {W} columns, fewer than the decoder's {prop} proprioceptive inputs")
+    dev = torch.device(device)
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=np.float32)), device=dev).contiguous()      # noqa: E731
+    w_ih, w_hh, b_hh = [], [], []
+    for k in range(L):
+        cell = dec[f"lstm_{k}"]
+        w_ih.append(t(np.concatenate([np.asarray(cell["i" + g]["kernel"]).T for g in LSTM_GATES], 0)))
+        w_hh.append(t(np.concatenate([np.asarray(cell["h" + g]["kernel"]).T for g in LSTM_GATES], 0)))
+        b_hh.append(t(np.concatenate([np.asarray(cell["h" + g]["bias"]).reshape(-1) for g in LSTM_GATES], 0)))
+        want = in0 if k == 0 else H
+        if w_ih[k].shape != (4 * H, want) or w_hh[k].shape != (4 * H, H) or b_hh[k].shape != (4 * H,):
+            raise ValueError(f"{who}: lstm_{k} is not an LSTM cell of {want} inputs and {H} hidden units")
+    proj = dec["lstm_projection"]
+    w_p, b_p = t(np.asarray(proj["kernel"]).T), t(np.asarray(proj["bias"]).reshape(-1))
+    if w_p.shape != (A2, H):
+        raise ValueError(f"{who}: lstm_projection takes {w_p.shape[1]} inputs, the cells have {H} hidden units")
+    mean = std = None
+    if normalize_observations:
+        mean = t(np.asarray(norm["mean"], dtype=np.float32).reshape(-1)[ref:])
+        std = t(np.asarray(norm["std"], dtype=np.float32).reshape(-1)[ref:])
+    return LSTMDecoderPolicy(w_ih, w_hh, b_hh, w_p, b_p, mean, std, Z, ref, trained_gemm_inputs)
+
+
+def _policy_trees_and_config(ckpt_path, step, who: str) -> tuple:
+    import json
+    import os
+    path = str(ckpt_path)
+    if os.path.isdir(path):
+        d = resolve_step_dir(path, step)
+        norm, ptree = load_policy(d)
+        meta = os.path.join(d, "config", "metadata")
+        cfg = {}
+        if os.path.exists(meta):
+            with open(meta) as f:
+                cfg = json.load(f) or {}
+    else:
+        if step is not None:
+            raise ValueError(f"{who}: `step` selects a step of a checkpoint directory; a .npz file holds one policy")
+        norm, ptree, _ = load_freeze_source(path)
+        with np.load(path) as z:
+            cfg = json.loads(bytes(z["config_json"]).decode()) if "config_json" in z.files else {}
+    return norm, ptree, cfg
+
+
+def make_lstm_decoder_policy_fn(ckpt_path, step: int | None = None, device="cuda") -> LSTMDecoderPolicy:
+    """The decoder-only inference function of a use_lstm checkpoint: a run directory (latest step, or `step`), a step directory, or a .npz of
+    save_npz.  normalize_observations=false in the saved config means no normaliser."""
+    norm, ptree, cfg = _policy_trees_and_config(ckpt_path, step, "make_lstm_decoder_policy_fn")
+    tc = (cfg.get("train_setup") or {}).get("train_config") or {}
+    gi = "bf16" if str(cfg.get("mlp_gemm_inputs", "f32")).lower() in ("bf16", "bfloat16") else "f32"
+    return lstm_decoder_policy_from_trees(norm, ptree, bool(tc.get("normalize_observations", True)), device, gi)

@@ -548,7 +548,10 @@ def replay_latents(cfg: dict, decoder_policy, clips: Sequence[int], latents: np.
     from ..environment.wrappers import HighLevelWrapper
     n, T = len(clips), latents.shape[1] + 1
     env = create_environment(cfg, n, decoder_policy.device)
-    hl = HighLevelWrapper(env, decoder_policy, decoder_policy.reference_obs_size, path=path)
+    from ..agent.checkpoint import LSTMDecoderPolicy
+    # (an LSTM decoder's carry starts from zero at the reset and is never reset afterwards, as in a plain roll-out)
+    kw = dict(reset_carry_on_done=False) if isinstance(decoder_policy, LSTMDecoderPolicy) else {}
+    hl = HighLevelWrapper(env, decoder_policy, decoder_policy.reference_obs_size, path=path, **kw)
     nq, nv = int(env.layout.nq), int(env.layout.nv)
     qn, vn = np.empty((nq, n), np.float32), np.empty((nv, n), np.float32)
     for j, c in enumerate(clips):
@@ -588,7 +591,8 @@ def _main_replay(opts: dict, cfg: dict, step_dir: str) -> int:
         print(f"[rollout] replay_latents: no clip_<i>.h5 in {src}", file=sys.stderr)
         return 2
     scale = float(opts.get("latent_scale", 1.0))
-    dp = ckpt.make_decoder_policy_fn(step_dir, device="cuda")
+    use_lstm = "lstm_decoder" in ckpt.load_policy(step_dir)[1].get("params", {})
+    dp = (ckpt.make_lstm_decoder_policy_fn if use_lstm else ckpt.make_decoder_policy_fn)(step_dir, device="cuda")
     metrics = tuple((cfg.get("logging_config") or {}).get("rollout_metrics", ROLLOUT_METRICS))
     out_dir = opts.get("out", os.path.join(step_dir, "replays"))
     os.makedirs(out_dir, exist_ok=True)
@@ -606,7 +610,7 @@ def _main_replay(opts: dict, cfg: dict, step_dir: str) -> int:
         used = res.pop("path")
         for j, c in enumerate(chunk):
             one = _index_j(res, j)
-            one["meta"] = {"seed": np.int64(seed), "clip_idx": np.int64(c), "checkpoint": str(step_dir), "model": "mlp", "replay_latents": str(src),
+            one["meta"] = {"seed": np.int64(seed), "clip_idx": np.int64(c), "checkpoint": str(step_dir), "model": "lstm" if use_lstm else "mlp", "replay_latents": str(src),
                            "latent_scale": np.float64(scale), "decoder_path": used, "rollout_gemm_inputs": "f32",
                            "trained_gemm_inputs": dp.trained_gemm_inputs}
             save_to_h5py(os.path.join(out_dir, f"clip_{c}.h5"), one)

@@ -8,6 +8,7 @@
 
 #include "../../include/tmjx.h"
 #include "lstm_kernels.h"
+#include "lstm_decoder_act.h"
 
 extern "C" int tmjx_internal_fail(int code, const char *msg);       // tmjx_hip.hip: records the calling thread's error message
 static int fail(int code, const std::string &msg) { return tmjx_internal_fail(code, msg.c_str()); }
@@ -48,6 +49,38 @@ static const char *bwd_why(const tmjx_lstm_bwd_t *a) {
   return nullptr;
 }
 
+static_assert(sizeof(tmjx_lstm_decoder_act_t) == 296, "tmjx_lstm_decoder_act_t: the layout hip.LstmDecoderAct declares");
+static const char *decoder_act_why(const tmjx_lstm_decoder_act_t *a) {
+  if (!a) return "null argument block";
+  if (!a->latents || !a->obs || !a->action_t || !a->Wp) return "null argument (latents / obs / action_t / Wp)";
+  if (!a->h || !a->c) return "null carry (h / c)";
+  if (!a->mean != !a->std) return "mean and std together";
+  if (a->n < 1) return "n >= 1";
+  if (a->H != LDA_H) return "H must be 128";
+  if (a->L < 1 || a->L > TMJX_LSTM_DECODER_MAX_LAYERS) return "1 .. 4 LSTM layers";
+  if (a->Z < 1 || a->ldz < a->Z) return "Z >= 1 and ldz >= Z";
+  if (a->ref_w < 0 || a->obs_w < a->ref_w) return "obs_w >= ref_w >= 0";
+  const long long K1 = (long long)a->Z + a->obs_w - a->ref_w;
+  if (K1 > LDA_XLD) return "the decoder's input (Z + obs_w - ref_w) is at most 320 columns wide";
+  if (a->A < 1 || 2 * a->A > 128) return "the action head has 2A <= 128 columns (A >= 1)";
+  for (const void *p : {(const void *)a->latents, (const void *)a->obs, (const void *)a->mean, (const void *)a->std, (const void *)a->reset, (const void *)a->h,
+                        (const void *)a->c, (const void *)a->action_t, (const void *)a->ctrl, (const void *)a->logits, (const void *)a->bp})
+    if (!al4(p)) return "float pointers must be 4-byte aligned";
+  for (int k = 0; k < a->L; k++) {
+    const tmjx_lstm_decoder_layer_t &y = a->layer[k];
+    if (!y.Wi || !y.Wh || !y.bh) return "null layer argument (Wi / Wh / bh)";
+    if ((y.ldwi & 3) || (y.ldwh & 3) || !al16(y.Wi) || !al16(y.Wh)) return "weight rows must be 16-byte aligned (ldw % 4 == 0)";
+    const long long K = k == 0 ? K1 : a->H;
+    if (y.ldwi < ((K + 3) & ~3ll) || y.ldwh < a->H) return "ldwi >= the layer's input width rounded up to 4, ldwh >= H";
+    if (!al4(y.bh)) return "float pointers must be 4-byte aligned";
+  }
+  if ((a->ldwp & 3) || !al16(a->Wp)) return "weight rows must be 16-byte aligned (ldw % 4 == 0)";
+  if (a->ldwp < a->H) return "ldwp >= H";
+  if (a->ld < a->L * a->H) return "the carry's ld >= L * H";
+  if (a->logits && a->ldl < 2 * a->A) return "ldl >= 2A";
+  return nullptr;
+}
+
 template <int H>
 static int launch_fwd(const LstmFwd &P, hipStream_t s) {
   hipLaunchKernelGGL(k_lstm_fwd<H>, dim3((P.rows + LSTM_RB - 1) / LSTM_RB), dim3(LSTM_NT), 0, s, P);
@@ -72,6 +105,27 @@ int tmjx_lstm_seq_fwd(const tmjx_lstm_fwd_t *a, void *stream) {
     case 128: return launch_fwd<128>(P, s);
     default: return launch_fwd<256>(P, s);
   }
+}
+
+int tmjx_lstm_decoder_act_ok(const tmjx_lstm_decoder_act_t *a) { return decoder_act_why(a) == nullptr; }
+int tmjx_lstm_decoder_act(const tmjx_lstm_decoder_act_t *a, void *stream) {
+  if (const char *why = decoder_act_why(a)) return fail(TMJX_EINVAL, std::string("tmjx_lstm_decoder_act: ") + why);
+  LstmDecAct P{};
+  P.lat = a->latents; P.ldz = a->ldz; P.obs = a->obs; P.s0 = a->obs_s0; P.s1 = a->obs_s1; P.mean = a->mean; P.stdv = a->std; P.reset = a->reset;
+  P.ref_w = a->ref_w; P.Z = a->Z; P.prop = a->obs_w - a->ref_w; P.M = a->n; P.L = a->L;
+  for (int k = 0; k < a->L; k++) P.l[k] = LstmDecLayer{a->layer[k].Wi, a->layer[k].Wh, a->layer[k].bh, a->layer[k].ldwi, a->layer[k].ldwh};
+  P.Wp = a->Wp; P.bp = a->bp; P.ldwp = a->ldwp; P.A = a->A;
+  P.h = a->h; P.c = a->c; P.ld = a->ld;
+  P.action_t = a->action_t; P.ctrl = a->ctrl; P.logits = a->logits; P.ldl = a->ldl;
+  constexpr size_t lds = sizeof(float) * (size_t)LDA_LDS_FLOATS;
+  static bool attr_set = false;            // > 64 KiB of dynamic LDS needs the attribute once per kernel
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute((const void *)k_lstm_decoder_act, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return fail(TMJX_EHIP, std::string("hipFuncSetAttribute(k_lstm_decoder_act): ") + hipGetErrorString(e));
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(k_lstm_decoder_act, dim3((P.M + LDA_BM - 1) / LDA_BM), dim3(LDA_NT), lds, (hipStream_t)stream, P);
+  return check_launch("k_lstm_decoder_act");
 }
 
 int tmjx_lstm_seq_bwd(const tmjx_lstm_bwd_t *a, void *stream) {

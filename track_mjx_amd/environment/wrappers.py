@@ -13,6 +13,8 @@ switches the handle to the align done-policy (include/tmjx.h: tmjx_set_done_poli
 HighLevelWrapper (wrappers.py:384-412) puts a pretrained decoder INSIDE the env: step(state, latents) takes an intention vector per env instead of
 joint controls.  With a DecoderPolicy (agent/checkpoint.py: make_decoder_policy_fn) the decoder runs as launches on the env's own device buffers —
 one fused launch (include/tmjx.h: tmjx_decoder_act) where the decoder qualifies, else the roll-out policy step's decoder half, layer by layer.
+With an LSTMDecoderPolicy (make_lstm_decoder_policy_fn) the wrapper also owns the decoder's carry (h, c) [n, L, H]; the launches are the LSTM
+roll-out step's decoder half, or one tmjx_lstm_decoder_act launch.
 """
 from __future__ import annotations
 
@@ -198,6 +200,108 @@ def decoder_act_why_not(dp, obs_w: int, n: int = 1) -> str | None:
     return L.tmjx_last_error().decode()
 
 
+class _LSTMDecoderStep:
+    """_DecoderStep for an LSTMDecoderPolicy: the carry h, c [n, L, H] lives here and is updated in place by the launches; `reset` (the env's done
+    buffer [n], or None) zeroes a row's carry of every layer before the step.
+
+    path "layers": tmjx_decoder_input -> per layer tmjx_linear_nolds (x W_i^T) + tmjx_lstm_seq_fwd (T = 1) -> tmjx_linear_nolds (projection) ->
+    tmjx_action_mode: the decoder half of analysis.rollout._PolicyStep's LSTM branch — its kernels, operand layouts and therefore its bits.
+    path "fused": one tmjx_lstm_decoder_act launch."""
+
+    def __init__(self, dp, n: int, obs_soa, path: str, reset=None):
+        import torch
+        from .. import hip as _hip
+        self._hip, self.L = _hip, _hip.lib()
+        dev = dp.device
+        self.n, self.path = int(n), path
+        Z, prop, A, ref = dp.latent_size, dp.proprioceptive_obs_size, dp.action_size, dp.reference_obs_size
+        Lk, H = dp.hidden_layer_num, dp.hidden_state_size
+        W = int(obs_soa.shape[0])
+        self.Z, self.A = Z, A
+        f32 = dict(dtype=torch.float32, device=dev)
+        p = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+        self.mean = self.std = None
+        if dp.mean is not None:
+            self.mean, self.std = torch.zeros(W, **f32), torch.ones(W, **f32)
+            self.mean[ref:].copy_(dp.mean); self.std[ref:].copy_(dp.std)
+        self.h, self.c = torch.zeros((n, Lk, H), **f32), torch.zeros((n, Lk, H), **f32)
+        self.ctrl = torch.empty((n, A), **f32)
+        self.action_t = torch.empty((A, n), **f32)
+        self.keep = [reset]
+
+        def pad(w):          # [N][ceil4(K)] fp32 copy with zero pad columns: 16-byte aligned rows for the matrix-core kernels
+            N, K = w.shape
+            buf = torch.zeros((N, _ceil4(K)), **f32)
+            buf[:, :K].copy_(w.detach())
+            self.keep.append(buf)
+            return buf
+
+        self.calls = []
+        wis, whs = [pad(w) for w in dp.w_ih], [w.detach().contiguous() for w in dp.w_hh]
+        wp = pad(dp.w_p)
+        self.keep += whs
+        if path == "fused":
+            d = self.desc = _hip.LstmDecoderAct()
+            d.obs, d.obs_s0, d.obs_s1, d.mean, d.std, d.reset = p(obs_soa), 1, n, p(self.mean), p(self.std), p(reset)
+            d.n, d.Z, d.obs_w, d.ref_w, d.L, d.H = n, Z, W, ref, Lk, H
+            for k in range(Lk):
+                y = d.layer[k]
+                y.Wi, y.Wh, y.bh, y.ldwi, y.ldwh = p(wis[k]), p(whs[k]), p(dp.b_hh[k]), wis[k].shape[1], H
+            d.Wp, d.bp, d.ldwp, d.A = p(wp), p(dp.b_p), wp.shape[1], A
+            d.h, d.c, d.ld = p(self.h), p(self.c), Lk * H
+            d.action_t, d.ctrl, d.logits, d.ldl = p(self.action_t), p(self.ctrl), None, 0
+        else:
+            self.x = torch.zeros((n, _ceil4(Z + prop)), **f32)
+            self.xg = torch.empty((n, 4 * H), **f32)
+            self.calls.append(["tmjx_decoder_input", [None, None, p(obs_soa), 1, n, p(self.mean), p(self.std), p(self.x), self.x.shape[1], n, Z, W, ref]])
+            a, lda = self.x, self.x.shape[1]
+            for k in range(Lk):
+                self.calls.append(["tmjx_linear_nolds", [p(a), lda, 1, p(wis[k]), None, p(self.xg), n, 4 * H, wis[k].shape[1]]])
+                hk, ck = self.h[:, k], self.c[:, k]
+                args = _hip.LstmFwd(p(self.xg), 4 * H, p(whs[k]), H, p(dp.b_hh[k]), p(hk), p(ck), Lk * H, p(reset), n, p(hk), p(ck), Lk * H, None, None, 1, n, H)
+                self.keep.append(args)
+                self.calls.append(["tmjx_lstm_seq_fwd", [C.byref(args)]])
+                a, lda = hk, Lk * H
+            self.logits = torch.empty((n, 2 * A), **f32)
+            self.calls.append(["tmjx_linear_nolds", [p(a), lda, 1, p(wp), p(dp.b_p), p(self.logits), n, 2 * A, wp.shape[1]]])
+            self.calls.append(["tmjx_action_mode", [p(self.logits), 2 * A, p(self.ctrl), p(self.action_t), n, A]])
+
+    def launch(self, lat_ptr: int, ldz: int, stream) -> None:
+        """The decoder's launches on `stream` (ctypes calls only: no torch operation)."""
+        L, check = self.L, self._hip.check
+        if self.path == "fused":
+            self.desc.latents, self.desc.ldz = lat_ptr, ldz
+            check(L.tmjx_lstm_decoder_act(C.byref(self.desc), stream), "tmjx_lstm_decoder_act")
+            return
+        first = self.calls[0][1]
+        first[0], first[1] = lat_ptr, ldz
+        for name, args in self.calls:
+            check(getattr(L, name)(*args, stream), name)
+
+
+def lstm_decoder_act_why_not(dp, obs_w: int, n: int = 1) -> str | None:
+    """None if the fused launch (tmjx_lstm_decoder_act) runs this LSTM decoder, else the library's reason (tmjx_lstm_decoder_act_ok on a descriptor of
+    its shapes)."""
+    from .. import hip as _hip
+    a = 1 << 20                  # a non-null, 16-byte aligned dummy address: the check reads shapes and alignments, never memory
+    d = _hip.LstmDecoderAct()
+    Lk, H = dp.hidden_layer_num, dp.hidden_state_size
+    d.latents, d.ldz, d.obs, d.obs_s0, d.obs_s1 = a, dp.latent_size, a, 1, n
+    d.n, d.Z, d.obs_w, d.ref_w, d.L, d.H = n, dp.latent_size, int(obs_w), dp.reference_obs_size, Lk, H
+    k = dp.latent_size + dp.proprioceptive_obs_size
+    for i in range(min(Lk, _hip.LSTM_DECODER_MAX_LAYERS)):
+        y = d.layer[i]
+        y.Wi, y.Wh, y.bh, y.ldwi, y.ldwh = a, a, a, _ceil4(k), H
+        k = H
+    d.Wp, d.bp, d.ldwp, d.A = a, a, _ceil4(H), dp.action_size
+    d.h, d.c, d.ld, d.action_t = a, a, Lk * H, a
+    L = _hip.lib()
+    if L.tmjx_lstm_decoder_act_ok(C.byref(d)) == 1:
+        return None
+    L.tmjx_lstm_decoder_act(C.byref(d), None)          # (refused before any device call: records the reason)
+    return L.tmjx_last_error().decode()
+
+
 class HighLevelWrapper:
     """step(state, latents): the decoder's action on concat([latents, state.obs[..., reference_obs_size:]]) drives the wrapped env
     (wrappers.py:384-412); reset and everything else are the wrapped env's, so it composes with wrap / AutoAlignWrapperTracking /
@@ -207,15 +311,25 @@ class HighLevelWrapper:
     calls only (no torch op, no allocation, no host synchronisation) and returns the same State object, whose tensors are views of the buffers
     the kernels update in place.  `path`: "fused" (one tmjx_decoder_act launch; ValueError if the decoder does not qualify), "layers" (the
     roll-out policy step's decoder half, any decoder shape), "auto" (fused where tmjx_decoder_act_ok says so AND AUTO_PREFERS_FUSED, else layers).
-    Any other callable fn(x) -> (action, extras) is called on the torch concat, as the reference does."""
+    Any other callable fn(x) -> (action, extras) is called on the torch concat, as the reference does.
+
+    An LSTMDecoderPolicy (agent.checkpoint.make_lstm_decoder_policy_fn) runs the same way; the wrapper then owns its carry (h, c) [n, L, H]: zeroed
+    by reset(), read with `hidden_state`, set with set_hidden_state(h, c).  reset_carry_on_done (LSTMAutoResetWrapperTracking's semantics, what the
+    roll-out's policy step does under align_on_fail): the env's done flags of the previous step go to the decoder as `reset`, so an env that ended
+    and was reset or aligned starts from a zero carry; False: the carry is never reset by the wrapper.  "layers" is the LSTM roll-out step's decoder
+    half, "fused" one tmjx_lstm_decoder_act launch, "auto" follows AUTO_PREFERS_FUSED_LSTM."""
 
     # "auto" takes the fused launch only once tools/decoder_act_bench.py has shown it faster than the layer-by-layer list at 4 096 AND 8 192 envs by
     # more than the spread of the alternating repeats (DESIGN.md §7).  That measurement has not been taken yet: "auto" means "layers", the fused
     # launch is selected with path="fused"
     AUTO_PREFERS_FUSED = False
+    # the same rule for the LSTM decoder's fused launch, and that measurement HAS been taken (tools/lstm_decoder_act_bench.py,
+    # profiles/lstm_decoder_act_bench.txt, DESIGN.md §7): 94.2 against 114.1 us per decoder step at 4 096 envs and 101.6 against 192.6 at 8 192,
+    # the alternating repeats within 0.2 us of each other — "auto" takes tmjx_lstm_decoder_act where tmjx_lstm_decoder_act_ok says so
+    AUTO_PREFERS_FUSED_LSTM = True
 
-    def __init__(self, env, decoder_inference_fn, reference_obs_size: int, path: str = "auto"):
-        from ..agent.checkpoint import DecoderPolicy
+    def __init__(self, env, decoder_inference_fn, reference_obs_size: int, path: str = "auto", reset_carry_on_done: bool = True):
+        from ..agent.checkpoint import DecoderPolicy, LSTMDecoderPolicy
         if path not in ("auto", "fused", "layers"):
             raise ValueError(f"HighLevelWrapper: path must be 'auto', 'fused' or 'layers', not {path!r}")
         if not callable(decoder_inference_fn):
@@ -226,7 +340,10 @@ class HighLevelWrapper:
             raise ValueError(f"HighLevelWrapper: reference_obs_size {self._ref} outside the observation's {W} columns")
         self._step = self._state = None
         self.path = "callable"
-        if isinstance(decoder_inference_fn, DecoderPolicy):
+        self._lstm = isinstance(decoder_inference_fn, LSTMDecoderPolicy)
+        self.reset_carry_on_done = bool(reset_carry_on_done)
+        self._h = self._c = None              # the callable path's carry (the device paths keep theirs in the launch list's buffers)
+        if isinstance(decoder_inference_fn, (DecoderPolicy, LSTMDecoderPolicy)):
             dp = decoder_inference_fn
             if dp.reference_obs_size != self._ref:
                 raise ValueError(f"HighLevelWrapper: reference_obs_size={self._ref}, but the decoder policy was built for {dp.reference_obs_size}")
@@ -237,10 +354,15 @@ class HighLevelWrapper:
             self._Z = dp.latent_size
             import torch
             if hasattr(env, "obs_buf") and dp.device.type == "cuda" and _same_device(env.device, dp.device):
-                why = decoder_act_why_not(dp, W, int(env.num_envs))
+                if self._lstm:
+                    why = lstm_decoder_act_why_not(dp, W, int(env.num_envs))
+                    shape, prefers = f"LSTM decoder (L = {dp.hidden_layer_num}, H = {dp.hidden_state_size})", self.AUTO_PREFERS_FUSED_LSTM
+                else:
+                    why = decoder_act_why_not(dp, W, int(env.num_envs))
+                    shape, prefers = f"decoder {list(dp.decoder_layer_sizes)}", self.AUTO_PREFERS_FUSED
                 if path == "fused" and why is not None:
-                    raise ValueError(f"HighLevelWrapper: path='fused' does not run this decoder {list(dp.decoder_layer_sizes)}: {why}")
-                self.path = "fused" if path == "fused" or (path == "auto" and why is None and self.AUTO_PREFERS_FUSED) else "layers"
+                    raise ValueError(f"HighLevelWrapper: path='fused' does not run this {shape}: {why}")
+                self.path = "fused" if path == "fused" or (path == "auto" and why is None and prefers) else "layers"
             elif path != "auto":
                 raise ValueError(f"HighLevelWrapper: path={path!r} needs the decoder policy on the env's device ({getattr(env, 'device', None)}), it is on {dp.device}")
         else:
@@ -264,7 +386,44 @@ class HighLevelWrapper:
 
     def reset(self, *a, **kw):
         self._state = None
+        self._h = self._c = None
+        if self._lstm and self._step is not None:
+            self._step.h.zero_(); self._step.c.zero_()
         return self.env.reset(*a, **kw)
+
+    def _carry(self):
+        if not self._lstm:
+            raise TypeError("HighLevelWrapper: only an LSTMDecoderPolicy carries a hidden state")
+        if self.path == "callable":
+            if self._h is None:
+                self._h, self._c = self._fn.zero_carry(int(self.env.num_envs), getattr(self.env, "device", None))
+            return self._h, self._c
+        if self._step is None:
+            self._make_step()
+        return self._step.h, self._step.c
+
+    @property
+    def hidden_state(self):
+        """(h, c) [n, L, H] of the LSTM decoder: views of the buffers the next step reads and overwrites."""
+        return self._carry()
+
+    def set_hidden_state(self, h, c) -> None:
+        hh, cc = self._carry()
+        if tuple(h.shape) != tuple(hh.shape) or tuple(c.shape) != tuple(cc.shape):
+            raise ValueError(f"HighLevelWrapper.set_hidden_state: h and c must be {tuple(hh.shape)}")
+        hh.copy_(h); cc.copy_(c)
+
+    def _make_step(self) -> None:
+        import torch
+        env, n = self.env, int(self.env.num_envs)
+        with torch.cuda.device(env.device):
+            if self._lstm:
+                self._step = _LSTMDecoderStep(self._fn, n, env.obs_buf, self.path, env.done_buf if self.reset_carry_on_done else None)
+            else:
+                self._step = _DecoderStep(self._fn, n, env.obs_buf, self.path)
+        p = lambda t: t.data_ptr()      # noqa: E731
+        self._env_args = (env._handle, p(env.state_buf), p(env.istate_buf), p(self._step.action_t), p(env.obs_buf), p(env.reward_buf), p(env.done_buf),
+                          p(env.trunc_buf), p(env.metrics_buf), p(env.workspace), n)
 
     def _check_latents(self, latents):
         n = int(self.env.num_envs)
@@ -279,7 +438,11 @@ class HighLevelWrapper:
         if self.path == "callable":
             import torch
             x = torch.cat([latents.to(state.obs.device), state.obs[..., self._ref:]], dim=-1)
-            action, _ = self._fn(x)
+            if self._lstm:
+                done = getattr(state, "done", None) if self.reset_carry_on_done else None
+                action, _, (self._h, self._c) = self._fn(x, hidden_state=self._carry(), reset=done)
+            else:
+                action, _ = self._fn(x)
             return env.step(state, action)
         import torch
         if latents.device.type != "cuda" or (latents.device.index is not None and self._fn.device.index is not None
@@ -289,11 +452,7 @@ class HighLevelWrapper:
             latents = latents.to(torch.float32).contiguous()
         n = int(env.num_envs)
         if self._step is None:
-            with torch.cuda.device(env.device):
-                self._step = _DecoderStep(self._fn, n, env.obs_buf, self.path)
-            p = lambda t: t.data_ptr()      # noqa: E731
-            self._env_args = (env._handle, p(env.state_buf), p(env.istate_buf), p(self._step.action_t), p(env.obs_buf), p(env.reward_buf), p(env.done_buf),
-                              p(env.trunc_buf), p(env.metrics_buf), p(env.workspace), n)
+            self._make_step()
         if self._state is None:
             self._state = env._state()
         if getattr(env, "_physics_events", None) is not None:

@@ -43,7 +43,7 @@ EXPORTS = ("tmjx_model_create", "tmjx_model_destroy", "tmjx_layout", "tmjx_clips
            "tmjx_chain_rows", "tmjx_chain_fwd_ok", "tmjx_chain_fwd", "tmjx_chain_bwd_ok", "tmjx_chain_bwd",
            "tmjx_lstm_hidden_ok", "tmjx_lstm_seq_fwd", "tmjx_lstm_seq_bwd",
            "tmjx_record_check", "tmjx_record_step", "tmjx_latent_concat_det", "tmjx_action_mode",
-           "tmjx_decoder_input", "tmjx_decoder_act_ok", "tmjx_decoder_act",
+           "tmjx_decoder_input", "tmjx_decoder_act_ok", "tmjx_decoder_act", "tmjx_lstm_decoder_act_ok", "tmjx_lstm_decoder_act",
            "tmjx_sensor_info", "tmjx_physics_sensors", "tmjx_step_sensors",
            "tmjx_set_done_policy", "tmjx_clips_upload_velocities", "tmjx_set_env_scales",
            "tmjx_debug_rows", "tmjx_last_error", "tmjx_version")
@@ -111,6 +111,23 @@ class DecoderAct(C.Structure):
                 ("std", C.c_void_p), ("n", C.c_int32), ("Z", C.c_int32), ("obs_w", C.c_int32), ("ref_w", C.c_int32), ("n_blocks", C.c_int32),
                 ("block", DecoderBlock * CHAIN_MAX_HIDDEN), ("Wf", C.c_void_p), ("bf", C.c_void_p), ("ldwf", C.c_int32), ("A", C.c_int32), ("eps", C.c_float),
                 ("action_t", C.c_void_p), ("ctrl", C.c_void_p), ("logits", C.c_void_p), ("ldl", C.c_int32)]
+
+
+LSTM_DECODER_MAX_LAYERS = 4  # TMJX_LSTM_DECODER_MAX_LAYERS (include/tmjx.h)
+
+
+class LstmDecoderLayer(C.Structure):
+    """tmjx_lstm_decoder_layer_t (include/tmjx.h)."""
+    _fields_ = [(k, C.c_void_p) for k in ("Wi", "Wh", "bh")] + [("ldwi", C.c_int32), ("ldwh", C.c_int32)]
+
+
+class LstmDecoderAct(C.Structure):
+    """tmjx_lstm_decoder_act_t (include/tmjx.h)."""
+    _fields_ = [("latents", C.c_void_p), ("ldz", C.c_int32), ("obs", C.c_void_p), ("obs_s0", C.c_int64), ("obs_s1", C.c_int64), ("mean", C.c_void_p),
+                ("std", C.c_void_p), ("reset", C.c_void_p), ("n", C.c_int32), ("Z", C.c_int32), ("obs_w", C.c_int32), ("ref_w", C.c_int32), ("L", C.c_int32),
+                ("H", C.c_int32), ("layer", LstmDecoderLayer * LSTM_DECODER_MAX_LAYERS), ("Wp", C.c_void_p), ("bp", C.c_void_p), ("ldwp", C.c_int32),
+                ("A", C.c_int32), ("h", C.c_void_p), ("c", C.c_void_p), ("ld", C.c_int32), ("action_t", C.c_void_p), ("ctrl", C.c_void_p),
+                ("logits", C.c_void_p), ("ldl", C.c_int32)]
 
 
 class ChainBwdStage(C.Structure):
@@ -363,6 +380,8 @@ def load(path: Path):
     sig.setdefault("tmjx_decoder_input", [None, None])[0] = [fp, C.c_int, fp, C.c_int64, C.c_int64, fp, fp, fp, C.c_int] + [C.c_int] * 4 + [vp]
     sig.setdefault("tmjx_decoder_act_ok", [None, None])[0] = [C.POINTER(DecoderAct)]
     sig.setdefault("tmjx_decoder_act", [None, None])[0] = [C.POINTER(DecoderAct), vp]
+    sig.setdefault("tmjx_lstm_decoder_act_ok", [None, None])[0] = [C.POINTER(LstmDecoderAct)]
+    sig.setdefault("tmjx_lstm_decoder_act", [None, None])[0] = [C.POINTER(LstmDecoderAct), vp]
     sig.setdefault("tmjx_debug_rows", [None, None])[0] = [vp, C.c_char_p, ip, ip]
     sig.setdefault("tmjx_last_error", [None, None])[1] = C.c_char_p
     sig.setdefault("tmjx_version", [None, None])[1] = C.c_char_p
