@@ -248,6 +248,24 @@ def test_lstm_decoder_act_validates_before_it_launches():
         assert b"tmjx_lstm_decoder_act" in err and word in err, (word, err)
 
 
+def test_both_decoder_launches_refuse_a_common_fault_with_the_same_words():
+    """The checks the two descriptors share (csrc/decoder_io.h): one fault in an otherwise valid descriptor, the same reason behind either name."""
+    from tests.test_highlevel_cpu import _desc as _mlp_desc
+    L = hip.lib()
+    faults = ((dict(std=None), b"mean and std together"), (dict(ldz=59), b"ldz >= Z"), (dict(ref_w=697), b"obs_w >= ref_w"),
+              (dict(Z=95), b"at most 320"), (dict(A=65), b"2A <= 128"), (dict(ldl=75), b"ldl >= 2A"))
+    assert _desc(Z=95).Z + 696 - 470 == 321 and _desc(A=65).A * 2 == 130 and _desc().logits and _mlp_desc().logits
+    for over, word in faults:
+        reasons = []
+        for name, d in (("tmjx_decoder_act", _mlp_desc(**over)), ("tmjx_lstm_decoder_act", _desc(**over))):
+            assert getattr(L, name + "_ok")(C.byref(d)) == 0, (name, over)
+            assert getattr(L, name)(C.byref(d), None) == -22, (name, over)
+            err = L.tmjx_last_error()
+            assert err.startswith(name.encode() + b": "), err
+            reasons.append(err[len(name) + 2:])
+        assert reasons[0] == reasons[1] and word in reasons[0], (over, reasons)
+
+
 def test_wrapper_reports_why_an_lstm_decoder_does_not_qualify():
     from track_mjx_amd.agent import checkpoint as ck
     from track_mjx_amd.environment.wrappers import lstm_decoder_act_why_not

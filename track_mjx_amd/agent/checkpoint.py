@@ -617,51 +617,42 @@ def decoder_policy_from_trees(norm: dict | None, ptree: dict, normalize_observat
         raise ValueError("make_decoder_policy_fn: params/decoder has no hidden_<i> layer")
     if "encoder" not in p or "fc2_mean" not in p["encoder"]:
         raise ValueError("make_decoder_policy_fn: the intention size is read from params/encoder/fc2_mean, which the checkpoint does not have")
-    Z = int(np.asarray(p["encoder"]["fc2_mean"]["kernel"]).shape[1])
     sizes = [int(np.asarray(dec[f"hidden_{i}"]["kernel"]).shape[1]) for i in range(n_dec)]
     A2 = int(np.asarray(dec[f"hidden_{n_dec}"]["kernel"]).shape[1])
     in0 = int(np.asarray(dec["hidden_0"]["kernel"]).shape[0])
-    prop = in0 - Z
-    if prop < 0 or A2 % 2:
-        raise ValueError(f"make_decoder_policy_fn: decoder input width {in0} < intention size {Z}, or an odd head width {A2}")
-    if norm is None or "mean" not in norm:
-        raise ValueError("make_decoder_policy_fn: the checkpoint has no normaliser (its width gives reference_obs_size)")
-    W = int(np.asarray(norm["mean"]).shape[-1])
-    ref = W - prop
-    if ref < 0:
-        raise ValueError(f"make_decoder_policy_fn: the normaliser has {W} columns, fewer than the decoder's {prop} proprioceptive inputs")
     dev = torch.device(device)
+    Z, ref, mean, std = _decoder_sizes_and_norm("make_decoder_policy_fn", p, norm, in0, A2, normalize_observations, dev)
     net = DecoderNet(in0, A2 // 2, sizes).to(dev).float().eval()
     for q in net.parameters():
         q.requires_grad_(False)
     decoder_from_flax(net, dec)
+    return DecoderPolicy(net, mean, std, Z, ref, trained_gemm_inputs)
+
+
+def _decoder_sizes_and_norm(who: str, p: dict, norm: dict | None, in0: int, A2: int, normalize_observations: bool, dev) -> tuple:
+    """(Z, reference_obs_size, mean, std) of a decoder-only policy whose first layer takes `in0` columns and whose head has `A2`: Z = fc2_mean's
+    width, proprioceptive width = in0 - Z, reference_obs_size = the normaliser's width - that; mean / std: the normaliser's columns
+    [reference_obs_size:] on `dev`, or None without normalize_observations."""
+    Z = int(np.asarray(p["encoder"]["fc2_mean"]["kernel"]).shape[1])
+    prop = in0 - Z
+    if prop < 0 or A2 % 2:
+        raise ValueError(f"{who}: decoder input width {in0} < intention size {Z}, or an odd head width {A2}")
+    if norm is None or "mean" not in norm:
+        raise ValueError(f"{who}: the checkpoint has no normaliser (its width gives reference_obs_size)")
+    W = int(np.asarray(norm["mean"]).shape[-1])
+    ref = W - prop
+    if ref < 0:
+        raise ValueError(f"{who}: the normaliser has {W} columns, fewer than the decoder's {prop} proprioceptive inputs")
     mean = std = None
     if normalize_observations:
-        mean = torch.as_tensor(np.asarray(norm["mean"], dtype=np.float32).reshape(-1)[ref:].copy(), device=dev).contiguous()
-        std = torch.as_tensor(np.asarray(norm["std"], dtype=np.float32).reshape(-1)[ref:].copy(), device=dev).contiguous()
-    return DecoderPolicy(net, mean, std, Z, ref, trained_gemm_inputs)
+        mean, std = (torch.as_tensor(np.asarray(norm[k], dtype=np.float32).reshape(-1)[ref:].copy(), device=dev).contiguous() for k in ("mean", "std"))
+    return Z, ref, mean, std
 
 
 def make_decoder_policy_fn(ckpt_path, step: int | None = None, device="cuda") -> DecoderPolicy:
     """The decoder-only inference function of a checkpoint (ppo_networks.py:193-238): a run directory (latest step, or `step`), a step directory, or
     a .npz of save_npz.  normalize_observations=false in the saved config means no normaliser."""
-    import json
-    import os
-    path = str(ckpt_path)
-    if os.path.isdir(path):
-        d = resolve_step_dir(path, step)
-        norm, ptree = load_policy(d)
-        meta = os.path.join(d, "config", "metadata")
-        cfg = {}
-        if os.path.exists(meta):
-            with open(meta) as f:
-                cfg = json.load(f) or {}
-    else:
-        if step is not None:
-            raise ValueError("make_decoder_policy_fn: `step` selects a step of a checkpoint directory; a .npz file holds one policy")
-        norm, ptree, _ = load_freeze_source(path)
-        with np.load(path) as z:
-            cfg = json.loads(bytes(z["config_json"]).decode()) if "config_json" in z.files else {}
+    norm, ptree, cfg = _policy_trees_and_config(ckpt_path, step, "make_decoder_policy_fn")
     tc = (cfg.get("train_setup") or {}).get("train_config") or {}
     gi = "bf16" if str(cfg.get("mlp_gemm_inputs", "f32")).lower() in ("bf16", "bfloat16") else "f32"
     return decoder_policy_from_trees(norm, ptree, bool(tc.get("normalize_observations", True)), device, gi)
@@ -749,20 +740,11 @@ def lstm_decoder_policy_from_trees(norm: dict | None, ptree: dict, normalize_obs
         raise ValueError(f"{who}: params/lstm_decoder has no lstm_projection")
     if "encoder" not in p or "fc2_mean" not in p["encoder"]:
         raise ValueError(f"{who}: the intention size is read from params/encoder/fc2_mean, which the checkpoint does not have")
-    Z = int(np.asarray(p["encoder"]["fc2_mean"]["kernel"]).shape[1])
     H = int(np.asarray(dec["lstm_0"]["hi"]["kernel"]).shape[0])
     in0 = int(np.asarray(dec["lstm_0"]["ii"]["kernel"]).shape[0])
     A2 = int(np.asarray(dec["lstm_projection"]["kernel"]).shape[1])
-    prop = in0 - Z
-    if prop < 0 or A2 % 2:
-        raise ValueError(f"{who}: decoder input width {in0} < intention size {Z}, or an odd head width {A2}")
-    if norm is None or "mean" not in norm:
-        raise ValueError(f"{who}: the checkpoint has no normaliser (its width gives reference_obs_size)")
-    W = int(np.asarray(norm["mean"]).shape[-1])
-    ref = W - prop
-    if ref < 0:
-        raise ValueError(f"{who}: the normaliser has {W} columns, fewer than the decoder's {prop} proprioceptive inputs")
     dev = torch.device(device)
+    Z, ref, mean, std = _decoder_sizes_and_norm(who, p, norm, in0, A2, normalize_observations, dev)
     t = lambda a: torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=np.float32)), device=dev).contiguous()      # noqa: E731
     w_ih, w_hh, b_hh = [], [], []
     for k in range(L):
@@ -777,10 +759,6 @@ def lstm_decoder_policy_from_trees(norm: dict | None, ptree: dict, normalize_obs
     w_p, b_p = t(np.asarray(proj["kernel"]).T), t(np.asarray(proj["bias"]).reshape(-1))
     if w_p.shape != (A2, H):
         raise ValueError(f"{who}: lstm_projection takes {w_p.shape[1]} inputs, the cells have {H} hidden units")
-    mean = std = None
-    if normalize_observations:
-        mean = t(np.asarray(norm["mean"], dtype=np.float32).reshape(-1)[ref:])
-        std = t(np.asarray(norm["std"], dtype=np.float32).reshape(-1)[ref:])
     return LSTMDecoderPolicy(w_ih, w_hh, b_hh, w_p, b_p, mean, std, Z, ref, trained_gemm_inputs)
 
 

@@ -48,20 +48,13 @@ import torch
 
 from .. import hip as _hip
 from .. import jax_random as _jr
+from ..agent.launch_list import LaunchList, ceil4 as _ceil4, ptr as _p
 from ..environment.task import METRIC_NAMES
 
 # logging_config.rollout_metrics of rodent-full-clips.yaml:97-113 (the default when a config has no logging_config)
 ROLLOUT_METRICS = ("pos_reward", "quat_reward", "joint_reward", "angvel_reward", "bodypos_reward", "endeff_reward", "summed_pos_distance",
                    "joint_distance", "quat_distance", "ctrl_cost", "ctrl_diff_cost", "energy_cost", "too_far", "bad_pose", "bad_quat", "fall")
 CLIPS_PER_BATCH = 1024
-
-
-def _ceil4(n: int) -> int:
-    return (int(n) + 3) // 4 * 4
-
-
-def _p(t) -> int | None:
-    return None if t is None else t.data_ptr()
 
 
 # ---------------------------------------------------------------------------------------------------------------- environment
@@ -161,104 +154,41 @@ class _PolicyStep:
             torch.reciprocal(self.std[:ref], out=self.fold_inv[:ref])
         else:
             self.fold_inv[:ref].fill_(1.0)
-        self._padded = {}
-        self.calls = []                     # (entry point, args) of the step, in launch order
+        ll = self.ll = LaunchList(n, dev)      # the step's calls in launch order (agent/launch_list.py: the decoder half is HighLevelWrapper's too)
         self.acts = {"encoder": {}}         # activation name -> (buffer, column offset, width, leading dimension)
-        h, first = None, True
+        h = None
         for i, blk in enumerate(pol.encoder):
-            if first:
-                y = self._block(self.stage, W, blk, norm=True)
-            else:
-                y = self._block(h, h.shape[1], blk)
-            self.acts["encoder"][f"layer_{i}"] = (y, 0, y.shape[1], y.shape[1])
-            h, first = y, False
-        self.fc2 = self._linear(h, h.shape[1], pol.fc2, bias=True)
+            h = ll.block(self.stage, W, blk, fold=(self.fold_mean, self.fold_inv)) if i == 0 else ll.block(h, h.shape[1], blk)
+            self.acts["encoder"][f"layer_{i}"] = (h, 0, h.shape[1], h.shape[1])
+        self.fc2 = ll.linear(h, h.shape[1], pol.fc2.weight, pol.fc2.bias)
         self.acts["encoder"]["mean"] = (self.fc2, 0, Z, 2 * Z)
         self.acts["encoder"]["logvar"] = (self.fc2, Z, Z, 2 * Z)
         prop = W - ref
         self.x = torch.zeros((n, _ceil4(Z + prop)), **f32)
         self.traj = torch.zeros((n, Kp), **f32)
-        self.calls.append(("tmjx_latent_concat_det", (_p(self.fc2), 2 * Z, _p(self.stage), W, 1, _p(self.mean), _p(self.std), _p(self.x), self.x.shape[1],
-                                                      _p(self.traj), self.traj.shape[1], n, Z, W, ref)))
+        ll.call("tmjx_latent_concat_det", _p(self.fc2), 2 * Z, _p(self.stage), W, 1, _p(self.mean), _p(self.std), _p(self.x), self.x.shape[1],
+                _p(self.traj), self.traj.shape[1], n, Z, W, ref)
         if rp.model == "lstm":
             Lk, H = pol.hidden_layer_num, pol.hidden_state_size
             self.h, self.c = torch.zeros((n, Lk, H), **f32), torch.zeros((n, Lk, H), **f32)
-            self.xg = torch.empty((n, 4 * H), **f32)
-            a, lda = self.x, self.x.shape[1]
-            for k in range(Lk):
-                wi = self._pad(pol.w_ih[k])
-                self.calls.append(("tmjx_linear_nolds", (_p(a), lda, 1, _p(wi), None, _p(self.xg), n, 4 * H, wi.shape[1])))
-                hk, ck = self.h[:, k], self.c[:, k]
-                wh = pol.w_hh[k].detach().contiguous()
-                self._keep(wh)
-                args = _hip.LstmFwd(_p(self.xg), 4 * H, _p(wh), H, _p(pol.b_hh[k]), _p(hk), _p(ck), Lk * H, _p(carry_reset), n, _p(hk), _p(ck), Lk * H, None, None, 1, n, H)
-                self._keep(args)
-                self.calls.append(("tmjx_lstm_seq_fwd", (C.byref(args),)))
-                a, lda = hk, Lk * H
-            self.logits = self._linear_raw(a, lda, pol.projection, bias=True)
+            _, self.logits, self.ctrl, self.action_t = ll.decoder(self.x, (), pol.projection.weight, pol.projection.bias,
+                                                                  lstm=(pol.w_ih, pol.w_hh, pol.b_hh, self.h, self.c, carry_reset))
             self.acts["decoder"] = {"lstm_projection": (self.logits, 0, 2 * A, 2 * A)}
         else:
-            h = self.x
-            self.acts["decoder"] = {}
-            for i, blk in enumerate(pol.decoder):
-                h = self._block(h, h.shape[1], blk)
-                self.acts["decoder"][f"layer_{i}"] = (h, 0, h.shape[1], h.shape[1])
-            self.logits = self._linear(h, h.shape[1], pol.head, bias=True)
+            ys, self.logits, self.ctrl, self.action_t = ll.decoder(self.x, pol.decoder, pol.head.weight, pol.head.bias)
+            self.acts["decoder"] = {f"layer_{i}": (y, 0, y.shape[1], y.shape[1]) for i, y in enumerate(ys)}
             self.acts["egocentric_obs"] = (self.x, Z, prop, self.x.shape[1])
             self.acts["traj_obs"] = (self.traj, 0, ref, self.traj.shape[1])
         self.acts["intention"] = (self.x, 0, Z, self.x.shape[1])
-        self.ctrl = torch.empty((n, A), **f32)
-        self.action_t = torch.empty((A, n), **f32)
-        self.calls.append(("tmjx_action_mode", (_p(self.logits), self.logits.shape[1], _p(self.ctrl), _p(self.action_t), n, A)))
         # the staging copy of the observation: one SoA stream into a [n][1][W] record
         st = _hip.RecordStream(_p(obs_soa), _p(self.stage), _hip.RECORD_SOA, n, W, W, 1, 0, 0)
         self.stage_table = _upload_table([st], n, 1, dev)
         self.stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
-    def _keep(self, obj):
-        self.__dict__.setdefault("_keepalive", []).append(obj)
-
-    def _pad(self, w: torch.Tensor) -> torch.Tensor:
-        """A [N][ceil4(K)] fp32 copy of a weight (zero pad columns): the float4 / matrix-core variant of tmjx_linear_nolds for every layer."""
-        key = id(w)
-        if key not in self._padded:
-            N, K = w.shape
-            buf = torch.zeros((N, _ceil4(K)), dtype=torch.float32, device=w.device)
-            buf[:, :K].copy_(w.detach())
-            self._padded[key] = buf
-        return self._padded[key]
-
-    def _linear_raw(self, a, lda, lin, bias):
-        w = self._pad(lin.weight)
-        out = torch.empty((self.n, lin.out_features), dtype=torch.float32, device=w.device)
-        self._keep(out)
-        self.calls.append(("tmjx_linear_nolds", (_p(a), lda, 1, _p(w), _p(lin.bias) if bias else None, _p(out), self.n, lin.out_features, w.shape[1])))
-        return out
-
-    def _linear(self, a, lda, lin, bias):
-        return self._linear_raw(a, lda, lin, bias)
-
-    def _block(self, a, lda, blk, norm=False):
-        n, N = self.n, blk.dense.out_features
-        w = self._pad(blk.dense.weight)
-        z = torch.empty((n, N), dtype=torch.float32, device=w.device)
-        if norm:
-            self.calls.append(("tmjx_linear_nolds_norm", (_p(a), lda, 1, _p(w), None, _p(z), n, N, w.shape[1], _p(self.fold_mean), _p(self.fold_inv))))
-        else:
-            self.calls.append(("tmjx_linear_nolds", (_p(a), lda, 1, _p(w), None, _p(z), n, N, w.shape[1])))
-        y = torch.empty_like(z)
-        stats = torch.empty((n, 2), dtype=torch.float32, device=w.device)
-        self._keep(z); self._keep(y); self._keep(stats)          # the launch list holds raw pointers: every buffer it names lives as long as the step
-        self.calls.append(("tmjx_silu_ln_fwd", (_p(z), _p(blk.dense.bias), _p(blk.norm.weight), _p(blk.norm.bias), _p(y), _p(stats), n, N,
-                                                float(blk.norm.eps))))
-        return y
-
     def launch(self) -> None:
         """The policy step's launches on the current stream (ctypes calls only: no torch operation)."""
-        L, s = self.L, self.stream
-        _hip.check(L.tmjx_record_step(self.stage_table.data_ptr(), 1, self.n, 0, 1, s), "tmjx_record_step")
-        for name, args in self.calls:
-            _hip.check(getattr(L, name)(*args, s), name)
+        _hip.check(self.L.tmjx_record_step(self.stage_table.data_ptr(), 1, self.n, 0, 1, self.stream), "tmjx_record_step")
+        self.ll.run(self.stream)
 
     def activation_views(self) -> dict:
         out = {}

@@ -5,33 +5,28 @@
 //
 // It is the INFERENCE form of the forward chain of mlp_chain.h: the same ChainGemm K loops (k-ordered MFMA chains) and the same EPI 1 epilogue
 // expressions, so the logits are bit-identical to tmjx_latent_concat_det -> tmjx_chain_fwd and the actions to tmjx_action_mode of them — but
-//   front   the first GEMM's A operand is built ON THE CU: an LDS image [BM][DEC_XLD] (chunks XOR-swizzled by row & 15, the Y image's scheme) filled
-//           from the latents (row-major) and from the env's raw [obs][n_env] observation buffer (read along the env axis: coalesced), normalised
-//           with k_latent_concat_det's expression, zeros from column Z + prop on — nobody writes a row-major image of x to global memory;
+//   front   the first GEMM's A operand is the X image built on the CU (decoder_io.h: dec_build_ximg), the first weight tiles travelling meanwhile;
 //   middle  a hidden layer's output lives in the LDS Y image only: no z, no y, no row statistics leave the CU (the K loops run without the
 //           image-to-global transit of the training chain, kstep<.., TR = 0>);
-//   tail    tanh (tmjx_action_mode's expression) of the head's first A columns from the accumulators, stored transposed as [A][n] (what tmjx_step
-//           takes), and optionally as ctrl [n][A] and logits [n][2A].
+//   tail    from the head's accumulators, one 16-column tile per wave (decoder_io.h: dec_tail): action_t [A][n], optionally ctrl [n][A] and logits.
 //
 // Row tile: 32 rows (MT = 2).  The launch sits between two physics steps, alone on the device, and the batch is a roll-out's (4 096 .. 8 192 envs): 32-row
 // tiles make 128 / 256 workgroups for the 256 CUs where 80-row tiles make 52 / 103 — the row-tile cost model of the layer-by-layer GEMMs (gemm_mt:
 // 2.2 against 5.0 per wave of workgroups) picks the same tile for every M <= 8 192.  LDS: the X image (32 x 320 floats, the Y image [32][256] aliases
 // its front once the first K loop is done) + two weight stages + the reduction scratch = 111 616 B, one workgroup per CU.
 #pragma once
+#include "decoder_io.h"
 #include "mlp_chain.h"
 
 #define DEC_MT 2
-#define DEC_XLD 320          // floats per row of the X image: Z + prop <= 320 (a multiple of 64: the swizzle permutes chunks inside groups of 16)
 struct DecoderBlock { const float *W, *bias, *gamma, *beta; int ldw; };
 struct DecoderAct {
-  const float *lat; int ldz;
-  const float *obs; long long s0, s1;
-  const float *mean, *stdv;
-  int ref_w, Z, prop, M, nh;
+  DecoderIn in;
+  int nh;
   DecoderBlock h[CHAIN_MAX_HIDDEN];
-  const float *Wf, *bf; int ldwf, A;
+  const float *Wf, *bf; int ldwf;
   float eps;
-  float *action_t, *ctrl, *logits; int ldl;
+  DecoderOut out;
 };
 template <int MT> struct DecoderLds {
   static constexpr int BM = 16 * MT, XIMG = BM * DEC_XLD, TOTAL = XIMG + 2 * CH_WSTAGE + 4 * BM * 8;
@@ -45,8 +40,8 @@ __global__ __launch_bounds__(CH_NT) void k_decoder_act(const DecoderAct P) {
   extern __shared__ __attribute__((aligned(16))) float gemm_lds[];
   float *ximg = gemm_lds, *yimg = gemm_lds, *wst = gemm_lds + LD::XIMG, *red1 = wst + 2 * CH_WSTAGE, *red2 = red1 + BM * NW;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 15, kq = lane >> 4, nw = wave * 32;
-  const int m0 = blockIdx.x * BM, M = P.M;
-  const int Z = P.Z, K1 = Z + P.prop;
+  const int m0 = blockIdx.x * BM, M = P.in.M;
+  const int K1 = P.in.Z + P.in.prop;
   gf4 acc[MT][2];
   auto zero = [&]() {
 #pragma unroll
@@ -60,21 +55,7 @@ __global__ __launch_bounds__(CH_NT) void k_decoder_act(const DecoderAct P) {
     ChainGemm<MT, 2, true, true, DEC_XLD> G0;
     G0.init(nullptr, 0, M, m0, P.h[0].W, P.h[0].ldw, 256, K1, ximg, wst);
     G0.gload(G0.R0, 0); G0.gload(G0.R1, GEMM_BK);        // the first weight tiles travel while the image is built
-    auto slot = [&](int r, int c) { return ximg + r * DEC_XLD + ((((c >> 2) ^ (r & 15)) << 2) | (c & 3)); };
-    for (int it = t; it < BM * Z; it += CH_NT) {         // latents: row-major, lanes along the columns
-      const int r = it / Z, c = it - r * Z;
-      *slot(r, c) = m0 + r < M ? P.lat[(long long)(m0 + r) * P.ldz + c] : 0.f;
-    }
-    for (int it = t; it < BM * (DEC_XLD - Z); it += CH_NT) {      // proprioception: lanes along the env axis; zeros from column K1 on
-      const int r = it % BM, c = Z + it / BM;
-      float v = 0.f;
-      if (c < K1 && m0 + r < M) {
-        const int oc = P.ref_w + c - Z;
-        v = P.obs[(long long)(m0 + r) * P.s0 + (long long)oc * P.s1];
-        if (P.mean) v = (v - P.mean[oc]) / P.stdv[oc];
-      }
-      *slot(r, c) = v;
-    }
+    dec_build_ximg<BM, CH_NT>(ximg, P.in, m0, t);
     G0.template swrite<true>(G0.R0, 0); G0.gload(G0.R0, 2 * GEMM_BK);
     __syncthreads();
     G0.fread(G0.F0, 0, 0, 0);
@@ -92,7 +73,7 @@ __global__ __launch_bounds__(CH_NT) void k_decoder_act(const DecoderAct P) {
     const DecoderBlock &H = P.h[l];
     const bool more = l + 1 < P.nh;         // (uniform)
     if (more) { G.init(nullptr, 0, M, m0, P.h[l + 1].W, P.h[l + 1].ldw, 256, 256, yimg, wst); G.early(); }
-    else { Gf.init(nullptr, 0, M, m0, P.Wf, P.ldwf, 2 * P.A, 256, yimg, wst); Gf.early(); }
+    else { Gf.init(nullptr, 0, M, m0, P.Wf, P.ldwf, 2 * P.out.A, 256, yimg, wst); Gf.early(); }
     // ---- block l's epilogue: k_chain_fwd's EPI 1, expression for expression, without the z / stats stores
     gf4 bv[2], gv[2], bev[2];
 #pragma unroll
@@ -159,33 +140,8 @@ __global__ __launch_bounds__(CH_NT) void k_decoder_act(const DecoderAct P) {
   for (int a = 0; a < MT; a++) accf[a][0] = gf4{0.f, 0.f, 0.f, 0.f};
   Gf.late();
   for (int kt = 0; kt < 8; kt += 2) { Gf.template kstep<true, 0>(accf, Gf.R1, 0, kt); Gf.template kstep<true, 0>(accf, Gf.R0, 1, kt + 1); }
-  const int col = wave * 16 + 4 * kq, Nf = 2 * P.A, A = P.A;
-  gf4 bvf = {0.f, 0.f, 0.f, 0.f};
-  if (P.bf) {
+  const int col = wave * 16 + 4 * kq;
+  const df4 bvf = dec_head_bias(P.bf, col, 2 * P.out.A);
 #pragma unroll
-    for (int r = 0; r < 4; r++) bvf[r] = col + r < Nf ? P.bf[col + r] : 0.f;
-  }
-  const bool vec = P.logits && !(P.ldl & 3) && !((uintptr_t)P.logits & 15);
-#pragma unroll
-  for (int a = 0; a < MT; a++) {
-    const int row = m0 + 16 * a + li;
-    const gf4 v = accf[a][0] + bvf;
-    if (row >= M) continue;
-    if (P.logits) {
-      float *o = P.logits + (long long)row * P.ldl + col;
-      if (vec && col + 3 < Nf) *reinterpret_cast<gf4 *>(o) = v;
-      else {
-#pragma unroll
-        for (int r = 0; r < 4; r++) if (col + r < Nf) o[r] = v[r];
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      if (col + r < A) {
-        const float act = tanhf(v[r]);
-        P.action_t[(long long)(col + r) * M + row] = act;
-        if (P.ctrl) P.ctrl[(long long)row * A + col + r] = act;
-      }
-    }
-  }
+  for (int a = 0; a < MT; a++) dec_tail(P.out, M, accf[a][0], bvf, m0 + 16 * a + li, col);
 }

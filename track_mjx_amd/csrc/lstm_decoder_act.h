@@ -20,9 +20,8 @@
 // units of a row in acc[a][2 g + b][r]: the cell update needs no exchange.  32 x 512 gates = 64 accumulator registers per thread.
 //
 // LDS (122 880 B, one workgroup per CU):
-//   X image [32][320]   the layer's input rows, 16-byte chunks XOR-swizzled by (row & 15) (decoder_act.h's X image); layer 0: built on the CU from the
-//                       latents and the env's raw [obs][n_env] buffer (k_latent_concat_det's expression), zeros from column Z + prop on; layer k > 0:
-//                       h_{k-1}' in its first 128 columns, written from the cell update's registers
+//   X image [32][320]   the layer's input rows, 16-byte chunks XOR-swizzled by (row & 15); layer 0: built on the CU (decoder_io.h: dec_build_ximg);
+//                       layer k > 0: h_{k-1}' in its first 128 columns, written from the cell update's registers
 //   H image [32][128]   the layer's carried h_k (zero where reset), same swizzle
 //   two weight stages [512][16]: K slabs of 16 of all 512 gate rows (chunk ^ 3 for rows with bit 3 set: each ds_read_b128 lane group of MI355X hits
 //                       16 distinct 16-byte slots), global -> registers -> LDS, the next slab requested before the current one's MFMAs
@@ -32,47 +31,42 @@
 // element runs over the input columns and then the hidden columns, the bias is added last: the gates are within rounding of, not bit-identical to, the
 // layer-by-layer path's (x W_i^T + b) + h W_h^T.
 #pragma once
+#include "decoder_io.h"
 #include "lstm_kernels.h"
-
-#include <stdint.h>
-
-typedef float __attribute__((ext_vector_type(4))) ldf4;
 
 #define LDA_NT 256
 #define LDA_BM 32
 #define LDA_H 128
-#define LDA_XLD 320
 #define LDA_WSTAGE (512 * 16)
 #define LDA_MAX_LAYERS 4
-#define LDA_LDS_FLOATS (LDA_BM * LDA_XLD + LDA_BM * LDA_H + 2 * LDA_WSTAGE)
+#define LDA_LDS_FLOATS (LDA_BM * DEC_XLD + LDA_BM * LDA_H + 2 * LDA_WSTAGE)
 
 struct LstmDecLayer { const float *Wi, *Wh, *bh; int ldwi, ldwh; };
 struct LstmDecAct {
-  const float *lat; int ldz;
-  const float *obs; long long s0, s1;
-  const float *mean, *stdv, *reset;
-  int ref_w, Z, prop, M, L;
+  DecoderIn in;
+  const float *reset;
+  int L;
   LstmDecLayer l[LDA_MAX_LAYERS];
-  const float *Wp, *bp; int ldwp, A;
+  const float *Wp, *bp; int ldwp;
   float *h, *c; int ld;
-  float *action_t, *ctrl, *logits; int ldl;
+  DecoderOut out;
 };
 
 // acc[a][j] += A[32 rows][K] . W[n][K]^T for the wave's NJ column tiles: tile j covers weight rows (j >> 1) * 128 + 32 wave + 16 (j & 1) + [0, 16).
 // aimg: the swizzled LDS image of A (ald floats per row, zeros from column K on up to the next multiple of 16).  Rows n >= N and columns k >= K of W
 // are read as exact zeros.  The first barrier also publishes what the caller wrote to the images; the last one leaves images and stages dead.
 template <int NJ>
-__device__ __forceinline__ void lda_gemm(ldf4 (&acc)[2][NJ], const float *aimg, int ald, const float *W, int ldw, int N, int K, float *wst,
+__device__ __forceinline__ void lda_gemm(df4 (&acc)[2][NJ], const float *aimg, int ald, const float *W, int ldw, int N, int K, float *wst,
                                          int t, int wave, int li, int kq) {
   constexpr int NP = 64 * NJ * 4 / LDA_NT;          // float4 per thread per slab (64 NJ weight rows of 16 floats)
-  ldf4 rg[NP];
+  df4 rg[NP];
   auto gload = [&](int k0) {
 #pragma unroll
     for (int p = 0; p < NP; p++) {
       const int f = t + LDA_NT * p, n = f >> 2, k = k0 + 4 * (f & 3);
-      ldf4 v = {0.f, 0.f, 0.f, 0.f};
+      df4 v = {0.f, 0.f, 0.f, 0.f};
       if (n < N && k < K) {                          // (ldw is a multiple of 4 and >= K: the four floats are inside the row)
-        v = *reinterpret_cast<const ldf4 *>(W + (long long)n * ldw + k);
+        v = *reinterpret_cast<const df4 *>(W + (long long)n * ldw + k);
         if (k + 3 >= K) {
 #pragma unroll
           for (int j = 1; j < 4; j++) if (k + j >= K) v[j] = 0.f;
@@ -86,7 +80,7 @@ __device__ __forceinline__ void lda_gemm(ldf4 (&acc)[2][NJ], const float *aimg, 
 #pragma unroll
     for (int p = 0; p < NP; p++) {
       const int f = t + LDA_NT * p, n = f >> 2, ch = f & 3;
-      *reinterpret_cast<ldf4 *>(sb + n * 16 + ((ch ^ (((n >> 3) & 1) * 3)) << 2)) = rg[p];
+      *reinterpret_cast<df4 *>(sb + n * 16 + ((ch ^ (((n >> 3) & 1) * 3)) << 2)) = rg[p];
     }
   };
   const int nk = (K + 15) >> 4;
@@ -96,13 +90,13 @@ __device__ __forceinline__ void lda_gemm(ldf4 (&acc)[2][NJ], const float *aimg, 
     const bool more = kt + 1 < nk;                   // (uniform)
     if (more) gload(16 * (kt + 1));
     const float *sb = wst + (kt & 1) * LDA_WSTAGE;
-    ldf4 fa[2], fb[NJ];
+    df4 fa[2], fb[NJ];
 #pragma unroll
-    for (int a = 0; a < 2; a++) fa[a] = *reinterpret_cast<const ldf4 *>(aimg + (16 * a + li) * ald + (((4 * kt + kq) ^ li) << 2));
+    for (int a = 0; a < 2; a++) fa[a] = *reinterpret_cast<const df4 *>(aimg + (16 * a + li) * ald + (((4 * kt + kq) ^ li) << 2));
 #pragma unroll
     for (int j = 0; j < NJ; j++) {
       const int n = (j >> 1) * 128 + 32 * wave + 16 * (j & 1) + li;
-      fb[j] = *reinterpret_cast<const ldf4 *>(sb + n * 16 + ((kq ^ (((li >> 3) & 1) * 3)) << 2));
+      fb[j] = *reinterpret_cast<const df4 *>(sb + n * 16 + ((kq ^ (((li >> 3) & 1) * 3)) << 2));
     }
 #pragma unroll
     for (int e = 0; e < 4; e++)
@@ -118,26 +112,11 @@ __device__ __forceinline__ void lda_gemm(ldf4 (&acc)[2][NJ], const float *aimg, 
 __global__ __launch_bounds__(LDA_NT) void k_lstm_decoder_act(const LstmDecAct P) {
   constexpr int BM = LDA_BM, H = LDA_H;
   extern __shared__ __attribute__((aligned(16))) float lda_lds[];
-  float *ximg = lda_lds, *himg = ximg + BM * LDA_XLD, *wst = himg + BM * H;
+  float *ximg = lda_lds, *himg = ximg + BM * DEC_XLD, *wst = himg + BM * H;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 15, kq = lane >> 4;
-  const int m0 = blockIdx.x * BM, M = P.M, Z = P.Z, K1 = Z + P.prop;
+  const int m0 = blockIdx.x * BM, M = P.in.M, K1 = P.in.Z + P.in.prop;
   const int ld = P.ld;
-  auto xslot = [&](int r, int c) { return ximg + r * LDA_XLD + ((((c >> 2) ^ (r & 15)) << 2) | (c & 3)); };
-  // ---- the X image of layer 0 (decoder_act.h's front)
-  for (int it = t; it < BM * Z; it += LDA_NT) {            // latents: row-major, lanes along the columns
-    const int r = it / Z, c = it - r * Z;
-    *xslot(r, c) = m0 + r < M ? P.lat[(long long)(m0 + r) * P.ldz + c] : 0.f;
-  }
-  for (int it = t; it < BM * (LDA_XLD - Z); it += LDA_NT) {      // proprioception: lanes along the env axis; zeros from column K1 on
-    const int r = it % BM, c = Z + it / BM;
-    float v = 0.f;
-    if (c < K1 && m0 + r < M) {
-      const int oc = P.ref_w + c - Z;
-      v = P.obs[(long long)(m0 + r) * P.s0 + (long long)oc * P.s1];
-      if (P.mean) v = (v - P.mean[oc]) / P.stdv[oc];
-    }
-    *xslot(r, c) = v;
-  }
+  dec_build_ximg<BM, LDA_NT>(ximg, P.in, m0, t);            // the X image of layer 0
   bool rs[2];                                              // the row's carry starts from zero
 #pragma unroll
   for (int a = 0; a < 2; a++) {
@@ -150,20 +129,20 @@ __global__ __launch_bounds__(LDA_NT) void k_lstm_decoder_act(const LstmDecAct P)
     // ---- the H image: the carried h_k (the previous layer's last barrier left it dead)
     for (int it = t; it < BM * (H / 4); it += LDA_NT) {
       const int r = it >> 5, c4 = it & 31, row = m0 + r;
-      ldf4 v = {0.f, 0.f, 0.f, 0.f};
+      df4 v = {0.f, 0.f, 0.f, 0.f};
       if (row < M && !(P.reset && P.reset[row] != 0.f)) {
         const float *src = P.h + (long long)row * ld + k * H + 4 * c4;
-        if (vec) v = *reinterpret_cast<const ldf4 *>(src);
+        if (vec) v = *reinterpret_cast<const df4 *>(src);
         else { v[0] = src[0]; v[1] = src[1]; v[2] = src[2]; v[3] = src[3]; }
       }
-      *reinterpret_cast<ldf4 *>(himg + r * H + ((c4 ^ (r & 15)) << 2)) = v;
+      *reinterpret_cast<df4 *>(himg + r * H + ((c4 ^ (r & 15)) << 2)) = v;
     }
-    ldf4 acc[2][8];
+    df4 acc[2][8];
 #pragma unroll
     for (int a = 0; a < 2; a++)
 #pragma unroll
-      for (int j = 0; j < 8; j++) acc[a][j] = ldf4{0.f, 0.f, 0.f, 0.f};
-    lda_gemm<8>(acc, ximg, LDA_XLD, Y.Wi, Y.ldwi, 4 * H, k == 0 ? K1 : H, wst, t, wave, li, kq);
+      for (int j = 0; j < 8; j++) acc[a][j] = df4{0.f, 0.f, 0.f, 0.f};
+    lda_gemm<8>(acc, ximg, DEC_XLD, Y.Wi, Y.ldwi, 4 * H, k == 0 ? K1 : H, wst, t, wave, li, kq);
     lda_gemm<8>(acc, himg, H, Y.Wh, Y.ldwh, 4 * H, H, wst, t, wave, li, kq);
     // ---- the cell: lane (li, kq) of wave `wave` holds the four gates of units 32 wave + 16 b + 4 kq + r of rows 16 a + li
 #pragma unroll
@@ -176,12 +155,12 @@ __global__ __launch_bounds__(LDA_NT) void k_lstm_decoder_act(const LstmDecAct P)
       for (int a = 0; a < 2; a++) {
         const int row = m0 + 16 * a + li;
         const long long off = (long long)row * ld + k * H + u0;
-        ldf4 cp = {0.f, 0.f, 0.f, 0.f};
+        df4 cp = {0.f, 0.f, 0.f, 0.f};
         if (row < M && !rs[a]) {
-          if (vec) cp = *reinterpret_cast<const ldf4 *>(P.c + off);
+          if (vec) cp = *reinterpret_cast<const df4 *>(P.c + off);
           else { cp[0] = P.c[off]; cp[1] = P.c[off + 1]; cp[2] = P.c[off + 2]; cp[3] = P.c[off + 3]; }
         }
-        ldf4 hn, cn;
+        df4 hn, cn;
 #pragma unroll
         for (int r = 0; r < 4; r++) {
           const float gi = lstm_sigmoid(acc[a][b][r] + bi[r]), gf = lstm_sigmoid(acc[a][2 + b][r] + bf[r]);
@@ -190,55 +169,30 @@ __global__ __launch_bounds__(LDA_NT) void k_lstm_decoder_act(const LstmDecAct P)
           hn[r] = go * tanhf(cn[r]);
         }
         if (row < M) {
-          if (vec) { *reinterpret_cast<ldf4 *>(P.h + off) = hn; *reinterpret_cast<ldf4 *>(P.c + off) = cn; }
+          if (vec) { *reinterpret_cast<df4 *>(P.h + off) = hn; *reinterpret_cast<df4 *>(P.c + off) = cn; }
           else {
 #pragma unroll
             for (int r = 0; r < 4; r++) { P.h[off + r] = hn[r]; P.c[off + r] = cn[r]; }
           }
         }
         // h_k' is the next layer's (or the head's) A operand: chunk u0 / 4 of row 16 a + li of the X image (every reader of it passed the last barrier)
-        *reinterpret_cast<ldf4 *>(ximg + (16 * a + li) * LDA_XLD + (((u0 >> 2) ^ li) << 2)) = hn;
+        *reinterpret_cast<df4 *>(ximg + (16 * a + li) * DEC_XLD + (((u0 >> 2) ^ li) << 2)) = hn;
       }
     }
   }
-  // ---- the projection and the tail (decoder_act.h's): wave w owns logits columns [32 w, 32 w + 32)
-  ldf4 accf[2][2];
+  // ---- the projection and the tail: wave w owns logits columns [32 w, 32 w + 32), two 16-column tiles
+  df4 accf[2][2];
 #pragma unroll
   for (int a = 0; a < 2; a++)
 #pragma unroll
-    for (int b = 0; b < 2; b++) accf[a][b] = ldf4{0.f, 0.f, 0.f, 0.f};
-  const int Nf = 2 * P.A, A = P.A;
-  lda_gemm<2>(accf, ximg, LDA_XLD, P.Wp, P.ldwp, Nf, H, wst, t, wave, li, kq);
-  const bool lvec = P.logits && !(P.ldl & 3) && !((uintptr_t)P.logits & 15);
+    for (int b = 0; b < 2; b++) accf[a][b] = df4{0.f, 0.f, 0.f, 0.f};
+  const int Nf = 2 * P.out.A;
+  lda_gemm<2>(accf, ximg, DEC_XLD, P.Wp, P.ldwp, Nf, H, wst, t, wave, li, kq);
 #pragma unroll
   for (int b = 0; b < 2; b++) {
     const int col = 32 * wave + 16 * b + 4 * kq;
-    ldf4 bv = {0.f, 0.f, 0.f, 0.f};
-    if (P.bp) {
+    const df4 bv = dec_head_bias(P.bp, col, Nf);
 #pragma unroll
-      for (int r = 0; r < 4; r++) bv[r] = col + r < Nf ? P.bp[col + r] : 0.f;
-    }
-#pragma unroll
-    for (int a = 0; a < 2; a++) {
-      const int row = m0 + 16 * a + li;
-      const ldf4 v = accf[a][b] + bv;
-      if (row >= M) continue;
-      if (P.logits) {
-        float *o = P.logits + (long long)row * P.ldl + col;
-        if (lvec && col + 3 < Nf) *reinterpret_cast<ldf4 *>(o) = v;
-        else {
-#pragma unroll
-          for (int r = 0; r < 4; r++) if (col + r < Nf) o[r] = v[r];
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        if (col + r < A) {
-          const float act = tanhf(v[r]);
-          P.action_t[(long long)(col + r) * M + row] = act;
-          if (P.ctrl) P.ctrl[(long long)row * A + col + r] = act;
-        }
-      }
-    }
+    for (int a = 0; a < 2; a++) dec_tail(P.out, M, accf[a][b], bv, m0 + 16 * a + li, col);
   }
 }

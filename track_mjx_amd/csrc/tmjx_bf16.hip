@@ -8,29 +8,17 @@
 
 #include "../../include/tmjx.h"
 #include "gemm_bf16.h"
+#include "host_launch.h"
 
-extern "C" int tmjx_internal_fail(int code, const char *msg);       // tmjx_hip.hip: records the calling thread's error message
 static int fail(int code, const std::string &msg) { return tmjx_internal_fail(code, msg.c_str()); }
 #define BZ_ALIGN (4 * sizeof(bz_t) - 1)      // a saved pre-activation row is accessed four elements at a time (bz_t: gemm_bf16.h)
 extern "C" int tmjx_bf16_z_bytes(void) { return (int)sizeof(bz_t); }
-static int check_launch(const char *what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(TMJX_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-  return TMJX_OK;
-}
 
 template <int MI, int NI, int EPI, bool AF32, bool DMA_A>
 static int launch_bgemm2(const void *A, int lda, const bf16_t *B, int ldb, const float *bias, float *C, int ldc, int M, int N, int K, const BgEpi &epi, hipStream_t s) {
   using Cfg = BgCfg<MI, NI>;
-  static bool attr_set = false;            // > 64 KiB of dynamic LDS needs the attribute once per kernel
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void *)k_bgemm_nt<MI, NI, EPI, AF32, DMA_A>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
-    if (e != hipSuccess) return fail(TMJX_EHIP, std::string("hipFuncSetAttribute(k_bgemm_nt): ") + hipGetErrorString(e));
-    attr_set = true;
-  }
   dim3 grid((M + Cfg::BM - 1) / Cfg::BM, (N + Cfg::BN - 1) / Cfg::BN);
-  hipLaunchKernelGGL((k_bgemm_nt<MI, NI, EPI, AF32, DMA_A>), grid, dim3(512), Cfg::LDS, s, A, lda, B, ldb, bias, C, ldc, M, N, K, epi);
-  return check_launch("k_bgemm_nt");
+  return launch_lds<k_bgemm_nt<MI, NI, EPI, AF32, DMA_A>>("k_bgemm_nt", grid, dim3(512), Cfg::LDS, s, A, lda, B, ldb, bias, C, ldc, M, N, K, epi);
 }
 template <int MI, int NI, int EPI, bool AF32>
 static int launch_bgemm(const void *A, int lda, const bf16_t *B, int ldb, const float *bias, float *C, int ldc, int M, int N, int K, const BgEpi &epi, hipStream_t s) {

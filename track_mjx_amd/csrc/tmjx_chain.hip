@@ -7,31 +7,17 @@
 #include <string>
 
 #include "../../include/tmjx.h"
+#include "host_launch.h"
 #include "mlp_chain.h"
 #include "decoder_act.h"
 
-extern "C" int tmjx_internal_fail(int code, const char *msg);       // tmjx_hip.hip: records the calling thread's error message
 extern "C" int tmjx_internal_gemm_mt(int M, int col_tiles);         // tmjx_hip.hip: the row tile (80 / 32 rows) the layer-by-layer kernels take
 static int fail(int code, const std::string &msg) { return tmjx_internal_fail(code, msg.c_str()); }
-static int check_launch(const char *what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(TMJX_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-  return TMJX_OK;
-}
-static bool al16(const void *p) { return !((uintptr_t)p & 15); }
 static bool rows16(const void *p, long long ld) { return al16(p) && !(ld & 3); }
 
 template <int MT, int EPI, int FIN>
 static int launch_chain_fwd(const ChainFwd &P, hipStream_t s) {
-  constexpr size_t lds = sizeof(float) * (size_t)ChainLds<MT>::TOTAL;
-  static bool attr_set = false;            // > 64 KiB of dynamic LDS needs the attribute once per kernel
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void *)k_chain_fwd<MT, EPI, FIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(TMJX_EHIP, std::string("hipFuncSetAttribute(k_chain_fwd): ") + hipGetErrorString(e));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((k_chain_fwd<MT, EPI, FIN>), dim3((P.M + 16 * MT - 1) / (16 * MT)), dim3(CH_NT), lds, s, P);
-  return check_launch("k_chain_fwd");
+  return launch_lds<k_chain_fwd<MT, EPI, FIN>>("k_chain_fwd", dim3((P.M + 16 * MT - 1) / (16 * MT)), dim3(CH_NT), sizeof(float) * (size_t)ChainLds<MT>::TOTAL, s, P);
 }
 template <int EPI, int FIN>
 static int chain_fwd_mt(const ChainFwd &P, hipStream_t s) {
@@ -64,15 +50,7 @@ static const char *chain_fwd_why(const tmjx_chain_fwd_t *c) {
 
 template <int MT, int EPI, bool HEAD, bool DX>
 static int launch_chain_bwd(const ChainBwd &P, hipStream_t s) {
-  constexpr size_t lds = sizeof(float) * (size_t)ChainLds<MT>::TOTAL;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void *)k_chain_bwd<MT, EPI, HEAD, DX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(TMJX_EHIP, std::string("hipFuncSetAttribute(k_chain_bwd): ") + hipGetErrorString(e));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((k_chain_bwd<MT, EPI, HEAD, DX>), dim3((P.M + 16 * MT - 1) / (16 * MT)), dim3(CH_NT), lds, s, P);
-  return check_launch("k_chain_bwd");
+  return launch_lds<k_chain_bwd<MT, EPI, HEAD, DX>>("k_chain_bwd", dim3((P.M + 16 * MT - 1) / (16 * MT)), dim3(CH_NT), sizeof(float) * (size_t)ChainLds<MT>::TOTAL, s, P);
 }
 template <int EPI, bool HEAD, bool DX>
 static int chain_bwd_mt(const ChainBwd &P, hipStream_t s) {
@@ -103,20 +81,12 @@ static const char *chain_bwd_why(const tmjx_chain_bwd_t *c) {
 }
 
 static_assert(sizeof(tmjx_decoder_act_t) == 304, "tmjx_decoder_act_t: the layout hip.DecoderAct declares");
-static bool al4(const void *p) { return !((uintptr_t)p & 3); }
 static const char *decoder_act_why(const tmjx_decoder_act_t *c) {
   if (!c || !c->latents || !c->obs || !c->action_t || !c->Wf) return "null argument (latents / obs / action_t / Wf)";
-  if (!c->mean != !c->std) return "mean and std together";
-  if (c->n < 1) return "n >= 1";
   if (c->n_blocks < 1 || c->n_blocks > TMJX_CHAIN_MAX_HIDDEN) return "1 .. 4 decoder blocks";
-  if (c->Z < 1 || c->ldz < c->Z) return "Z >= 1 and ldz >= Z";
-  if (c->ref_w < 0 || c->obs_w < c->ref_w) return "obs_w >= ref_w >= 0";
+  if (const char *why = decoder_io_why(c)) return why;
+  if (!al4(c->bf)) return "float pointers must be 4-byte aligned";
   const long long K1 = (long long)c->Z + c->obs_w - c->ref_w;
-  if (K1 > DEC_XLD) return "the decoder's input (Z + obs_w - ref_w) is at most 320 columns wide";
-  if (c->A < 1 || 2 * c->A > 128) return "the action head has 2A <= 128 columns (A >= 1)";
-  for (const void *p : {(const void *)c->latents, (const void *)c->obs, (const void *)c->mean, (const void *)c->std, (const void *)c->action_t, (const void *)c->ctrl,
-                        (const void *)c->logits, (const void *)c->bf})
-    if (!al4(p)) return "float pointers must be 4-byte aligned";
   for (int l = 0; l < c->n_blocks; l++) {
     const tmjx_decoder_block_t &h = c->block[l];
     if (h.width != 256) return "every decoder block is 256 wide";
@@ -126,7 +96,6 @@ static const char *decoder_act_why(const tmjx_decoder_act_t *c) {
     if ((h.ldw & 3) || h.ldw < ((K + 3) & ~3ll)) return "block ldw: a multiple of 4, at least the input width rounded up to 4";
   }
   if (!rows16(c->Wf, c->ldwf) || c->ldwf < 256) return "the head's weight rows must be 16-byte aligned with ldwf >= 256";
-  if (c->logits && c->ldl < 2 * c->A) return "ldl >= 2A";
   return nullptr;
 }
 
@@ -135,20 +104,11 @@ int tmjx_decoder_act_ok(const tmjx_decoder_act_t *c) { return decoder_act_why(c)
 int tmjx_decoder_act(const tmjx_decoder_act_t *c, void *stream) {
   if (const char *why = decoder_act_why(c)) return fail(TMJX_EINVAL, std::string("tmjx_decoder_act: ") + why);
   DecoderAct P{};
-  P.lat = c->latents; P.ldz = c->ldz; P.obs = c->obs; P.s0 = c->obs_s0; P.s1 = c->obs_s1; P.mean = c->mean; P.stdv = c->std;
-  P.ref_w = c->ref_w; P.Z = c->Z; P.prop = c->obs_w - c->ref_w; P.M = c->n; P.nh = c->n_blocks;
+  P.in = decoder_in(c); P.nh = c->n_blocks;
   for (int l = 0; l < c->n_blocks; l++) P.h[l] = DecoderBlock{c->block[l].W, c->block[l].bias, c->block[l].gamma, c->block[l].beta, c->block[l].ldw};
-  P.Wf = c->Wf; P.bf = c->bf; P.ldwf = c->ldwf; P.A = c->A; P.eps = c->eps;
-  P.action_t = c->action_t; P.ctrl = c->ctrl; P.logits = c->logits; P.ldl = c->ldl;
-  constexpr size_t lds = sizeof(float) * (size_t)DecoderLds<DEC_MT>::TOTAL;
-  static bool attr_set = false;            // > 64 KiB of dynamic LDS needs the attribute once per kernel
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void *)k_decoder_act<DEC_MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(TMJX_EHIP, std::string("hipFuncSetAttribute(k_decoder_act): ") + hipGetErrorString(e));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((k_decoder_act<DEC_MT>), dim3((P.M + 16 * DEC_MT - 1) / (16 * DEC_MT)), dim3(CH_NT), lds, (hipStream_t)stream, P);
-  return check_launch("k_decoder_act");
+  P.Wf = c->Wf; P.bf = c->bf; P.ldwf = c->ldwf; P.eps = c->eps; P.out = decoder_out(c);
+  return launch_lds<k_decoder_act<DEC_MT>>("k_decoder_act", dim3((P.in.M + 16 * DEC_MT - 1) / (16 * DEC_MT)), dim3(CH_NT), sizeof(float) * (size_t)DecoderLds<DEC_MT>::TOTAL,
+                                           (hipStream_t)stream, P);
 }
 int tmjx_chain_rows(int M) { return M < 1 ? 0 : chain_rows(M); }
 int tmjx_chain_bwd_ok(const tmjx_chain_bwd_t *c) { return chain_bwd_why(c) == nullptr; }

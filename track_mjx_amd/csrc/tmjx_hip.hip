@@ -13,6 +13,7 @@
 
 #include "../../include/tmjx.h"
 #include "env_core.h"
+#include "host_launch.h"
 #include "model_host.h"
 #include "wave_physics.h"
 #ifdef TMJX_LANE_IMPL
@@ -489,11 +490,6 @@ static float *wave_record(const tmjx_model *m, float *workspace, int n_env) {
   if (!workspace) return nullptr;
   if ((size_t)m->h.w_rows * (size_t)n_env < WAVE_REC_OFFSET(m, n_env) + (size_t)WAVE_REC_STRIDE(m) * (size_t)n_env) return nullptr;
   return workspace + WAVE_REC_OFFSET(m, n_env);
-}
-static int check_launch(const char *what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(TMJX_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-  return TMJX_OK;
 }
 #define GRID(m, n) dim3(((n) + (m)->block - 1) / (m)->block), dim3((m)->block)
 #define WAVE_LDS(m) ((size_t)(m)->h.lds_floats * sizeof(float))
@@ -1059,15 +1055,8 @@ template <int NIW, bool BT, bool AVEC, bool WVEC, int MT = 5, int EPI = 0>
 static int launch_gemm_act(const float *A, int lda, const float *W, int ldw, const float *bias, float *C, int ldc, int M, int N, int K, hipStream_t s, GemmLN ln = GemmLN{}) {
   constexpr int BN = 64 * NIW, BM = 16 * MT;
   constexpr size_t lds = 2 * sizeof(float) * (size_t)((BM + 8) * GEMM_LDA + (BT ? BN * GEMM_LDA : GEMM_BK * (BN + 4)));
-  static bool attr_set = false;            // > 64 KiB of dynamic LDS needs the attribute once per kernel
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void *)k_gemm_act<NIW, BT, AVEC, WVEC, EPI, MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(TMJX_EHIP, std::string("hipFuncSetAttribute(k_gemm_act): ") + hipGetErrorString(e));
-    attr_set = true;
-  }
   dim3 grid((M + BM - 1) / BM, (N + BN - 1) / BN);
-  hipLaunchKernelGGL((k_gemm_act<NIW, BT, AVEC, WVEC, EPI, MT>), grid, dim3(GemmCfg<NIW>::THREADS), lds, s, A, lda, W, ldw, bias, C, ldc, M, N, K, ln);
-  return check_launch("k_gemm_act");
+  return launch_lds<k_gemm_act<NIW, BT, AVEC, WVEC, EPI, MT>>("k_gemm_act", grid, dim3(GemmCfg<NIW>::THREADS), lds, s, A, lda, W, ldw, bias, C, ldc, M, N, K, ln);
 }
 // the input gradient of a Dense -> SiLU layer's consumer with that layer's SiLU backward in the epilogue (k_gemm_act<.., EPI = 4>; aligned operands only)
 template <int NIW>
@@ -1102,14 +1091,8 @@ template <int NIW, int MT>
 static int launch_gemm_ln(const float *A, int lda, const float *W, int ldw, const float *bias, float *Z, int ldc, int M, int N, int K, GemmLN ln, hipStream_t s) {
   constexpr int BN = 64 * NIW, BM = 16 * MT;
   constexpr size_t lds = 2 * sizeof(float) * (size_t)((BM + 8) * GEMM_LDA + BN * GEMM_LDA);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void *)k_gemm_act<NIW, true, true, true, 1, MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(TMJX_EHIP, std::string("hipFuncSetAttribute(k_gemm_act LN): ") + hipGetErrorString(e));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((k_gemm_act<NIW, true, true, true, 1, MT>), dim3((M + BM - 1) / BM, 1), dim3(GemmCfg<NIW>::THREADS), lds, s, A, lda, W, ldw, bias, Z, ldc, M, N, K, ln);
-  return check_launch("k_gemm_act(LN)");
+  return launch_lds<k_gemm_act<NIW, true, true, true, 1, MT>>("k_gemm_act(LN)", dim3((M + BM - 1) / BM, 1), dim3(GemmCfg<NIW>::THREADS), lds, s, A, lda, W, ldw, bias, Z, ldc, M, N,
+                                                              K, ln);
 }
 template <bool YVEC, bool XVEC>
 static int launch_gemm_dw(const float *dY, int ldy, const float *X, int ldx, float *scratch, int M, int N, int K, int with_bias, int rps, int S, int ld, hipStream_t s) {
@@ -1128,15 +1111,9 @@ template <int NIW, int MT>
 static int launch_gemm_silu(const float *A, int lda, const float *W, int ldw, const float *bias, float *Z, float *Y, int ldc, int M, int N, int K, hipStream_t s) {
   constexpr int BN = 64 * NIW, BM = 16 * MT;
   constexpr size_t lds = 2 * sizeof(float) * (size_t)((BM + 8) * GEMM_LDA + BN * GEMM_LDA);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void *)k_gemm_act<NIW, true, true, true, 3, MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(TMJX_EHIP, std::string("hipFuncSetAttribute(k_gemm_act SiLU): ") + hipGetErrorString(e));
-    attr_set = true;
-  }
   GemmLN ln{nullptr, nullptr, Y, nullptr, 0.f, nullptr, nullptr};
-  hipLaunchKernelGGL((k_gemm_act<NIW, true, true, true, 3, MT>), dim3((M + BM - 1) / BM, (N + BN - 1) / BN), dim3(GemmCfg<NIW>::THREADS), lds, s, A, lda, W, ldw, bias, Z, ldc, M, N, K, ln);
-  return check_launch("k_gemm_act(SiLU)");
+  return launch_lds<k_gemm_act<NIW, true, true, true, 3, MT>>("k_gemm_act(SiLU)", dim3((M + BM - 1) / BM, (N + BN - 1) / BN), dim3(GemmCfg<NIW>::THREADS), lds, s, A, lda, W, ldw, bias,
+                                                              Z, ldc, M, N, K, ln);
 }
 extern "C" {
 int tmjx_gemm_nt(const float *A, int lda, const float *W, int ldw, const float *bias, float *C, int ldc, int M, int N, int K, void *stream) {
@@ -1236,14 +1213,8 @@ template <int MT>
 static int launch_gemm_ln_bwd(const float *dY, int ldy, const float *W, int ldw, const float *bias, float *dz, int M, int N, int K, GemmLN ln, hipStream_t s) {
   constexpr int BM = 16 * MT;
   constexpr size_t lds = 2 * sizeof(float) * (size_t)((BM + 8) * GEMM_LDA + GEMM_BK * (256 + 4));
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void *)k_gemm_act<4, false, true, true, 2, MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(TMJX_EHIP, std::string("hipFuncSetAttribute(k_gemm_act LN bwd): ") + hipGetErrorString(e));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((k_gemm_act<4, false, true, true, 2, MT>), dim3((M + BM - 1) / BM, 1), dim3(GemmCfg<4>::THREADS), lds, s, dY, ldy, W, ldw, bias, dz, N, M, N, K, ln);
-  return check_launch("k_gemm_act(LN bwd)");
+  return launch_lds<k_gemm_act<4, false, true, true, 2, MT>>("k_gemm_act(LN bwd)", dim3((M + BM - 1) / BM, 1), dim3(GemmCfg<4>::THREADS), lds, s, dY, ldy, W, ldw, bias, dz, N, M, N, K,
+                                                             ln);
 }
 extern "C" {
 int tmjx_gemm_nn_ln_bwd_ok(const float *dY, int ldy, const float *W, int ldw, int N) { return N == 256 && aligned16(dY, ldy) && aligned16(W, ldw); }

@@ -7,18 +7,11 @@
 #include <string>
 
 #include "../../include/tmjx.h"
+#include "host_launch.h"
 #include "lstm_kernels.h"
 #include "lstm_decoder_act.h"
 
-extern "C" int tmjx_internal_fail(int code, const char *msg);       // tmjx_hip.hip: records the calling thread's error message
 static int fail(int code, const std::string &msg) { return tmjx_internal_fail(code, msg.c_str()); }
-static int check_launch(const char *what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(TMJX_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-  return TMJX_OK;
-}
-static bool al4(const void *p) { return !((uintptr_t)p & 3); }
-static bool al16(const void *p) { return !((uintptr_t)p & 15); }
 static bool hidden_ok(int H) { return H == 32 || H == 64 || H == 128 || H == 256; }
 
 static const char *fwd_why(const tmjx_lstm_fwd_t *a) {
@@ -54,18 +47,11 @@ static const char *decoder_act_why(const tmjx_lstm_decoder_act_t *a) {
   if (!a) return "null argument block";
   if (!a->latents || !a->obs || !a->action_t || !a->Wp) return "null argument (latents / obs / action_t / Wp)";
   if (!a->h || !a->c) return "null carry (h / c)";
-  if (!a->mean != !a->std) return "mean and std together";
-  if (a->n < 1) return "n >= 1";
   if (a->H != LDA_H) return "H must be 128";
   if (a->L < 1 || a->L > TMJX_LSTM_DECODER_MAX_LAYERS) return "1 .. 4 LSTM layers";
-  if (a->Z < 1 || a->ldz < a->Z) return "Z >= 1 and ldz >= Z";
-  if (a->ref_w < 0 || a->obs_w < a->ref_w) return "obs_w >= ref_w >= 0";
+  if (const char *why = decoder_io_why(a)) return why;
+  if (!al4(a->reset) || !al4(a->h) || !al4(a->c) || !al4(a->bp)) return "float pointers must be 4-byte aligned";
   const long long K1 = (long long)a->Z + a->obs_w - a->ref_w;
-  if (K1 > LDA_XLD) return "the decoder's input (Z + obs_w - ref_w) is at most 320 columns wide";
-  if (a->A < 1 || 2 * a->A > 128) return "the action head has 2A <= 128 columns (A >= 1)";
-  for (const void *p : {(const void *)a->latents, (const void *)a->obs, (const void *)a->mean, (const void *)a->std, (const void *)a->reset, (const void *)a->h,
-                        (const void *)a->c, (const void *)a->action_t, (const void *)a->ctrl, (const void *)a->logits, (const void *)a->bp})
-    if (!al4(p)) return "float pointers must be 4-byte aligned";
   for (int k = 0; k < a->L; k++) {
     const tmjx_lstm_decoder_layer_t &y = a->layer[k];
     if (!y.Wi || !y.Wh || !y.bh) return "null layer argument (Wi / Wh / bh)";
@@ -77,7 +63,6 @@ static const char *decoder_act_why(const tmjx_lstm_decoder_act_t *a) {
   if ((a->ldwp & 3) || !al16(a->Wp)) return "weight rows must be 16-byte aligned (ldw % 4 == 0)";
   if (a->ldwp < a->H) return "ldwp >= H";
   if (a->ld < a->L * a->H) return "the carry's ld >= L * H";
-  if (a->logits && a->ldl < 2 * a->A) return "ldl >= 2A";
   return nullptr;
 }
 
@@ -111,21 +96,11 @@ int tmjx_lstm_decoder_act_ok(const tmjx_lstm_decoder_act_t *a) { return decoder_
 int tmjx_lstm_decoder_act(const tmjx_lstm_decoder_act_t *a, void *stream) {
   if (const char *why = decoder_act_why(a)) return fail(TMJX_EINVAL, std::string("tmjx_lstm_decoder_act: ") + why);
   LstmDecAct P{};
-  P.lat = a->latents; P.ldz = a->ldz; P.obs = a->obs; P.s0 = a->obs_s0; P.s1 = a->obs_s1; P.mean = a->mean; P.stdv = a->std; P.reset = a->reset;
-  P.ref_w = a->ref_w; P.Z = a->Z; P.prop = a->obs_w - a->ref_w; P.M = a->n; P.L = a->L;
+  P.in = decoder_in(a); P.reset = a->reset; P.L = a->L;
   for (int k = 0; k < a->L; k++) P.l[k] = LstmDecLayer{a->layer[k].Wi, a->layer[k].Wh, a->layer[k].bh, a->layer[k].ldwi, a->layer[k].ldwh};
-  P.Wp = a->Wp; P.bp = a->bp; P.ldwp = a->ldwp; P.A = a->A;
-  P.h = a->h; P.c = a->c; P.ld = a->ld;
-  P.action_t = a->action_t; P.ctrl = a->ctrl; P.logits = a->logits; P.ldl = a->ldl;
-  constexpr size_t lds = sizeof(float) * (size_t)LDA_LDS_FLOATS;
-  static bool attr_set = false;            // > 64 KiB of dynamic LDS needs the attribute once per kernel
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void *)k_lstm_decoder_act, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(TMJX_EHIP, std::string("hipFuncSetAttribute(k_lstm_decoder_act): ") + hipGetErrorString(e));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(k_lstm_decoder_act, dim3((P.M + LDA_BM - 1) / LDA_BM), dim3(LDA_NT), lds, (hipStream_t)stream, P);
-  return check_launch("k_lstm_decoder_act");
+  P.Wp = a->Wp; P.bp = a->bp; P.ldwp = a->ldwp;
+  P.h = a->h; P.c = a->c; P.ld = a->ld; P.out = decoder_out(a);
+  return launch_lds<k_lstm_decoder_act>("k_lstm_decoder_act", dim3((P.in.M + LDA_BM - 1) / LDA_BM), dim3(LDA_NT), sizeof(float) * (size_t)LDA_LDS_FLOATS, (hipStream_t)stream, P);
 }
 
 int tmjx_lstm_seq_bwd(const tmjx_lstm_bwd_t *a, void *stream) {

@@ -8,17 +8,11 @@
 #include <string>
 
 #include "../../include/tmjx.h"
+#include "host_launch.h"
 #include "rollout_kernels.h"
 
-extern "C" int tmjx_internal_fail(int code, const char *msg);       // tmjx_hip.hip: records the calling thread's error message
 static_assert(sizeof(tmjx_record_stream_t) == 176, "tmjx_record_stream_t: the layout hip.RecordStream declares");
 static int fail(int code, const std::string &msg) { return tmjx_internal_fail(code, msg.c_str()); }
-static int check_launch(const char *what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(TMJX_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-  return TMJX_OK;
-}
-static bool al4(const void *p) { return !((uintptr_t)p & 3); }
 static int grid_of(long long total) { long long g = (total + 255) / 256; return (int)(g < 4096 ? (g > 0 ? g : 1) : 4096); }
 
 static std::string stream_why(const tmjx_record_stream_t &s, int n_env, int T) {

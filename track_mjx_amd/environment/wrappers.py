@@ -14,7 +14,8 @@ HighLevelWrapper (wrappers.py:384-412) puts a pretrained decoder INSIDE the env:
 joint controls.  With a DecoderPolicy (agent/checkpoint.py: make_decoder_policy_fn) the decoder runs as launches on the env's own device buffers —
 one fused launch (include/tmjx.h: tmjx_decoder_act) where the decoder qualifies, else the roll-out policy step's decoder half, layer by layer.
 With an LSTMDecoderPolicy (make_lstm_decoder_policy_fn) the wrapper also owns the decoder's carry (h, c) [n, L, H]; the launches are the LSTM
-roll-out step's decoder half, or one tmjx_lstm_decoder_act launch.
+roll-out step's decoder half, or one tmjx_lstm_decoder_act launch.  Both policy kinds run through one _DecoderStep; its layer-by-layer list is built by
+agent/launch_list.py, the builder of the roll-out's own policy step.
 """
 from __future__ import annotations
 
@@ -87,10 +88,6 @@ class EvalClipWrapperTracking:
         return e.reset(rng, ci, start_frame=torch.zeros(n, dtype=torch.int32), qvel_noise=torch.zeros((int(e.layout.nv), n)))
 
 
-def _ceil4(n: int) -> int:
-    return (int(n) + 3) // 4 * 4
-
-
 def _same_device(a, b) -> bool:
     import torch
     a, b = torch.device(a), torch.device(b)
@@ -102,204 +99,106 @@ def _same_device(a, b) -> bool:
     return (cur if a.index is None else a.index) == (cur if b.index is None else b.index)
 
 
-class _DecoderStep:
-    """Preallocated buffers and the launch list of the decoder policy for `n` envs reading the env's raw observation buffer obs_soa [W][n] and
-    writing the action as [nu][n] rows (what tmjx_step takes) — the decoder half of analysis.rollout._PolicyStep, fed with latents.
+def _is_lstm(dp) -> bool:
+    from ..agent.checkpoint import LSTMDecoderPolicy
+    return isinstance(dp, LSTMDecoderPolicy)
 
-    path "layers": tmjx_decoder_input (tmjx_latent_concat_det's kernel, for latents [n][ldz >= Z]) -> per block tmjx_linear_nolds + tmjx_silu_ln_fwd ->
-    head (tmjx_linear_nolds) -> tmjx_action_mode: the kernels, operand layouts and therefore the bits of the roll-out's policy step.
-    path "fused": one tmjx_decoder_act launch."""
 
-    def __init__(self, dp, n: int, obs_soa, path: str):
-        import torch
-        from .. import hip as _hip
-        self._hip, self.L = _hip, _hip.lib()
-        net, dev = dp.net, dp.device
-        self.n, self.path = int(n), path
-        Z, prop, A, ref = dp.latent_size, dp.proprioceptive_obs_size, dp.action_size, dp.reference_obs_size
-        W = int(obs_soa.shape[0])
-        self.Z, self.A = Z, A
-        f32 = dict(dtype=torch.float32, device=dev)
-        p = lambda t: None if t is None else t.data_ptr()      # noqa: E731
-        # the normaliser as tmjx_latent_concat_det / tmjx_decoder_act index it: by observation column (the reference columns are never read)
-        self.mean = self.std = None
-        if dp.mean is not None:
-            self.mean, self.std = torch.zeros(W, **f32), torch.ones(W, **f32)
-            self.mean[ref:].copy_(dp.mean); self.std[ref:].copy_(dp.std)
-        self.ctrl = torch.empty((n, A), **f32)
-        self.action_t = torch.empty((A, n), **f32)
-        self.keep = []
-
-        def pad(w):          # [N][ceil4(K)] fp32 copy with zero pad columns: 16-byte aligned rows for the matrix-core kernels
-            N, K = w.shape
-            buf = torch.zeros((N, _ceil4(K)), **f32)
-            buf[:, :K].copy_(w.detach())
-            self.keep.append(buf)
-            return buf
-
-        self.calls = []              # (entry point, argument tuple with `None` where the latents' pointer / row stride go)
-        if path == "fused":
-            d = self.desc = _hip.DecoderAct()
-            d.obs, d.obs_s0, d.obs_s1, d.mean, d.std = p(obs_soa), 1, n, p(self.mean), p(self.std)
-            d.n, d.Z, d.obs_w, d.ref_w, d.n_blocks = n, Z, W, ref, len(net.decoder)
-            for i, blk in enumerate(net.decoder):
-                w = pad(blk.dense.weight)
-                b = d.block[i]
-                b.W, b.bias, b.gamma, b.beta, b.width, b.ldw = p(w), p(blk.dense.bias), p(blk.norm.weight), p(blk.norm.bias), blk.dense.out_features, w.shape[1]
-            wf = pad(net.head.weight)
-            d.Wf, d.bf, d.ldwf, d.A = p(wf), p(net.head.bias), wf.shape[1], A
-            d.eps = float(net.decoder[0].norm.eps)
-            d.action_t, d.ctrl, d.logits, d.ldl = p(self.action_t), p(self.ctrl), None, 0
-        else:
-            self.x = torch.zeros((n, _ceil4(Z + prop)), **f32)
-            self.calls.append(["tmjx_decoder_input", [None, None, p(obs_soa), 1, n, p(self.mean), p(self.std), p(self.x), self.x.shape[1], n, Z, W, ref]])
-            h = self.x
-            for blk in net.decoder:
-                N = blk.dense.out_features
-                w = pad(blk.dense.weight)
-                z, y, stats = torch.empty((n, N), **f32), torch.empty((n, N), **f32), torch.empty((n, 2), **f32)
-                self.keep += [z, y, stats]
-                self.calls.append(["tmjx_linear_nolds", [p(h), h.shape[1], 1, p(w), None, p(z), n, N, w.shape[1]]])
-                self.calls.append(["tmjx_silu_ln_fwd", [p(z), p(blk.dense.bias), p(blk.norm.weight), p(blk.norm.bias), p(y), p(stats), n, N, float(blk.norm.eps)]])
-                h = y
-            wf = pad(net.head.weight)
-            self.logits = torch.empty((n, 2 * A), **f32)
-            self.calls.append(["tmjx_linear_nolds", [p(h), h.shape[1], 1, p(wf), p(net.head.bias), p(self.logits), n, 2 * A, wf.shape[1]]])
-            self.calls.append(["tmjx_action_mode", [p(self.logits), 2 * A, p(self.ctrl), p(self.action_t), n, A]])
-
-    def launch(self, lat_ptr: int, ldz: int, stream) -> None:
-        """The decoder's launches on `stream` (ctypes calls only: no torch operation)."""
-        L, check = self.L, self._hip.check
-        if self.path == "fused":
-            self.desc.latents, self.desc.ldz = lat_ptr, ldz
-            check(L.tmjx_decoder_act(C.byref(self.desc), stream), "tmjx_decoder_act")
-            return
-        first = self.calls[0][1]
-        first[0], first[1] = lat_ptr, ldz
-        for name, args in self.calls:
-            check(getattr(L, name)(*args, stream), name)
+def _fused_desc(dp, obs_w: int, n: int, p, **addr):
+    """(entry point, descriptor) of the fused launch of a decoder policy on observations `obs_w` wide for `n` envs.  p(tensor, pad=False): the address
+    the kernel reads one of the policy's tensors at (pad: as a copy with rows padded to ceil4 columns); addr: the other pointer fields, by name."""
+    from .. import hip as _hip
+    from ..agent.launch_list import ceil4
+    lstm = _is_lstm(dp)
+    d = (_hip.LstmDecoderAct if lstm else _hip.DecoderAct)()
+    d.ldz, d.obs_s0, d.obs_s1 = dp.latent_size, 1, n
+    d.n, d.Z, d.obs_w, d.ref_w, d.A = n, dp.latent_size, int(obs_w), dp.reference_obs_size, dp.action_size
+    if lstm:
+        d.L, d.H = dp.hidden_layer_num, dp.hidden_state_size
+        for y, wi, wh, bh in zip(d.layer, dp.w_ih, dp.w_hh, dp.b_hh):       # (zip stops at the descriptor's 4 layers: a deeper decoder is refused by L)
+            y.Wi, y.Wh, y.bh, y.ldwi, y.ldwh = p(wi, True), p(wh), p(bh), ceil4(wi.shape[1]), d.H
+        d.Wp, d.bp, d.ldwp, d.ld = p(dp.w_p, True), p(dp.b_p), ceil4(d.H), d.L * d.H
+    else:
+        net = dp.net
+        d.n_blocks = len(net.decoder)
+        for b, blk in zip(d.block, net.decoder):                              # (likewise: refused by n_blocks)
+            w = blk.dense.weight
+            b.W, b.bias, b.gamma, b.beta, b.width, b.ldw = p(w, True), p(blk.dense.bias), p(blk.norm.weight), p(blk.norm.bias), w.shape[0], ceil4(w.shape[1])
+        d.Wf, d.bf, d.ldwf = p(net.head.weight, True), p(net.head.bias), ceil4(net.head.weight.shape[1])
+        d.eps = float(net.decoder[0].norm.eps) if d.n_blocks else 0.0
+    for name, a in addr.items():
+        setattr(d, name, a)
+    return ("tmjx_lstm_decoder_act" if lstm else "tmjx_decoder_act"), d
 
 
 def decoder_act_why_not(dp, obs_w: int, n: int = 1) -> str | None:
-    """None if the fused launch (tmjx_decoder_act) runs this decoder, else the library's reason (tmjx_decoder_act_ok on a descriptor of its shapes)."""
+    """None if the fused launch (tmjx_decoder_act; tmjx_lstm_decoder_act for an LSTMDecoderPolicy) runs this decoder, else the library's reason
+    (tmjx_*_decoder_act_ok on the descriptor the step would launch, every address a dummy: `dp` is a DecoderPolicy or an LSTMDecoderPolicy)."""
     from .. import hip as _hip
     a = 1 << 20                  # a non-null, 16-byte aligned dummy address: the check reads shapes and alignments, never memory
-    d = _hip.DecoderAct()
-    d.latents, d.ldz, d.obs, d.obs_s0, d.obs_s1 = a, dp.latent_size, a, 1, n
-    d.n, d.Z, d.obs_w, d.ref_w, d.n_blocks = n, dp.latent_size, int(obs_w), dp.reference_obs_size, len(dp.decoder_layer_sizes)
-    k = dp.latent_size + dp.proprioceptive_obs_size
-    for i, wd in enumerate(dp.decoder_layer_sizes[:_hip.CHAIN_MAX_HIDDEN]):
-        b = d.block[i]
-        b.W, b.bias, b.gamma, b.beta, b.width, b.ldw = a, a, a, a, wd, _ceil4(k)
-        k = wd
-    d.Wf, d.bf, d.ldwf, d.A, d.eps, d.action_t = a, a, _ceil4(k), dp.action_size, 1e-6, a
+    carry = dict(h=a, c=a) if _is_lstm(dp) else {}
+    entry, d = _fused_desc(dp, obs_w, n, lambda t, pad=False: a, latents=a, obs=a, action_t=a, **carry)
     L = _hip.lib()
-    if L.tmjx_decoder_act_ok(C.byref(d)) == 1:
+    if getattr(L, entry + "_ok")(C.byref(d)) == 1:
         return None
-    L.tmjx_decoder_act(C.byref(d), None)          # (refused before any device call: records the reason)
+    getattr(L, entry)(C.byref(d), None)          # (refused before any device call: records the reason)
     return L.tmjx_last_error().decode()
 
 
-class _LSTMDecoderStep:
-    """_DecoderStep for an LSTMDecoderPolicy: the carry h, c [n, L, H] lives here and is updated in place by the launches; `reset` (the env's done
-    buffer [n], or None) zeroes a row's carry of every layer before the step.
+lstm_decoder_act_why_not = decoder_act_why_not
 
-    path "layers": tmjx_decoder_input -> per layer tmjx_linear_nolds (x W_i^T) + tmjx_lstm_seq_fwd (T = 1) -> tmjx_linear_nolds (projection) ->
-    tmjx_action_mode: the decoder half of analysis.rollout._PolicyStep's LSTM branch — its kernels, operand layouts and therefore its bits.
-    path "fused": one tmjx_lstm_decoder_act launch."""
+
+class _DecoderStep:
+    """Preallocated buffers and the launch list of a decoder policy for `n` envs reading the env's raw observation buffer obs_soa [W][n] and writing
+    the action as [nu][n] rows (what tmjx_step takes).  For an LSTMDecoderPolicy the carry h, c [n, L, H] lives here and is updated in place by the
+    launches; `reset` (the env's done buffer [n], or None) zeroes a row's carry of every layer before the step.
+
+    path "layers": tmjx_decoder_input (tmjx_latent_concat_det's kernel, for latents [n][ldz >= Z]), then the decoder half of the roll-out's policy step
+    (agent/launch_list.py, which analysis.rollout._PolicyStep builds from too): its kernels, operand layouts and therefore its bits.
+    path "fused": one tmjx_decoder_act / tmjx_lstm_decoder_act launch."""
 
     def __init__(self, dp, n: int, obs_soa, path: str, reset=None):
-        import torch
-        from .. import hip as _hip
-        self._hip, self.L = _hip, _hip.lib()
-        dev = dp.device
-        self.n, self.path = int(n), path
+        from ..agent.launch_list import LaunchList, ceil4, ptr
+        ll = self.ll = LaunchList(n, dp.device)
+        lstm = _is_lstm(dp)
         Z, prop, A, ref = dp.latent_size, dp.proprioceptive_obs_size, dp.action_size, dp.reference_obs_size
-        Lk, H = dp.hidden_layer_num, dp.hidden_state_size
         W = int(obs_soa.shape[0])
-        self.Z, self.A = Z, A
-        f32 = dict(dtype=torch.float32, device=dev)
-        p = lambda t: None if t is None else t.data_ptr()      # noqa: E731
-        self.mean = self.std = None
+        # the normaliser as tmjx_latent_concat_det / the fused launches index it: by observation column (the reference columns are never read)
+        mean = std = None
         if dp.mean is not None:
-            self.mean, self.std = torch.zeros(W, **f32), torch.ones(W, **f32)
-            self.mean[ref:].copy_(dp.mean); self.std[ref:].copy_(dp.std)
-        self.h, self.c = torch.zeros((n, Lk, H), **f32), torch.zeros((n, Lk, H), **f32)
-        self.ctrl = torch.empty((n, A), **f32)
-        self.action_t = torch.empty((A, n), **f32)
-        self.keep = [reset]
-
-        def pad(w):          # [N][ceil4(K)] fp32 copy with zero pad columns: 16-byte aligned rows for the matrix-core kernels
-            N, K = w.shape
-            buf = torch.zeros((N, _ceil4(K)), **f32)
-            buf[:, :K].copy_(w.detach())
-            self.keep.append(buf)
-            return buf
-
-        self.calls = []
-        wis, whs = [pad(w) for w in dp.w_ih], [w.detach().contiguous() for w in dp.w_hh]
-        wp = pad(dp.w_p)
-        self.keep += whs
+            mean, std = ll.buf(W, zero=True), ll.buf(W).fill_(1.0)
+            mean[ref:].copy_(dp.mean); std[ref:].copy_(dp.std)
+        carry = {}
+        self.h = self.c = self.desc = None
+        if lstm:
+            self.h, self.c = (ll.buf(n, dp.hidden_layer_num, dp.hidden_state_size, zero=True) for _ in range(2))
+            carry = dict(h=ptr(self.h), c=ptr(self.c), reset=ptr(reset))
         if path == "fused":
-            d = self.desc = _hip.LstmDecoderAct()
-            d.obs, d.obs_s0, d.obs_s1, d.mean, d.std, d.reset = p(obs_soa), 1, n, p(self.mean), p(self.std), p(reset)
-            d.n, d.Z, d.obs_w, d.ref_w, d.L, d.H = n, Z, W, ref, Lk, H
-            for k in range(Lk):
-                y = d.layer[k]
-                y.Wi, y.Wh, y.bh, y.ldwi, y.ldwh = p(wis[k]), p(whs[k]), p(dp.b_hh[k]), wis[k].shape[1], H
-            d.Wp, d.bp, d.ldwp, d.A = p(wp), p(dp.b_p), wp.shape[1], A
-            d.h, d.c, d.ld = p(self.h), p(self.c), Lk * H
-            d.action_t, d.ctrl, d.logits, d.ldl = p(self.action_t), p(self.ctrl), None, 0
+            self.ctrl, self.action_t = ll.buf(n, A), ll.buf(A, n)
+            ll.keep.append(reset)              # (the layers path: lstm_layers keeps it)
+
+            def p(t, pad=False):
+                t = ll.pad(t) if pad else t.detach().contiguous()
+                ll.keep.append(t)
+                return t.data_ptr()
+            entry, self.desc = _fused_desc(dp, W, n, p, obs=ptr(obs_soa), mean=ptr(mean), std=ptr(std), action_t=ptr(self.action_t), ctrl=ptr(self.ctrl), **carry)
+            ll.call(entry, C.byref(self.desc))
         else:
-            self.x = torch.zeros((n, _ceil4(Z + prop)), **f32)
-            self.xg = torch.empty((n, 4 * H), **f32)
-            self.calls.append(["tmjx_decoder_input", [None, None, p(obs_soa), 1, n, p(self.mean), p(self.std), p(self.x), self.x.shape[1], n, Z, W, ref]])
-            a, lda = self.x, self.x.shape[1]
-            for k in range(Lk):
-                self.calls.append(["tmjx_linear_nolds", [p(a), lda, 1, p(wis[k]), None, p(self.xg), n, 4 * H, wis[k].shape[1]]])
-                hk, ck = self.h[:, k], self.c[:, k]
-                args = _hip.LstmFwd(p(self.xg), 4 * H, p(whs[k]), H, p(dp.b_hh[k]), p(hk), p(ck), Lk * H, p(reset), n, p(hk), p(ck), Lk * H, None, None, 1, n, H)
-                self.keep.append(args)
-                self.calls.append(["tmjx_lstm_seq_fwd", [C.byref(args)]])
-                a, lda = hk, Lk * H
-            self.logits = torch.empty((n, 2 * A), **f32)
-            self.calls.append(["tmjx_linear_nolds", [p(a), lda, 1, p(wp), p(dp.b_p), p(self.logits), n, 2 * A, wp.shape[1]]])
-            self.calls.append(["tmjx_action_mode", [p(self.logits), 2 * A, p(self.ctrl), p(self.action_t), n, A]])
+            x = ll.buf(n, ceil4(Z + prop), zero=True)
+            ll.call("tmjx_decoder_input", None, None, ptr(obs_soa), 1, n, ptr(mean), ptr(std), ptr(x), x.shape[1], n, Z, W, ref)
+            if lstm:
+                out = ll.decoder(x, (), dp.w_p, dp.b_p, lstm=(dp.w_ih, dp.w_hh, dp.b_hh, self.h, self.c, reset))
+            else:
+                out = ll.decoder(x, dp.net.decoder, dp.net.head.weight, dp.net.head.bias)
+            self.ctrl, self.action_t = out[2:]
 
     def launch(self, lat_ptr: int, ldz: int, stream) -> None:
         """The decoder's launches on `stream` (ctypes calls only: no torch operation)."""
-        L, check = self.L, self._hip.check
-        if self.path == "fused":
+        if self.desc is not None:
             self.desc.latents, self.desc.ldz = lat_ptr, ldz
-            check(L.tmjx_lstm_decoder_act(C.byref(self.desc), stream), "tmjx_lstm_decoder_act")
-            return
-        first = self.calls[0][1]
-        first[0], first[1] = lat_ptr, ldz
-        for name, args in self.calls:
-            check(getattr(L, name)(*args, stream), name)
-
-
-def lstm_decoder_act_why_not(dp, obs_w: int, n: int = 1) -> str | None:
-    """None if the fused launch (tmjx_lstm_decoder_act) runs this LSTM decoder, else the library's reason (tmjx_lstm_decoder_act_ok on a descriptor of
-    its shapes)."""
-    from .. import hip as _hip
-    a = 1 << 20                  # a non-null, 16-byte aligned dummy address: the check reads shapes and alignments, never memory
-    d = _hip.LstmDecoderAct()
-    Lk, H = dp.hidden_layer_num, dp.hidden_state_size
-    d.latents, d.ldz, d.obs, d.obs_s0, d.obs_s1 = a, dp.latent_size, a, 1, n
-    d.n, d.Z, d.obs_w, d.ref_w, d.L, d.H = n, dp.latent_size, int(obs_w), dp.reference_obs_size, Lk, H
-    k = dp.latent_size + dp.proprioceptive_obs_size
-    for i in range(min(Lk, _hip.LSTM_DECODER_MAX_LAYERS)):
-        y = d.layer[i]
-        y.Wi, y.Wh, y.bh, y.ldwi, y.ldwh = a, a, a, _ceil4(k), H
-        k = H
-    d.Wp, d.bp, d.ldwp, d.A = a, a, _ceil4(H), dp.action_size
-    d.h, d.c, d.ld, d.action_t = a, a, Lk * H, a
-    L = _hip.lib()
-    if L.tmjx_lstm_decoder_act_ok(C.byref(d)) == 1:
-        return None
-    L.tmjx_lstm_decoder_act(C.byref(d), None)          # (refused before any device call: records the reason)
-    return L.tmjx_last_error().decode()
+        else:
+            self.ll.calls[0][1][:2] = lat_ptr, ldz
+        self.ll.run(stream)
 
 
 class HighLevelWrapper:
@@ -354,11 +253,10 @@ class HighLevelWrapper:
             self._Z = dp.latent_size
             import torch
             if hasattr(env, "obs_buf") and dp.device.type == "cuda" and _same_device(env.device, dp.device):
+                why = decoder_act_why_not(dp, W, int(env.num_envs))
                 if self._lstm:
-                    why = lstm_decoder_act_why_not(dp, W, int(env.num_envs))
                     shape, prefers = f"LSTM decoder (L = {dp.hidden_layer_num}, H = {dp.hidden_state_size})", self.AUTO_PREFERS_FUSED_LSTM
                 else:
-                    why = decoder_act_why_not(dp, W, int(env.num_envs))
                     shape, prefers = f"decoder {list(dp.decoder_layer_sizes)}", self.AUTO_PREFERS_FUSED
                 if path == "fused" and why is not None:
                     raise ValueError(f"HighLevelWrapper: path='fused' does not run this {shape}: {why}")
@@ -417,10 +315,7 @@ class HighLevelWrapper:
         import torch
         env, n = self.env, int(self.env.num_envs)
         with torch.cuda.device(env.device):
-            if self._lstm:
-                self._step = _LSTMDecoderStep(self._fn, n, env.obs_buf, self.path, env.done_buf if self.reset_carry_on_done else None)
-            else:
-                self._step = _DecoderStep(self._fn, n, env.obs_buf, self.path)
+            self._step = _DecoderStep(self._fn, n, env.obs_buf, self.path, env.done_buf if self._lstm and self.reset_carry_on_done else None)
         p = lambda t: t.data_ptr()      # noqa: E731
         self._env_args = (env._handle, p(env.state_buf), p(env.istate_buf), p(self._step.action_t), p(env.obs_buf), p(env.reward_buf), p(env.done_buf),
                           p(env.trunc_buf), p(env.metrics_buf), p(env.workspace), n)
@@ -460,7 +355,7 @@ class HighLevelWrapper:
         with torch.cuda.device(env.device):
             stream = C.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)
             self._step.launch(latents.data_ptr(), latents.stride(0), stream)
-            self._step._hip.check(self._step.L.tmjx_step(*self._env_args, stream), "tmjx_step")
+            self._step.ll.hip.check(self._step.ll.L.tmjx_step(*self._env_args, stream), "tmjx_step")
         self._keep_lat = latents
         return self._state
 
