@@ -89,6 +89,18 @@ int tmjx_set_done_policy(tmjx_model *m, int policy);
  * tmjx_physics_sensors / tmjx_step_sensors refuse a handle with scales (the recording kernel has no RAND build), as does a handle of the
  * lane-per-env cross-check implementation.  Per-env models, masses and per-geom / per-dof / per-actuator vectors are not supported. */
 int tmjx_set_env_scales(tmjx_model *m, const float *scales_dev, int n_env);
+/* Per-env gravity, the second table of the same kernel: `gravity_dev` is DEVICE memory, float32 [3][n_env], rows gx, gy, gz in the world frame
+ * (m/s^2).  Env e of a launch integrates with column e in place of the model's `gravity`, which the physics reads in one place — the root
+ * acceleration of the bias-force pass —, so env e reproduces bit for bit a handle created from the blob with `gravity` set to that column.  A
+ * tilted vector is, in this model's flat world, an inclined floor; a shorter one body-weight support.  The contract is tmjx_set_env_scales':
+ * the caller owns the memory and keeps it alive and unchanged while launches read it, nothing on the device is validated, n_env >= 1, NULL
+ * clears the table, the wave-per-env implementation is needed.  The two tables are independent: the RAND kernel runs while either is set and
+ * takes unit scales / the model's gravity for the one that is not; with both cleared the handle launches the product kernel again.  Honoured by
+ * every launch of the physics kernel (tmjx_step under all three done-policies, tmjx_physics, tmjx_physics_step, the forward pass of
+ * tmjx_forward / tmjx_reset, split launches with their env offset); a launch of more envs than `n_env` fails with TMJX_EINVAL before anything is
+ * enqueued.  tmjx_physics_sensors / tmjx_step_sensors refuse a handle with a gravity table (the recording kernel's sensor stage reads the
+ * model's gravity). */
+int tmjx_set_env_gravity(tmjx_model *m, const float *gravity_dev, int n_env);
 /* `action_repeat` of wrappers.wrap (track_mjx/environment/wrappers.py:21,43 -> brax EpisodeWrapper.step [3P]): tmjx_step then runs the
  * tracking env's own step `action_repeat` times with the same action (no termination check in between), returns the SUM of the repeats'
  * rewards, advances the episode's step counter by `action_repeat`, and takes observation / done / truncation / metrics from the last

@@ -965,7 +965,7 @@ def train(environment, num_timesteps: int, episode_length: int, ckpt_mgr=None, c
     `use_lstm`: the recurrent learner (agent/lstm.py: LSTMPPOLearner, the reference's agent/lstm_ppo) with `hidden_layer_num` LSTM layers of
     `hidden_state_size` features; the acting policies (evaluator, make_policy) then carry their own hidden state.
 
-    `randomization_fn` (ppo.py:147,455-473,631-659): per-env domain randomisation, restricted to three scales per env.  fn(model, rng) ->
+    `randomization_fn` (ppo.py:147,455-473,631-659): per-env domain randomisation, restricted to three scales and a gravity vector per env.  fn(model, rng) ->
     environment.DomainRandomization for model["num_envs"] envs (environment.uniform_randomization_fn builds one from ranges).  The training envs'
     scales are ONE global draw from key_env over all ranks' envs — every rank evaluates the same key and takes its shard, every env group of the
     pipelined roll-out its slice of that —, the evaluator's a draw of `num_eval_envs` from eval_key; both keys come from `seed` alone

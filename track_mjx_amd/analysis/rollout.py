@@ -216,13 +216,18 @@ def _upload_table(streams: Sequence, n: int, T: int, dev) -> torch.Tensor:
 # ---------------------------------------------------------------------------------------------------------------- generator
 def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, model: str = "mlp", log_activations: bool = False,
                              log_metrics: bool = False, log_sensor_data: bool = False, clips_per_batch: int = CLIPS_PER_BATCH,
-                             align_on_fail: bool = False, friction_scale=None, actuator_scale=None, damping_scale=None):
+                             align_on_fail: bool = False, friction_scale=None, actuator_scale=None, damping_scale=None,
+                             gravity_scale=None, slope_deg=None):
     """rollout.py:73-269.  Returns generate_rollout(clip_idx=None, seed=42): one clip (int / None) -> dict of arrays; a sequence of clips -> the
     same dict with a leading [N] axis (batches larger than `clips_per_batch` run in chunks).
 
     `friction_scale` / `actuator_scale` / `damping_scale` (the perturbation experiment): one float for every clip, or one per clip of a
     generate_rollout call — each roll-out env then runs with its clip's scales of the model's sliding friction, actuator force and dof damping
-    (environment.DomainRandomization), and the result carries them as `domain_scales` [3].  All None: the env as it was given."""
+    (environment.DomainRandomization), and the result carries them as `domain_scales` [3].  All None: the env as it was given.
+
+    `gravity_scale` / `slope_deg` (one float, or one per clip, likewise): the clip's env runs with the gravity vector slope_gravity(|g|, s, a) =
+    s |g| (sin a, 0, -cos a), |g| the magnitude of the model's gravity — s < 1 is body-weight support, a > 0 a floor inclined so that +x is
+    downhill — and the result carries it as `gravity` [3]."""
     given_scales = {k: v for k, v in (("friction", friction_scale), ("actuator", actuator_scale), ("damping", damping_scale)) if v is not None}
     if given_scales and not hasattr(environment, "set_domain_randomization"):
         raise NotImplementedError(f"friction_scale / actuator_scale / damping_scale: {type(environment).__name__} has no per-env scales "
@@ -231,6 +236,14 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
         raise NotImplementedError("log_sensor_data cannot be combined with friction_scale / actuator_scale / damping_scale: the recording physics "
                                   "kernel that produces sensor_readings and joint_forces has no domain-randomisation build; run the perturbed "
                                   "roll-out without log_sensor_data, or the sensor roll-out without scales")
+    given_gravity = {k: v for k, v in (("gravity_scale", gravity_scale), ("slope_deg", slope_deg)) if v is not None}
+    if given_gravity and not hasattr(environment, "set_domain_randomization"):
+        raise NotImplementedError(f"gravity_scale / slope_deg: {type(environment).__name__} has no per-env gravity "
+                                  "(MultiClipTracking.set_domain_randomization)")
+    if given_gravity and log_sensor_data:
+        raise NotImplementedError("log_sensor_data cannot be combined with gravity_scale / slope_deg: the recording physics kernel that produces "
+                                  "sensor_readings and joint_forces reads the model's gravity and has no per-env build; run the perturbed "
+                                  "roll-out without log_sensor_data, or the sensor roll-out without them")
     if log_sensor_data and not hasattr(environment, "sensor_buffers"):
         raise NotImplementedError("log_sensor_data: cfrc_ext and sensordata are not computed by the physics kernel of this environment: they "
                                   "come from MultiClipTracking's recording kernel (tmjx_step_sensors), and the environment given is "
@@ -290,12 +303,25 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
             tab[r] = v[0] if v.size == 1 else v[offset:offset + n]
         return tab
 
-    def run_batch(clips: list, seed: int, scales=None) -> dict:
+    def gravity_of(n: int, offset: int, total: int):
+        """[n, 3] gravity vectors of clips offset .. offset + n of a call of `total` clips, or None."""
+        if not given_gravity:
+            return None
+        per = {}
+        for name, default in (("gravity_scale", 1.0), ("slope_deg", 0.0)):
+            v = np.atleast_1d(np.asarray(given_gravity.get(name, default), dtype=np.float64)).ravel()
+            if v.size not in (1, total):
+                raise ValueError(f"{name}: {v.size} values for {total} clips (one value, or one per clip)")
+            per[name] = np.full(n, v[0]) if v.size == 1 else v[offset:offset + n]
+        return slope_gravity(model_gravity_magnitude(env0), per["gravity_scale"], per["slope_deg"])
+
+    def run_batch(clips: list, seed: int, scales=None, gravity=None) -> dict:
         n = len(clips)
         env = env_of(n)
-        if scales is not None:
+        if scales is not None or gravity is not None:
             from ..environment import DomainRandomization
-            env.set_domain_randomization(DomainRandomization(scales[0], scales[1], scales[2]))
+            sc = (None, None, None) if scales is None else (scales[0], scales[1], scales[2])
+            env.set_domain_randomization(DomainRandomization(*sc, num_envs=n, gravity=gravity))
         dev, Lay = env.device, env.layout
         nq, nv = int(Lay.nq), int(Lay.nv)
         qn, vn = np.empty((nq, n), np.float32), np.empty((nv, n), np.float32)
@@ -374,6 +400,8 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
         out["qposes_ref"] = np.stack(rows)
         if scales is not None:
             out["domain_scales"] = np.ascontiguousarray(scales.T)          # [n, 3]: friction, actuator, damping of each clip's env
+        if gravity is not None:
+            out["gravity"] = np.ascontiguousarray(gravity, dtype=np.float32)        # [n, 3]: each clip's env's gravity vector (world frame)
         if align_on_fail:
             out["aligned"] = host["aligned"][:, :, 0] != 0
             out["n_alignments"] = out["aligned"].sum(axis=1).astype(np.int64)
@@ -400,9 +428,13 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
             out["activations"] = acts
         return out
 
-    def generate_rollout(clip_idx: int | Sequence[int] | None = None, seed: int = 42, scales: dict | None = None) -> dict:
+    def generate_rollout(clip_idx: int | Sequence[int] | None = None, seed: int = 42, scales: dict | None = None, gravity: dict | None = None) -> dict:
         """`scales`: {"friction" | "actuator" | "damping": float or one per clip} for THIS call, in place of the generator's own (a generator made
-        without scales takes none: its sensor / env checks were made for the plain env)."""
+        without scales takes none: its sensor / env checks were made for the plain env).  `gravity`: {"gravity_scale" | "slope_deg": ...}, likewise."""
+        if gravity is not None:
+            if not given_gravity:
+                raise ValueError("generate_rollout(gravity=...): the generator was created without gravity_scale / slope_deg")
+            given_gravity.clear(); given_gravity.update({k: v for k, v in gravity.items() if v is not None})
         if scales is not None:
             if not given_scales:
                 raise ValueError("generate_rollout(scales=...): the generator was created without friction_scale / actuator_scale / damping_scale")
@@ -418,7 +450,8 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
         bad = [c for c in clips if not 0 <= c < env0._n_clips]
         if bad:
             raise IndexError(f"clip indices {bad[:5]} outside the table's {env0._n_clips} clips")
-        parts = [run_batch(clips[i:i + clips_per_batch], seed, scales_of(len(clips[i:i + clips_per_batch]), i, len(clips)))
+        parts = [run_batch(clips[i:i + clips_per_batch], seed, scales_of(len(clips[i:i + clips_per_batch]), i, len(clips)),
+                           gravity_of(len(clips[i:i + clips_per_batch]), i, len(clips)))
                  for i in range(0, len(clips), int(clips_per_batch))]
         out = _concat(parts) if len(parts) > 1 else parts[0]
         return out if batched else _index0(out)
@@ -469,7 +502,30 @@ def _parse_clips(spec: str, n_clips: int) -> list:
 
 
 CLI_OPTIONS = ("checkpoint", "clips", "seed", "out", "log_activations", "log_metrics", "log_sensor_data", "align_on_fail", "step",
-               "replay_latents", "latent_scale", "path", "friction_scale", "actuator_scale", "damping_scale")
+               "replay_latents", "latent_scale", "path", "friction_scale", "actuator_scale", "damping_scale", "gravity_scale", "slope_deg")
+
+
+def slope_gravity(magnitude: float, gravity_scale=1.0, slope_deg=0.0) -> np.ndarray:
+    """[..., 3] float32: s |g| (sin a, 0, -cos a) — gravity of magnitude s |g| in a world whose floor is inclined by a degrees about the y axis,
+    +x downhill for a > 0 (the floor stays the plane z = 0: the gravity vector is tilted instead).  Formed in float64."""
+    s, a = np.broadcast_arrays(np.asarray(gravity_scale, dtype=np.float64), np.deg2rad(np.asarray(slope_deg, dtype=np.float64)))
+    if not (np.isfinite(s).all() and np.isfinite(a).all()) or (s <= 0).any() or (np.abs(a) >= np.pi / 2).any():
+        raise ValueError("gravity_scale must be > 0 and |slope_deg| < 90")
+    return (s[..., None] * float(magnitude) * np.stack([np.sin(a), np.zeros_like(a), -np.cos(a)], -1)).astype(np.float32)
+
+
+def model_gravity_magnitude(env) -> float:
+    """|gravity| of the env's model (its blob entry `gravity`)."""
+    from .. import blob as _blob
+    return float(np.linalg.norm(np.asarray(_blob.unpack(env._blob)["gravity"], dtype=np.float64)))
+
+
+def parse_per_clip(name: str, text, n_clips: int):
+    """A command-line value `v` or `v0,v1,..`: a list of one float, or of one per clip (anything else is a ValueError)."""
+    v = [float(x) for x in str(text).split(",") if x.strip() != ""]
+    if len(v) not in (1, int(n_clips)):
+        raise ValueError(f"{name}: {len(v)} values for {n_clips} clips (one value, or one per clip)")
+    return v
 
 
 def replay_latents(cfg: dict, decoder_policy, clips: Sequence[int], latents: np.ndarray, seed: int = 42, path: str = "auto", metrics=ROLLOUT_METRICS) -> dict:
@@ -564,7 +620,7 @@ def main(argv=None) -> int:
     if "checkpoint" not in opts:
         print("usage: python -m track_mjx_amd.analysis.rollout checkpoint=<run dir | step dir> [data_path=...] [clips=all|a:b|i,j,k] [seed=42] "
               "[out=<dir>] [log_activations=true] [log_metrics=true] [log_sensor_data=false] [align_on_fail=false] "
-              "[friction_scale=<s | s0,s1,..>] [actuator_scale=..] [damping_scale=..] "
+              "[friction_scale=<s | s0,s1,..>] [actuator_scale=..] [damping_scale=..] [gravity_scale=<s | s0,s1,..>] [slope_deg=<a | a0,a1,..>] "
               "[replay_latents=<dir of clip_<i>.h5> [latent_scale=1.0] [path=auto|fused|layers]] [key=value config overrides ...]", file=sys.stderr)
         return 2
     yes = lambda v: str(v).lower() in ("1", "true", "yes")     # noqa: E731
@@ -602,8 +658,10 @@ def main(argv=None) -> int:
             raise ValueError(f"{name}: {len(v)} values for {len(clips)} clips (one value, or one per clip)")
         return v
     scale_lists = {k: scale_opt(k) for k in ("friction_scale", "actuator_scale", "damping_scale")}
+    gravity_lists = {k: parse_per_clip(k, opts[k], len(clips)) for k in ("gravity_scale", "slope_deg") if k in opts}
     gen = create_rollout_generator(cfg, env, fn, model=fn.model, log_activations=log_act, log_metrics=log_met, log_sensor_data=log_sens,
-                                   align_on_fail=align, **{k: (None if v is None else 1.0) for k, v in scale_lists.items()})
+                                   align_on_fail=align, **{k: (None if v is None else 1.0) for k, v in scale_lists.items()},
+                                   **{k: (1.0 if k == "gravity_scale" else 0.0) for k in gravity_lists})
     print(f"[rollout] done-policy: {gen.done_policy}" + (" (a done env is re-aligned to the clip frame it has reached; `aligned` / `n_alignments` "
                                                         "are recorded)" if align else " (the env keeps stepping after done)"), flush=True)
     out_dir = opts.get("out", os.path.join(step_dir, "rollouts"))
@@ -623,7 +681,8 @@ def main(argv=None) -> int:
     for i in range(0, len(clips), CLIPS_PER_BATCH):
         chunk = clips[i:i + CLIPS_PER_BATCH]
         sc = {k.split("_")[0]: (v[0] if len(v) == 1 else v[i:i + len(chunk)]) for k, v in scale_lists.items() if v is not None}
-        res = gen(chunk, seed=seed, **({"scales": sc} if sc else {}))
+        gr = {k: (v[0] if len(v) == 1 else v[i:i + len(chunk)]) for k, v in gravity_lists.items()}
+        res = gen(chunk, seed=seed, **({"scales": sc} if sc else {}), **({"gravity": gr} if gr else {}))
         for j, c in enumerate(chunk):
             one = _index_j(res, j)
             one["meta"] = dict(meta_common, clip_idx=np.int64(c))

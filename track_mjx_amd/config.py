@@ -53,7 +53,9 @@ def default_config() -> dict[str, Any]:
                 "var_window_size": 50, "var_coeff": 5e-3, "jerk_coeff": 5e-4,
                 "penalty_pos_distance_scale": [1.0, 1.0, 0.5],
             },
-            # per-env domain randomisation (environment/randomization.py): (lo, hi) of the uniform draw of each scale; null = off
+            # per-env domain randomisation (environment/randomization.py): (lo, hi) of the uniform draw of each scale; null = off.  Two more keys
+            # are accepted and are null when absent: gravity_scale_range (multiples of the model's |gravity|) and gravity_tilt_range (degrees
+            # between the env's gravity and the model's: an inclined floor)
             "domain_randomization": {"friction_range": None, "actuator_range": None, "damping_range": None},
         },
         "reference_config": {"clip_length": 250, "random_init_range": 50, "traj_length": 5},

@@ -38,6 +38,10 @@ struct tmjx_model {
   // not randomised: the product kernel.  Set: every physics launch goes to the RAND kernel (csrc/tmjx_wave_rand.hip)
   const float *env_scales = nullptr;
   int env_scales_n = 0;
+  // per-env gravity (tmjx_set_env_gravity): the CALLER's device array [3][env_gravity_n] (gx | gy | gz), or null = the model's gravity.  Either
+  // table set: the RAND kernel, which takes a null for the other
+  const float *env_gravity = nullptr;
+  int env_gravity_n = 0;
 };
 #define WAVE_SPILL_STRIDE(m) ((((m)->h.nnz) + 63) & ~63)
 // record stride: state rows qpos .. qfrc_actuator, then the action, rounded up to 16 words
@@ -210,10 +214,12 @@ extern "C" void tmjx_internal_launch_physics_wave_sensors(int rodent, int cnt, s
                                                           const float *action, int nsub, int do_euler, float *ws_dump, int n, int e0, int rs,
                                                           float *spill, int spill_stride, float *sensordata, float *cfrc_ext);
 
-// K2 with per-env friction / actuator / damping scales (csrc/tmjx_wave_rand.hip): launched instead of K2 while the handle has scales set
+// K2 with per-env friction / actuator / damping scales and / or per-env gravity (csrc/tmjx_wave_rand.hip): launched instead of K2 while the
+// handle has either table set (a null table: unit scales / the model's gravity)
 extern "C" void tmjx_internal_launch_physics_wave_rand(int rodent, int cnt, size_t lds, hipStream_t stream, const DModel *mp, float *st,
                                                        const float *action, int nsub, int do_euler, float *ws_dump, int n, int e0, int rs,
-                                                       float *spill, int spill_stride, const float *env_scales, int scales_n);
+                                                       float *spill, int spill_stride, const float *env_scales, int scales_n,
+                                                       const float *env_gravity, int gravity_n);
 
 __global__ void k_reset_pre(const DModel *__restrict__ mp, float *st, int *is, const int *clip, const int *start, const float *qn,
                             const float *vn, float *ws, int n) {
@@ -363,6 +369,15 @@ int tmjx_set_env_scales(tmjx_model *m, const float *scales_dev, int n_env) {
   return TMJX_OK;
 }
 
+int tmjx_set_env_gravity(tmjx_model *m, const float *gravity_dev, int n_env) {
+  if (!m) return fail(TMJX_EINVAL, "null argument");
+  if (!gravity_dev) { m->env_gravity = nullptr; m->env_gravity_n = 0; return TMJX_OK; }
+  if (n_env < 1) return fail(TMJX_EINVAL, "tmjx_set_env_gravity: n_env must be >= 1");
+  if (!m->wave) return fail(TMJX_EINVAL, "tmjx_set_env_gravity: per-env gravity needs the wave-per-env implementation (the lane-per-env cross-check has no domain-randomisation path)");
+  m->env_gravity = gravity_dev; m->env_gravity_n = n_env;
+  return TMJX_OK;
+}
+
 int tmjx_set_action_repeat(tmjx_model *m, int action_repeat) {
   if (!m) return fail(TMJX_EINVAL, "null argument");
   if (action_repeat < 1 || action_repeat > TM_REP_MAX) return fail(TMJX_EINVAL, "action_repeat must be in 1 .. " + std::to_string(TM_REP_MAX));
@@ -440,16 +455,29 @@ int tmjx_clips_share(tmjx_model *m, const tmjx_model *owner) {
   return TMJX_OK;
 }
 
-static int launch_wave(const tmjx_model *m, float *state, const float *action, int nsub, int do_euler, float *ws, int n_env, hipStream_t stream,
-                       float *rec, float *sensordata, float *cfrc_ext) {
-  // the compile-time (rodent) kernel uses the chain layout, the run-time one the generic layout of the same dims
-  size_t lds = (size_t)(m->rodent ? m->h.lds_floats : tmjx_host::make_wave_layout(m->h, false).lds_floats) * sizeof(float);
-  if (m->env_scales) {   // (checked in front of everything a launch allocates or enqueues: a refused call has launched nothing)
-    if (cfrc_ext) return fail(TMJX_EINVAL, "tmjx_physics_sensors / tmjx_step_sensors: the handle has per-env scales set (tmjx_set_env_scales) and the "
+// the handle's per-env tables (tmjx_set_env_scales / tmjx_set_env_gravity) against a launch of `n_env` envs (`sensors`: of the recording kernel),
+// checked in front of everything a call allocates or enqueues: a refused call has launched nothing
+static int check_env_tables(const tmjx_model *m, int n_env, bool sensors) {
+  if (m->env_scales) {
+    if (sensors) return fail(TMJX_EINVAL, "tmjx_physics_sensors / tmjx_step_sensors: the handle has per-env scales set (tmjx_set_env_scales) and the "
                                            "recording kernel has no domain-randomisation build; clear the scales (NULL) or step without the sensor outputs");
     if (n_env > m->env_scales_n) return fail(TMJX_EINVAL, "launch of " + std::to_string(n_env) + " envs on a handle with per-env scales for " +
                                                               std::to_string(m->env_scales_n) + " (tmjx_set_env_scales)");
   }
+  if (m->env_gravity) {
+    if (sensors) return fail(TMJX_EINVAL, "tmjx_physics_sensors / tmjx_step_sensors: the handle has per-env gravity set (tmjx_set_env_gravity) and the "
+                                           "recording kernel has no domain-randomisation build; clear the gravity table (NULL) or step without the sensor outputs");
+    if (n_env > m->env_gravity_n) return fail(TMJX_EINVAL, "launch of " + std::to_string(n_env) + " envs on a handle with per-env gravity for " +
+                                                               std::to_string(m->env_gravity_n) + " (tmjx_set_env_gravity)");
+  }
+  return TMJX_OK;
+}
+
+static int launch_wave(const tmjx_model *m, float *state, const float *action, int nsub, int do_euler, float *ws, int n_env, hipStream_t stream,
+                       float *rec, float *sensordata, float *cfrc_ext) {
+  // the compile-time (rodent) kernel uses the chain layout, the run-time one the generic layout of the same dims
+  size_t lds = (size_t)(m->rodent ? m->h.lds_floats : tmjx_host::make_wave_layout(m->h, false).lds_floats) * sizeof(float);
+  if (int rc = check_env_tables(m, n_env, cfrc_ext != nullptr)) return rc;   // (in front of everything a launch allocates or enqueues)
   if (cfrc_ext) {   // recording kernel: the sensor stage's scratch behind the product image (wave_physics.h: TmwSens)
     lds = (size_t)tmw_sens_layout(m->rodent ? tmjx_host::make_wave_layout(m->h) : tmjx_host::make_wave_layout(m->h, false)).end * sizeof(float);
     if (lds > 64 * 1024) return fail(TMJX_EINVAL, "the sensor stage needs more than 64 KiB of LDS per env for this model");
@@ -477,8 +505,9 @@ static int launch_wave(const tmjx_model *m, float *state, const float *action, i
     int cnt = n_env / parts, e0 = p * cnt;
     if (cfrc_ext) tmjx_internal_launch_physics_wave_sensors(m->rodent ? 1 : 0, cnt, lds, stream, m->d, st, action, nsub, do_euler, ws, n_env, e0, rs, spill,
                                                             sstride, sensordata, cfrc_ext);
-    else if (m->env_scales) tmjx_internal_launch_physics_wave_rand(m->rodent ? 1 : 0, cnt, lds, stream, m->d, st, action, nsub, do_euler, ws, n_env, e0, rs, spill,
-                                                                   sstride, m->env_scales, m->env_scales_n);
+    else if (m->env_scales || m->env_gravity)
+      tmjx_internal_launch_physics_wave_rand(m->rodent ? 1 : 0, cnt, lds, stream, m->d, st, action, nsub, do_euler, ws, n_env, e0, rs, spill, sstride,
+                                             m->env_scales, m->env_scales_n, m->env_gravity, m->env_gravity_n);
     else tmjx_internal_launch_physics_wave(m->rodent ? 1 : 0, cnt, lds, stream, m->d, st, action, nsub, do_euler, ws, n_env, e0, rs, spill, sstride);
   }
   if (rec) hipLaunchKernelGGL(k_rec_out, dim3((n_env + 63) / 64, (m->h.s_prev_ctrl - m->h.s_qpos + REC_ROWS_PER_THREAD - 1) / REC_ROWS_PER_THREAD), dim3(64), 0, stream, m->d, state, (const float *)rec, n_env, rs);
@@ -500,6 +529,7 @@ int tmjx_reset(tmjx_model *m, float *state, int32_t *istate, const int32_t *clip
   if (n_env < 1) return fail(TMJX_EINVAL, "n_env must be >= 1");
   if (!m->h.clip_pos) return fail(TMJX_EINVAL, "tmjx_clips_upload has not been called");
   if (m->wave) {
+    if (int rc = check_env_tables(m, n_env, false)) return rc;   // (k_reset_pre is enqueued in front of the forward pass's launch)
     hipLaunchKernelGGL(k_reset_pre, GRID(m, n_env), 0, (hipStream_t)stream, m->d, state, istate, clip_idx, start_frame, qpos_noise,
                        qvel_noise, workspace, n_env);
     if (int rc = launch_wave(m, state, (const float *)nullptr, 1, 0, (float *)nullptr, n_env, (hipStream_t)stream)) return rc;

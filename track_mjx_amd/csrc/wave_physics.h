@@ -92,10 +92,15 @@ TM_DEV float tmw_rand_invweight(float t, float mu, float impratio) {
   return e / impratio;
 }
 #define TMW_CON_IW(cc) tmw_rand_invweight(m.con_tw[cc], TMW_MU(cc), m.impratio)
+// per-env gravity (tmjx_set_env_gravity): component k of THIS env's gravity vector, read in one place — the root acceleration of the bias-force
+// pass.  WCtx::has_g == 0 (what aggregate initialisation leaves: tests/hostemu) means the model's; the kernel unit always fills c.g (from its
+// table, or from the model when it has none) and sets the flag, so the choice costs the device nothing per use.
+#define TMW_GRAV(k) (c.has_g ? c.g[k] : m.gravity[k])
 #else
 #define TMW_RAND_ONLY(...)
 #define TMW_SCALE(x, s) x
 #define TMW_CON_IW(cc) m.con_invweight[cc]
+#define TMW_GRAV(k) m.gravity[k]
 #endif
 #define TMW_EMU_HAS_QA 1      // (tests/hostemu: WCtx carries the qa* / ma* registers)
 struct WCtx {
@@ -121,6 +126,7 @@ struct WCtx {
   int tp0[TMW_NL], tp1[TMW_NL];       // lean layout: packed index word of dof lane / lane + 64 (DModel::tpack; round 5: the table left LDS)
   float *mspill;              // chain layout (WLayout::m_spilled): this env's copy of M in global memory (nnz words, 64 readable words in front)
   TMW_RAND_ONLY(float s_f, s_a, s_d;)   // RAND build: this env's friction / actuator / damping scale (wave-uniform: one scalar load each per launch)
+  TMW_RAND_ONLY(int has_g; float g[3];) // RAND build: this env's gravity (world frame, wave-uniform), valid while has_g != 0; 0 = the model's (TMW_GRAV)
 };
 // solver statistics of the last substep, kept in the spare LDS word behind the centre of mass (registers are what this kernel has none
 // left of): 64 * CG iterations (MJX data.solver_niter) + line-search iterations summed over them; tmw_dump unpacks it for the tests
@@ -739,7 +745,7 @@ TM_DEV void tmw_velocity_inertia(WCtx &c, const WLayout &K) {
       int b = lane + 64 * slot;
       if (b >= K.nbody) continue;
       const float *cv = slot ? cv1[TMW_LI] : cv0[TMW_LI];
-      float ca[6] = {0.f, 0.f, 0.f, -m.gravity[0], -m.gravity[1], -m.gravity[2]}, I[10], f1[6], t[6], f2[6];
+      float ca[6] = {0.f, 0.f, 0.f, -TMW_GRAV(0), -TMW_GRAV(1), -TMW_GRAV(2)}, I[10], f1[6], t[6], f2[6];
       int ld = m.body_lastdof[b];
       if (ld >= 0) for (int k = 0; k < 6; k++) ca[k] += L[K.l_dscanA + ld * TMW_DS + k];
       for (int k = 0; k < 10; k++) I[k] = L[K.l_cinert + b * 10 + k];

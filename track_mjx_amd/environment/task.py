@@ -113,6 +113,7 @@ class MultiClipTracking:
         self._clip_owner = share_clips_with
         self._domain_randomization = None     # set_domain_randomization: the current per-env scales
         self._scales_dev = None               # ... and their [3][n] device tensor, which the handle reads by pointer
+        self._gravity_dev = None              # ... and the [3][n] per-env gravity table (tmjx_set_env_gravity), likewise
         self._create_handle()
         self._alloc()
 
@@ -367,9 +368,10 @@ class MultiClipTracking:
         return self._domain_randomization
 
     def set_domain_randomization(self, dr) -> None:
-        """Per-env friction / actuator / damping scales for every later physics launch of this env (None clears them: the handle then launches
-        the plain kernel again).  Uploads the [3][num_envs] table, keeps it alive and hands its pointer to the handle.  The sensor-recording step
-        (step_sensors) refuses an env with scales."""
+        """Per-env friction / actuator / damping scales and per-env gravity for every later physics launch of this env (None clears both: the
+        handle then launches the plain kernel again).  Uploads the [3][num_envs] tables, keeps them alive and hands their pointers to the handle:
+        the scales unless `dr` gives gravity alone, the gravity table when `dr.gravity` is set.  The sensor-recording step (step_sensors) refuses
+        an env with either."""
         from .randomization import DomainRandomization
         if dr is not None and not isinstance(dr, DomainRandomization):
             raise TypeError(f"set_domain_randomization takes a DomainRandomization or None, not {type(dr).__name__}")
@@ -377,14 +379,19 @@ class MultiClipTracking:
             raise ValueError(f"DomainRandomization for {dr.num_envs} envs on an env of {self.num_envs}")
         with torch.cuda.device(self.device):
             torch.cuda.synchronize(self.device)        # no launch of this handle may still read the old table
-            if dr is None:
-                _hip.check(self._L.tmjx_set_env_scales(self._handle, None, 0), "tmjx_set_env_scales")
-                self._scales_dev = None
-            else:
-                t = torch.from_numpy(dr.table()).to(self.device).contiguous()
+            tabs = {"scales": None, "gravity": None}
+            if dr is not None:
+                if dr.has_scales or dr.gravity is None:
+                    tabs["scales"] = torch.from_numpy(dr.table()).to(self.device).contiguous()
+                if dr.gravity is not None:
+                    tabs["gravity"] = torch.from_numpy(dr.gravity_table()).to(self.device).contiguous()
                 torch.cuda.synchronize(self.device)
-                _hip.check(self._L.tmjx_set_env_scales(self._handle, _ptr(t), self.num_envs), "tmjx_set_env_scales")
-                self._scales_dev = t
+            for name, t in tabs.items():
+                if name == "gravity" and t is None and self._gravity_dev is None:
+                    continue                       # (this env never set a gravity table: nothing to clear)
+                entry = f"tmjx_set_env_{name}"
+                _hip.check(getattr(self._L, entry)(self._handle, None if t is None else _ptr(t), 0 if t is None else self.num_envs), entry)
+            self._scales_dev, self._gravity_dev = tabs["scales"], tabs["gravity"]
         self._domain_randomization = dr
 
     def configure_wrappers(self, episode_length: int, auto_reset: bool, action_repeat: int = 1, done_policy: str | None = None) -> None:

@@ -34,7 +34,7 @@ def wrap(env: MultiClipTracking, episode_length: int = 1000, action_repeat: int 
     env.configure_wrappers(int(episode_length), auto_reset=True, action_repeat=int(action_repeat))
     if randomization_fn is not None:
         # brax's DomainRandomizationVmapWrapper (wrappers.py:44-47) steps every env with its own copy of the mjx.Model; the physics kernel reads
-        # ONE model from constant memory (csrc/dmodel.h) plus three per-env SCALARS (csrc/tmjx_wave_rand.hip): randomization_fn(model) returns a
+        # ONE model from constant memory (csrc/dmodel.h) plus three per-env SCALARS and the env's gravity (csrc/tmjx_wave_rand.hip): randomization_fn(model) returns a
         # DomainRandomization (environment/randomization.py); a per-env model raises NotImplementedError
         from .randomization import apply_randomization_fn
         apply_randomization_fn(env, randomization_fn)

@@ -45,7 +45,7 @@ EXPORTS = ("tmjx_model_create", "tmjx_model_destroy", "tmjx_layout", "tmjx_clips
            "tmjx_record_check", "tmjx_record_step", "tmjx_latent_concat_det", "tmjx_action_mode",
            "tmjx_decoder_input", "tmjx_decoder_act_ok", "tmjx_decoder_act", "tmjx_lstm_decoder_act_ok", "tmjx_lstm_decoder_act",
            "tmjx_sensor_info", "tmjx_physics_sensors", "tmjx_step_sensors",
-           "tmjx_set_done_policy", "tmjx_clips_upload_velocities", "tmjx_set_env_scales",
+           "tmjx_set_done_policy", "tmjx_clips_upload_velocities", "tmjx_set_env_scales", "tmjx_set_env_gravity",
            "tmjx_debug_rows", "tmjx_last_error", "tmjx_version")
 
 
@@ -360,6 +360,7 @@ def load(path: Path):
     sig.setdefault("tmjx_set_action_repeat", [None, None])[0] = [vp, C.c_int]
     sig.setdefault("tmjx_set_done_policy", [None, None])[0] = [vp, C.c_int]
     sig.setdefault("tmjx_set_env_scales", [None, None])[0] = [vp, fp, C.c_int]
+    sig.setdefault("tmjx_set_env_gravity", [None, None])[0] = [vp, fp, C.c_int]
     sig.setdefault("tmjx_clips_upload_velocities", [None, None])[0] = [vp, vp, vp, C.c_int, C.c_int]
     sig.setdefault("tmjx_stats_scratch_floats", [None, None])[0] = [C.c_int]
     sig.setdefault("tmjx_stats_sums", [None, None])[0] = [fp, fp, fp, fp, C.c_longlong, C.c_int, vp]

@@ -85,14 +85,18 @@ def restore_options(cfg: dict) -> dict:
 
 
 def randomization_options(cfg: dict) -> dict:
-    """ppo.train keywords of env_config.domain_randomization {friction_range, actuator_range, damping_range}: each (lo, hi) or null; all null
-    (the default) = no randomisation and no keyword.  A bad range is a ValueError here, before anything touches the GPU."""
+    """ppo.train keywords of env_config.domain_randomization {friction_range, actuator_range, damping_range, gravity_scale_range,
+    gravity_tilt_range}: each (lo, hi) or null; all null (the default; the two gravity keys are null when absent) = no randomisation and no
+    keyword.  gravity_scale_range multiplies the model's |gravity|, gravity_tilt_range is in degrees.  A bad range is a ValueError here, before
+    anything touches the GPU."""
     from .environment import uniform_randomization_fn
     dr = (cfg.get("env_config") or {}).get("domain_randomization") or {}
-    unknown = set(dr) - {"friction_range", "actuator_range", "damping_range"}
+    known = ("friction_range", "actuator_range", "damping_range", "gravity_scale_range", "gravity_tilt_range")
+    unknown = set(dr) - set(known)
     if unknown:
-        raise ValueError(f"env_config.domain_randomization: unknown keys {sorted(unknown)} (friction_range, actuator_range, damping_range)")
-    fn = uniform_randomization_fn(friction=dr.get("friction_range"), actuator=dr.get("actuator_range"), damping=dr.get("damping_range"))
+        raise ValueError(f"env_config.domain_randomization: unknown keys {sorted(unknown)} ({', '.join(known)})")
+    fn = uniform_randomization_fn(friction=dr.get("friction_range"), actuator=dr.get("actuator_range"), damping=dr.get("damping_range"),
+                                  gravity_scale=dr.get("gravity_scale_range"), gravity_tilt_deg=dr.get("gravity_tilt_range"))
     return {} if fn is None else {"randomization_fn": fn}
 
 
