@@ -695,6 +695,43 @@ typedef struct {
 int tmjx_lstm_decoder_act_ok(const tmjx_lstm_decoder_act_t *a);
 int tmjx_lstm_decoder_act(const tmjx_lstm_decoder_act_t *a, void *stream);
 
+/* ---- Rendering roll-outs (csrc/tmjx_render.hip, csrc/render_core.h; DESIGN.md "Rendering"): a ray-caster for the model's analytic primitives
+ * (plane, sphere, capsule, ellipsoid, box: the visible geoms of the blob's rgeom_* entries, tools/compile_model.py render_entries), the walker at
+ * `qpos` and optionally a translucent ghost at `qpos_ghost`, seen from one camera.  A handle whose blob carries no rgeom_* entries has no render
+ * tables: every entry point that takes the handle returns TMJX_EINVAL.  All device memory is the caller's, everything runs on the caller's stream,
+ * nothing synchronises.
+ *   Stage A (tmjx_render_pose): qpos [F][nq] row-major (and qpos_ghost [F_ghost][nq] or NULL; F_ghost must equal F) -> the workspace:
+ *     [F][cam_floats] camera records | [F][nprim][rec_floats] world-space primitive tables (at prims_offset) | the stage's scratch.
+ *     primitive record (20 floats): centre [3], rotation world-from-local row-major [9], size [3], rgb [3], type | id << 8 (int32 bits), ghost flag
+ *     (int32 bits; non-zero: drawn translucent grey);  camera record (16 floats): origin [3], X [3], Y [3], Z [3], tan(fovy / 2), 3 unused.
+ *   Stage B (tmjx_render_prims): tables prims [F][P][20] (16-byte aligned, 1 <= P <= 256) and cameras cams [F][16] -> rgba uint8 [F][H][W][4]
+ *     (alpha 255), optionally depth float [F][H][W] (distance along the ray of the nearest surface, inf on a miss) and geom_id int32 [F][H][W]
+ *     (the nearest surface's id: the visible-geom index, + ngeom where the ghost is nearest; -1 on a miss); NULL: not written.
+ *   tmjx_render: A then B (the same launches, the same bits).
+ * Camera: looks along -Z of its frame, +X right, +Y up, fovy the vertical field of view in degrees.  TMJX_CAMERA_TRACKCOM: origin =
+ * subtree_com(body) + offset, `quat` the orientation in WORLD axes (it does not turn with the body); TMJX_CAMERA_FIXED: offset and quat in the
+ * body's frame.  TMJX_CAMERA_TRACK is refused by name.  tmjx_render_camera fills the struct for one of the blob's named cameras (a trackcom
+ * camera with the offset and world orientation it has at qpos0); callers may also fill one themselves.
+ * Errors are returned before any launch: no render tables, unknown camera name, W or H < 1, F < 1, F_ghost != F, a body out of range. */
+#define TMJX_CAMERA_FIXED 0
+#define TMJX_CAMERA_TRACK 1
+#define TMJX_CAMERA_TRACKCOM 2
+typedef struct { int32_t body, mode; float offset[3], quat[4], fovy; } tmjx_camera_t;
+typedef struct {
+  int32_t ngeom, ncam;             /* visible geoms, named cameras */
+  int32_t rec_floats, cam_floats;  /* floats per primitive / camera record */
+  int32_t nprim;                   /* primitives per frame for the (F, ghost) asked about */
+  int64_t prims_offset;            /* workspace float index of the primitive tables (the cameras are at 0) */
+  int64_t workspace_floats;
+} tmjx_render_info_t;
+int tmjx_render_info(const tmjx_model *m, int F, int ghost, tmjx_render_info_t *out);
+int tmjx_render_camera(const tmjx_model *m, const char *name, tmjx_camera_t *out);
+int tmjx_render_pose(const tmjx_model *m, const float *qpos, const float *qpos_ghost, int F, int F_ghost, const tmjx_camera_t *cam, float *workspace,
+                     void *stream);
+int tmjx_render_prims(const float *prims, const float *cams, int F, int P, int W, int H, uint8_t *rgba, float *depth, int32_t *geom_id, void *stream);
+int tmjx_render(const tmjx_model *m, const float *qpos, const float *qpos_ghost, int F, int F_ghost, const tmjx_camera_t *cam, int W, int H,
+                float *workspace, uint8_t *rgba, float *depth, int32_t *geom_id, void *stream);
+
 const char *tmjx_last_error(void);
 const char *tmjx_version(void);
 

@@ -16,6 +16,7 @@ Output: track_mjx_amd/assets/rodent_model.tmjx  (binary blob, float64/int32)
         track_mjx_amd/assets/rodent_model_dump.txt (human-readable review copy)
 (side files are named after the output's stem: --out .../rodent_model_pos080.tmjx.txt writes rodent_model_pos080.names.txt and
 rodent_model_pos080_dump.txt; an --out ending in .tmjx.txt writes the blob's lossless text form, track_mjx_amd/blob.py).
+Every model also gets <stem>.render.tmjx.txt: the render tables (rgeom_* / rcam_*: render_entries) in text form.
 A model with a <sensor> block also gets <stem>.sensors.tmjx.txt: the sensor entries (site_* / sensor_*: sensor_entries) in text form.
 
 Actuator modes: torque_actuators=True rewrites the position servos into torque motors (the reference's default walker);
@@ -49,6 +50,10 @@ GEOM_PLANE, GEOM_SPHERE, GEOM_CAPSULE, GEOM_ELLIPSOID, GEOM_CYLINDER, GEOM_BOX =
 GEOM_TYPES = {"plane": 0, "hfield": 1, "sphere": 2, "capsule": 3, "ellipsoid": 4,
               "cylinder": 5, "box": 6, "mesh": 7}
 JNT_FREE, JNT_BALL, JNT_SLIDE, JNT_HINGE = 0, 1, 2, 3
+# camera mode codes of the render entry rcam_mode (mjtCamLight's numbering for the three modes that need no target body)
+CAMERA_MODES = {"fixed": 0, "track": 1, "trackcom": 2}
+RENDER_GROUPS = (0, 1, 2)      # visible geom groups: MuJoCo's default geomgroup
+RENDER_NAME_LEN = 32           # rcam_name: one row of character codes per camera, zero padded
 
 
 # --------------------------------------------------------------------------- math
@@ -115,6 +120,15 @@ def zaxis_to_quat(z):
     return axis_angle_quat(ax / s, ang)
 
 
+def xyaxes_to_quat(xy):
+    """MuJoCo xyaxes semantics: x normalised, y made orthogonal to x and normalised, z = x cross y; the frame's axes are the matrix columns."""
+    x, y = np.asarray(xy[:3], float), np.asarray(xy[3:6], float)
+    x = x / np.linalg.norm(x)
+    y = y - x * (x @ y)
+    y = y / np.linalg.norm(y)
+    return mat_to_quat(np.stack([x, y, np.cross(x, y)], axis=1))
+
+
 def fvec(s):
     return np.array([float(x) for x in s.split()], dtype=float)
 
@@ -126,6 +140,7 @@ class Body:
         self.pos = np.zeros(3)
         self.quat = np.array([1.0, 0, 0, 0])
         self.joints, self.geoms, self.sites, self.children = [], [], [], []
+        self.cameras = []
         self.id = -1
 
 
@@ -174,6 +189,13 @@ def orientation(attrs, eulerseq="xyz"):
     return np.array([1.0, 0, 0, 0])
 
 
+def camera_orientation(attrs):
+    """Orientation of a <camera>: xyaxes as well as what `orientation` resolves (quat / euler / zaxis)."""
+    if "xyaxes" in attrs and "quat" not in attrs:
+        return xyaxes_to_quat(fvec(attrs["xyaxes"]))
+    return orientation(attrs)
+
+
 def parse_body(el, parent, classes, childclass, bodies):
     b = Body(el.attrib.get("name", f"body{len(bodies)}"), parent)
     b.id = len(bodies)
@@ -194,6 +216,10 @@ def parse_body(el, parent, classes, childclass, bodies):
             a = resolve(ch, "site", classes, cc)
             a["_body"] = b
             b.sites.append(a)
+        elif ch.tag == "camera":
+            a = resolve(ch, "camera", classes, cc)
+            a["_body"] = b
+            b.cameras.append(a)
     for ch in el:
         if ch.tag == "body":
             b.children.append(parse_body(ch, b, classes, cc, bodies))
@@ -368,7 +394,8 @@ def compile_model(xml_path, torque_actuators=True, rescale_factor=0.9, affine_bi
                 friction=fvec(g.get("friction", "1 0.005 0.0001")),
                 solref=fvec(g.get("solref", "0.02 1")), solimp=g.get("solimp", "0.9 0.95 0.001 0.5 2"),
                 margin=float(g.get("margin", 0)), gap=float(g.get("gap", 0)),
-                solmix=float(g.get("solmix", 1))))
+                solmix=float(g.get("solmix", 1)),
+                rgba=fvec(g.get("rgba", "0.5 0.5 0.5 1")), group=int(g.get("group", 0))))
     ngeom = len(geoms)
 
     # ---- inertia from geoms (inertiafromgeom=auto, no <inertial> elements in this model)
@@ -505,6 +532,17 @@ def compile_model(xml_path, torque_actuators=True, rescale_factor=0.9, affine_bi
         sensor_adr.append(nsensordata)
         nsensordata += SENSOR_DIM[t]
 
+    # ---- cameras (render side file only: render_entries).  Camera positions are NOT rescaled (dm_scale_spec leaves cameras alone)
+    cameras = []
+    for bb in bodies:
+        for a in bb.cameras:
+            mode = a.get("mode", "fixed")
+            if mode not in CAMERA_MODES:
+                raise NotImplementedError(f"camera {a.get('name')}: mode {mode} is not compiled (supported: {', '.join(CAMERA_MODES)})")
+            cameras.append(dict(name=a.get("name", f"camera{len(cameras)}"), body=bb.id, mode=CAMERA_MODES[mode],
+                                pos=fvec(a["pos"]) if "pos" in a else np.zeros(3), quat=camera_orientation(a),
+                                fovy=float(a.get("fovy", 45.0))))
+
     # ---- options
     opt = {}
     for o in root.findall("option"):
@@ -531,6 +569,7 @@ def compile_model(xml_path, torque_actuators=True, rescale_factor=0.9, affine_bi
         act_ctrlrange=np.array(act_ctrlrange),
         gravity=gravity, geoms=geoms,
         site_names=site_names, sensor_names=sensor_names, nsensordata=nsensordata,
+        cameras=cameras,
     )
     if sensor_names:
         m["site_bodyid"], m["site_pos"], m["site_quat"] = np.array(site_bodyid), np.array(site_pos), np.array(site_quat)
@@ -755,6 +794,67 @@ def sensor_entries(m):
     return e
 
 
+def subtree_com(m, qpos, body):
+    """Centre of mass of `body` and every body below it, in float64 (bodies are numbered depth first)."""
+    xpos, xquat, _, _ = fk(m, qpos)
+    tot, acc = 0.0, np.zeros(3)
+    for b in range(body, m["nbody"]):
+        a = b
+        while a > body:
+            a = m["body_parentid"][a]
+        if a != body:
+            continue
+        tot += m["body_mass"][b]
+        acc += m["body_mass"][b] * (xpos[b] + quat_to_mat(xquat[b]) @ m["body_ipos"][b])
+    return acc / tot
+
+
+def render_entries(m):
+    """The render tables: every VISIBLE geom (groups 0-2) in XML order and every <camera>.  Like `sensor_entries` they are not part of the model
+    blob: they travel in the text side file <stem>.render.tmjx.txt, which walker.Rodent appends to the blob it loads.
+      rgeom_body / rgeom_type (GEOM_* codes) / rgeom_group [n], rgeom_size [n, 3] (scaled), rgeom_pos [n, 3] / rgeom_quat [n, 4] (body-local),
+      rgeom_rgba [n, 4];
+      rcam_name [ncam, 32] (character codes, zero padded), rcam_body / rcam_mode [ncam], rcam_pos [ncam, 3] / rcam_quat [ncam, 4] (body-local),
+      rcam_fovy [ncam] (degrees), and what a trackcom camera keeps from qpos0: rcam_off0 [ncam, 3] = world position - subtree_com(body),
+      rcam_wquat0 [ncam, 4] = world orientation."""
+    vis = [g for g in m["geoms"] if g["group"] in RENDER_GROUPS]
+    for g in vis:
+        if g["type"] in (GEOM_TYPES["mesh"], GEOM_TYPES["hfield"], GEOM_CYLINDER):
+            kind = [k for k, v in GEOM_TYPES.items() if v == g["type"]][0]
+            raise NotImplementedError(f"geom {g['name']}: type {kind} is not rendered (supported: plane, sphere, capsule, ellipsoid, box)")
+    e = OrderedDict()
+    e["rgeom_body"] = np.array([g["body"] for g in vis], dtype=np.int32)
+    e["rgeom_type"] = np.array([g["type"] for g in vis], dtype=np.int32)
+    e["rgeom_group"] = np.array([g["group"] for g in vis], dtype=np.int32)
+    for k, w in (("size", 3), ("pos", 3), ("quat", 4), ("rgba", 4)):
+        e[f"rgeom_{k}"] = np.array([g[k] for g in vis], dtype=np.float64).reshape(len(vis), w).ravel()
+    cams = m.get("cameras", [])
+    if cams:
+        names = np.zeros((len(cams), RENDER_NAME_LEN), dtype=np.int32)
+        for i, c in enumerate(cams):
+            code = c["name"].encode()
+            if len(code) >= RENDER_NAME_LEN:
+                raise ValueError(f"camera name too long: {c['name']}")
+            names[i, :len(code)] = list(code)
+        xpos, xquat, _, _ = fk(m, m["qpos0"])
+        off0, wq0 = [], []
+        for c in cams:
+            b = c["body"]
+            wpos = xpos[b] + quat_to_mat(xquat[b]) @ c["pos"]
+            off0.append(wpos - subtree_com(m, m["qpos0"], b) if m["body_mass"][b:].sum() > 0 and b > 0 else wpos)
+            wq = quat_mul(xquat[b], c["quat"])
+            wq0.append(wq / np.linalg.norm(wq))
+        e["rcam_name"] = names.ravel()
+        e["rcam_body"] = np.array([c["body"] for c in cams], dtype=np.int32)
+        e["rcam_mode"] = np.array([c["mode"] for c in cams], dtype=np.int32)
+        e["rcam_pos"] = np.array([c["pos"] for c in cams], dtype=np.float64).ravel()
+        e["rcam_quat"] = np.array([c["quat"] for c in cams], dtype=np.float64).ravel()
+        e["rcam_fovy"] = np.array([c["fovy"] for c in cams], dtype=np.float64)
+        e["rcam_off0"] = np.array(off0, dtype=np.float64).ravel()
+        e["rcam_wquat0"] = np.array(wq0, dtype=np.float64).ravel()
+    return e
+
+
 def dump_text(m, path):
     np.set_printoptions(precision=10, linewidth=160, suppress=False)
     with open(path, "w") as f:
@@ -807,6 +907,7 @@ def main():
     se = sensor_entries(m)
     if se:      # sensors: a text side file (blob.py's text form) named after the blob's stem
         blob.save(Path(args.out).with_name(blob.stem(args.out) + ".sensors" + blob.TEXT_SUFFIX), se)
+    blob.save(Path(args.out).with_name(blob.stem(args.out) + ".render" + blob.TEXT_SUFFIX), render_entries(m))
     names = Path(args.out).with_name(blob.stem(args.out) + ".names.txt")
     with open(names, "w") as f:
         for kind, lst in (("body", m["body_names"]), ("joint", m["jnt_names"]), ("actuator", m["act_names"]),

@@ -42,7 +42,12 @@ struct tmjx_model {
   // table set: the RAND kernel, which takes a null for the other
   const float *env_gravity = nullptr;
   int env_gravity_n = 0;
+  void *render = nullptr;    // render tables (csrc/tmjx_render.hip: tmjx_internal_render_create), null for a blob without rgeom_* entries
 };
+// the renderer's translation unit owns what `render` points to
+extern "C" int tmjx_internal_render_create(const void *blob, size_t nbytes, void **out);
+extern "C" void tmjx_internal_render_destroy(void *p);
+extern "C" const void *tmjx_internal_render(const tmjx_model *m) { return m->render; }
 #define WAVE_SPILL_STRIDE(m) ((((m)->h.nnz) + 63) & ~63)
 // record stride: state rows qpos .. qfrc_actuator, then the action, rounded up to 16 words
 #define WAVE_REC_STRIDE(m) ((((m)->h.s_prev_ctrl + (m)->h.nu) + 15) & ~15)
@@ -297,6 +302,7 @@ int tmjx_model_create(const void *blob, size_t nbytes, tmjx_model **out) {
   if (e != hipSuccess) { delete m; return fail(TMJX_ENOMEM, std::string("hipMalloc(DModel): ") + hipGetErrorString(e)); }
   e = hipMemcpy(m->d, &m->h, sizeof(DModel), hipMemcpyHostToDevice);
   if (e != hipSuccess) { hipFree(m->d); delete m; return fail(TMJX_EHIP, std::string("hipMemcpy(DModel): ") + hipGetErrorString(e)); }
+  if (int rc = tmjx_internal_render_create(blob, nbytes, &m->render)) { hipFree(m->d); delete m; return rc; }
   *out = m;
   return TMJX_OK;
 }
@@ -306,6 +312,7 @@ void tmjx_model_destroy(tmjx_model *m) {
   for (int i = 0; i < 7; i++) if (m->clips[i] && m->clips_owned) hipFree(m->clips[i]);
   if (m->d) hipFree(m->d);
   if (m->mspill) hipFree(m->mspill);
+  tmjx_internal_render_destroy(m->render);
   delete m;
 }
 

@@ -15,7 +15,7 @@ _PKG = Path(__file__).resolve().parent
 SO_PATH = Path(os.environ.get("TMJX_SO", str(_PKG / "libtmjx_hip.so")))  # TMJX_SO: alternative build (profiling)
 CSRC = _PKG / "csrc"
 SOURCES = (CSRC / "tmjx_hip.hip", CSRC / "tmjx_bf16.hip", CSRC / "tmjx_wave.hip", CSRC / "tmjx_chain.hip", CSRC / "tmjx_lstm.hip",
-           CSRC / "tmjx_rollout.hip", CSRC / "tmjx_wave_sensors.hip", CSRC / "tmjx_wave_align.hip", CSRC / "tmjx_wave_rand.hip")
+           CSRC / "tmjx_rollout.hip", CSRC / "tmjx_wave_sensors.hip", CSRC / "tmjx_wave_align.hip", CSRC / "tmjx_wave_rand.hip", CSRC / "tmjx_render.hip")
 # per-source compiler flags: the physics kernel's unit is built without machine LICM (csrc/tmjx_wave.hip says why)
 SOURCE_FLAGS = {"tmjx_wave.hip": ("-mllvm", "-disable-machine-licm"),
                 "tmjx_wave_sensors.hip": ("-mllvm", "-disable-machine-licm"),      # (the recording kernel: the same loop body)
@@ -46,6 +46,7 @@ EXPORTS = ("tmjx_model_create", "tmjx_model_destroy", "tmjx_layout", "tmjx_clips
            "tmjx_decoder_input", "tmjx_decoder_act_ok", "tmjx_decoder_act", "tmjx_lstm_decoder_act_ok", "tmjx_lstm_decoder_act",
            "tmjx_sensor_info", "tmjx_physics_sensors", "tmjx_step_sensors",
            "tmjx_set_done_policy", "tmjx_clips_upload_velocities", "tmjx_set_env_scales", "tmjx_set_env_gravity",
+           "tmjx_render_info", "tmjx_render_camera", "tmjx_render_pose", "tmjx_render_prims", "tmjx_render",
            "tmjx_debug_rows", "tmjx_last_error", "tmjx_version")
 
 
@@ -163,6 +164,19 @@ class RecordStream(C.Structure):
     """tmjx_record_stream_t (include/tmjx.h)."""
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p)] + [(k, C.c_int32) for k in ("layout", "ld", "w", "src_extent", "T", "t0", "n_idx")] + \
                [("idx", C.c_int32 * RECORD_MAX_IDX), ("pad_", C.c_int32)]
+
+
+CAMERA_FIXED, CAMERA_TRACK, CAMERA_TRACKCOM = 0, 1, 2      # TMJX_CAMERA_* (include/tmjx.h)
+
+
+class Camera(C.Structure):
+    """tmjx_camera_t (include/tmjx.h)."""
+    _fields_ = [("body", C.c_int32), ("mode", C.c_int32), ("offset", C.c_float * 3), ("quat", C.c_float * 4), ("fovy", C.c_float)]
+
+
+class RenderInfo(C.Structure):
+    """tmjx_render_info_t (include/tmjx.h)."""
+    _fields_ = [(k, C.c_int32) for k in ("ngeom", "ncam", "rec_floats", "cam_floats", "nprim")] + [("prims_offset", C.c_int64), ("workspace_floats", C.c_int64)]
 
 
 class PpoCfg(C.Structure):
@@ -383,6 +397,11 @@ def load(path: Path):
     sig.setdefault("tmjx_decoder_act", [None, None])[0] = [C.POINTER(DecoderAct), vp]
     sig.setdefault("tmjx_lstm_decoder_act_ok", [None, None])[0] = [C.POINTER(LstmDecoderAct)]
     sig.setdefault("tmjx_lstm_decoder_act", [None, None])[0] = [C.POINTER(LstmDecoderAct), vp]
+    sig.setdefault("tmjx_render_info", [None, None])[0] = [vp, C.c_int, C.c_int, C.POINTER(RenderInfo)]
+    sig.setdefault("tmjx_render_camera", [None, None])[0] = [vp, C.c_char_p, C.POINTER(Camera)]
+    sig.setdefault("tmjx_render_pose", [None, None])[0] = [vp, fp, fp, C.c_int, C.c_int, C.POINTER(Camera), fp, vp]
+    sig.setdefault("tmjx_render_prims", [None, None])[0] = [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp, fp, vp, vp]
+    sig.setdefault("tmjx_render", [None, None])[0] = [vp, fp, fp, C.c_int, C.c_int, C.POINTER(Camera), C.c_int, C.c_int, fp, vp, fp, vp, vp]
     sig.setdefault("tmjx_debug_rows", [None, None])[0] = [vp, C.c_char_p, ip, ip]
     sig.setdefault("tmjx_last_error", [None, None])[1] = C.c_char_p
     sig.setdefault("tmjx_version", [None, None])[1] = C.c_char_p

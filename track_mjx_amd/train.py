@@ -1,6 +1,7 @@
 """`python -m track_mjx_amd.train key=value ...` — mirror of the reference entrypoint
 (`python -m track_mjx.train`, track_mjx/train.py:56-363): builds walker, reward config, clips, env and the
-network sizes from the config and calls ppo.train.  hydra/wandb/orbax/rendering are out of scope;
+network sizes from the config and calls ppo.train.  hydra/wandb/orbax are out of scope; roll-outs are rendered by
+`python -m track_mjx_amd.analysis.render` (env_config.render_camera_name / render_fps, both optional), not during training;
 the derived quantities follow train.py:221-225 (episode_length) and :298-301 (num_evals, num_resets_per_eval).
 
 Multi-GPU: one process per GPU.  `python -m track_mjx_amd.train num_gpus=N ...` starts its own N ranks as a child

@@ -4,7 +4,7 @@ Reference: track_mjx/environment/walker/rodent.py:16-114 (constructor arguments,
 tables) and walker/base.py:70-88 (index properties).  The MuJoCo compile step is replaced by
 pre-compiled model blobs (tools/compile_model.py), one per (torque_actuators, rescale_factor)
 pair in `BLOBS` (binary `.tmjx`, or its lossless text form `.tmjx.txt`: blob.py; the sensor entries, when the model has sensors, in the text
-side file `<stem>.sensors.tmjx.txt`, appended to the loaded entries):
+side file `<stem>.sensors.tmjx.txt`, the render tables in `<stem>.render.tmjx.txt`, both appended to the loaded entries):
   - (True, 0.9)  `assets/rodent_model.tmjx`: the torque-actuator rewrite and the 0.9 rescale of
     rodent-full-clips.yaml:116-117 (the default walker of both named configurations);
   - (False, 0.8) `assets/rodent_model_pos080.tmjx.txt`: rodent.xml's position servos kept as written
@@ -55,6 +55,14 @@ class Rodent:
         self._body_names = list(body_names)
         self._end_eff_names = list(end_eff_names)
         self.model = _blob.load(self.blob_path)
+        # render tables (tools/compile_model.py render_entries): the text side file <stem>.render.tmjx.txt, appended behind the blob's own entries and in front of the sensor entries, which stay last
+        rend = _ASSETS / f"{_blob.stem(fname)}.render{_blob.TEXT_SUFFIX}"
+        if rend.exists():
+            extra = _blob.load(rend)
+            clash = [k for k in extra if k in self.model]
+            if clash:
+                raise ValueError(f"{rend.name}: entries {clash} are already in {fname}")
+            self.model.update(extra)
         # sensors (tools/compile_model.py sensor_entries): a text side file <stem>.sensors.tmjx.txt appended behind the blob's own entries
         sens = _ASSETS / f"{_blob.stem(fname)}.sensors{_blob.TEXT_SUFFIX}"
         if sens.exists():
@@ -80,6 +88,33 @@ class Rodent:
         adr = [int(a) for a in self.model["sensor_adr"]]
         ends = adr[1:] + [self.nsensordata]
         return [(n, a, e - a) for n, a, e in zip(names, adr, ends)]
+
+    def render_table(self) -> "dict[str, np.ndarray]":
+        """The visible geoms of the blob in XML order: body, type, group [n], size, pos [n, 3], quat, rgba [n, 4]; {} for a blob without
+        render tables."""
+        if "rgeom_type" not in self.model:
+            return {}
+        n = len(self.model["rgeom_type"])
+        out = {k: np.asarray(self.model[f"rgeom_{k}"]) for k in ("body", "type", "group")}
+        out.update({k: np.asarray(self.model[f"rgeom_{k}"], np.float64).reshape(n, w) for k, w in (("size", 3), ("pos", 3), ("quat", 4), ("rgba", 4))})
+        return out
+
+    def cameras(self) -> "dict[str, dict]":
+        """name -> {body, mode ('fixed' | 'track' | 'trackcom'), pos, quat (body-local), fovy (degrees), off0, wquat0 (a trackcom camera's world
+        offset from its body's subtree centre of mass and world orientation at qpos0)}, in XML order; {} for a blob without cameras."""
+        if "rcam_name" not in self.model:
+            return {}
+        names = np.asarray(self.model["rcam_name"]).reshape(-1, 32)
+        modes = {0: "fixed", 1: "track", 2: "trackcom"}
+        out = {}
+        for i, row in enumerate(names):
+            name = bytes(int(c) for c in row if c).decode()
+            out[name] = dict(body=int(self.model["rcam_body"][i]), mode=modes[int(self.model["rcam_mode"][i])],
+                             pos=np.asarray(self.model["rcam_pos"], np.float64).reshape(-1, 3)[i],
+                             quat=np.asarray(self.model["rcam_quat"], np.float64).reshape(-1, 4)[i], fovy=float(self.model["rcam_fovy"][i]),
+                             off0=np.asarray(self.model["rcam_off0"], np.float64).reshape(-1, 3)[i],
+                             wquat0=np.asarray(self.model["rcam_wquat0"], np.float64).reshape(-1, 4)[i])
+        return out
 
     @property
     def nsensordata(self) -> int:
