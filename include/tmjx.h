@@ -695,6 +695,37 @@ typedef struct {
 int tmjx_lstm_decoder_act_ok(const tmjx_lstm_decoder_act_t *a);
 int tmjx_lstm_decoder_act(const tmjx_lstm_decoder_act_t *a, void *stream);
 
+/* ---- The acting policy as ONE small-footprint launch (csrc/policy_act.h, csrc/tmjx_act.hip; make_inference_fn, ppo_networks.py:46-96; the intention
+ * network's encoder, reparameterize and decoder, intention_network.py:32-44,68-88):
+ *   h = encoder blocks((obs[:, :ref_w] - mean) * inv_std);  fc2 = h W2^T + b2 = [latent mean | latent logvar];
+ *   x = [ mean + eps exp(logvar / 2) | (obs[:, ref_w:] - nmean) / nstd | 0 .. ];  logits = decoder blocks(x) Wh^T + bh;
+ *   raw = loc + scale noise, action = tanh(raw), logp = log-prob of the sample — every block Dense -> SiLU -> LayerNorm, 256 wide.
+ * It replaces, with the same bits in every output, the launches tmjx_linear_act / tmjx_silu_ln_fwd (per block), tmjx_linear_act (fc2),
+ * tmjx_latent_concat, the decoder's blocks, tmjx_linear_act (head) and tmjx_sample_action.  One workgroup of 256 threads owns 16 rows through the whole
+ * policy: <= 96 registers and 18 944 bytes of LDS, so that it runs next to a full house of physics waves; no activation leaves the CU.
+ * obs: the raw observation, row-major [n][ldo] with 16-byte aligned rows.  K0 = ref_w rounded up to a multiple of 4: the row length of enc[0].W, whose
+ * columns [ref_w, K0) are zero, and of mean / inv_std (both or neither; pad 0 / 0).  nmean / nstd [obs_w] (both or neither): the normaliser of the
+ * proprioceptive columns, applied as a division.  enc[0].W [256][ldw >= K0], dec[0].W [256][ldw >= Z + obs_w - ref_w rounded up to 4] (pad columns
+ * zero), every other block [256][ldw >= 256], W2 [2Z][ldw2 >= 256], Wh [2A][ldwh >= 256]: rows 16-byte aligned; bias / gamma / beta 16-byte aligned.
+ * eps [n][Z] and noise [n][A]: the caller's N(0, 1) draws, or both NULL: Philox streams 2 and 3 of (seed, rng_state[0]), and the launch advances
+ * rng_state[0] by one (rng_state [2] int64: draw counter, ticket) as tmjx_sample_action does.
+ * Outputs: fc2 [n][2Z], logits [n][2A], raw [n][A], action_t [A][n] (the layout tmjx_step takes), logp [n].
+ * Qualifying shapes: every block width == 256, 1 .. TMJX_CHAIN_MAX_HIDDEN blocks per stack, Z + obs_w - ref_w <= 288, 2Z <= 256, 2A <= 256, any n >= 1.
+ * tmjx_policy_act_ok says whether a descriptor qualifies (no error recorded, no device call); the entry point returns TMJX_EINVAL with the reason
+ * before any device call. */
+typedef struct {
+  const float *obs; int64_t ldo;
+  const float *mean, *inv_std, *nmean, *nstd;
+  int32_t n, K0, Z, obs_w, ref_w, A, n_enc, n_dec;
+  tmjx_decoder_block_t enc[TMJX_CHAIN_MAX_HIDDEN], dec[TMJX_CHAIN_MAX_HIDDEN];
+  const float *W2, *b2; int32_t ldw2, ldwh; const float *Wh, *bh;
+  const float *eps, *noise; uint64_t seed; int64_t *rng_state;
+  float ln_eps; int32_t pad_;
+  float *fc2, *logits, *raw, *action_t, *logp;
+} tmjx_policy_act_t;
+int tmjx_policy_act_ok(const tmjx_policy_act_t *a);
+int tmjx_policy_act(const tmjx_policy_act_t *a, void *stream);
+
 /* ---- Rendering roll-outs (csrc/tmjx_render.hip, csrc/render_core.h; DESIGN.md "Rendering"): a ray-caster for the model's analytic primitives
  * (plane, sphere, capsule, ellipsoid, box: the visible geoms of the blob's rgeom_* entries, tools/compile_model.py render_entries), the walker at
  * `qpos` and optionally a translucent ghost at `qpos_ghost`, seen from one camera.  A handle whose blob carries no rgeom_* entries has no render

@@ -524,6 +524,19 @@ class PPOLearner:
                 rs = self._act_rng_state(gen)
                 rng_state, rng_seed = rs[0], rs[1]
             eps = None if device_rng else torch.randn((n, Z), generator=gen, device=self.dev)
+            # the whole policy as ONE small-footprint launch (tmjx_policy_act, csrc/policy_act.h) where the nets qualify: fp32, 256-wide blocks, a
+            # row-major observation — the same bits as the launches below, which everything else keeps (TMJX_NO_POLICY_ACT=1: all of it)
+            if lds_free and bf is None and not os.environ.get("TMJX_NO_POLICY_ACT"):
+                d = self._policy_act_descriptor(src, fold)
+                if d is not None:
+                    noise = None if device_rng else torch.randn((n, A), generator=gen, device=self.dev)
+                    fc2, logits = torch.empty((n, 2 * Z), **f32), torch.empty((n, 2 * A), **f32)
+                    raw, action_t, logp = torch.empty((n, A), **f32), torch.empty((A, n), **f32), torch.empty(n, **f32)
+                    d.eps, d.noise, d.seed, d.rng_state = p(eps), p(noise), rng_seed if device_rng else 0, p(rng_state) if device_rng else None
+                    d.fc2, d.logits, d.raw, d.action_t, d.logp = p(fc2), p(logits), p(raw), p(action_t), p(logp)
+                    _hip.check(L.tmjx_policy_act(C.byref(d), stream), "tmjx_policy_act")
+                    mean, logvar = torch.chunk(fc2, 2, dim=-1)
+                    return action_t.t(), {"raw_action": raw, "log_prob": logp, "logits": logits, "latent_mean": mean, "latent_logvar": logvar}
             if lds_free:
                 h, first = None, True
                 for blk in pol.encoder:
@@ -552,6 +565,43 @@ class PPOLearner:
                                             p(rng_state) if device_rng else None, stream), "tmjx_sample_action")
         mean, logvar = torch.chunk(fc2, 2, dim=-1)
         return action_t.t(), {"raw_action": raw, "log_prob": logp, "logits": logits, "latent_mean": mean, "latent_logvar": logvar}
+
+    def _policy_act_descriptor(self, src: torch.Tensor, fold: bool):
+        """tmjx_policy_act_t of this policy on the raw observation `src` (without the draws and the outputs), or None where the kernel does not
+        take the nets or the operand (tmjx_policy_act_ok: other widths, a K-major observation, ...): the caller then launches layer by layer."""
+        import ctypes
+        from .. import hip as _hip
+        pol = self.policy
+        enc, dec = list(pol.encoder), list(pol.decoder)
+        if not (1 <= len(enc) <= _hip.CHAIN_MAX_HIDDEN and 1 <= len(dec) <= _hip.CHAIN_MAX_HIDDEN) or src.stride(1) != 1:
+            return None
+        if len({float(blk.norm.eps) for blk in enc + dec}) != 1:
+            return None
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        d = _hip.PolicyAct()
+        d.obs, d.ldo = src.data_ptr(), src.stride(0)
+        if fold:
+            d.mean, d.inv_std, d.nmean, d.nstd = self._fold[0].data_ptr(), self._fold[1].data_ptr(), self.normalizer.mean.data_ptr(), self.normalizer.std.data_ptr()
+        d.n, d.Z, d.obs_w, d.ref_w, d.A, d.n_enc, d.n_dec = src.shape[0], pol.latents, src.shape[1], pol.reference_obs_size, pol.action_size, len(enc), len(dec)
+        for blocks, dst in ((enc, d.enc), (dec, d.dec)):
+            for l, blk in enumerate(blocks):
+                w = self._padded_weight(blk.dense)
+                if w.dtype != torch.float32 or blk.dense.bias is None:
+                    return None
+                dst[l] = _hip.DecoderBlock(w.data_ptr(), blk.dense.bias.data_ptr(), blk.norm.weight.data_ptr(), blk.norm.bias.data_ptr(), blk.dense.out_features, w.stride(0))
+        d.K0 = self._padded_weight(enc[0].dense).shape[1]
+        for lin in (pol.fc2, pol.head):
+            if lin.in_features % 4 or lin.weight.dtype != torch.float32:
+                return None
+        d.W2, d.b2, d.ldw2 = pol.fc2.weight.data_ptr(), ptr(pol.fc2.bias), pol.fc2.weight.stride(0)
+        d.Wh, d.bh, d.ldwh = pol.head.weight.data_ptr(), ptr(pol.head.bias), pol.head.weight.stride(0)
+        if pol.fc2.out_features != 2 * pol.latents or pol.head.out_features != 2 * pol.action_size:
+            return None
+        d.ln_eps = float(enc[0].norm.eps)
+        # (outputs and draws are the caller's: the predicate is asked with stand-ins that pass its null checks)
+        d.fc2 = d.logits = d.raw = d.action_t = d.logp = d.obs
+        d.rng_state = d.obs
+        return d if _hip.lib().tmjx_policy_act_ok(ctypes.byref(d)) else None
 
     def _act_rng_state(self, gen):
         """(device counter [2] int64, Philox key, generator) of the acting noise stream that belongs to a torch generator."""

@@ -10,6 +10,7 @@
 //   out     [8]: total, policy_loss, v_loss, entropy_loss, kl_latent_loss, adv_mean, adv_std, entropy
 #pragma once
 #include "silu_math.h"
+#include "act_shared.h"          // ppo_softplus, ppo_fldj, PPO_G, ppo_group_sum, wave_sum, Philox, and the acting policy's shared epilogue bodies
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -22,9 +23,7 @@ struct PpoCfg {
 
 #define PPO_BLOCK 256
 #define PPO_ALPHA 0.95f
-__device__ __forceinline__ float ppo_softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }
 __device__ __forceinline__ float ppo_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-__device__ __forceinline__ float ppo_fldj(float x) { return 2.f * (0.69314718055994531f - x - ppo_softplus(-2.f * x)); }
 
 // block-wide sum of NV values per thread; result valid in thread 0
 template <int NV>
@@ -46,8 +45,6 @@ __device__ __forceinline__ void ppo_block_sum(float *v, float *lds) {
 
 // A: per (t, b): log-prob of the stored action, entropy sample, latent-KL sums.  PPO_G = 8 lanes share one (t, b): lane s takes
 // the action / latent dims s, s + 8, .. (8 consecutive floats per load instead of one float per 304-byte row per lane)
-#define PPO_G 8
-__device__ __forceinline__ float ppo_group_sum(float x) { x += __shfl_xor(x, 4); x += __shfl_xor(x, 2); x += __shfl_xor(x, 1); return x; }
 __global__ __launch_bounds__(PPO_BLOCK) void k_ppo_a(PpoCfg c, const float *__restrict__ logits, const float *__restrict__ raw_action,
                                                      const float *__restrict__ noise, const float *__restrict__ fc2, float *scratch, int nblk) {
   __shared__ float lds[64];
@@ -426,7 +423,6 @@ __global__ void k_ppo_d(PpoCfg c, const float *scratch, float *out, int nblk, co
 // shuffles.  The backward kernel also produces the column sums d_gamma, d_beta, d_bias as per-block partials (rows are
 // dealt to blocks in contiguous slabs) that a second small kernel adds up: deterministic, no atomics.
 #define BLK_ROWS_PER_BLOCK 32
-__device__ __forceinline__ float wave_sum(float x) { for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off); return x; }
 
 // Column of register k of a lane: the lane's VPT columns are dealt in groups of four CONSECUTIVE ones, group j of lane l at column 4 (64 j + l):
 // a wave instruction then reads 64 adjacent 16-byte pieces = whole cache lines (VPT consecutive columns per lane — 32 / 64 bytes apart at H = 512 /
@@ -481,16 +477,9 @@ __global__ __launch_bounds__(256) void k_silu_ln_fwd(const float *__restrict__ z
   silu_ln_load<VPT>(b, bias, lane); silu_ln_load<VPT>(g, gamma, lane); silu_ln_load<VPT>(be, beta, lane);
   const int wpb = blockDim.x >> 6;         // waves (= rows in flight) per block: 4, or 1 for the acting policy (tmjx_silu_ln_fwd)
   for (int r = blockIdx.x * wpb + w; r < rows; r += gridDim.x * wpb) {
-    float a[VPT], s = 0.f;
+    float a[VPT], mean, rstd;
     silu_ln_load<VPT>(a, z + (size_t)r * H, lane);
-#pragma unroll
-    for (int k = 0; k < VPT; k++) { float v = a[k] + b[k]; a[k] = tm_silu(v); s += a[k]; }
-    float mean = wave_sum(s) / (float)H, q = 0.f;
-#pragma unroll
-    for (int k = 0; k < VPT; k++) { float d = a[k] - mean; q += d * d; }
-    float rstd = rsqrtf(wave_sum(q) / (float)H + eps);
-#pragma unroll
-    for (int k = 0; k < VPT; k++) a[k] = (a[k] - mean) * rstd * g[k] + be[k];
+    silu_ln_row<VPT>(a, b, g, be, eps, mean, rstd);          // (csrc/act_shared.h: the body k_policy_act runs on its LDS image)
     silu_ln_store<VPT, OUT16>(a, OUT16 ? nullptr : y + (size_t)r * H, OUT16 ? y16 + (size_t)r * ldy16 : nullptr, lane);
     if (lane == 0) { stats[2 * (size_t)r] = mean; stats[2 * (size_t)r + 1] = rstd; }
   }
@@ -777,30 +766,7 @@ struct MinibatchGather {
   int T, R, B, W, A, Z, advance;
   unsigned short *obs_n16; int ld16;      // optional bf16 twin of obs_n: [T B][ld16 >= W] (columns beyond W are the caller's: zeros)
 };
-// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11; the Random123 constants)
-__device__ __forceinline__ void tm_philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned *out) {
-#pragma unroll
-  for (int r = 0; r < 10; r++) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (unsigned)p1; c3 = (unsigned)p0; c0 = n0; c2 = n2;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-// four N(0, 1) draws for elements 4 q .. 4 q + 3 of stream `sid` at draw counter `ctr` (Box-Muller on 24-bit uniforms in (0, 1))
-__device__ __forceinline__ void tm_normal4(unsigned long long seed, unsigned long long ctr, unsigned sid, unsigned q, float *n) {
-  unsigned x[4];
-  tm_philox4x32_10(q, sid, (unsigned)ctr, (unsigned)(ctr >> 32), (unsigned)seed, (unsigned)(seed >> 32), x);
-#pragma unroll
-  for (int h = 0; h < 2; h++) {
-    const float u1 = ((float)(x[2 * h] >> 8) + 0.5f) * (1.f / 16777216.f), u2 = ((float)(x[2 * h + 1] >> 8) + 0.5f) * (1.f / 16777216.f);
-    const float r = sqrtf(-2.f * logf(u1));
-    float sn, cs;
-    sincospif(2.f * u2, &sn, &cs);
-    n[2 * h] = r * cs; n[2 * h + 1] = r * sn;
-  }
-}
+// (Philox4x32-10 and the N(0, 1) draws, tm_philox4x32_10 / tm_normal4: csrc/act_shared.h)
 __global__ __launch_bounds__(256) void k_gather_minibatch(MinibatchGather g) {
   const int w4 = g.W >> 2;
   // every block reads the state before it can have been advanced: the advance is made by the block that FINISHES last (ticket below)
@@ -885,11 +851,8 @@ __global__ __launch_bounds__(256) void k_latent_concat(const float *__restrict__
     int c = (int)(i % x_stride); size_t e = i / x_stride;
     float v = 0.f;
     if (c < Z) {
-      float ep;
-      if (eps) ep = eps[e * Z + c];
-      else { float v4[4]; const size_t idx = e * Z + c; tm_normal4(seed, ctr, 2u, (unsigned)(idx >> 2), v4); ep = v4[idx & 3]; }
-      v = fmaf(ep, expf(0.5f * fc2[e * 2 * Z + Z + c]), fc2[e * 2 * Z + c]);       // (written as the fused multiply-add it compiles to: the encoder chain's latent tail, csrc/mlp_chain.h, forms the same)
-    } else if (c < W) { int k = ref_w + c - Z; v = obs[(long long)e * obs_s0 + (long long)k * obs_s1]; if (mean) v = (v - mean[k]) / stdv[k]; }
+      v = tm_latent_sample(tm_normal_at(eps, seed, ctr, 2u, e * Z + c), fc2[e * 2 * Z + Z + c], fc2[e * 2 * Z + c]);       // (csrc/act_shared.h)
+    } else if (c < W) { int k = ref_w + c - Z; v = obs[(long long)e * obs_s0 + (long long)k * obs_s1]; if (mean) v = tm_obs_normalised(v, mean[k], stdv[k]); }
     x[e * (size_t)x_stride + c] = v;
   }
 }
@@ -918,18 +881,7 @@ __global__ __launch_bounds__(PPO_BLOCK) void k_sample_action(const float *__rest
   const int gid = blockIdx.x * blockDim.x + threadIdx.x, e = gid / PPO_G, sub = gid % PPO_G;
   const unsigned long long ctr = rng_state ? (unsigned long long)rng_state[0] : 0ull;
   float lp = 0.f;
-  if (e < n) {
-    const float *lg = logits + (size_t)e * 2 * A;
-    for (int a = sub; a < A; a += PPO_G) {
-      float nz;
-      if (noise) nz = noise[(size_t)e * A + a];
-      else { float v4[4]; const size_t idx = (size_t)e * A + a; tm_normal4(seed, ctr, 3u, (unsigned)(idx >> 2), v4); nz = v4[idx & 3]; }
-      float loc = lg[a], scale = ppo_softplus(lg[A + a]) + 0.001f, x = loc + scale * nz, d = (x - loc) / scale;
-      raw[(size_t)e * A + a] = x;
-      action_t[(size_t)a * n + e] = tanhf(x);          // [A][n]: the env-minor layout tmjx_step takes
-      lp += -0.5f * d * d - logf(scale) - 0.91893853320467274f - ppo_fldj(x);
-    }
-  }
+  if (e < n) lp = sample_action_lane(logits + (size_t)e * 2 * A, noise, raw, action_t, n, A, (size_t)e, sub, seed, ctr);      // (csrc/act_shared.h)
   lp = ppo_group_sum(lp);
   if (e < n && sub == 0) logp[e] = lp;
   if (rng_state) {

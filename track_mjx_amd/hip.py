@@ -15,7 +15,7 @@ _PKG = Path(__file__).resolve().parent
 SO_PATH = Path(os.environ.get("TMJX_SO", str(_PKG / "libtmjx_hip.so")))  # TMJX_SO: alternative build (profiling)
 CSRC = _PKG / "csrc"
 SOURCES = (CSRC / "tmjx_hip.hip", CSRC / "tmjx_bf16.hip", CSRC / "tmjx_wave.hip", CSRC / "tmjx_chain.hip", CSRC / "tmjx_lstm.hip",
-           CSRC / "tmjx_rollout.hip", CSRC / "tmjx_wave_sensors.hip", CSRC / "tmjx_wave_align.hip", CSRC / "tmjx_wave_rand.hip", CSRC / "tmjx_render.hip")
+           CSRC / "tmjx_rollout.hip", CSRC / "tmjx_wave_sensors.hip", CSRC / "tmjx_wave_align.hip", CSRC / "tmjx_wave_rand.hip", CSRC / "tmjx_render.hip", CSRC / "tmjx_act.hip")
 # per-source compiler flags: the physics kernel's unit is built without machine LICM (csrc/tmjx_wave.hip says why)
 SOURCE_FLAGS = {"tmjx_wave.hip": ("-mllvm", "-disable-machine-licm"),
                 "tmjx_wave_sensors.hip": ("-mllvm", "-disable-machine-licm"),      # (the recording kernel: the same loop body)
@@ -44,6 +44,7 @@ EXPORTS = ("tmjx_model_create", "tmjx_model_destroy", "tmjx_layout", "tmjx_clips
            "tmjx_lstm_hidden_ok", "tmjx_lstm_seq_fwd", "tmjx_lstm_seq_bwd",
            "tmjx_record_check", "tmjx_record_step", "tmjx_latent_concat_det", "tmjx_action_mode",
            "tmjx_decoder_input", "tmjx_decoder_act_ok", "tmjx_decoder_act", "tmjx_lstm_decoder_act_ok", "tmjx_lstm_decoder_act",
+           "tmjx_policy_act_ok", "tmjx_policy_act",
            "tmjx_sensor_info", "tmjx_physics_sensors", "tmjx_step_sensors",
            "tmjx_set_done_policy", "tmjx_clips_upload_velocities", "tmjx_set_env_scales", "tmjx_set_env_gravity",
            "tmjx_render_info", "tmjx_render_camera", "tmjx_render_pose", "tmjx_render_prims", "tmjx_render",
@@ -112,6 +113,16 @@ class DecoderAct(C.Structure):
                 ("std", C.c_void_p), ("n", C.c_int32), ("Z", C.c_int32), ("obs_w", C.c_int32), ("ref_w", C.c_int32), ("n_blocks", C.c_int32),
                 ("block", DecoderBlock * CHAIN_MAX_HIDDEN), ("Wf", C.c_void_p), ("bf", C.c_void_p), ("ldwf", C.c_int32), ("A", C.c_int32), ("eps", C.c_float),
                 ("action_t", C.c_void_p), ("ctrl", C.c_void_p), ("logits", C.c_void_p), ("ldl", C.c_int32)]
+
+
+class PolicyAct(C.Structure):
+    """tmjx_policy_act_t (include/tmjx.h)."""
+    _fields_ = ([("obs", C.c_void_p), ("ldo", C.c_int64)] + [(k, C.c_void_p) for k in ("mean", "inv_std", "nmean", "nstd")] +
+                [(k, C.c_int32) for k in ("n", "K0", "Z", "obs_w", "ref_w", "A", "n_enc", "n_dec")] +
+                [("enc", DecoderBlock * CHAIN_MAX_HIDDEN), ("dec", DecoderBlock * CHAIN_MAX_HIDDEN), ("W2", C.c_void_p), ("b2", C.c_void_p),
+                 ("ldw2", C.c_int32), ("ldwh", C.c_int32), ("Wh", C.c_void_p), ("bh", C.c_void_p), ("eps", C.c_void_p), ("noise", C.c_void_p),
+                 ("seed", C.c_uint64), ("rng_state", C.c_void_p), ("ln_eps", C.c_float), ("pad_", C.c_int32)] +
+                [(k, C.c_void_p) for k in ("fc2", "logits", "raw", "action_t", "logp")])
 
 
 LSTM_DECODER_MAX_LAYERS = 4  # TMJX_LSTM_DECODER_MAX_LAYERS (include/tmjx.h)
@@ -397,6 +408,8 @@ def load(path: Path):
     sig.setdefault("tmjx_decoder_act", [None, None])[0] = [C.POINTER(DecoderAct), vp]
     sig.setdefault("tmjx_lstm_decoder_act_ok", [None, None])[0] = [C.POINTER(LstmDecoderAct)]
     sig.setdefault("tmjx_lstm_decoder_act", [None, None])[0] = [C.POINTER(LstmDecoderAct), vp]
+    sig.setdefault("tmjx_policy_act_ok", [None, None])[0] = [C.POINTER(PolicyAct)]
+    sig.setdefault("tmjx_policy_act", [None, None])[0] = [C.POINTER(PolicyAct), vp]
     sig.setdefault("tmjx_render_info", [None, None])[0] = [vp, C.c_int, C.c_int, C.POINTER(RenderInfo)]
     sig.setdefault("tmjx_render_camera", [None, None])[0] = [vp, C.c_char_p, C.POINTER(Camera)]
     sig.setdefault("tmjx_render_pose", [None, None])[0] = [vp, fp, fp, C.c_int, C.c_int, C.POINTER(Camera), fp, vp]
