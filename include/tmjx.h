@@ -763,6 +763,45 @@ int tmjx_render_prims(const float *prims, const float *cams, int F, int P, int W
 int tmjx_render(const tmjx_model *m, const float *qpos, const float *qpos_ghost, int F, int F_ghost, const tmjx_camera_t *cam, int W, int H,
                 float *workspace, uint8_t *rgba, float *depth, int32_t *geom_id, void *stream);
 
+/* ---- PCA of recorded activations and the progression panel (csrc/tmjx_pca.hip, csrc/pca_core.h; DESIGN.md "PCA").  No model handle; all device
+ * memory is the caller's; everything runs on the caller's stream.
+ *   tmjx_pca_workspace: *floats = the float count of the workspace tmjx_pca_fit needs for an [n][d] input.
+ *   tmjx_pca_fit: x [n][ldx] float32 (the first d columns are used, ldx >= d: a column slice of a wider buffer is fine) -> mean [d],
+ *     components [d][d] (row j: the unit-norm principal axis of the j-th largest variance, its largest-magnitude coefficient positive, the lowest
+ *     index winning a tie) and variance [d] (eigenvalues of the covariance with divisor n - 1, clamped at 0, descending).  Two passes over x (column
+ *     means in float64; the centred Gram matrix in float32 per PCA_ROWS_PER_WG = 256 rows, the partials added in a fixed order in float64: no
+ *     atomics, the same bits on every run), then one workgroup of parallel-ordered cyclic Jacobi on the float32 covariance.  The call WAITS for the
+ *     stream (it reads the solver's report back) and fills *info; a solver that reaches its sweep limit without off(A) <= 2^-24 ||A||_F (a NaN in x
+ *     does that) returns TMJX_ENOCONV, with mean / components / variance written but not to be used.  Zero total variance: variance 0, components
+ *     the identity.  Refused before any launch (TMJX_EINVAL): d < 1, d > 128 (by name, with the limit), n < 2, ldx < d, a null pointer, a workspace
+ *     that is not 16-byte aligned.
+ *   tmjx_pca_transform: out [n][ldo], columns [0, k) = (x - mean) . components[c] for the first k rows of components [k..][d] (row stride d);
+ *     nothing synchronises.  Refused: d < 1, d > 128, n < 1, ldx < d, k < 1, k > d, ldo < k, a null pointer.
+ *   tmjx_plot_strips: the progression panel, rgba uint8 [F][H][W][4] (alpha 255, the renderer's layout), one thread per pixel.  proj [T][ldp] (device),
+ *     k <= 8 curves; frame f shows the timesteps [0, i), i = frame_idx[f] clamped to [0, T] (frame_idx [F] int32, device); flags [F] uint8 (device, or
+ *     NULL for none): bit 0 draws the "terminated" line at x = i.  The geometry (plot rectangle, scrolling x range, lines as distance to segments,
+ *     markers, draw order) is fixed in DESIGN.md "PCA".  No text.  Refused: T < 1, k outside 1 .. 8, ldp < k, F < 1, W or H < 1, window < 1, a y range
+ *     that is not finite and increasing, margins that leave less than 3 x 3 pixels, a line half-width outside (0, 1e4], a null pointer. */
+#define TMJX_ENOCONV (-34)
+typedef struct {
+  int32_t sweeps;              /* Jacobi sweeps run */
+  int32_t converged;           /* 0: the sweep limit was reached first (the call returns TMJX_ENOCONV) */
+  float off_rel;               /* final off(A) / ||A||_F */
+  float moments_ms, jacobi_ms; /* device time of the two moment passes with their reductions, and of the eigen-solver */
+} tmjx_pca_info_t;
+typedef struct {
+  int32_t margin_left, margin_right, margin_top, margin_bottom;   /* pixels between the panel's edge and the plot rectangle */
+  float line_half_width, marker_radius;                           /* pixels */
+  uint8_t colour[8][4];                                           /* r g b (a ignored) of curve c */
+  uint8_t background[4], axes[4], terminated[4];
+} tmjx_strip_style_t;
+int tmjx_pca_workspace(int n, int d, int64_t *floats);
+int tmjx_pca_fit(const float *x, int n, int d, int64_t ldx, float *mean, float *components, float *variance, float *workspace, tmjx_pca_info_t *info,
+                 void *stream);
+int tmjx_pca_transform(const float *x, int n, int d, int64_t ldx, const float *mean, const float *components, int k, float *out, int64_t ldo, void *stream);
+int tmjx_plot_strips(const float *proj, int T, int k, int64_t ldp, const int32_t *frame_idx, const uint8_t *flags, int F, float ymin, float ymax, int window,
+                     const tmjx_strip_style_t *style, int W, int H, uint8_t *rgba, void *stream);
+
 const char *tmjx_last_error(void);
 const char *tmjx_version(void);
 

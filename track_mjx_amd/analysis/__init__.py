@@ -1,2 +1,2 @@
-"""Analysis of trained policies: checkpoint roll-outs that record the network's activations (track_mjx/analysis of the reference;
-rendering, PCA and plotting are not built)."""
+"""Analysis of trained policies: checkpoint roll-outs that record the network's activations, their rendering, PCA of a recorded feature and the
+PCA-progression video (track_mjx/analysis of the reference; text in plots and mp4 output are not built)."""

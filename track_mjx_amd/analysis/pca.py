@@ -1,0 +1,213 @@
+"""PCA of recorded activations on the GPU (csrc/tmjx_pca.hip; DESIGN.md "PCA").
+
+Reference: track_mjx/analysis/render.py fits sklearn's PCA on a recorded feature (the intention, ctrl or a layer) over many clips and plots the
+first components of one clip against the timestep.  Here the fit is two passes over the rows and one workgroup of Jacobi rotations; features up to
+128 wide (wider layers are refused by name).
+
+    python -m track_mjx_amd.analysis.pca rollouts=<dir of clip_<i>.h5> [feature=intention] [n_components=4] out=<pca.h5>
+
+writes mean, components, explained_variance, explained_variance_ratio, feature, n_samples, clips and projections/clip_<i> [T - 1, K];
+`python -m track_mjx_amd.analysis.render ... pca=<pca.h5>` draws them beside the frames.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import re
+import sys
+
+import numpy as np
+
+from .. import hip as _hip
+
+CLI_OPTIONS = ("rollouts", "out", "feature", "n_components")
+# the first eight of matplotlib's default colour cycle (what the reference's curves get), then background, axes, "terminated" line
+STRIP_COLOURS = ((31, 119, 180), (255, 127, 14), (44, 160, 44), (214, 39, 40), (148, 103, 189), (140, 86, 75), (227, 119, 194), (127, 127, 127))
+
+
+def strip_style(width: int, height: int, line_half_width: float = 1.0, marker_radius: float = 3.0, colours=STRIP_COLOURS, background=(255, 255, 255),
+                axes=(0, 0, 0), terminated=(255, 0, 0), margins=None) -> _hip.StripStyle:
+    """tmjx_strip_style_t: `margins` (left, right, top, bottom) in pixels, by default a sixteenth of the panel on every side (at least 2)."""
+    st = _hip.StripStyle()
+    mx, my = max(int(width) // 16, 2), max(int(height) // 16, 2)
+    st.margin_left, st.margin_right, st.margin_top, st.margin_bottom = (mx, mx, my, my) if margins is None else (int(v) for v in margins)
+    st.line_half_width, st.marker_radius = float(line_half_width), float(marker_radius)
+    for c in range(8):
+        st.colour[c][:] = [*colours[c % len(colours)], 255]
+    st.background[:], st.axes[:], st.terminated[:] = [*background, 255], [*axes, 255], [*terminated, 255]
+    return st
+
+
+class HipBackend:
+    """The four entry points on torch device tensors.  A stand-in with the same methods (the CPU tests pass the host emulation's) is accepted
+    wherever a `backend` is."""
+
+    def __init__(self, device="cuda", lib=None):
+        import torch
+        self.device = torch.device(device)
+        self._L = _hip.lib() if lib is None else lib
+
+    def _stream(self):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def asarray(self, x):
+        """A 2-D float32 device tensor whose columns are contiguous; a row stride (a column slice of a wider buffer) is kept."""
+        import torch
+        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.array(x, dtype=np.float32, order="C"))      # (a copy: read-only arrays are fine)
+        if t.dim() != 2:
+            raise ValueError(f"expected a 2-D array [n, d], got shape {tuple(t.shape)}")
+        t = t.to(device=self.device, dtype=torch.float32)
+        return t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.contiguous()
+
+    @staticmethod
+    def to_numpy(t):
+        return t.cpu().numpy()
+
+    def fit(self, x):
+        """x from asarray -> (mean [d], components [d, d], variance [d]) float32 numpy, and the call's hip.PcaInfo."""
+        import torch
+        n, d = x.shape
+        floats, info = C.c_int64(0), _hip.PcaInfo()
+        _hip.check(self._L.tmjx_pca_workspace(n, d, C.byref(floats)), "tmjx_pca_workspace")
+        ws = torch.empty(int(floats.value), dtype=torch.float32, device=self.device)
+        mean, comp, var = (torch.empty(s, dtype=torch.float32, device=self.device) for s in ((d,), (d, d), (d,)))
+        with torch.cuda.device(self.device):
+            _hip.check(self._L.tmjx_pca_fit(x.data_ptr(), n, d, x.stride(0), mean.data_ptr(), comp.data_ptr(), var.data_ptr(), ws.data_ptr(), C.byref(info),
+                                            self._stream()), "tmjx_pca_fit")
+        return mean.cpu().numpy(), comp.cpu().numpy(), var.cpu().numpy(), info
+
+    def transform(self, x, mean, components):
+        """(x - mean) . components^T as a device tensor [n, k]; mean [d] and components [k, d] numpy."""
+        import torch
+        n, d = x.shape
+        k = components.shape[0]
+        m = torch.as_tensor(np.ascontiguousarray(mean, np.float32), device=self.device)
+        c = torch.as_tensor(np.ascontiguousarray(components, np.float32), device=self.device)
+        out = torch.empty((n, k), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _hip.check(self._L.tmjx_pca_transform(x.data_ptr(), n, d, x.stride(0), m.data_ptr(), c.data_ptr(), k, out.data_ptr(), k, self._stream()),
+                       "tmjx_pca_transform")
+        return out
+
+    def strips(self, proj, k, frame_idx, flags, ymin, ymax, window, style, width, height):
+        """One tmjx_plot_strips call: proj from asarray, frame_idx / flags numpy -> rgba uint8 numpy [F, H, W, 4]."""
+        import torch
+        fi = torch.as_tensor(np.ascontiguousarray(frame_idx, np.int32), device=self.device)
+        fl = torch.as_tensor(np.ascontiguousarray(flags, np.uint8), device=self.device)
+        F = fi.shape[0]
+        out = torch.empty((F, max(height, 0), max(width, 0), 4), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _hip.check(self._L.tmjx_plot_strips(proj.data_ptr(), proj.shape[0], k, proj.stride(0), fi.data_ptr(), fl.data_ptr(), F, ymin, ymax, window,
+                                                C.byref(style), width, height, out.data_ptr(), self._stream()), "tmjx_plot_strips")
+        return out.cpu().numpy()
+
+
+class PCA:
+    """Principal components of [n, d] rows, d <= 128: `fit`, `transform`, `fit_transform`, and after a fit `mean_` [D], `components_` [K, D] (unit rows,
+    descending variance, the largest-magnitude coefficient of each positive), `explained_variance_` [K], `explained_variance_ratio_` [K] (zeros when
+    the total variance is 0), `n_samples_`, `n_sweeps_`.  Inputs: numpy arrays, or torch device tensors (a row stride is fine: activations are
+    stored as column slices of wider buffers).  `transform` returns numpy for numpy, a device tensor for a tensor."""
+
+    def __init__(self, n_components: int | None = None, device="cuda", backend=None):
+        if n_components is not None and int(n_components) < 1:
+            raise ValueError(f"n_components must be >= 1 (got {n_components})")
+        self.n_components = None if n_components is None else int(n_components)
+        self._b = HipBackend(device) if backend is None else backend
+
+    def fit(self, x):
+        xa = self._b.asarray(x)
+        n, d = (int(v) for v in xa.shape)
+        k = min(n, d) if self.n_components is None else self.n_components
+        if k > d:
+            raise ValueError(f"n_components = {k} exceeds the {d} features")
+        mean, comp, var, info = self._b.fit(xa)
+        total = float(var.astype(np.float64).sum())
+        self.mean_, self.components_, self.explained_variance_ = mean, np.ascontiguousarray(comp[:k]), var[:k].copy()
+        self.explained_variance_ratio_ = (var[:k].astype(np.float64) / total).astype(np.float32) if total > 0.0 else np.zeros(k, np.float32)
+        self.n_samples_, self.n_features_, self.n_sweeps_, self.off_rel_ = n, d, int(info.sweeps), float(info.off_rel)
+        self.moments_ms_, self.jacobi_ms_ = float(info.moments_ms), float(info.jacobi_ms)
+        return self
+
+    def transform(self, x):
+        if not hasattr(self, "components_"):
+            raise ValueError("this PCA is not fitted")
+        xa = self._b.asarray(x)
+        if xa.shape[1] != self.n_features_:
+            raise ValueError(f"expected {self.n_features_} features, got {xa.shape[1]}")
+        out = self._b.transform(xa, self.mean_, self.components_)
+        return self._b.to_numpy(out) if isinstance(x, np.ndarray) else out
+
+    def fit_transform(self, x):
+        return self.fit(x).transform(x)
+
+
+def _feature_of(rollout, feature: str, where: str) -> np.ndarray:
+    """The recorded feature of one roll-out as [T, D]: `ctrl`, or a path under activations/ (intention, decoder/layer_0, hidden_state/h, ...)."""
+    node, path = rollout, ([feature] if feature == "ctrl" else ["activations", *[p for p in feature.split("/") if p]])
+    for part in path:
+        try:
+            node = node[part]
+        except (KeyError, IndexError, TypeError):
+            raise KeyError(f"{where} has no {'/'.join(path)}" + (" (roll it out with log_activations=true)" if feature != "ctrl" else "")) from None
+    if hasattr(node, "keys"):
+        raise KeyError(f"{where}: {'/'.join(path)} is a group ({', '.join(node.keys())}), not a recorded array")
+    a = np.asarray(node if isinstance(node, (np.ndarray, list, tuple)) else node[()], np.float32)      # (an h5lite dataset reads with [()])
+    if a.ndim < 2:
+        raise ValueError(f"{where}: {'/'.join(path)} has shape {a.shape}, expected [T, D]")
+    return a.reshape(-1, a.shape[-1])
+
+
+def fit_rollouts(rollouts, feature: str = "intention", n_components: int | None = None, device="cuda", backend=None):
+    """Fit one PCA on `feature` over every roll-out and project each.  `rollouts`: a directory of clip_<i>.h5, or a list of roll-out dicts.
+    -> (pca, projections): projections[j] float32 [T_j, K] of roll-out j; pca.clips_ are the clip numbers (the list positions for dicts)."""
+    if isinstance(rollouts, (str, os.PathLike)):
+        from .. import h5lite
+        ids = sorted(int(m.group(1)) for m in (re.fullmatch(r"clip_(\d+)\.h5", f) for f in os.listdir(rollouts)) if m)
+        if not ids:
+            raise ValueError(f"no clip_<i>.h5 in {rollouts}")
+        feats = []
+        for c in ids:
+            with h5lite.File(os.path.join(rollouts, f"clip_{c}.h5")) as h:
+                feats.append(_feature_of(h, feature, f"clip_{c}.h5"))
+    else:
+        ids = list(range(len(rollouts)))
+        if not ids:
+            raise ValueError("no roll-outs to fit")
+        feats = [_feature_of(r, feature, f"roll-out {j}") for j, r in enumerate(rollouts)]
+    widths = {f.shape[1] for f in feats}
+    if len(widths) != 1:
+        raise ValueError(f"{feature} has different widths across roll-outs: {sorted(widths)}")
+    pca = PCA(n_components, device=device, backend=backend)
+    x = pca._b.asarray(np.concatenate(feats, 0))
+    proj = pca._b.to_numpy(pca.fit(x).transform(x))
+    pca.clips_, pca.feature_ = ids, feature
+    ends = np.cumsum([f.shape[0] for f in feats])
+    return pca, [proj[e - f.shape[0]:e] for e, f in zip(ends, feats)]
+
+
+def main(argv=None, backend=None) -> int:
+    from .. import h5lite
+    argv = list(sys.argv[1:] if argv is None else argv)
+    opts = dict(a.split("=", 1) for a in argv if "=" in a and a.split("=", 1)[0] in CLI_OPTIONS)
+    if "rollouts" not in opts or "out" not in opts or len(opts) != len(argv):
+        print("usage: python -m track_mjx_amd.analysis.pca rollouts=<dir of clip_<i>.h5> [feature=intention] [n_components=4] out=<pca.h5>", file=sys.stderr)
+        return 2
+    feature = opts.get("feature", "intention")
+    try:
+        pca, proj = fit_rollouts(opts["rollouts"], feature, int(opts.get("n_components", 4)), backend=backend)
+    except (KeyError, ValueError) as e:
+        print(f"[pca] {e.args[0] if e.args else e}", file=sys.stderr)
+        return 2
+    os.makedirs(os.path.dirname(os.path.abspath(opts["out"])), exist_ok=True)
+    h5lite.write_tree(opts["out"], {"mean": pca.mean_, "components": pca.components_, "explained_variance": pca.explained_variance_,
+                                    "explained_variance_ratio": pca.explained_variance_ratio_, "feature": feature, "n_samples": np.int64(pca.n_samples_),
+                                    "clips": np.asarray(pca.clips_, np.int64), "projections": {f"clip_{c}": p for c, p in zip(pca.clips_, proj)}})
+    ratio = ", ".join(f"{100 * r:.1f}%" for r in pca.explained_variance_ratio_)
+    print(f"[pca] {feature}: {pca.n_samples_} samples x {pca.n_features_} features from {len(proj)} clips, {pca.n_sweeps_} sweeps; explained variance "
+          f"{ratio}; wrote {opts['out']}", flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

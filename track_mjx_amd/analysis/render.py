@@ -5,9 +5,11 @@ analytic primitives are ray-cast directly: no meshes, textures, shadows, sites o
 in DESIGN.md so that a float64 restatement can check it.
 
     python -m track_mjx_amd.analysis.render rollouts=<dir of clip_<i>.h5> out=<dir> [camera=close_profile] [size=640x480] [ghost=true] [every=1]
-        [checkpoint=<run dir | step dir>] [key=value config overrides ...]
+        [checkpoint=<run dir | step dir>] [pca=<pca.h5>] [pca_window=530] [key=value config overrides ...]
 
-writes clip_<i>.frames.h5 (frames uint8 [F, H, W, 3], fps, camera) per roll-out file, and clip_<i>.gif where PIL imports.
+writes clip_<i>.frames.h5 (frames uint8 [F, H, W, 3], fps, camera) per roll-out file, and clip_<i>.gif where PIL imports.  With pca=<the file
+python -m track_mjx_amd.analysis.pca wrote> every frame carries the PCA-progression panel on its right (reference: render_with_pca_progression;
+DESIGN.md "PCA") and the file also holds pca_feature, pca_explained_variance_ratio and pca_colors: the legend as data, no text is drawn.
 """
 from __future__ import annotations
 
@@ -21,7 +23,7 @@ import numpy as np
 from .. import hip as _hip
 from .. import walker as _walker
 
-CLI_OPTIONS = ("rollouts", "out", "camera", "size", "ghost", "every", "checkpoint", "step")
+CLI_OPTIONS = ("rollouts", "out", "camera", "size", "ghost", "every", "checkpoint", "step", "pca", "pca_window")
 MAX_FRAMES_PER_CALL = 64      # frames rendered per launch pair: bounds the output buffers (64 frames of 640 x 480: 79 MB rgba)
 
 
@@ -187,6 +189,55 @@ def render_rollout(cfg, rollout, height: int = 480, width: int = 640, render_gho
     return r.render(q, g), render_fps(cfg)
 
 
+def plot_pca_progression(projections, frame_idx, n_components: int = 4, window_size: int = 530, size=(640, 480), terminated=None, device="cuda",
+                         backend=None, style=None) -> np.ndarray:
+    """The progression panel of every frame (reference: plot_pca_intention, one matplotlib figure per frame): uint8 [F, H, Wp, 3].  Frame f shows the
+    first `n_components` columns of `projections` [T, K] over the timesteps [0, frame_idx[f]); `terminated` [F] bool marks the frames that draw the
+    terminated line.  The y limits are min - 0.2 / max + 0.2 over those columns of the whole clip, as the reference takes them.  Drawn in batches of
+    MAX_FRAMES_PER_CALL frames; `backend`: a stand-in for pca.HipBackend."""
+    from . import pca as _pca
+    b = _pca.HipBackend(device) if backend is None else backend
+    width, height = int(size[0]), int(size[1])
+    host = projections if isinstance(projections, np.ndarray) else None
+    p = b.asarray(projections)
+    k = int(n_components)
+    if not 1 <= k <= min(int(p.shape[1]), _hip.PCA_MAX_K):
+        raise ValueError(f"n_components = {k}: a panel draws 1 .. {min(int(p.shape[1]), _hip.PCA_MAX_K)} of the {int(p.shape[1])} projected components")
+    idx = np.asarray(frame_idx, np.int64).reshape(-1)
+    if idx.size and (idx.min() < 0 or idx.max() > p.shape[0]):
+        raise ValueError(f"frame_idx must lie in [0, {int(p.shape[0])}] (got {int(idx.min())} .. {int(idx.max())})")
+    flags = np.zeros(idx.size, np.uint8) if terminated is None else np.asarray(terminated).reshape(-1).astype(bool).astype(np.uint8)
+    if flags.size != idx.size:
+        raise ValueError(f"terminated has {flags.size} entries for {idx.size} frames")
+    cols = (host if host is not None else b.to_numpy(p))[:, :k]
+    finite = cols[np.isfinite(cols)]
+    lo, hi = (float(finite.min()), float(finite.max())) if finite.size else (0.0, 0.0)
+    st = _pca.strip_style(width, height) if style is None else style
+    out = [b.strips(p, k, idx[i:i + MAX_FRAMES_PER_CALL], flags[i:i + MAX_FRAMES_PER_CALL], lo - 0.2, hi + 0.2, int(window_size), st, width, height)[..., :3]
+           for i in range(0, idx.size, MAX_FRAMES_PER_CALL)]
+    return np.concatenate(out, 0) if out else np.zeros((0, height, width, 3), np.uint8)
+
+
+def render_with_pca_progression(cfg, rollout, pca_projections, n_components: int = 4, feature_name: str = "ctrl", hold: int = 50, window_size: int = 530,
+                                panel_width: int = 640, backend=None, **render_kwargs):
+    """(frames uint8 [F + hold, H, W + Wp, 3], fps): render_rollout's frames with the progression panel on the right (reference:
+    render_with_pca_progression).  Frame f shows the curves up to timestep f * every; the last frame is repeated `hold` times with the terminated
+    line, the reference's stoppage.  `feature_name` is not drawn (no text in the panel): the command-line tool stores it beside the frames.
+    `render_kwargs` go to render_rollout (height, width, every, camera, render_ghost, device, renderer_cls)."""
+    frames, fps = render_rollout(cfg, rollout, **render_kwargs)
+    every = int(render_kwargs.get("every", 1))
+    T = int(np.shape(pca_projections)[0])
+    idx = np.minimum(np.arange(frames.shape[0]) * every, T)
+    idx = np.concatenate([idx, idx[-1:]])                      # the last frame once more, terminated
+    term = np.zeros(idx.size, bool)
+    term[-1] = True
+    panel = plot_pca_progression(pca_projections, idx, n_components, window_size, (int(panel_width), frames.shape[1]), term,
+                                 device=render_kwargs.get("device", "cuda"), backend=backend)
+    wide = np.concatenate([frames, panel[:-1]], 2)
+    stop = np.concatenate([frames[-1], panel[-1]], 1)[None]
+    return np.concatenate([wide, np.repeat(stop, int(hold), 0)], 0), fps
+
+
 def _write_gif(path, frames, fps) -> bool:
     try:
         from PIL import Image
@@ -197,7 +248,7 @@ def _write_gif(path, frames, fps) -> bool:
     return True
 
 
-def main(argv=None, renderer_cls=None) -> int:
+def main(argv=None, renderer_cls=None, pca_backend=None) -> int:
     from .. import config as _config
     from .. import h5lite
     argv = list(sys.argv[1:] if argv is None else argv)
@@ -205,7 +256,7 @@ def main(argv=None, renderer_cls=None) -> int:
     rest = [a for a in argv if not ("=" in a and a.split("=", 1)[0] in opts)]
     if "rollouts" not in opts or "out" not in opts:
         print("usage: python -m track_mjx_amd.analysis.render rollouts=<dir of clip_<i>.h5> out=<dir> [camera=close_profile] [size=640x480] "
-              "[ghost=true] [every=1] [checkpoint=<run dir | step dir>] [key=value config overrides ...]", file=sys.stderr)
+              "[ghost=true] [every=1] [checkpoint=<run dir | step dir>] [pca=<pca.h5>] [pca_window=530] [key=value config overrides ...]", file=sys.stderr)
         return 2
     cfg = _config.default_config()
     if "checkpoint" in opts:
@@ -232,16 +283,33 @@ def main(argv=None, renderer_cls=None) -> int:
     os.makedirs(opts["out"], exist_ok=True)
     camera = opts.get("camera") or cfg["env_config"].get("render_camera_name", "close_profile") or "close_profile"
     gifs = 0
+    pca = None
+    if "pca" in opts:
+        with h5lite.File(opts["pca"]) as h:
+            pca = {"feature": bytes(h["feature"][()]).decode(), "ratio": np.asarray(h["explained_variance_ratio"][()], np.float32),
+                   "projections": {k: np.asarray(h["projections"][k][()], np.float32) for k in h["projections"].keys()}}
     for f in files:
         with h5lite.File(os.path.join(opts["rollouts"], f)) as h:
             rollout = {k: np.asarray(h[k][()]) for k in ("qposes_rollout", "qposes_ref") if k in h}
         if ghost and "qposes_ref" not in rollout:
             print(f"[render] {f}: no qposes_ref (ghost=false renders without)", file=sys.stderr)
             return 2
-        frames, fps = render_rollout(cfg, rollout, height=height, width=width, render_ghost=ghost, every=every, camera=camera, renderer_cls=renderer_cls)
-        fps = fps / every
         stem = f[:-3]
-        h5lite.write_tree(os.path.join(opts["out"], stem + ".frames.h5"), {"frames": frames, "fps": np.float64(fps), "camera": camera})
+        tree = {}
+        if pca is None:
+            frames, fps = render_rollout(cfg, rollout, height=height, width=width, render_ghost=ghost, every=every, camera=camera, renderer_cls=renderer_cls)
+        else:
+            if stem not in pca["projections"]:
+                print(f"[render] {opts['pca']} has no projections/{stem}", file=sys.stderr)
+                return 2
+            k = min(4, pca["ratio"].size, _hip.PCA_MAX_K)
+            from . import pca as _pca
+            frames, fps = render_with_pca_progression(cfg, rollout, pca["projections"][stem], n_components=k, feature_name=pca["feature"],
+                                                      window_size=int(opts.get("pca_window", 530)), backend=pca_backend, height=height, width=width,
+                                                      render_ghost=ghost, every=every, camera=camera, renderer_cls=renderer_cls)
+            tree = {"pca_feature": pca["feature"], "pca_explained_variance_ratio": pca["ratio"][:k], "pca_colors": np.asarray(_pca.STRIP_COLOURS[:k], np.uint8)}
+        fps = fps / every
+        h5lite.write_tree(os.path.join(opts["out"], stem + ".frames.h5"), {"frames": frames, "fps": np.float64(fps), "camera": camera, **tree})
         gifs += _write_gif(os.path.join(opts["out"], stem + ".gif"), frames, fps)
     print(f"[render] wrote {len(files)} frame files to {opts['out']} ({width}x{height}, camera {camera}, ghost {ghost}, {gifs} gifs)", flush=True)
     return 0

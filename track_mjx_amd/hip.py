@@ -15,7 +15,7 @@ _PKG = Path(__file__).resolve().parent
 SO_PATH = Path(os.environ.get("TMJX_SO", str(_PKG / "libtmjx_hip.so")))  # TMJX_SO: alternative build (profiling)
 CSRC = _PKG / "csrc"
 SOURCES = (CSRC / "tmjx_hip.hip", CSRC / "tmjx_bf16.hip", CSRC / "tmjx_wave.hip", CSRC / "tmjx_chain.hip", CSRC / "tmjx_lstm.hip",
-           CSRC / "tmjx_rollout.hip", CSRC / "tmjx_wave_sensors.hip", CSRC / "tmjx_wave_align.hip", CSRC / "tmjx_wave_rand.hip", CSRC / "tmjx_render.hip", CSRC / "tmjx_act.hip")
+           CSRC / "tmjx_rollout.hip", CSRC / "tmjx_wave_sensors.hip", CSRC / "tmjx_wave_align.hip", CSRC / "tmjx_wave_rand.hip", CSRC / "tmjx_render.hip", CSRC / "tmjx_act.hip", CSRC / "tmjx_pca.hip")
 # per-source compiler flags: the physics kernel's unit is built without machine LICM (csrc/tmjx_wave.hip says why)
 SOURCE_FLAGS = {"tmjx_wave.hip": ("-mllvm", "-disable-machine-licm"),
                 "tmjx_wave_sensors.hip": ("-mllvm", "-disable-machine-licm"),      # (the recording kernel: the same loop body)
@@ -48,6 +48,7 @@ EXPORTS = ("tmjx_model_create", "tmjx_model_destroy", "tmjx_layout", "tmjx_clips
            "tmjx_sensor_info", "tmjx_physics_sensors", "tmjx_step_sensors",
            "tmjx_set_done_policy", "tmjx_clips_upload_velocities", "tmjx_set_env_scales", "tmjx_set_env_gravity",
            "tmjx_render_info", "tmjx_render_camera", "tmjx_render_pose", "tmjx_render_prims", "tmjx_render",
+           "tmjx_pca_workspace", "tmjx_pca_fit", "tmjx_pca_transform", "tmjx_plot_strips",
            "tmjx_debug_rows", "tmjx_last_error", "tmjx_version")
 
 
@@ -188,6 +189,22 @@ class Camera(C.Structure):
 class RenderInfo(C.Structure):
     """tmjx_render_info_t (include/tmjx.h)."""
     _fields_ = [(k, C.c_int32) for k in ("ngeom", "ncam", "rec_floats", "cam_floats", "nprim")] + [("prims_offset", C.c_int64), ("workspace_floats", C.c_int64)]
+
+
+ENOCONV = -34                     # TMJX_ENOCONV (include/tmjx.h)
+PCA_MAX_D, PCA_ROWS_PER_WG, PCA_MAX_K = 128, 256, 8      # csrc/pca_core.h
+
+
+class PcaInfo(C.Structure):
+    """tmjx_pca_info_t (include/tmjx.h)."""
+    _fields_ = [("sweeps", C.c_int32), ("converged", C.c_int32), ("off_rel", C.c_float), ("moments_ms", C.c_float), ("jacobi_ms", C.c_float)]
+
+
+class StripStyle(C.Structure):
+    """tmjx_strip_style_t (include/tmjx.h)."""
+    _fields_ = [(k, C.c_int32) for k in ("margin_left", "margin_right", "margin_top", "margin_bottom")] + \
+               [("line_half_width", C.c_float), ("marker_radius", C.c_float), ("colour", (C.c_uint8 * 4) * 8)] + \
+               [(k, C.c_uint8 * 4) for k in ("background", "axes", "terminated")]
 
 
 class PpoCfg(C.Structure):
@@ -415,6 +432,11 @@ def load(path: Path):
     sig.setdefault("tmjx_render_pose", [None, None])[0] = [vp, fp, fp, C.c_int, C.c_int, C.POINTER(Camera), fp, vp]
     sig.setdefault("tmjx_render_prims", [None, None])[0] = [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp, fp, vp, vp]
     sig.setdefault("tmjx_render", [None, None])[0] = [vp, fp, fp, C.c_int, C.c_int, C.POINTER(Camera), C.c_int, C.c_int, fp, vp, fp, vp, vp]
+    sig.setdefault("tmjx_pca_workspace", [None, None])[0] = [C.c_int, C.c_int, C.POINTER(C.c_int64)]
+    sig.setdefault("tmjx_pca_fit", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, fp, fp, fp, fp, C.POINTER(PcaInfo), vp]
+    sig.setdefault("tmjx_pca_transform", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, fp, fp, C.c_int, fp, C.c_int64, vp]
+    sig.setdefault("tmjx_plot_strips", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, vp, vp, C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(StripStyle),
+                                                           C.c_int, C.c_int, vp, vp]
     sig.setdefault("tmjx_debug_rows", [None, None])[0] = [vp, C.c_char_p, ip, ip]
     sig.setdefault("tmjx_last_error", [None, None])[1] = C.c_char_p
     sig.setdefault("tmjx_version", [None, None])[1] = C.c_char_p
