@@ -802,6 +802,26 @@ int tmjx_pca_transform(const float *x, int n, int d, int64_t ldx, const float *m
 int tmjx_plot_strips(const float *proj, int T, int k, int64_t ldp, const int32_t *frame_idx, const uint8_t *flags, int F, float ymin, float ymax, int window,
                      const tmjx_strip_style_t *style, int W, int H, uint8_t *rgba, void *stream);
 
+/* ---- Wide PCA, 129 <= d <= 1024 (csrc/tmjx_pca_wide.hip, csrc/pca_wide_core.h; DESIGN.md "PCA", wide fit): the argument lists, outputs and
+ * conventions of tmjx_pca_workspace / tmjx_pca_fit / tmjx_pca_transform.  For d <= 128 the three forward to those and give their bits.
+ *   tmjx_pca_wide_workspace: the float count tmjx_pca_fit_wide needs.  The row split of the moments is fixed by n alone (at most 16 super-chunks of
+ *     256-row chunks), so the size grows with d^2 only: 137 MiB at d = 1024, whatever n is.
+ *   tmjx_pca_fit_wide: float64 column sums; the centred Gram matrix in 128 x 128 tiles (float32 FMAs within a chunk, float64 across chunks and
+ *     super-chunks, a fixed order, no atomics: the same bits on every run); then block Jacobi on the covariance in global memory — blocks of 64
+ *     columns (the last may be smaller; nothing is padded), paired by the round-robin tournament; a pair's sub-matrix (at most 128 x 128) is
+ *     diagonalised by the narrow fit's one-workgroup solver and its eigenvector rows rotate the pair's rows of A and V^T, then its columns of A.
+ *     After every block sweep the call WAITS for the stream and reads off(A)^2 and ||A||_F^2 back (float64); it stops at off(A) <= 2^-24 ||A||_F
+ *     (info->sweeps: the block sweeps; jacobi_ms: the whole iteration) or returns TMJX_ENOCONV after 30 block sweeps.  A covariance that is not
+ *     finite (a NaN in x) is refused after the moment pass, before any rotation is launched: TMJX_EINVAL, "non-finite".  Refused before any launch
+ *     (TMJX_EINVAL): d < 1, d > 1024 ("exceeds the wide PCA limit of 1024"), n < 2, ldx < d, a null pointer, a workspace not 16-byte aligned.
+ *   tmjx_pca_transform_wide: as tmjx_pca_transform, 1 <= k <= d <= 1024; one fmaf chain per output in ascending feature order. */
+#define PCA_WIDE_MAX_D 1024
+int tmjx_pca_wide_workspace(int n, int d, int64_t *floats);
+int tmjx_pca_fit_wide(const float *x, int n, int d, int64_t ldx, float *mean, float *components, float *variance, float *workspace, tmjx_pca_info_t *info,
+                      void *stream);
+int tmjx_pca_transform_wide(const float *x, int n, int d, int64_t ldx, const float *mean, const float *components, int k, float *out, int64_t ldo,
+                            void *stream);
+
 const char *tmjx_last_error(void);
 const char *tmjx_version(void);
 

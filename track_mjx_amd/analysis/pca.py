@@ -1,8 +1,9 @@
 """PCA of recorded activations on the GPU (csrc/tmjx_pca.hip; DESIGN.md "PCA").
 
 Reference: track_mjx/analysis/render.py fits sklearn's PCA on a recorded feature (the intention, ctrl or a layer) over many clips and plots the
-first components of one clip against the timestep.  Here the fit is two passes over the rows and one workgroup of Jacobi rotations; features up to
-128 wide (wider layers are refused by name).
+first components of one clip against the timestep.  Here the fit is two passes over the rows and, for features up to 128 wide, one workgroup of
+Jacobi rotations; wider features (the 256- to 1024-wide layers, the LSTM carry), up to 1024, go through block Jacobi on the covariance in global
+memory (csrc/tmjx_pca_wide.hip), whose inner solver is that same workgroup.
 
     python -m track_mjx_amd.analysis.pca rollouts=<dir of clip_<i>.h5> [feature=intention] [n_components=4] out=<pca.h5>
 
@@ -39,8 +40,8 @@ def strip_style(width: int, height: int, line_half_width: float = 1.0, marker_ra
 
 
 class HipBackend:
-    """The four entry points on torch device tensors.  A stand-in with the same methods (the CPU tests pass the host emulation's) is accepted
-    wherever a `backend` is."""
+    """The PCA and panel entry points on torch device tensors.  A stand-in with the same methods (the CPU tests pass the host emulation's) is
+    accepted wherever a `backend` is; one without `fit_wide` / `transform_wide` serves features up to 128 wide only."""
 
     def __init__(self, device="cuda", lib=None):
         import torch
@@ -66,19 +67,25 @@ class HipBackend:
 
     def fit(self, x):
         """x from asarray -> (mean [d], components [d, d], variance [d]) float32 numpy, and the call's hip.PcaInfo."""
+        return self._fit(x, "tmjx_pca_workspace", "tmjx_pca_fit")
+
+    def _fit(self, x, workspace_entry, fit_entry):
         import torch
         n, d = x.shape
         floats, info = C.c_int64(0), _hip.PcaInfo()
-        _hip.check(self._L.tmjx_pca_workspace(n, d, C.byref(floats)), "tmjx_pca_workspace")
+        _hip.check(getattr(self._L, workspace_entry)(n, d, C.byref(floats)), workspace_entry)
         ws = torch.empty(int(floats.value), dtype=torch.float32, device=self.device)
         mean, comp, var = (torch.empty(s, dtype=torch.float32, device=self.device) for s in ((d,), (d, d), (d,)))
         with torch.cuda.device(self.device):
-            _hip.check(self._L.tmjx_pca_fit(x.data_ptr(), n, d, x.stride(0), mean.data_ptr(), comp.data_ptr(), var.data_ptr(), ws.data_ptr(), C.byref(info),
-                                            self._stream()), "tmjx_pca_fit")
+            _hip.check(getattr(self._L, fit_entry)(x.data_ptr(), n, d, x.stride(0), mean.data_ptr(), comp.data_ptr(), var.data_ptr(), ws.data_ptr(),
+                                                   C.byref(info), self._stream()), fit_entry)
         return mean.cpu().numpy(), comp.cpu().numpy(), var.cpu().numpy(), info
 
     def transform(self, x, mean, components):
         """(x - mean) . components^T as a device tensor [n, k]; mean [d] and components [k, d] numpy."""
+        return self._transform(x, mean, components, "tmjx_pca_transform")
+
+    def _transform(self, x, mean, components, entry):
         import torch
         n, d = x.shape
         k = components.shape[0]
@@ -86,9 +93,16 @@ class HipBackend:
         c = torch.as_tensor(np.ascontiguousarray(components, np.float32), device=self.device)
         out = torch.empty((n, k), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            _hip.check(self._L.tmjx_pca_transform(x.data_ptr(), n, d, x.stride(0), m.data_ptr(), c.data_ptr(), k, out.data_ptr(), k, self._stream()),
-                       "tmjx_pca_transform")
+            _hip.check(getattr(self._L, entry)(x.data_ptr(), n, d, x.stride(0), m.data_ptr(), c.data_ptr(), k, out.data_ptr(), k, self._stream()), entry)
         return out
+
+    def fit_wide(self, x):
+        """`fit` for d <= 1024 (tmjx_pca_fit_wide: block Jacobi above 128 features, the narrow fit's bits up to 128); info.sweeps: block sweeps."""
+        return self._fit(x, "tmjx_pca_wide_workspace", "tmjx_pca_fit_wide")
+
+    def transform_wide(self, x, mean, components):
+        """`transform` for d <= 1024 (tmjx_pca_transform_wide)."""
+        return self._transform(x, mean, components, "tmjx_pca_transform_wide")
 
     def strips(self, proj, k, frame_idx, flags, ymin, ymax, window, style, width, height):
         """One tmjx_plot_strips call: proj from asarray, frame_idx / flags numpy -> rgba uint8 numpy [F, H, W, 4]."""
@@ -104,9 +118,10 @@ class HipBackend:
 
 
 class PCA:
-    """Principal components of [n, d] rows, d <= 128: `fit`, `transform`, `fit_transform`, and after a fit `mean_` [D], `components_` [K, D] (unit rows,
+    """Principal components of [n, d] rows, d <= 1024: `fit`, `transform`, `fit_transform`, and after a fit `mean_` [D], `components_` [K, D] (unit rows,
     descending variance, the largest-magnitude coefficient of each positive), `explained_variance_` [K], `explained_variance_ratio_` [K] (zeros when
-    the total variance is 0), `n_samples_`, `n_sweeps_`.  Inputs: numpy arrays, or torch device tensors (a row stride is fine: activations are
+    the total variance is 0), `n_samples_`, `n_sweeps_` (Jacobi sweeps; above 128 features the block sweeps, also in `n_block_sweeps_`, which is 0
+    for a narrow fit).  Features wider than 128 go through the backend's `fit_wide` / `transform_wide` where it has them.  Inputs: numpy arrays, or torch device tensors (a row stride is fine: activations are
     stored as column slices of wider buffers).  `transform` returns numpy for numpy, a device tensor for a tensor."""
 
     def __init__(self, n_components: int | None = None, device="cuda", backend=None):
@@ -121,12 +136,13 @@ class PCA:
         k = min(n, d) if self.n_components is None else self.n_components
         if k > d:
             raise ValueError(f"n_components = {k} exceeds the {d} features")
-        mean, comp, var, info = self._b.fit(xa)
+        wide = d > _hip.PCA_MAX_D and hasattr(self._b, "fit_wide")
+        mean, comp, var, info = self._b.fit_wide(xa) if wide else self._b.fit(xa)
         total = float(var.astype(np.float64).sum())
         self.mean_, self.components_, self.explained_variance_ = mean, np.ascontiguousarray(comp[:k]), var[:k].copy()
         self.explained_variance_ratio_ = (var[:k].astype(np.float64) / total).astype(np.float32) if total > 0.0 else np.zeros(k, np.float32)
         self.n_samples_, self.n_features_, self.n_sweeps_, self.off_rel_ = n, d, int(info.sweeps), float(info.off_rel)
-        self.moments_ms_, self.jacobi_ms_ = float(info.moments_ms), float(info.jacobi_ms)
+        self.moments_ms_, self.jacobi_ms_, self.n_block_sweeps_ = float(info.moments_ms), float(info.jacobi_ms), int(info.sweeps) if wide else 0
         return self
 
     def transform(self, x):
@@ -135,7 +151,8 @@ class PCA:
         xa = self._b.asarray(x)
         if xa.shape[1] != self.n_features_:
             raise ValueError(f"expected {self.n_features_} features, got {xa.shape[1]}")
-        out = self._b.transform(xa, self.mean_, self.components_)
+        wide = self.n_features_ > _hip.PCA_MAX_D and hasattr(self._b, "transform_wide")
+        out = self._b.transform_wide(xa, self.mean_, self.components_) if wide else self._b.transform(xa, self.mean_, self.components_)
         return self._b.to_numpy(out) if isinstance(x, np.ndarray) else out
 
     def fit_transform(self, x):
@@ -159,7 +176,7 @@ def _feature_of(rollout, feature: str, where: str) -> np.ndarray:
 
 
 def fit_rollouts(rollouts, feature: str = "intention", n_components: int | None = None, device="cuda", backend=None):
-    """Fit one PCA on `feature` over every roll-out and project each.  `rollouts`: a directory of clip_<i>.h5, or a list of roll-out dicts.
+    """Fit one PCA on `feature` (up to 1024 wide) over every roll-out and project each.  `rollouts`: a directory of clip_<i>.h5, or a list of roll-out dicts.
     -> (pca, projections): projections[j] float32 [T_j, K] of roll-out j; pca.clips_ are the clip numbers (the list positions for dicts)."""
     if isinstance(rollouts, (str, os.PathLike)):
         from .. import h5lite
