@@ -822,6 +822,36 @@ int tmjx_pca_fit_wide(const float *x, int n, int d, int64_t ldx, float *mean, fl
 int tmjx_pca_transform_wide(const float *x, int n, int d, int64_t ldx, const float *mean, const float *components, int k, float *out, int64_t ldo,
                             void *stream);
 
+/* ---- Linear readout: ridge regression from recorded activations x [n][d] (d <= 1024) to targets y [n][m] (m <= 512), for up to 16 penalties at once
+ * (csrc/tmjx_readout.hip, csrc/readout_core.h; DESIGN.md "Readout").  No model handle; all device memory is the caller's; everything runs on the
+ * caller's stream.  x and y are float32 and may be column slices of wider buffers (ldx >= d, ldy >= m).
+ *   tmjx_readout_workspace: *floats = the float count that covers a fit, the weights and a score of up to n rows: every call of 2 <= n' <= n rows with
+ *     the same d, m and at most n_lambda penalties stays inside it (the layouts of fewer rows are not all smaller; the size allows for that).
+ *   tmjx_readout_fit: mean_x [d], components [d][d] and variance [d] are tmjx_pca_fit_wide's for the same x, to the bit (it is called as it is, the
+ *     narrow fit for d <= 128; *info is its report, and TMJX_ENOCONV or its "non-finite" refusal pass through unchanged); mean_y [m] from float64 column
+ *     sums; C = (x - mean_x)^T (y - mean_y) / (n - 1) by the row split of the wide PCA's moments (float32 FMAs within a chunk of 256 rows, float64
+ *     across chunks and super-chunks, a fixed order, no atomics); z [d][m] = components . C.  The call WAITS for the stream.
+ *   tmjx_readout_weights: w [L][d][m], w[i] = components^T diag(1 / (variance_j + lambdas[i])) z; lambdas [L] is HOST memory, absolute penalties.
+ *     Nothing synchronises.
+ *   tmjx_readout_predict: out [n][ldo], columns [0, m) = (x - mean_x) w + mean_y for ONE w [d][m]; one fmaf chain per output in ascending feature order.
+ *   tmjx_readout_score: for every penalty i and target c, sse [L][m] = sum_r (y[r][c] - yhat_i[r][c])^2 over the n rows given (yhat: what
+ *     tmjx_readout_predict stores; it is never written to memory) and sst [m] = sum_r (y[r][c] - mean(y[:, c]))^2 with the float64 column mean of
+ *     these rows; float64, device memory, reduced in a fixed order.  R^2 = 1 - sse / sst is the caller's.  w: [L][d][m].  Nothing synchronises.
+ *   Refused before any launch (TMJX_EINVAL, the message names the value): d < 1, d > 1024, m < 1, m > 512, n_lambda outside 1 .. 16, n < 2 (fit, score,
+ *   workspace) or n < 1 (predict), ldx < d, ldy < m, ldo < m, a lambda that is not finite or not > 0 once rounded to float32 (as
+ *   the kernels take it: 1e-50 rounds to 0 and is refused), a null pointer, a workspace not 16-byte aligned. */
+#define READOUT_MAX_M 512
+#define READOUT_MAX_L 16
+int tmjx_readout_workspace(int n, int d, int m, int n_lambda, int64_t *floats);
+int tmjx_readout_fit(const float *x, int n, int d, int64_t ldx, const float *y, int m, int64_t ldy, float *mean_x, float *components, float *variance,
+                     float *mean_y, float *z, float *workspace, tmjx_pca_info_t *info, void *stream);
+int tmjx_readout_weights(const float *components, const float *variance, const float *z, int d, int m, const double *lambdas, int n_lambda, float *w,
+                         void *stream);
+int tmjx_readout_predict(const float *x, int n, int d, int64_t ldx, const float *mean_x, const float *w, const float *mean_y, int m, float *out, int64_t ldo,
+                         void *stream);
+int tmjx_readout_score(const float *x, int n, int d, int64_t ldx, const float *y, int m, int64_t ldy, const float *mean_x, const float *w, const float *mean_y,
+                       int n_lambda, double *sse, double *sst, float *workspace, void *stream);
+
 const char *tmjx_last_error(void);
 const char *tmjx_version(void);
 

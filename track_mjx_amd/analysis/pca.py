@@ -41,7 +41,8 @@ def strip_style(width: int, height: int, line_half_width: float = 1.0, marker_ra
 
 class HipBackend:
     """The PCA and panel entry points on torch device tensors.  A stand-in with the same methods (the CPU tests pass the host emulation's) is
-    accepted wherever a `backend` is; one without `fit_wide` / `transform_wide` serves features up to 128 wide only."""
+    accepted wherever a `backend` is; one without `fit_wide` / `transform_wide` serves features up to 128 wide only.  The `readout_*` methods are
+    analysis.readout's (tmjx_readout_*)."""
 
     def __init__(self, device="cuda", lib=None):
         import torch
@@ -103,6 +104,63 @@ class HipBackend:
     def transform_wide(self, x, mean, components):
         """`transform` for d <= 1024 (tmjx_pca_transform_wide)."""
         return self._transform(x, mean, components, "tmjx_pca_transform_wide")
+
+    # the linear readout (analysis/readout.py; tmjx_readout_*): x and y from asarray, everything else float32 numpy
+    def _dev(self, a):
+        import torch
+        return torch.as_tensor(np.ascontiguousarray(a, np.float32), device=self.device)
+
+    def _readout_workspace(self, n, d, m, n_lambda):
+        import torch
+        floats = C.c_int64(0)
+        _hip.check(self._L.tmjx_readout_workspace(n, d, m, n_lambda, C.byref(floats)), "tmjx_readout_workspace")
+        return torch.empty(int(floats.value), dtype=torch.float32, device=self.device)
+
+    def readout_fit(self, x, y):
+        """-> (mean_x [d], components [d, d], variance [d], mean_y [m], z [d, m]) float32 numpy and the PCA part's hip.PcaInfo (tmjx_readout_fit)."""
+        import torch
+        (n, d), m = x.shape, y.shape[1]
+        ws, info = self._readout_workspace(n, d, m, 1), _hip.PcaInfo()
+        mean_x, comp, var, mean_y, z = (torch.empty(s, dtype=torch.float32, device=self.device) for s in ((d,), (d, d), (d,), (m,), (d, m)))
+        with torch.cuda.device(self.device):
+            _hip.check(self._L.tmjx_readout_fit(x.data_ptr(), n, d, x.stride(0), y.data_ptr(), m, y.stride(0), mean_x.data_ptr(), comp.data_ptr(), var.data_ptr(),
+                                                mean_y.data_ptr(), z.data_ptr(), ws.data_ptr(), C.byref(info), self._stream()), "tmjx_readout_fit")
+        return (*(t.cpu().numpy() for t in (mean_x, comp, var, mean_y, z)), info)
+
+    def readout_weights(self, components, variance, z, lambdas):
+        """lambdas: absolute penalties [L] -> w [L, d, m] float32 numpy (tmjx_readout_weights)."""
+        import torch
+        d, m = z.shape
+        lam = np.ascontiguousarray(lambdas, np.float64)
+        comp, var, zz = self._dev(components), self._dev(variance), self._dev(z)
+        w = torch.empty((max(lam.shape[0], 1), d, m), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _hip.check(self._L.tmjx_readout_weights(comp.data_ptr(), var.data_ptr(), zz.data_ptr(), d, m, lam.ctypes.data_as(C.POINTER(C.c_double)), lam.shape[0],
+                                                    w.data_ptr(), self._stream()), "tmjx_readout_weights")
+        return w.cpu().numpy()
+
+    def readout_predict(self, x, mean_x, w, mean_y):
+        """w [d, m] -> (x - mean_x) w + mean_y as a device tensor [n, m] (tmjx_readout_predict)."""
+        import torch
+        (n, d), m = x.shape, w.shape[1]
+        mx, ww, my = self._dev(mean_x), self._dev(w), self._dev(mean_y)
+        out = torch.empty((n, m), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _hip.check(self._L.tmjx_readout_predict(x.data_ptr(), n, d, x.stride(0), mx.data_ptr(), ww.data_ptr(), my.data_ptr(), m, out.data_ptr(), m,
+                                                    self._stream()), "tmjx_readout_predict")
+        return out
+
+    def readout_score(self, x, y, mean_x, w, mean_y):
+        """w [L, d, m] -> (sse [L, m], sst [m]) float64 numpy over the rows given (tmjx_readout_score)."""
+        import torch
+        (n, d), (L, _, m) = x.shape, w.shape
+        mx, ww, my = self._dev(mean_x), self._dev(w), self._dev(mean_y)
+        ws = self._readout_workspace(n, d, m, L)
+        sse, sst = torch.empty((L, m), dtype=torch.float64, device=self.device), torch.empty((m,), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _hip.check(self._L.tmjx_readout_score(x.data_ptr(), n, d, x.stride(0), y.data_ptr(), m, y.stride(0), mx.data_ptr(), ww.data_ptr(), my.data_ptr(), L,
+                                                  sse.data_ptr(), sst.data_ptr(), ws.data_ptr(), self._stream()), "tmjx_readout_score")
+        return sse.cpu().numpy(), sst.cpu().numpy()
 
     def strips(self, proj, k, frame_idx, flags, ymin, ymax, window, style, width, height):
         """One tmjx_plot_strips call: proj from asarray, frame_idx / flags numpy -> rgba uint8 numpy [F, H, W, 4]."""
