@@ -852,6 +852,30 @@ int tmjx_readout_predict(const float *x, int n, int d, int64_t ldx, const float 
 int tmjx_readout_score(const float *x, int n, int d, int64_t ldx, const float *y, int m, int64_t ldy, const float *mean_x, const float *w, const float *mean_y,
                        int n_lambda, double *sse, double *sst, float *workspace, void *stream);
 
+/* ---- Activation intervention (csrc/tmjx_intervene.hip, csrc/intervene_core.h; DESIGN.md "Interventions"): one launch that edits, in place, the
+ * columns [0, w) of the rows h [n][ld] — a layer's output buffer, or a column slice of one — between two launches of a policy step.  Row r at step t:
+ *   subspace mode:  p_k = sum_j (h_j - c_j) v_kj;  e_j = sum_k ((g_k - 1) p_k + o_k) v_kj;  h'_j = h_j + dose_r e_j   (dirs [K][ldv], gain / offset [K])
+ *   units mode:     h'_j = h_j + dose_r ((g_j - 1)(h_j - c_j) + o_j)                                                   (gain / offset [w])
+ * A row is ON when t_on[r] <= t < t_off[r] and dose[r] != 0; an OFF row is never stored to.  proj (optional, subspace mode) receives p_k of EVERY
+ * row at every call, ON or OFF.  One wave per row, the row in registers, read once; per-lane partial sums over j = lane, lane + 64, .. ascending,
+ * a fixed cross-lane tree, k ascending, no atomics: a row's bits do not depend on n, its position or the other rows' gates.
+ * Refused before any device call (TMJX_EINVAL, the message names the value): a null descriptor or required pointer, a pointer that is not 4-byte
+ * aligned, w outside 1 .. 1024, ld < w, n < 1, an unknown mode, K outside 1 .. 16, ldv < w, ldp < K, proj in units mode.  center may be null (0). */
+#define TMJX_INTERVENE_SUBSPACE 0
+#define TMJX_INTERVENE_UNITS 1
+typedef struct {
+  float *h; int32_t ld, w;           /* target rows [n][ld >= w] */
+  int32_t n, mode;
+  const float *dirs; int32_t K, ldv; /* subspace mode: [K][ldv >= w] */
+  const float *center;               /* optional [w] */
+  const float *gain, *offset;        /* [K] (subspace) or [w] (units) */
+  const float *dose;                 /* [n] */
+  const int32_t *t_on, *t_off;       /* [n] */
+  float *proj; int32_t ldp, pad_;    /* optional [n][ldp >= K], subspace mode only */
+} tmjx_intervene_t;
+int tmjx_intervene_ok(const tmjx_intervene_t *d);            /* 1 / 0, reason in tmjx_last_error */
+int tmjx_intervene(const tmjx_intervene_t *d, int t, void *stream);
+
 const char *tmjx_last_error(void);
 const char *tmjx_version(void);
 

@@ -66,6 +66,47 @@ class LaunchList:
         self.call("tmjx_linear_nolds_norm", ptr(a), lda, 1, ptr(w), None, ptr(out), self.n, N, w.shape[1], ptr(fold_mean), ptr(fold_inv))
         return out
 
+    def intervene(self, buf, c0: int, w: int, ld: int, spec_buffers):
+        """Append tmjx_intervene on columns [c0, c0 + w) of buf [n][ld] (the edit of analysis.intervene.InterventionBuffers `spec_buffers`, which
+        must hold one gate per row of this list) and return its entry of `calls`: [name, [descriptor, t]] — the step loop writes the control-step
+        index into entry[1][1] before each run."""
+        sb = spec_buffers
+        if sb.n != self.n:
+            raise ValueError(f"intervention buffers for {sb.n} rows in a launch list of {self.n}")
+        if sb.w != int(w):
+            raise ValueError(f"the intervention is {sb.w} wide, the target buffer {int(w)}")
+        d = self.hip.Intervene(buf.data_ptr() + 4 * int(c0), int(ld), int(w), self.n, sb.mode, ptr(sb.dirs), sb.K, sb.ldv, ptr(sb.center), ptr(sb.gain),
+                               ptr(sb.offset), ptr(sb.dose), ptr(sb.t_on), ptr(sb.t_off), ptr(sb.proj), sb.ldp, 0)
+        if not self.L.tmjx_intervene_ok(C.byref(d)):
+            raise ValueError(self.L.tmjx_last_error().decode())
+        self.keep += [buf, sb, d]
+        self.call("tmjx_intervene", C.byref(d), 0)
+        return self.calls[-1]
+
+    def place_intervention(self, intervention, window, dose, x, Z: int, layers: dict, h=None):
+        """Insert the tmjx_intervene call of `intervention` (analysis.intervene.Intervention; window [n, 2], dose [n]) into the finished list,
+        directly behind the call that produces its target, and return (the call's entry, its buffers).  x [n][ldx]: the decoder's input, whose
+        columns [0, Z) are the intention; layers: {"encoder/layer_0": y, ..} the Dense -> SiLU -> LayerNorm outputs; h [n][L][H]: the LSTM carry."""
+        target = intervention.target
+        supported = ["intention", *layers] + ([f"hidden_state/h:{k}" for k in range(h.shape[1])] if h is not None else [])
+
+        def index(pred, nth=0):
+            return [i for i, (name, args) in enumerate(self.calls) if pred(name, args)][nth]
+        if target == "intention":
+            at, buf, c0, w, ld = index(lambda nm, a: nm in ("tmjx_latent_concat_det", "tmjx_decoder_input")), x, 0, int(Z), x.shape[1]
+        elif target in layers:
+            y = layers[target]
+            at, buf, c0, w, ld = index(lambda nm, a: nm == "tmjx_silu_ln_fwd" and a[4] == y.data_ptr()), y, 0, y.shape[1], y.shape[1]
+        elif h is not None and target in supported:
+            k = int(target.rpartition(":")[2])
+            at, buf, c0, w, ld = index(lambda nm, a: nm == "tmjx_lstm_seq_fwd", k), h[:, k], 0, h.shape[2], h.shape[1] * h.shape[2]
+        else:
+            raise ValueError(f"intervention target {target!r} does not exist in this policy step; it has: {', '.join(supported)}")
+        sb = intervention.buffers(self.n, w, self.device, window, dose)
+        entry = self.intervene(buf, c0, w, ld, sb)
+        self.calls.insert(at + 1, self.calls.pop())
+        return entry, sb
+
     def block(self, a, lda: int, blk, fold=None):
         """Dense -> SiLU -> LayerNorm: y [n][N]; `fold` = (fold_mean, fold_inv) takes linear_norm for the dense layer."""
         z = self.linear(a, lda, blk.dense.weight) if fold is None else self.linear_norm(a, lda, blk.dense.weight, *fold)

@@ -8,6 +8,7 @@ step is a fixed sequence of launches on preallocated buffers, with no torch oper
     staging copy of the observation (tmjx_record_step, T = 1)  ->  encoder: tmjx_linear_nolds_norm / tmjx_linear_nolds + tmjx_silu_ln_fwd  ->
     fc2 (tmjx_linear_nolds)  ->  tmjx_latent_concat_det  ->  decoder blocks / LSTM layers (tmjx_linear_nolds [+ tmjx_lstm_seq_fwd, T = 1])  ->
     head  ->  tmjx_action_mode  ->  tmjx_step (tmjx_step_sensors with log_sensor_data)  ->  tmjx_record_step
+    (with an intervention, analysis/intervene.py: one tmjx_intervene directly behind the launch that produces its target; without one, exactly these)
 
 Every dense layer is the matrix-core variant of tmjx_linear_nolds (row-major operands with 16-byte aligned rows, K padded to a multiple of 4):
 its per-row arithmetic does not depend on the number of rows, so a clip's record is the same bits alone or in any batch.  The recorder
@@ -35,6 +36,9 @@ CLI:  python -m track_mjx_amd.analysis.rollout checkpoint=<run dir | step dir> [
       replay_latents=<dir of clip_<i>.h5> [latent_scale=1.0] [path=auto|fused|layers]: instead of running the encoder, re-run the clips of those files
       through a HighLevelWrapper env (environment/wrappers.py: the checkpoint's decoder inside the env) fed their recorded activations/intention
       (times latent_scale), and write the same clip_<i>.h5 layout (activations: the intention that was fed).
+      intervene_pca=<pca.h5> [intervene_components=a:b] | intervene_readout=<readout.h5> [intervene_columns=a:b] | intervene_units=<target>:i,j,k
+      [intervene_mean=<pca.h5>], with [intervene_gain=0] [intervene_offset=0] [intervene_window=a:b] [intervene_dose=<d | d0,d1,..>]: the roll-out (or the
+      replay) runs with that edit of one activation (analysis/intervene.py) and every clip_<i>.h5 gains the group `intervention`.
 """
 from __future__ import annotations
 
@@ -112,14 +116,17 @@ class RolloutPolicy:
         self.action_size = int(policy.action_size)
 
     @torch.no_grad()
-    def __call__(self, obs: torch.Tensor, key=None, hidden_state=None):
-        """obs [n, W] (raw) -> (ctrl [n, nu], {"activations": ...}) (+ the new (h, c) [n, L, H] for the LSTM policy, from `hidden_state` or zeros)."""
+    def __call__(self, obs: torch.Tensor, key=None, hidden_state=None, intervention=None, t: int = 0):
+        """obs [n, W] (raw) -> (ctrl [n, nu], {"activations": ...}) (+ the new (h, c) [n, L, H] for the LSTM policy, from `hidden_state` or zeros).
+        `intervention` (analysis.intervene.Intervention): the step runs with its edit, gated as at control step `t` (its window / dose: one value,
+        or one per row of obs); the activations are what the rest of the network saw."""
         obs = obs.to(device=self.device, dtype=torch.float32)
         n = obs.shape[0]
-        step = _PolicyStep(self, n, obs.t().contiguous(), record=False)
+        step = _PolicyStep(self, n, obs.t().contiguous(), record=False, intervention=intervention,
+                           gates=None if intervention is None else intervention.per_clip(n))
         if self.model == "lstm" and hidden_state is not None:
             step.h.copy_(hidden_state[0]); step.c.copy_(hidden_state[1])
-        step.launch()
+        step.launch(t)
         torch.cuda.current_stream(self.device).synchronize()
         ctrl = step.ctrl.clone()
         extras = {"activations": {k: v.clone() for k, v in step.activation_views().items()}} if self.get_activation else {}
@@ -132,8 +139,11 @@ class _PolicyStep:
     """Preallocated buffers and the launch sequence of one deterministic policy step for `n` envs reading the env's raw observation
     buffer obs_soa [W][n]."""
 
-    def __init__(self, rp: RolloutPolicy, n: int, obs_soa: torch.Tensor, record: bool = True, carry_reset: torch.Tensor | None = None):
-        """`carry_reset` [n] float32 (LSTM policy): where it is non-zero when the step is launched, the row's (h, c) are zeroed first."""
+    def __init__(self, rp: RolloutPolicy, n: int, obs_soa: torch.Tensor, record: bool = True, carry_reset: torch.Tensor | None = None,
+                 intervention=None, gates=None):
+        """`carry_reset` [n] float32 (LSTM policy): where it is non-zero when the step is launched, the row's (h, c) are zeroed first.
+        `intervention` (analysis.intervene.Intervention) with `gates` = (window [n, 2], dose [n]): one tmjx_intervene call directly behind the
+        launch that produces its target; without one the list is what it always was."""
         pol, dev = rp.policy, rp.device
         self.rp, self.n, self.obs_soa = rp, int(n), obs_soa
         self.L = _hip.lib()
@@ -183,10 +193,18 @@ class _PolicyStep:
         # the staging copy of the observation: one SoA stream into a [n][1][W] record
         st = _hip.RecordStream(_p(obs_soa), _p(self.stage), _hip.RECORD_SOA, n, W, W, 1, 0, 0)
         self.stage_table = _upload_table([st], n, 1, dev)
-        self.stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        # (a list built on the host, to be inspected and never launched, has no stream)
+        self.stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if torch.device(dev).type == "cuda" else None
+        self.iv_entry = self.iv = None
+        if intervention is not None:
+            layers = {f"{part}/{k}": v[0] for part in ("encoder", "decoder") for k, v in self.acts[part].items() if k.startswith("layer_")}
+            self.iv_entry, self.iv = ll.place_intervention(intervention, gates[0], gates[1], self.x, Z, layers, self.h if rp.model == "lstm" else None)
 
-    def launch(self) -> None:
-        """The policy step's launches on the current stream (ctypes calls only: no torch operation)."""
+    def launch(self, t: int = 0) -> None:
+        """The policy step's launches on the current stream (ctypes calls only: no torch operation); `t`: the control-step index an
+        intervention's gate sees."""
+        if self.iv_entry is not None:
+            self.iv_entry[1][1] = t
         _hip.check(self.L.tmjx_record_step(self.stage_table.data_ptr(), 1, self.n, 0, 1, self.stream), "tmjx_record_step")
         self.ll.run(self.stream)
 
@@ -217,7 +235,7 @@ def _upload_table(streams: Sequence, n: int, T: int, dev) -> torch.Tensor:
 def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, model: str = "mlp", log_activations: bool = False,
                              log_metrics: bool = False, log_sensor_data: bool = False, clips_per_batch: int = CLIPS_PER_BATCH,
                              align_on_fail: bool = False, friction_scale=None, actuator_scale=None, damping_scale=None,
-                             gravity_scale=None, slope_deg=None):
+                             gravity_scale=None, slope_deg=None, intervention=None):
     """rollout.py:73-269.  Returns generate_rollout(clip_idx=None, seed=42): one clip (int / None) -> dict of arrays; a sequence of clips -> the
     same dict with a leading [N] axis (batches larger than `clips_per_batch` run in chunks).
 
@@ -227,7 +245,18 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
 
     `gravity_scale` / `slope_deg` (one float, or one per clip, likewise): the clip's env runs with the gravity vector slope_gravity(|g|, s, a) =
     s |g| (sin a, 0, -cos a), |g| the magnitude of the model's gravity — s < 1 is body-weight support, a > 0 a floor inclined so that +x is
-    downhill — and the result carries it as `gravity` [3]."""
+    downhill — and the result carries it as `gravity` [3].
+
+    `intervention` (analysis.intervene.Intervention): the policy step runs with its edit of one activation (one more launch, tmjx_intervene, behind
+    the one that produces the target); its window and dose are one value, or one per clip of a generate_rollout call (a clip may be repeated in
+    clip_idx with different doses).  The result gains the group `intervention` (target, mode, directions | units, center, gain, offset, window [2],
+    dose and, in subspace mode, projection [T - 1, K]: the pre-edit coordinates of every step, ON or OFF), and the recorded activation of the
+    target is its value after the edit."""
+    if intervention is not None:
+        from .intervene import Intervention
+        if not isinstance(intervention, Intervention):
+            raise TypeError(f"intervention must be an analysis.intervene.Intervention, got {type(intervention).__name__}")
+    iv_gates: dict = {}
     given_scales = {k: v for k, v in (("friction", friction_scale), ("actuator", actuator_scale), ("damping", damping_scale)) if v is not None}
     if given_scales and not hasattr(environment, "set_domain_randomization"):
         raise NotImplementedError(f"friction_scale / actuator_scale / damping_scale: {type(environment).__name__} has no per-env scales "
@@ -315,7 +344,7 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
             per[name] = np.full(n, v[0]) if v.size == 1 else v[offset:offset + n]
         return slope_gravity(model_gravity_magnitude(env0), per["gravity_scale"], per["slope_deg"])
 
-    def run_batch(clips: list, seed: int, scales=None, gravity=None) -> dict:
+    def run_batch(clips: list, seed: int, scales=None, gravity=None, gates=None) -> dict:
         n = len(clips)
         env = env_of(n)
         if scales is not None or gravity is not None:
@@ -331,7 +360,8 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
             env.reset(None, torch.tensor(clips, dtype=torch.int32), start_frame=torch.zeros(n, dtype=torch.int32),
                       qpos_noise=torch.from_numpy(qn), qvel_noise=torch.from_numpy(vn))
             # align_on_fail: the LSTM carry of an env is zeroed in the policy step that follows its alignment (done_buf is 0 after reset)
-            step = _PolicyStep(inference_fn, n, env.obs_buf, carry_reset=env.done_buf if align_on_fail and inference_fn.model == "lstm" else None)
+            step = _PolicyStep(inference_fn, n, env.obs_buf, carry_reset=env.done_buf if align_on_fail and inference_fn.model == "lstm" else None,
+                               intervention=intervention, gates=gates)
             f32 = dict(dtype=torch.float32, device=dev)
             rec: dict = {}
             state_streams, step_streams = [], []
@@ -377,6 +407,9 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
                 step_streams.append(add("joint_forces", _p(cf_buf), _hip.RECORD_SOA, n, nb6, nb6, T - 1, 0))
             if align_on_fail:
                 step_streams.append(add("aligned", _p(env.done_buf), _hip.RECORD_SOA, n, 1, 1, T - 1, 0))
+            if step.iv is not None and step.iv.proj is not None:
+                K = step.iv.K
+                step_streams.append(add("intervention:projection", _p(step.iv.proj), _hip.RECORD_ROWMAJOR, K, K, K, T - 1, 0))
             init_tab = _upload_table(init_streams, n, 1, dev)
             state_tab = _upload_table(state_streams, n, T - 1, dev)
             step_tab = _upload_table(step_streams, n, T - 1, dev)
@@ -405,6 +438,8 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
         if align_on_fail:
             out["aligned"] = host["aligned"][:, :, 0] != 0
             out["n_alignments"] = out["aligned"].sum(axis=1).astype(np.int64)
+        if intervention is not None:
+            out["intervention"] = intervention.record(gates[0], gates[1], host.get("intervention:projection"))
         if log_sensor_data:
             out["joint_forces"] = host["joint_forces"].reshape(n, T - 1, -1, 6)
             out["sensor_readings"] = host["sensor_readings"] if "sensor_readings" in host else np.zeros((n, T - 1, 0), np.float32)
@@ -428,9 +463,15 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
             out["activations"] = acts
         return out
 
-    def generate_rollout(clip_idx: int | Sequence[int] | None = None, seed: int = 42, scales: dict | None = None, gravity: dict | None = None) -> dict:
+    def generate_rollout(clip_idx: int | Sequence[int] | None = None, seed: int = 42, scales: dict | None = None, gravity: dict | None = None,
+                         gates: dict | None = None) -> dict:
         """`scales`: {"friction" | "actuator" | "damping": float or one per clip} for THIS call, in place of the generator's own (a generator made
-        without scales takes none: its sensor / env checks were made for the plain env).  `gravity`: {"gravity_scale" | "slope_deg": ...}, likewise."""
+        without scales takes none: its sensor / env checks were made for the plain env).  `gravity`: {"gravity_scale" | "slope_deg": ...}, likewise.
+        `gates`: {"window" | "dose": one value or one per clip} of the generator's intervention for THIS call, in place of the intervention's own."""
+        if gates is not None:
+            if intervention is None:
+                raise ValueError("generate_rollout(gates=...): the generator was created without an intervention")
+            iv_gates.clear(); iv_gates.update({k: v for k, v in gates.items() if v is not None})
         if gravity is not None:
             if not given_gravity:
                 raise ValueError("generate_rollout(gravity=...): the generator was created without gravity_scale / slope_deg")
@@ -450,8 +491,12 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
         bad = [c for c in clips if not 0 <= c < env0._n_clips]
         if bad:
             raise IndexError(f"clip indices {bad[:5]} outside the table's {env0._n_clips} clips")
+        win = dose = None
+        if intervention is not None:
+            win, dose = intervention.per_clip(len(clips), iv_gates.get("window"), iv_gates.get("dose"))
         parts = [run_batch(clips[i:i + clips_per_batch], seed, scales_of(len(clips[i:i + clips_per_batch]), i, len(clips)),
-                           gravity_of(len(clips[i:i + clips_per_batch]), i, len(clips)))
+                           gravity_of(len(clips[i:i + clips_per_batch]), i, len(clips)),
+                           None if intervention is None else (win[i:i + clips_per_batch], dose[i:i + clips_per_batch]))
                  for i in range(0, len(clips), int(clips_per_batch))]
         out = _concat(parts) if len(parts) > 1 else parts[0]
         return out if batched else _index0(out)
@@ -467,7 +512,7 @@ def _step_loop(step: _PolicyStep, L, s, hdl, env_args, state_tab: int, ks: int, 
     """The T - 1 control steps: policy launches, tmjx_action_mode (inside step.launch), tmjx_step (or tmjx_step_sensors), tmjx_record_step x 2."""
     env_step = getattr(L, step_fn)
     for t in range(T - 1):
-        step.launch()
+        step.launch(t)
         _hip.check(env_step(hdl, *env_args, s), step_fn)
         _hip.check(L.tmjx_record_step(step_tab, kp, n, t, T - 1, s), "tmjx_record_step")
         _hip.check(L.tmjx_record_step(state_tab, ks, n, t, T - 1, s), "tmjx_record_step")
@@ -502,7 +547,9 @@ def _parse_clips(spec: str, n_clips: int) -> list:
 
 
 CLI_OPTIONS = ("checkpoint", "clips", "seed", "out", "log_activations", "log_metrics", "log_sensor_data", "align_on_fail", "step",
-               "replay_latents", "latent_scale", "path", "friction_scale", "actuator_scale", "damping_scale", "gravity_scale", "slope_deg")
+               "replay_latents", "latent_scale", "path", "friction_scale", "actuator_scale", "damping_scale", "gravity_scale", "slope_deg",
+               "intervene_pca", "intervene_components", "intervene_readout", "intervene_columns", "intervene_units", "intervene_mean", "intervene_gain",
+               "intervene_offset", "intervene_window", "intervene_dose")
 
 
 def slope_gravity(magnitude: float, gravity_scale=1.0, slope_deg=0.0) -> np.ndarray:
@@ -528,16 +575,20 @@ def parse_per_clip(name: str, text, n_clips: int):
     return v
 
 
-def replay_latents(cfg: dict, decoder_policy, clips: Sequence[int], latents: np.ndarray, seed: int = 42, path: str = "auto", metrics=ROLLOUT_METRICS) -> dict:
+def replay_latents(cfg: dict, decoder_policy, clips: Sequence[int], latents: np.ndarray, seed: int = 42, path: str = "auto", metrics=ROLLOUT_METRICS,
+                   intervention=None) -> dict:
     """Step a HighLevelWrapper env (the decoder inside the env) from generate_rollout's reset of `clips` with latents [n, T - 1, Z]: the roll-out
-    dict ([n] leading axis) with qposes_rollout, ctrl, state_rewards, qposes_ref, rollout_metrics and activations/intention (what was fed)."""
+    dict ([n] leading axis) with qposes_rollout, ctrl, state_rewards, qposes_ref, rollout_metrics and activations/intention (what was fed).
+    `intervention` (analysis.intervene.Intervention on intention, decoder/layer_<i> or hidden_state/h:<k>; window / dose: one value, or one per
+    clip): the decoder runs with its edit on the "layers" path (path="fused" raises), and the dict gains the group `intervention`."""
     from ..environment.wrappers import HighLevelWrapper
     n, T = len(clips), latents.shape[1] + 1
     env = create_environment(cfg, n, decoder_policy.device)
     from ..agent.checkpoint import LSTMDecoderPolicy
     # (an LSTM decoder's carry starts from zero at the reset and is never reset afterwards, as in a plain roll-out)
     kw = dict(reset_carry_on_done=False) if isinstance(decoder_policy, LSTMDecoderPolicy) else {}
-    hl = HighLevelWrapper(env, decoder_policy, decoder_policy.reference_obs_size, path=path, **kw)
+    hl = HighLevelWrapper(env, decoder_policy, decoder_policy.reference_obs_size, path=path, intervention=intervention, **kw)
+    gates = None if intervention is None else intervention.per_clip(n)
     nq, nv = int(env.layout.nq), int(env.layout.nv)
     qn, vn = np.empty((nq, n), np.float32), np.empty((nv, n), np.float32)
     for j, c in enumerate(clips):
@@ -549,10 +600,13 @@ def replay_latents(cfg: dict, decoder_policy, clips: Sequence[int], latents: np.
         f32 = dict(dtype=torch.float32, device=env.device)
         qpos, rew = torch.empty((T, n, nq), **f32), torch.empty((T, n), **f32)
         met, ctrl = torch.empty((T, len(METRIC_NAMES), n), **f32), torch.empty((T - 1, n, decoder_policy.action_size), **f32)
+        proj = torch.empty((T - 1, n, intervention.K), **f32) if intervention is not None and intervention.mode == "subspace" else None
         qpos[0].copy_(st.pipeline_state["qpos"]); rew[0].copy_(st.reward); met[0].copy_(env.metrics_buf)
         for t in range(T - 1):
-            st = hl.step(st, lat[:, t])
+            st = hl.step(st, lat[:, t], t)
             qpos[t + 1].copy_(st.pipeline_state["qpos"]); rew[t + 1].copy_(st.reward); met[t + 1].copy_(env.metrics_buf); ctrl[t].copy_(hl.last_ctrl)
+            if proj is not None:
+                proj[t].copy_(hl.intervention_projection)
         qpos, rew, met, ctrl = (v.cpu().numpy() for v in (qpos, rew, met, ctrl))
     spf = int(env._steps_for_cur_frame)
     ref = env._reference_clips
@@ -561,10 +615,12 @@ def replay_latents(cfg: dict, decoder_policy, clips: Sequence[int], latents: np.
     return {"qposes_rollout": np.ascontiguousarray(qpos.transpose(1, 0, 2)), "ctrl": np.ascontiguousarray(ctrl.transpose(1, 0, 2)),
             "state_rewards": np.ascontiguousarray(rew.T), "qposes_ref": np.stack(rows),
             "rollout_metrics": {f"{m}s": np.ascontiguousarray(met[:, METRIC_NAMES.index(m)].T) for m in metrics},
-            "activations": {"intention": np.ascontiguousarray(latents, dtype=np.float32)}, "path": hl.path}
+            "activations": {"intention": np.ascontiguousarray(latents, dtype=np.float32)}, "path": hl.path,
+            **({} if intervention is None else {"intervention": intervention.record(
+                gates[0], gates[1], None if proj is None else np.ascontiguousarray(proj.cpu().numpy().transpose(1, 0, 2)))})}
 
 
-def _main_replay(opts: dict, cfg: dict, step_dir: str) -> int:
+def _main_replay(opts: dict, cfg: dict, step_dir: str, intervention=None) -> int:
     import re
     from ..agent import checkpoint as ckpt
     from .utils import load_from_h5py, save_to_h5py
@@ -592,7 +648,12 @@ def _main_replay(opts: dict, cfg: dict, step_dir: str) -> int:
         lat = np.stack([np.asarray(r["activations"]["intention"], np.float32) for r in recs])
         if scale != 1.0:
             lat = lat * np.float32(scale)
-        res = replay_latents(cfg, dp, chunk, lat, seed=seed, path=opts.get("path", "auto"), metrics=metrics)
+        iv = intervention
+        if iv is not None:      # (this chunk's doses of a per-clip list)
+            import copy
+            iv = copy.copy(intervention)
+            iv.dose = intervention.per_clip(len(found))[1][i:i + len(chunk)]
+        res = replay_latents(cfg, dp, chunk, lat, seed=seed, path=opts.get("path", "auto"), metrics=metrics, intervention=iv)
         used = res.pop("path")
         for j, c in enumerate(chunk):
             one = _index_j(res, j)
@@ -621,7 +682,10 @@ def main(argv=None) -> int:
         print("usage: python -m track_mjx_amd.analysis.rollout checkpoint=<run dir | step dir> [data_path=...] [clips=all|a:b|i,j,k] [seed=42] "
               "[out=<dir>] [log_activations=true] [log_metrics=true] [log_sensor_data=false] [align_on_fail=false] "
               "[friction_scale=<s | s0,s1,..>] [actuator_scale=..] [damping_scale=..] [gravity_scale=<s | s0,s1,..>] [slope_deg=<a | a0,a1,..>] "
-              "[replay_latents=<dir of clip_<i>.h5> [latent_scale=1.0] [path=auto|fused|layers]] [key=value config overrides ...]", file=sys.stderr)
+              "[replay_latents=<dir of clip_<i>.h5> [latent_scale=1.0] [path=auto|fused|layers]] "
+              "[intervene_pca=<pca.h5> [intervene_components=a:b] | intervene_readout=<readout.h5> [intervene_columns=a:b] | "
+              "intervene_units=<target>:i,j,k [intervene_mean=<pca.h5>]] [intervene_gain=0] [intervene_offset=0] [intervene_window=a:b] "
+              "[intervene_dose=<d | d0,d1,..>] [key=value config overrides ...]", file=sys.stderr)
         return 2
     yes = lambda v: str(v).lower() in ("1", "true", "yes")     # noqa: E731
     path = opts["checkpoint"]
@@ -636,8 +700,22 @@ def main(argv=None) -> int:
         import yaml
         node[key.split(".")[-1]] = yaml.safe_load(val)
     step_dir = ckpt.resolve_step_dir(path, step_no)
+    from . import intervene as _iv
+    try:
+        intervention = _iv.from_cli(opts)
+        if intervention is not None and "replay_latents" in opts and opts.get("path") == "fused":
+            raise ValueError("path=fused cannot run an intervention (the fused decoder launch has no seam between its layers): path=layers or auto")
+    except ValueError as e:
+        print(f"[rollout] {e}", file=sys.stderr)
+        return 2
     if "replay_latents" in opts:
-        return _main_replay(opts, cfg, step_dir)
+        try:
+            return _main_replay(opts, cfg, step_dir, intervention)
+        except ValueError as e:
+            if intervention is None:
+                raise
+            print(f"[rollout] {e}", file=sys.stderr)
+            return 2
     if "latent_scale" in opts or "path" in opts:
         print("[rollout] latent_scale / path go with replay_latents=<dir>", file=sys.stderr)
         return 2
@@ -659,9 +737,15 @@ def main(argv=None) -> int:
         return v
     scale_lists = {k: scale_opt(k) for k in ("friction_scale", "actuator_scale", "damping_scale")}
     gravity_lists = {k: parse_per_clip(k, opts[k], len(clips)) for k in ("gravity_scale", "slope_deg") if k in opts}
+    if intervention is not None:
+        try:
+            _, iv_dose = intervention.per_clip(len(clips))
+        except ValueError as e:
+            print(f"[rollout] intervene_{e}", file=sys.stderr)
+            return 2
     gen = create_rollout_generator(cfg, env, fn, model=fn.model, log_activations=log_act, log_metrics=log_met, log_sensor_data=log_sens,
                                    align_on_fail=align, **{k: (None if v is None else 1.0) for k, v in scale_lists.items()},
-                                   **{k: (1.0 if k == "gravity_scale" else 0.0) for k in gravity_lists})
+                                   **{k: (1.0 if k == "gravity_scale" else 0.0) for k in gravity_lists}, intervention=intervention)
     print(f"[rollout] done-policy: {gen.done_policy}" + (" (a done env is re-aligned to the clip frame it has reached; `aligned` / `n_alignments` "
                                                         "are recorded)" if align else " (the env keeps stepping after done)"), flush=True)
     out_dir = opts.get("out", os.path.join(step_dir, "rollouts"))
@@ -682,7 +766,14 @@ def main(argv=None) -> int:
         chunk = clips[i:i + CLIPS_PER_BATCH]
         sc = {k.split("_")[0]: (v[0] if len(v) == 1 else v[i:i + len(chunk)]) for k, v in scale_lists.items() if v is not None}
         gr = {k: (v[0] if len(v) == 1 else v[i:i + len(chunk)]) for k, v in gravity_lists.items()}
-        res = gen(chunk, seed=seed, **({"scales": sc} if sc else {}), **({"gravity": gr} if gr else {}))
+        try:
+            res = gen(chunk, seed=seed, **({"scales": sc} if sc else {}), **({"gravity": gr} if gr else {}),
+                      **({"gates": {"dose": iv_dose[i:i + len(chunk)]}} if intervention is not None else {}))
+        except ValueError as e:      # an intervention the policy step refuses (a target it does not have, a width that does not match)
+            if intervention is None:
+                raise
+            print(f"[rollout] {e}", file=sys.stderr)
+            return 2
         for j, c in enumerate(chunk):
             one = _index_j(res, j)
             one["meta"] = dict(meta_common, clip_idx=np.int64(c))

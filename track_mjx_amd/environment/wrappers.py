@@ -155,9 +155,12 @@ class _DecoderStep:
 
     path "layers": tmjx_decoder_input (tmjx_latent_concat_det's kernel, for latents [n][ldz >= Z]), then the decoder half of the roll-out's policy step
     (agent/launch_list.py, which analysis.rollout._PolicyStep builds from too): its kernels, operand layouts and therefore its bits.
-    path "fused": one tmjx_decoder_act / tmjx_lstm_decoder_act launch."""
+    path "fused": one tmjx_decoder_act / tmjx_lstm_decoder_act launch.
 
-    def __init__(self, dp, n: int, obs_soa, path: str, reset=None):
+    `intervention` (analysis.intervene.Intervention) with `gates` = (window [n, 2], dose [n]), layers path only: one tmjx_intervene call directly
+    behind the launch that produces its target (intention, decoder/layer_<i>, hidden_state/h:<k>)."""
+
+    def __init__(self, dp, n: int, obs_soa, path: str, reset=None, intervention=None, gates=None):
         from ..agent.launch_list import LaunchList, ceil4, ptr
         ll = self.ll = LaunchList(n, dp.device)
         lstm = _is_lstm(dp)
@@ -191,9 +194,17 @@ class _DecoderStep:
             else:
                 out = ll.decoder(x, dp.net.decoder, dp.net.head.weight, dp.net.head.bias)
             self.ctrl, self.action_t = out[2:]
+        self.iv_entry = self.iv = None
+        if intervention is not None:
+            if path == "fused":
+                raise ValueError("an intervention needs path='layers': the fused decoder launch has no seam between its layers")
+            layers = {f"decoder/layer_{i}": y for i, y in enumerate(out[0])}
+            self.iv_entry, self.iv = ll.place_intervention(intervention, gates[0], gates[1], x, Z, layers, self.h)
 
-    def launch(self, lat_ptr: int, ldz: int, stream) -> None:
-        """The decoder's launches on `stream` (ctypes calls only: no torch operation)."""
+    def launch(self, lat_ptr: int, ldz: int, stream, t: int = 0) -> None:
+        """The decoder's launches on `stream` (ctypes calls only: no torch operation); `t`: the control-step index an intervention's gate sees."""
+        if self.iv_entry is not None:
+            self.iv_entry[1][1] = t
         if self.desc is not None:
             self.desc.latents, self.desc.ldz = lat_ptr, ldz
         else:
@@ -227,10 +238,21 @@ class HighLevelWrapper:
     # the alternating repeats within 0.2 us of each other — "auto" takes tmjx_lstm_decoder_act where tmjx_lstm_decoder_act_ok says so
     AUTO_PREFERS_FUSED_LSTM = True
 
-    def __init__(self, env, decoder_inference_fn, reference_obs_size: int, path: str = "auto", reset_carry_on_done: bool = True):
+    def __init__(self, env, decoder_inference_fn, reference_obs_size: int, path: str = "auto", reset_carry_on_done: bool = True, intervention=None):
+        """`intervention` (analysis.intervene.Intervention; its window / dose: one value, or one per env): the decoder runs with its edit, one more
+        launch of the "layers" list; step counts the control steps since reset() for its gate.  path="fused" then raises (the fused launches have
+        no seam) and path="auto" takes "layers"."""
         from ..agent.checkpoint import DecoderPolicy, LSTMDecoderPolicy
         if path not in ("auto", "fused", "layers"):
             raise ValueError(f"HighLevelWrapper: path must be 'auto', 'fused' or 'layers', not {path!r}")
+        if intervention is not None:
+            if path == "fused":
+                raise ValueError("HighLevelWrapper: path='fused' cannot run an intervention: the fused decoder launch has no seam between its layers; "
+                                 "use path='layers' (or 'auto', which takes it)")
+            if not isinstance(decoder_inference_fn, (DecoderPolicy, LSTMDecoderPolicy)):
+                raise ValueError("HighLevelWrapper: an intervention needs a DecoderPolicy / LSTMDecoderPolicy (the launch-list path)")
+            path = "layers"
+        self._intervention, self._t = intervention, 0
         if not callable(decoder_inference_fn):
             raise TypeError("HighLevelWrapper: decoder_inference_fn must be a DecoderPolicy or a callable fn(x) -> (action, extras)")
         self.env, self._fn, self._ref = env, decoder_inference_fn, int(reference_obs_size)
@@ -285,6 +307,7 @@ class HighLevelWrapper:
     def reset(self, *a, **kw):
         self._state = None
         self._h = self._c = None
+        self._t = 0
         if self._lstm and self._step is not None:
             self._step.h.zero_(); self._step.c.zero_()
         return self.env.reset(*a, **kw)
@@ -315,7 +338,9 @@ class HighLevelWrapper:
         import torch
         env, n = self.env, int(self.env.num_envs)
         with torch.cuda.device(env.device):
-            self._step = _DecoderStep(self._fn, n, env.obs_buf, self.path, env.done_buf if self._lstm and self.reset_carry_on_done else None)
+            iv = self._intervention
+            self._step = _DecoderStep(self._fn, n, env.obs_buf, self.path, env.done_buf if self._lstm and self.reset_carry_on_done else None,
+                                      intervention=iv, gates=None if iv is None else iv.per_clip(n))
         p = lambda t: t.data_ptr()      # noqa: E731
         self._env_args = (env._handle, p(env.state_buf), p(env.istate_buf), p(self._step.action_t), p(env.obs_buf), p(env.reward_buf), p(env.done_buf),
                           p(env.trunc_buf), p(env.metrics_buf), p(env.workspace), n)
@@ -327,8 +352,11 @@ class HighLevelWrapper:
         if self._Z is not None and latents.shape[1] != self._Z:
             raise ValueError(f"HighLevelWrapper.step: latents have {latents.shape[1]} columns, the decoder's intention size is {self._Z}")
 
-    def step(self, state, latents):
+    def step(self, state, latents, t: int | None = None):
+        """`t`: the control-step index an intervention's gate sees (default: the steps taken since reset())."""
         self._check_latents(latents)
+        if t is not None:
+            self._t = int(t)
         env = self.env
         if self.path == "callable":
             import torch
@@ -354,10 +382,16 @@ class HighLevelWrapper:
             raise RuntimeError("HighLevelWrapper: the K2-bracketing measurement mode steps the plain env")
         with torch.cuda.device(env.device):
             stream = C.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)
-            self._step.launch(latents.data_ptr(), latents.stride(0), stream)
+            self._step.launch(latents.data_ptr(), latents.stride(0), stream, self._t)
             self._step.ll.hip.check(self._step.ll.L.tmjx_step(*self._env_args, stream), "tmjx_step")
+        self._t += 1
         self._keep_lat = latents
         return self._state
+
+    @property
+    def intervention_projection(self):
+        """[n, K] view of the pre-edit coordinates of the last device-path step under a subspace intervention (else None)."""
+        return None if self._step is None or self._step.iv is None else self._step.iv.proj
 
     @property
     def last_ctrl(self):
