@@ -852,6 +852,38 @@ int tmjx_readout_predict(const float *x, int n, int d, int64_t ldx, const float 
 int tmjx_readout_score(const float *x, int n, int d, int64_t ldx, const float *y, int m, int64_t ldy, const float *mean_x, const float *w, const float *mean_y,
                        int n_lambda, double *sse, double *sst, float *workspace, void *stream);
 
+/* ---- k-means of recorded activations x [n][d] (1 <= d <= 1024) into 1 <= k <= 256 clusters, k <= n: Lloyd's iteration with k-means++ seeding
+ * (csrc/tmjx_kmeans.hip, csrc/kmeans_core.h; DESIGN.md "Clustering").  No model handle; all device memory is the caller's; everything runs on the
+ * caller's stream.  x is float32 and may be a column slice of a wider buffer (ldx >= d).  Fixed-order arithmetic, no floating-point atomics: the same
+ * bits on every run.
+ *   tmjx_kmeans_workspace: *floats = the size of the scratch every call below takes for these n, d, k (it does not scale with n k d).
+ *   tmjx_kmeans_assign: labels [n] = the nearest centroid of every row, the lowest index on a tie; the [n][k] distances are never written.  Scores
+ *     are cnorm_j - 2 (x - mean) . (c_j - mean) with the float64 column mean of x rounded to float32, one fmaf chain per pair in ascending feature
+ *     order; dist2 [n] (optional) = max(0, ||x - mean||^2 + score) of the chosen one; *inertia (device float64) = the sum of the float32 dist2 in a
+ *     fixed order; *changed (device int32, optional) = the rows whose label differs from labels_prev [n] (all n when labels_prev is null;
+ *     labels_prev may not be the labels buffer itself).
+ *   tmjx_kmeans_update: every non-empty cluster's centroid = the mean of its rows, accumulated in float64 from the first add in a fixed order and
+ *     rounded once; an empty cluster keeps its bits; counts [k] (device int32) = the rows of each.  A label outside [0, k) is skipped.
+ *   tmjx_kmeans_seed: k-means++.  u [k] (HOST, uniforms in [0, 1)); centre 0 is row min(floor(u_0 n), n - 1); before centre j >= 1 every row's
+ *     d2 = min(d2, ||x - c_(j-1)||^2) in float32, then the smallest row i with cum[i] > u_j total is taken, cum the float64 prefix sum of d2 in row
+ *     order (total == 0: row min(floor(u_j n), n - 1)).  One pass over x per centre; index [k] (HOST, out) are the rows chosen.  WAITS for the stream.
+ *   tmjx_kmeans_fit: from the centroids given, iterations of assign then update until no label changed, or the inertia fell by no more than
+ *     tol x the previous inertia, or max_iter; then one assign against the final centroids, whose labels, dist2 (optional) and inertia are returned.
+ *     It reads one int32 and one float64 back per iteration and WAITS for the stream.  info->n_iter counts the assigns of the loop.
+ *   Refused before any launch (TMJX_EINVAL, the message names the value): n < 1, d outside 1 .. 1024, k outside 1 .. 256, k > n, ldx < d, a null
+ *   required pointer, a workspace not 16-byte aligned, a u outside [0, 1), max_iter < 1, tol < 0 or NaN. */
+#define KMEANS_MAX_D 1024
+#define KMEANS_MAX_K 256
+typedef struct { int32_t n_iter, changed; double inertia; float assign_ms, update_ms; } tmjx_kmeans_info_t;
+int tmjx_kmeans_workspace(int n, int d, int k, int64_t *floats);
+int tmjx_kmeans_assign(const float *x, int n, int d, int64_t ldx, const float *centroids, int k, const int32_t *labels_prev, int32_t *labels, float *dist2,
+                       double *inertia, int32_t *changed, float *workspace, void *stream);
+int tmjx_kmeans_update(const float *x, int n, int d, int64_t ldx, const int32_t *labels, int k, float *centroids, int32_t *counts, float *workspace,
+                       void *stream);
+int tmjx_kmeans_seed(const float *x, int n, int d, int64_t ldx, int k, const double *u, float *centroids, int32_t *index, float *workspace, void *stream);
+int tmjx_kmeans_fit(const float *x, int n, int d, int64_t ldx, int k, float *centroids, int32_t *labels, float *dist2, int max_iter, double tol,
+                    tmjx_kmeans_info_t *info, float *workspace, void *stream);
+
 /* ---- Activation intervention (csrc/tmjx_intervene.hip, csrc/intervene_core.h; DESIGN.md "Interventions"): one launch that edits, in place, the
  * columns [0, w) of the rows h [n][ld] — a layer's output buffer, or a column slice of one — between two launches of a policy step.  Row r at step t:
  *   subspace mode:  p_k = sum_j (h_j - c_j) v_kj;  e_j = sum_k ((g_k - 1) p_k + o_k) v_kj;  h'_j = h_j + dose_r e_j   (dirs [K][ldv], gain / offset [K])

@@ -32,7 +32,7 @@ T_END = 2 ** 31 - 1
 RANK_TOL = 1e-6
 SUPPORTED = "intention, encoder/layer_<i>, decoder/layer_<i>, hidden_state/h:<k> (LSTM policies)"
 _TARGET = re.compile(r"intention|(encoder|decoder)/layer_\d+|hidden_state/h:\d+")
-CLI_OPTIONS = ("intervene_pca", "intervene_components", "intervene_readout", "intervene_columns", "intervene_units", "intervene_mean", "intervene_gain",
+CLI_OPTIONS = ("intervene_pca", "intervene_components", "intervene_readout", "intervene_centroids", "intervene_columns", "intervene_units", "intervene_mean", "intervene_gain",
                "intervene_offset", "intervene_window", "intervene_dose")
 
 
@@ -212,6 +212,17 @@ class Intervention:
         return cls(_text(f["feature"][()]), "subspace", directions=coef[:, idx].T, center=np.asarray(f["mean_x"][()], np.float32), **kw)
 
     @classmethod
+    def from_centroids(cls, path, columns="0:3", **kw):
+        """Target, directions and center from a clusters.h5 (analysis.cluster: `centroids` [k, d], `feature`): the rows `columns` of
+        centroids - mean(centroids) are the directions, the mean of the centroids the center."""
+        from .. import h5lite
+        f = h5lite.File(str(path))
+        cen = np.asarray(f["centroids"][()], np.float64)
+        idx = _slice(columns, cen.shape[0], "columns")
+        mean = cen.mean(0)
+        return cls(_text(f["feature"][()]), "subspace", directions=(cen - mean)[idx], center=mean.astype(np.float32), **kw)
+
+    @classmethod
     def units(cls, target, indices, center=None, **kw):      # noqa: F811  (the instance attribute `units` shadows it on instances only)
         """A units-mode intervention; center: None (0), an array [w], or the path of a pca.h5 of the same feature (its `mean`)."""
         if isinstance(center, (str, os.PathLike)):
@@ -227,18 +238,19 @@ class Intervention:
 def from_cli(opts: dict):
     """The Intervention of the roll-out command line's intervene_* options (analysis.rollout), or None; (window, dose) stay per-clip lists for
     per_clip.  ValueError: a usage error."""
-    given = [k for k in ("intervene_pca", "intervene_readout", "intervene_units") if k in opts]
+    given = [k for k in ("intervene_pca", "intervene_readout", "intervene_centroids", "intervene_units") if k in opts]
     if not given:
         extra = [k for k in CLI_OPTIONS if k in opts]
         if extra:
-            raise ValueError(f"{', '.join(extra)}: no intervention is given (intervene_pca= | intervene_readout= | intervene_units=)")
+            raise ValueError(f"{', '.join(extra)}: no intervention is given (intervene_pca= | intervene_readout= | intervene_centroids= | intervene_units=)")
         return None
     if len(given) > 1:
-        raise ValueError(f"exactly one of intervene_pca / intervene_readout / intervene_units may be given (got {', '.join(given)})")
+        raise ValueError(f"exactly one of intervene_pca / intervene_readout / intervene_centroids / intervene_units may be given (got {', '.join(given)})")
     src = given[0]
-    for opt, owner in (("intervene_components", "intervene_pca"), ("intervene_columns", "intervene_readout"), ("intervene_mean", "intervene_units")):
-        if opt in opts and owner != src:
-            raise ValueError(f"{opt} goes with {owner}=")
+    for opt, owners in (("intervene_components", ("intervene_pca",)), ("intervene_columns", ("intervene_readout", "intervene_centroids")),
+                        ("intervene_mean", ("intervene_units",))):
+        if opt in opts and src not in owners:
+            raise ValueError(f"{opt} goes with {owners[0]}=" + "".join(f" or {o}=" for o in owners[1:]))
     floats = lambda k, d: [float(x) for x in str(opts[k]).split(",") if x.strip()] if k in opts else d      # noqa: E731
     kw = dict(gain=floats("intervene_gain", 0.0), offset=floats("intervene_offset", 0.0), dose=floats("intervene_dose", 1.0))
     if "intervene_window" in opts:
@@ -251,6 +263,8 @@ def from_cli(opts: dict):
             return Intervention.from_pca(opts[src], opts.get("intervene_components", "0:2"), **kw)
         if src == "intervene_readout":
             return Intervention.from_readout(opts[src], opts.get("intervene_columns", "0:3"), **kw)
+        if src == "intervene_centroids":
+            return Intervention.from_centroids(opts[src], opts.get("intervene_columns", "0:3"), **kw)
         target, sep, idx = str(opts[src]).rpartition(":")
         if target.startswith("hidden_state/h") and target.count(":") == 0:      # hidden_state/h:<k>:i,j
             raise ValueError("intervene_units=hidden_state/h:<k>:i,j,k")

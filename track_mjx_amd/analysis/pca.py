@@ -42,7 +42,7 @@ def strip_style(width: int, height: int, line_half_width: float = 1.0, marker_ra
 class HipBackend:
     """The PCA and panel entry points on torch device tensors.  A stand-in with the same methods (the CPU tests pass the host emulation's) is
     accepted wherever a `backend` is; one without `fit_wide` / `transform_wide` serves features up to 128 wide only.  The `readout_*` methods are
-    analysis.readout's (tmjx_readout_*)."""
+    analysis.readout's (tmjx_readout_*), the `kmeans_*` methods analysis.cluster's (tmjx_kmeans_*)."""
 
     def __init__(self, device="cuda", lib=None):
         import torch
@@ -161,6 +161,67 @@ class HipBackend:
             _hip.check(self._L.tmjx_readout_score(x.data_ptr(), n, d, x.stride(0), y.data_ptr(), m, y.stride(0), mx.data_ptr(), ww.data_ptr(), my.data_ptr(), L,
                                                   sse.data_ptr(), sst.data_ptr(), ws.data_ptr(), self._stream()), "tmjx_readout_score")
         return sse.cpu().numpy(), sst.cpu().numpy()
+
+    # k-means (analysis/cluster.py; tmjx_kmeans_*): x from asarray, centroids float32 numpy [k, d], labels int32 numpy
+    def _kmeans_workspace(self, n, d, k):
+        import torch
+        floats = C.c_int64(0)
+        _hip.check(self._L.tmjx_kmeans_workspace(n, d, k, C.byref(floats)), "tmjx_kmeans_workspace")
+        return torch.empty(int(floats.value), dtype=torch.float32, device=self.device)
+
+    def _labels(self, labels):
+        import torch
+        return torch.as_tensor(np.array(labels, dtype=np.int32), device=self.device)      # (a copy: read-only arrays are fine)
+
+    def kmeans_seed(self, x, k, u):
+        """k-means++ with the uniforms u [k] -> (centroids [k, d] float32, index [k] int32: the rows chosen) numpy (tmjx_kmeans_seed)."""
+        import torch
+        n, d = x.shape
+        uu = np.ascontiguousarray(u, np.float64)
+        if uu.shape != (k,):
+            raise ValueError(f"expected {k} uniforms, got shape {uu.shape}")
+        ws, index = self._kmeans_workspace(n, d, k), np.zeros(k, np.int32)
+        cen = torch.empty((k, d), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _hip.check(self._L.tmjx_kmeans_seed(x.data_ptr(), n, d, x.stride(0), k, uu.ctypes.data_as(C.POINTER(C.c_double)), cen.data_ptr(),
+                                                index.ctypes.data_as(C.POINTER(C.c_int32)), ws.data_ptr(), self._stream()), "tmjx_kmeans_seed")
+        return cen.cpu().numpy(), index
+
+    def kmeans_assign(self, x, centroids, labels_prev=None):
+        """-> (labels [n] int32, dist2 [n] float32, inertia float, changed int: the rows whose label differs from labels_prev, n without one)
+        (tmjx_kmeans_assign)."""
+        import torch
+        (n, d), k = x.shape, centroids.shape[0]
+        cen, ws = self._dev(np.array(centroids, dtype=np.float32)), self._kmeans_workspace(n, d, k)
+        prev = None if labels_prev is None else self._labels(labels_prev)
+        labels, dist2 = torch.empty(n, dtype=torch.int32, device=self.device), torch.empty(n, dtype=torch.float32, device=self.device)
+        inertia, changed = torch.zeros(1, dtype=torch.float64, device=self.device), torch.zeros(1, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _hip.check(self._L.tmjx_kmeans_assign(x.data_ptr(), n, d, x.stride(0), cen.data_ptr(), k, None if prev is None else prev.data_ptr(), labels.data_ptr(),
+                                                  dist2.data_ptr(), inertia.data_ptr(), changed.data_ptr(), ws.data_ptr(), self._stream()), "tmjx_kmeans_assign")
+        return labels.cpu().numpy(), dist2.cpu().numpy(), float(inertia.item()), int(changed.item())
+
+    def kmeans_update(self, x, labels, centroids):
+        """-> (centroids [k, d] float32: the mean of each cluster's rows, an empty cluster's row as given; counts [k] int32) (tmjx_kmeans_update)."""
+        import torch
+        (n, d), k = x.shape, centroids.shape[0]
+        cen, lab, ws = self._dev(np.array(centroids, dtype=np.float32)), self._labels(labels), self._kmeans_workspace(n, d, k)
+        counts = torch.empty(k, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _hip.check(self._L.tmjx_kmeans_update(x.data_ptr(), n, d, x.stride(0), lab.data_ptr(), k, cen.data_ptr(), counts.data_ptr(), ws.data_ptr(),
+                                                  self._stream()), "tmjx_kmeans_update")
+        return cen.cpu().numpy(), counts.cpu().numpy()
+
+    def kmeans_fit(self, x, centroids, max_iter=100, tol=1e-4):
+        """Lloyd's iteration from `centroids` -> (centroids, labels int32 [n], dist2 float32 [n]) numpy and the call's hip.KMeansInfo (tmjx_kmeans_fit)."""
+        import torch
+        (n, d), k = x.shape, centroids.shape[0]
+        cen, ws, info = self._dev(np.array(centroids, dtype=np.float32)), self._kmeans_workspace(n, d, k), _hip.KMeansInfo()
+        labels, dist2 = torch.empty(n, dtype=torch.int32, device=self.device), torch.empty(n, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _hip.check(self._L.tmjx_kmeans_fit(x.data_ptr(), n, d, x.stride(0), k, cen.data_ptr(), labels.data_ptr(), dist2.data_ptr(), int(max_iter), float(tol),
+                                               C.byref(info), ws.data_ptr(), self._stream()), "tmjx_kmeans_fit")
+        return cen.cpu().numpy(), labels.cpu().numpy(), dist2.cpu().numpy(), info
 
     def strips(self, proj, k, frame_idx, flags, ymin, ymax, window, style, width, height):
         """One tmjx_plot_strips call: proj from asarray, frame_idx / flags numpy -> rgba uint8 numpy [F, H, W, 4]."""

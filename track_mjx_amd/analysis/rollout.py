@@ -36,7 +36,7 @@ CLI:  python -m track_mjx_amd.analysis.rollout checkpoint=<run dir | step dir> [
       replay_latents=<dir of clip_<i>.h5> [latent_scale=1.0] [path=auto|fused|layers]: instead of running the encoder, re-run the clips of those files
       through a HighLevelWrapper env (environment/wrappers.py: the checkpoint's decoder inside the env) fed their recorded activations/intention
       (times latent_scale), and write the same clip_<i>.h5 layout (activations: the intention that was fed).
-      intervene_pca=<pca.h5> [intervene_components=a:b] | intervene_readout=<readout.h5> [intervene_columns=a:b] | intervene_units=<target>:i,j,k
+      intervene_pca=<pca.h5> [intervene_components=a:b] | intervene_readout=<readout.h5> [intervene_columns=a:b] | intervene_centroids=<clusters.h5> [intervene_columns=a:b] | intervene_units=<target>:i,j,k
       [intervene_mean=<pca.h5>], with [intervene_gain=0] [intervene_offset=0] [intervene_window=a:b] [intervene_dose=<d | d0,d1,..>]: the roll-out (or the
       replay) runs with that edit of one activation (analysis/intervene.py) and every clip_<i>.h5 gains the group `intervention`.
 """
@@ -548,7 +548,7 @@ def _parse_clips(spec: str, n_clips: int) -> list:
 
 CLI_OPTIONS = ("checkpoint", "clips", "seed", "out", "log_activations", "log_metrics", "log_sensor_data", "align_on_fail", "step",
                "replay_latents", "latent_scale", "path", "friction_scale", "actuator_scale", "damping_scale", "gravity_scale", "slope_deg",
-               "intervene_pca", "intervene_components", "intervene_readout", "intervene_columns", "intervene_units", "intervene_mean", "intervene_gain",
+               "intervene_pca", "intervene_components", "intervene_readout", "intervene_centroids", "intervene_columns", "intervene_units", "intervene_mean", "intervene_gain",
                "intervene_offset", "intervene_window", "intervene_dose")
 
 
@@ -683,7 +683,7 @@ def main(argv=None) -> int:
               "[out=<dir>] [log_activations=true] [log_metrics=true] [log_sensor_data=false] [align_on_fail=false] "
               "[friction_scale=<s | s0,s1,..>] [actuator_scale=..] [damping_scale=..] [gravity_scale=<s | s0,s1,..>] [slope_deg=<a | a0,a1,..>] "
               "[replay_latents=<dir of clip_<i>.h5> [latent_scale=1.0] [path=auto|fused|layers]] "
-              "[intervene_pca=<pca.h5> [intervene_components=a:b] | intervene_readout=<readout.h5> [intervene_columns=a:b] | "
+              "[intervene_pca=<pca.h5> [intervene_components=a:b] | intervene_readout=<readout.h5> [intervene_columns=a:b] | intervene_centroids=<clusters.h5> [intervene_columns=a:b] | "
               "intervene_units=<target>:i,j,k [intervene_mean=<pca.h5>]] [intervene_gain=0] [intervene_offset=0] [intervene_window=a:b] "
               "[intervene_dose=<d | d0,d1,..>] [key=value config overrides ...]", file=sys.stderr)
         return 2
