@@ -884,6 +884,56 @@ int tmjx_kmeans_seed(const float *x, int n, int d, int64_t ldx, int k, const dou
 int tmjx_kmeans_fit(const float *x, int n, int d, int64_t ldx, int k, float *centroids, int32_t *labels, float *dist2, int max_iter, double tol,
                     tmjx_kmeans_info_t *info, float *workspace, void *stream);
 
+/* ---- A hidden Markov model over recorded activations x [n][d] (1 <= d <= 1024): 1 <= k <= 128 states with diagonal-covariance Gaussian emissions
+ * (csrc/tmjx_hmm.hip, csrc/hmm_core.h; DESIGN.md "Sequence model").  The conventions of tmjx_kmeans_*: no model handle; all device memory is the
+ * caller's; everything runs on the caller's stream; x is float32 and may be a column slice of a wider buffer (ldx >= d); fixed-order arithmetic, no
+ * floating-point atomics: the same bits on every run.  The model: means [k][d], vars [k][d], transmat [k][k] (rows sum to 1), startprob [k], float32
+ * on the device.  The rows form S sequences given by seq_start [S + 1] (HOST int32: seq_start[0] = 0, strictly increasing, seq_start[S] = n); no
+ * transition crosses a sequence boundary.  The offsets are checked on the host and copied to the workspace on the stream: the array must stay
+ * valid until the work the call queued has run (tmjx_hmm_fit waits itself).
+ *   tmjx_hmm_workspace: *floats = the size of the scratch every call below takes for these n, d, k.  UNLIKE the k-means' it scales with n k: it holds
+ *     logb, the scaled forward variables, the backward weights and gamma, [n][k] float32 each, and the [n][k] uint8 back-pointers (S sizes nothing).
+ *   tmjx_hmm_emission: logb [n][k] = c_j - 1/2 sum_c (x_tc - mu_jc)^2 / var_jc.  The quadratic form is written directly, v = x - mu,
+ *     q = fma(v, v (1 / var), q), one chain per (row, state) in ascending feature order: every term is non-negative, nothing cancels.
+ *     c_j = -1/2 sum_c log(2 pi var_jc) in float64, rounded once.
+ *   tmjx_hmm_forward_backward: the scaled recursion from logb, one workgroup per sequence.  With m_t = max_j logb_t(j) and
+ *     bt_t(j) = exp(logb_t(j) - m_t) the forward variables are normalised every step by c_t and the backward ones scaled by the same c_t.
+ *     gamma [n][k] float32 (every row normalised to sum 1); xi [k][k] float64 = A o (ahat^T W), W_t(j) = bt_(t+1)(j) bhat_(t+1)(j) / c_(t+1) inside a
+ *     sequence: the expected transition counts, the products summed in float64 in row order over fixed row parts, the parts in part order, A
+ *     multiplied in once; start [k] float64 = the sum of gamma at each sequence's first row, in sequence order; loglik [S] float64 =
+ *     sum_t (log c_t + m_t), and *total their sum in sequence order.  All on the device.  A sequence the model gives probability zero (some
+ *     c_t == 0) reports loglik = -inf and gamma rows of zeros (all of its rows) and adds nothing to xi and start: a defined result, not an error.
+ *   tmjx_hmm_mstep: weight [k] (device float64) = sum_t gamma_tk; with m the float32 column mean of x (as tmjx_kmeans_assign forms it)
+ *     S1 = sum gamma (x - m), S2 = sum gamma (x - m)^2 in float64 in row order over fixed row parts, the parts in part order; mu = m + S1 / w,
+ *     var = max(S2 / w - (S1 / w)^2, min_var), rounded once.  A state with w < min_weight (or w == 0) keeps the bits of its mu and var.
+ *   tmjx_hmm_transitions: transmat_ij = (xi_ij + prior + kappa [i == j]) / sum_j (...), startprob_j = (start_j + prior) / sum_j (...), float64,
+ *     rounded once; prior, kappa >= 0 are Dirichlet pseudo-counts (kappa on the diagonal: a "sticky" model); a row whose denominator is 0 keeps its bits.
+ *   tmjx_hmm_viterbi: delta_0(j) = log pi_j + logb_0(j), delta_t(j) = logb_t(j) + max_i (delta_(t-1)(i) + log A_ij) in float32, the lowest i on a tie,
+ *     log 0 = -inf; labels [n] int32 = the best path of every sequence, path_logprob [S] (device float64) its score.  logspace != 0: transmat and
+ *     startprob already hold logarithms.
+ *   tmjx_hmm_fit: EM from the parameters given: emission and forward-backward, the read-back of the total loglik (one float64 per iteration: the only
+ *     synchronisation), stop when it > 0 and loglik - previous <= tol |previous| or after max_iter iterations, else mstep and transitions and
+ *     repeat; after max_iter M-steps one more emission and forward-backward; then Viterbi.  The parameters are updated in place; gamma [n][k]
+ *     (optional), labels [n] and info describe the final parameters.  It WAITS for the stream.
+ * Each returns TMJX_EINVAL before any launch, with a message that names the value, for n < 1, d or k outside the limits, S < 1 or S > n, a
+ * seq_start that breaks the rules, ldx < d, a null required pointer, a workspace that is not 16-byte aligned, max_iter < 1, or a tol, prior, kappa,
+ * min_var or min_weight that is negative or NaN. */
+#define HMM_MAX_D 1024
+#define HMM_MAX_K 128
+typedef struct { int32_t n_iter, converged; double loglik; float emission_ms, fb_ms, mstep_ms, viterbi_ms; } tmjx_hmm_info_t;
+int tmjx_hmm_workspace(int n, int d, int k, int S, int64_t *floats);
+int tmjx_hmm_emission(const float *x, int n, int d, int64_t ldx, const float *means, const float *vars, int k, float *logb, float *workspace, void *stream);
+int tmjx_hmm_forward_backward(const float *logb, int n, int k, const int32_t *seq_start, int S, const float *transmat, const float *startprob, float *gamma,
+                              double *xi, double *start, double *loglik, double *total, float *workspace, void *stream);
+int tmjx_hmm_mstep(const float *x, int n, int d, int64_t ldx, const float *gamma, int k, double min_var, double min_weight, float *means, float *vars,
+                   double *weight, float *workspace, void *stream);
+int tmjx_hmm_transitions(const double *xi, const double *start, int k, double prior, double kappa, float *transmat, float *startprob, void *stream);
+int tmjx_hmm_viterbi(const float *logb, int n, int k, const int32_t *seq_start, int S, const float *transmat, const float *startprob, int logspace,
+                     int32_t *labels, double *path_logprob, float *workspace, void *stream);
+int tmjx_hmm_fit(const float *x, int n, int d, int64_t ldx, const int32_t *seq_start, int S, int k, float *means, float *vars, float *transmat,
+                 float *startprob, float *gamma, int32_t *labels, int max_iter, double tol, double prior, double kappa, double min_var, double min_weight,
+                 tmjx_hmm_info_t *info, float *workspace, void *stream);
+
 /* ---- Activation intervention (csrc/tmjx_intervene.hip, csrc/intervene_core.h; DESIGN.md "Interventions"): one launch that edits, in place, the
  * columns [0, w) of the rows h [n][ld] — a layer's output buffer, or a column slice of one — between two launches of a policy step.  Row r at step t:
  *   subspace mode:  p_k = sum_j (h_j - c_j) v_kj;  e_j = sum_k ((g_k - 1) p_k + o_k) v_kj;  h'_j = h_j + dose_r e_j   (dirs [K][ldv], gain / offset [K])

@@ -42,7 +42,7 @@ def strip_style(width: int, height: int, line_half_width: float = 1.0, marker_ra
 class HipBackend:
     """The PCA and panel entry points on torch device tensors.  A stand-in with the same methods (the CPU tests pass the host emulation's) is
     accepted wherever a `backend` is; one without `fit_wide` / `transform_wide` serves features up to 128 wide only.  The `readout_*` methods are
-    analysis.readout's (tmjx_readout_*), the `kmeans_*` methods analysis.cluster's (tmjx_kmeans_*)."""
+    analysis.readout's (tmjx_readout_*), the `kmeans_*` methods analysis.cluster's (tmjx_kmeans_*), the `hmm_*` methods analysis.hmm's (tmjx_hmm_*)."""
 
     def __init__(self, device="cuda", lib=None):
         import torch
@@ -222,6 +222,98 @@ class HipBackend:
             _hip.check(self._L.tmjx_kmeans_fit(x.data_ptr(), n, d, x.stride(0), k, cen.data_ptr(), labels.data_ptr(), dist2.data_ptr(), int(max_iter), float(tol),
                                                C.byref(info), ws.data_ptr(), self._stream()), "tmjx_kmeans_fit")
         return cen.cpu().numpy(), labels.cpu().numpy(), dist2.cpu().numpy(), info
+
+    # the hidden Markov model (analysis/hmm.py; tmjx_hmm_*): x from asarray; logb, gamma and the parameters float32 numpy; seq_start int32 [S + 1]
+    def _hmm_workspace(self, n, d, k, S):
+        import torch
+        floats = C.c_int64(0)
+        _hip.check(self._L.tmjx_hmm_workspace(n, d, k, S, C.byref(floats)), "tmjx_hmm_workspace")
+        return torch.empty(int(floats.value), dtype=torch.float32, device=self.device)
+
+    @staticmethod
+    def _seq(seq_start):
+        seq = np.ascontiguousarray(seq_start, np.int32)
+        return seq, seq.ctypes.data_as(C.POINTER(C.c_int32)), seq.shape[0] - 1
+
+    def _devc(self, a):
+        return self._dev(np.array(a, dtype=np.float32))      # (a copy: read-only arrays are fine)
+
+    def _f64(self, shape):
+        import torch
+        return torch.empty(shape, dtype=torch.float64, device=self.device)
+
+    def hmm_emission(self, x, means, vars):
+        """-> logb [n, k] float32: the log density of every row under every state's diagonal Gaussian (tmjx_hmm_emission)."""
+        import torch
+        (n, d), k = x.shape, means.shape[0]
+        mu, var, ws = self._devc(means), self._devc(vars), self._hmm_workspace(n, d, k, 1)
+        logb = torch.empty((n, k), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _hip.check(self._L.tmjx_hmm_emission(x.data_ptr(), n, d, x.stride(0), mu.data_ptr(), var.data_ptr(), k, logb.data_ptr(), ws.data_ptr(), self._stream()),
+                       "tmjx_hmm_emission")
+        return logb.cpu().numpy()
+
+    def hmm_forward_backward(self, logb, seq_start, transmat, startprob):
+        """-> (gamma [n, k] float32, xi [k, k] float64, start [k] float64, loglik [S] float64, their total) (tmjx_hmm_forward_backward)."""
+        import torch
+        n, k = logb.shape
+        seq, seq_p, S = self._seq(seq_start)
+        lb, A, pi, ws = self._devc(logb), self._devc(transmat), self._devc(startprob), self._hmm_workspace(n, 1, k, S)
+        gamma = torch.empty((n, k), dtype=torch.float32, device=self.device)
+        xi, start, loglik, total = self._f64((k, k)), self._f64((k,)), self._f64((S,)), self._f64((1,))
+        with torch.cuda.device(self.device):
+            _hip.check(self._L.tmjx_hmm_forward_backward(lb.data_ptr(), n, k, seq_p, S, A.data_ptr(), pi.data_ptr(), gamma.data_ptr(), xi.data_ptr(), start.data_ptr(),
+                                                         loglik.data_ptr(), total.data_ptr(), ws.data_ptr(), self._stream()), "tmjx_hmm_forward_backward")
+        return gamma.cpu().numpy(), xi.cpu().numpy(), start.cpu().numpy(), loglik.cpu().numpy(), float(total.item())
+
+    def hmm_mstep(self, x, gamma, means, vars, min_var=0.0, min_weight=0.0):
+        """-> (means, vars [k, d] float32, weight [k] float64): the weighted moments of every state; one below min_weight as given (tmjx_hmm_mstep)."""
+        (n, d), k = x.shape, means.shape[0]
+        g, mu, var, ws, weight = self._devc(gamma), self._devc(means), self._devc(vars), self._hmm_workspace(n, d, k, 1), self._f64((k,))
+        import torch
+        with torch.cuda.device(self.device):
+            _hip.check(self._L.tmjx_hmm_mstep(x.data_ptr(), n, d, x.stride(0), g.data_ptr(), k, float(min_var), float(min_weight), mu.data_ptr(), var.data_ptr(),
+                                              weight.data_ptr(), ws.data_ptr(), self._stream()), "tmjx_hmm_mstep")
+        return mu.cpu().numpy(), var.cpu().numpy(), weight.cpu().numpy()
+
+    def hmm_transitions(self, xi, start, prior, kappa, transmat, startprob):
+        """-> (transmat [k, k], startprob [k]) float32 from expected counts and Dirichlet pseudo-counts; a row without mass as given (tmjx_hmm_transitions)."""
+        import torch
+        k = len(start)
+        xx = torch.as_tensor(np.ascontiguousarray(xi, np.float64), device=self.device)
+        st = torch.as_tensor(np.ascontiguousarray(start, np.float64), device=self.device)
+        A, pi = self._devc(transmat), self._devc(startprob)
+        with torch.cuda.device(self.device):
+            _hip.check(self._L.tmjx_hmm_transitions(xx.data_ptr(), st.data_ptr(), k, float(prior), float(kappa), A.data_ptr(), pi.data_ptr(), self._stream()),
+                       "tmjx_hmm_transitions")
+        return A.cpu().numpy(), pi.cpu().numpy()
+
+    def hmm_viterbi(self, logb, seq_start, transmat, startprob, logspace=False):
+        """-> (labels [n] int32: the best path of every sequence, path_logprob [S] float64); logspace: the parameters hold logarithms (tmjx_hmm_viterbi)."""
+        import torch
+        n, k = logb.shape
+        seq, seq_p, S = self._seq(seq_start)
+        lb, A, pi, ws = self._devc(logb), self._devc(transmat), self._devc(startprob), self._hmm_workspace(n, 1, k, S)
+        labels, path = torch.empty(n, dtype=torch.int32, device=self.device), self._f64((S,))
+        with torch.cuda.device(self.device):
+            _hip.check(self._L.tmjx_hmm_viterbi(lb.data_ptr(), n, k, seq_p, S, A.data_ptr(), pi.data_ptr(), int(bool(logspace)), labels.data_ptr(), path.data_ptr(),
+                                                ws.data_ptr(), self._stream()), "tmjx_hmm_viterbi")
+        return labels.cpu().numpy(), path.cpu().numpy()
+
+    def hmm_fit(self, x, seq_start, means, vars, transmat, startprob, max_iter=50, tol=1e-4, prior=0.0, kappa=0.0, min_var=0.0, min_weight=0.0):
+        """EM from the parameters given -> (means, vars, transmat, startprob, gamma [n, k], labels [n] int32) numpy and the call's hip.HmmInfo
+        (tmjx_hmm_fit)."""
+        import torch
+        (n, d), k = x.shape, means.shape[0]
+        seq, seq_p, S = self._seq(seq_start)
+        mu, var, A, pi = (self._devc(a) for a in (means, vars, transmat, startprob))
+        ws, info = self._hmm_workspace(n, d, k, S), _hip.HmmInfo()
+        gamma, labels = torch.empty((n, k), dtype=torch.float32, device=self.device), torch.empty(n, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _hip.check(self._L.tmjx_hmm_fit(x.data_ptr(), n, d, x.stride(0), seq_p, S, k, mu.data_ptr(), var.data_ptr(), A.data_ptr(), pi.data_ptr(), gamma.data_ptr(),
+                                            labels.data_ptr(), int(max_iter), float(tol), float(prior), float(kappa), float(min_var), float(min_weight),
+                                            C.byref(info), ws.data_ptr(), self._stream()), "tmjx_hmm_fit")
+        return (*(t.cpu().numpy() for t in (mu, var, A, pi, gamma, labels)), info)
 
     def strips(self, proj, k, frame_idx, flags, ymin, ymax, window, style, width, height):
         """One tmjx_plot_strips call: proj from asarray, frame_idx / flags numpy -> rgba uint8 numpy [F, H, W, 4]."""

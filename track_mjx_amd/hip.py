@@ -15,7 +15,7 @@ _PKG = Path(__file__).resolve().parent
 SO_PATH = Path(os.environ.get("TMJX_SO", str(_PKG / "libtmjx_hip.so")))  # TMJX_SO: alternative build (profiling)
 CSRC = _PKG / "csrc"
 SOURCES = (CSRC / "tmjx_hip.hip", CSRC / "tmjx_bf16.hip", CSRC / "tmjx_wave.hip", CSRC / "tmjx_chain.hip", CSRC / "tmjx_lstm.hip",
-           CSRC / "tmjx_rollout.hip", CSRC / "tmjx_wave_sensors.hip", CSRC / "tmjx_wave_align.hip", CSRC / "tmjx_wave_rand.hip", CSRC / "tmjx_render.hip", CSRC / "tmjx_act.hip", CSRC / "tmjx_pca.hip", CSRC / "tmjx_pca_wide.hip", CSRC / "tmjx_readout.hip", CSRC / "tmjx_intervene.hip", CSRC / "tmjx_kmeans.hip")
+           CSRC / "tmjx_rollout.hip", CSRC / "tmjx_wave_sensors.hip", CSRC / "tmjx_wave_align.hip", CSRC / "tmjx_wave_rand.hip", CSRC / "tmjx_render.hip", CSRC / "tmjx_act.hip", CSRC / "tmjx_pca.hip", CSRC / "tmjx_pca_wide.hip", CSRC / "tmjx_readout.hip", CSRC / "tmjx_intervene.hip", CSRC / "tmjx_kmeans.hip", CSRC / "tmjx_hmm.hip")
 # per-source compiler flags: the physics kernel's unit is built without machine LICM (csrc/tmjx_wave.hip says why)
 SOURCE_FLAGS = {"tmjx_wave.hip": ("-mllvm", "-disable-machine-licm"),
                 "tmjx_wave_sensors.hip": ("-mllvm", "-disable-machine-licm"),      # (the recording kernel: the same loop body)
@@ -53,6 +53,7 @@ EXPORTS = ("tmjx_model_create", "tmjx_model_destroy", "tmjx_layout", "tmjx_clips
            "tmjx_readout_workspace", "tmjx_readout_fit", "tmjx_readout_weights", "tmjx_readout_predict", "tmjx_readout_score",
            "tmjx_intervene_ok", "tmjx_intervene",
            "tmjx_kmeans_workspace", "tmjx_kmeans_assign", "tmjx_kmeans_update", "tmjx_kmeans_seed", "tmjx_kmeans_fit",
+           "tmjx_hmm_workspace", "tmjx_hmm_emission", "tmjx_hmm_forward_backward", "tmjx_hmm_mstep", "tmjx_hmm_transitions", "tmjx_hmm_viterbi", "tmjx_hmm_fit",
            "tmjx_debug_rows", "tmjx_last_error", "tmjx_version")
 
 
@@ -205,6 +206,15 @@ KMEANS_MAX_D, KMEANS_MAX_K = 1024, 256      # csrc/kmeans_core.h
 class KMeansInfo(C.Structure):
     """tmjx_kmeans_info_t (include/tmjx.h)."""
     _fields_ = [("n_iter", C.c_int32), ("changed", C.c_int32), ("inertia", C.c_double), ("assign_ms", C.c_float), ("update_ms", C.c_float)]
+
+
+HMM_MAX_D, HMM_MAX_K = 1024, 128      # csrc/hmm_core.h
+
+
+class HmmInfo(C.Structure):
+    """tmjx_hmm_info_t (include/tmjx.h)."""
+    _fields_ = [("n_iter", C.c_int32), ("converged", C.c_int32), ("loglik", C.c_double), ("emission_ms", C.c_float), ("fb_ms", C.c_float),
+                ("mstep_ms", C.c_float), ("viterbi_ms", C.c_float)]
 
 
 INTERVENE_SUBSPACE, INTERVENE_UNITS, INTERVENE_MAX_W, INTERVENE_MAX_K = 0, 1, 1024, 16      # include/tmjx.h, csrc/intervene_core.h
@@ -472,6 +482,15 @@ def load(path: Path):
     sig.setdefault("tmjx_kmeans_update", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, vp, C.c_int, fp, vp, fp, vp]
     sig.setdefault("tmjx_kmeans_seed", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_double), fp, C.POINTER(C.c_int32), fp, vp]
     sig.setdefault("tmjx_kmeans_fit", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, C.c_int, fp, vp, fp, C.c_int, C.c_double, C.POINTER(KMeansInfo), fp, vp]
+    i32p, dbl = C.POINTER(C.c_int32), C.c_double
+    sig.setdefault("tmjx_hmm_workspace", [None, None])[0] = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+    sig.setdefault("tmjx_hmm_emission", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, fp, fp, C.c_int, fp, fp, vp]
+    sig.setdefault("tmjx_hmm_forward_backward", [None, None])[0] = [fp, C.c_int, C.c_int, i32p, C.c_int, fp, fp, fp, vp, vp, vp, vp, fp, vp]
+    sig.setdefault("tmjx_hmm_mstep", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, fp, C.c_int, dbl, dbl, fp, fp, vp, fp, vp]
+    sig.setdefault("tmjx_hmm_transitions", [None, None])[0] = [vp, vp, C.c_int, dbl, dbl, fp, fp, vp]
+    sig.setdefault("tmjx_hmm_viterbi", [None, None])[0] = [fp, C.c_int, C.c_int, i32p, C.c_int, fp, fp, C.c_int, vp, vp, fp, vp]
+    sig.setdefault("tmjx_hmm_fit", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, i32p, C.c_int, C.c_int, fp, fp, fp, fp, fp, vp, C.c_int, dbl, dbl, dbl, dbl,
+                                                       dbl, C.POINTER(HmmInfo), fp, vp]
     sig.setdefault("tmjx_plot_strips", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, vp, vp, C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(StripStyle),
                                                            C.c_int, C.c_int, vp, vp]
     sig.setdefault("tmjx_debug_rows", [None, None])[0] = [vp, C.c_char_p, ip, ip]
