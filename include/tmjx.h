@@ -934,6 +934,44 @@ int tmjx_hmm_fit(const float *x, int n, int d, int64_t ldx, const int32_t *seq_s
                  float *startprob, float *gamma, int32_t *labels, int max_iter, double tol, double prior, double kappa, double min_var, double min_weight,
                  tmjx_hmm_info_t *info, float *workspace, void *stream);
 
+/* ---- Morlet wavelet spectrograms of recorded signals x [n][C] (1 <= C <= 1024) at 1 <= F <= 64 centre frequencies (csrc/tmjx_spectrogram.hip,
+ * csrc/spectrogram_core.h; DESIGN.md "Spectrogram").  The conventions of tmjx_hmm_*: no model handle; all device memory is the caller's; everything
+ * runs on the caller's stream; x is float32 and may be a column slice of a wider buffer (ldx >= C); the rows form S sequences given by
+ * seq_start [S + 1] (HOST int32: seq_start[0] = 0, strictly increasing, seq_start[S] = n); fixed-order arithmetic, no atomics: the same bits on
+ * every run, and the bits of a sequence's rows do not depend on where it sits in the call or on what else is in it.
+ *   The bank (HOST functions, float64 rounded once to float32): for frequency f_j at sampling rate `rate`, sigma_j = omega0 rate / (2 pi f_j)
+ *     samples, R_j = ceil(support sigma_j), and for tau = -R_j .. R_j   g_j[tau] = exp(-tau^2 / (2 sigma_j^2)),
+ *     wr_j[tau] = g_j[tau] cos(2 pi f_j tau / rate),  wi_j[tau] = -g_j[tau] sin(2 pi f_j tau / rate).  bank holds, for every frequency in turn, the
+ *     tables g, wr, wi of 2 R_j + 1 floats each; offset [F + 1] says where each frequency starts (offset[F] = the size), radius [F] = R_j.
+ *     tmjx_wavelet_bank_size gives *floats = offset[F]; tmjx_wavelet_bank fills bank, offset and radius (host memory).  Refused: F outside 1 .. 64,
+ *     a frequency outside (0, rate / 2], an R_j above 4096, rate, omega0 or support not positive and finite, a null pointer.
+ *   tmjx_spectrogram: bank is that table on the DEVICE; offset and radius stay on the HOST (checked there, copied to the workspace on the stream,
+ *     like seq_start: the arrays must stay valid until the queued work has run).  With detrend != 0, m_sc = the mean of channel c over sequence s
+ *     (float64 sums of the row classes t mod 4 in row order, the classes added in order, the quotient rounded to float32) and xt = x - m in
+ *     float32; otherwise xt = x.  For row t of a sequence of T rows (t counted inside it) only the taps inside the sequence are taken:
+ *     lo = max(-R_j, -t), hi = min(R_j, T - 1 - t),
+ *       re = sum_{tau = lo .. hi} wr_j[tau] xt[t + tau][c],  im likewise with wi_j  (one float32 FMA chain each, ascending tau),
+ *       G = sum_{tau = lo .. hi} g_j[tau]  (a difference of the float64 prefix sums of g_j, rounded once),  A = 2 sqrt(re^2 + im^2) / G.
+ *     out [n][ldo >= F C] float32, column j C + c (frequency-major): A with TMJX_SPECTROGRAM_AMPLITUDE, ln(max(A, log_floor)) with
+ *     TMJX_SPECTROGRAM_LOG (log_floor > 0); columns beyond F C are not written.  coverage [n][F] = G / (the sum of all of g_j): the share of the
+ *     window inside the sequence, exactly 1 where it fits.  A unit sinusoid at f_j gives A = 1, also near an edge.  A NaN in a sequence makes
+ *     that sequence's outputs NaN and no other's.
+ *   tmjx_spectrogram_workspace: *floats = the scratch for these C, F, S (the sequence means and tables; n sizes nothing).
+ * Each returns TMJX_EINVAL before any launch, with a message that names the value, for n < 1, C or F outside the limits, S < 1 or S > n, a
+ * seq_start that breaks the rules, ldx < C, ldo < F C, a radius outside 0 .. 4096, offsets that do not follow from the radii, an unknown
+ * output_kind, a log_floor that is not positive (log output), a null pointer, a workspace that is not 16-byte aligned. */
+#define TMJX_SPECTROGRAM_MAX_C 1024
+#define TMJX_SPECTROGRAM_MAX_F 64
+#define TMJX_SPECTROGRAM_MAX_R 4096
+#define TMJX_SPECTROGRAM_AMPLITUDE 0
+#define TMJX_SPECTROGRAM_LOG 1
+int tmjx_wavelet_bank_size(double rate, const double *freqs, int F, double omega0, double support, int64_t *floats);
+int tmjx_wavelet_bank(double rate, const double *freqs, int F, double omega0, double support, float *bank, int32_t *offset, int32_t *radius);
+int tmjx_spectrogram_workspace(int n, int C, int F, int S, int64_t *floats);
+int tmjx_spectrogram(const float *x, int n, int C, int64_t ldx, const int32_t *seq_start, int S, const float *bank, const int32_t *offset,
+                     const int32_t *radius, int F, int detrend, int output_kind, float log_floor, float *out, int64_t ldo, float *coverage, float *workspace,
+                     void *stream);
+
 /* ---- Activation intervention (csrc/tmjx_intervene.hip, csrc/intervene_core.h; DESIGN.md "Interventions"): one launch that edits, in place, the
  * columns [0, w) of the rows h [n][ld] — a layer's output buffer, or a column slice of one — between two launches of a policy step.  Row r at step t:
  *   subspace mode:  p_k = sum_j (h_j - c_j) v_kj;  e_j = sum_k ((g_k - 1) p_k + o_k) v_kj;  h'_j = h_j + dose_r e_j   (dirs [K][ldv], gain / offset [K])

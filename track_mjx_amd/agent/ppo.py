@@ -24,7 +24,27 @@ from .networks import Bf16Shadows, IntentionPolicy, NormalTanh, RunningStatistic
 
 
 import contextlib
+import gc
 import os
+
+
+@contextlib.contextmanager
+def _capture(graph):
+    """`torch.cuda.graph(graph, capture_error_mode="thread_local")` with the garbage collector out of the way.  torch no longer collects before a
+    capture, so a dead reference cycle that holds hipGraphs and their memory pools (an earlier learner of the same process) could be collected by an
+    automatic run INSIDE the capture; destroying a graph while this thread captures another aborts the process.  Collect before, hold the
+    collector during."""
+    gc.collect()
+    enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+            yield
+    finally:
+        if enabled:
+            gc.enable()
+
+
 _nullctx = contextlib.nullcontext
 
 
@@ -671,7 +691,7 @@ class PPOLearner:
                 cur.wait_stream(side)
                 graph = torch.cuda.CUDAGraph()
                 graph.register_generator_state(gen)
-                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                with _capture(graph):
                     out = self.act(obs, gen=gen)
                 ent = (graph, key, out)
             except Exception as e:  # noqa: BLE001
@@ -847,12 +867,12 @@ class PPOLearner:
         torch.cuda.synchronize(self.dev)
         g1, gv, gp = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         # thread_local: the RCCL watchdog thread polls events concurrently and must not invalidate the capture
-        with torch.cuda.graph(g1, capture_error_mode="thread_local"):
+        with _capture(g1):
             outs, gouts, out8 = self._mb_forward(self._g_idx, kl_w)
             self._g_out = self._acc8 if selfadv else out8[self._metric_index]
-        with torch.cuda.graph(gv, capture_error_mode="thread_local"):
+        with _capture(gv):
             self._mb_backward(outs, gouts, "value")
-        with torch.cuda.graph(gp, capture_error_mode="thread_local"):
+        with _capture(gp):
             self._mb_backward(outs, gouts, "policy")
         del outs, gouts
         self._split_graphs, self._graph_kl, self._graph_selfadv = (g1, gv, gp), kl_w, selfadv
@@ -896,7 +916,7 @@ class PPOLearner:
         self._mb_state[0:1].copy_(draw0)
         graph = torch.cuda.CUDAGraph()
         # thread_local: the RCCL watchdog thread polls events concurrently (world > 1) and must not invalidate the capture
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+        with _capture(graph):
             self._g_out = self._minibatch_grads(self._g_idx, kl_w)
         self._graph, self._graph_kl, self._graph_selfadv = graph, kl_w, selfadv
 

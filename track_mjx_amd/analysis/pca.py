@@ -42,7 +42,8 @@ def strip_style(width: int, height: int, line_half_width: float = 1.0, marker_ra
 class HipBackend:
     """The PCA and panel entry points on torch device tensors.  A stand-in with the same methods (the CPU tests pass the host emulation's) is
     accepted wherever a `backend` is; one without `fit_wide` / `transform_wide` serves features up to 128 wide only.  The `readout_*` methods are
-    analysis.readout's (tmjx_readout_*), the `kmeans_*` methods analysis.cluster's (tmjx_kmeans_*), the `hmm_*` methods analysis.hmm's (tmjx_hmm_*)."""
+    analysis.readout's (tmjx_readout_*), the `kmeans_*` methods analysis.cluster's (tmjx_kmeans_*), the `hmm_*` methods analysis.hmm's (tmjx_hmm_*), `wavelet_bank` and
+    `spectrogram` analysis.spectrogram's (tmjx_wavelet_bank, tmjx_spectrogram)."""
 
     def __init__(self, device="cuda", lib=None):
         import torch
@@ -314,6 +315,40 @@ class HipBackend:
                                             labels.data_ptr(), int(max_iter), float(tol), float(prior), float(kappa), float(min_var), float(min_weight),
                                             C.byref(info), ws.data_ptr(), self._stream()), "tmjx_hmm_fit")
         return (*(t.cpu().numpy() for t in (mu, var, A, pi, gamma, labels)), info)
+
+    # the wavelet spectrogram (analysis/spectrogram.py; tmjx_wavelet_bank*, tmjx_spectrogram*): x from asarray, the bank as wavelet_bank returns it
+    def wavelet_bank(self, rate, freqs, omega0=5.0, support=4.0):
+        """-> (bank float32, offset int32 [F + 1], radius int32 [F]) numpy: the Morlet tables of every frequency (tmjx_wavelet_bank, a host function)."""
+        fr = np.ascontiguousarray(freqs, np.float64).reshape(-1)
+        F, floats, dp = fr.shape[0], C.c_int64(0), fr.ctypes.data_as(C.POINTER(C.c_double))
+        _hip.check(self._L.tmjx_wavelet_bank_size(float(rate), dp, F, float(omega0), float(support), C.byref(floats)), "tmjx_wavelet_bank_size")
+        bank, offset, radius = np.zeros(int(floats.value), np.float32), np.zeros(F + 1, np.int32), np.zeros(F, np.int32)
+        _hip.check(self._L.tmjx_wavelet_bank(float(rate), dp, F, float(omega0), float(support), bank.ctypes.data, offset.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             radius.ctypes.data_as(C.POINTER(C.c_int32))), "tmjx_wavelet_bank")
+        return bank, offset, radius
+
+    def spectrogram(self, x, seq_start, bank, offset, radius, detrend=True, log=False, floor=1e-3, out=None):
+        """-> (out [n, F C], coverage [n, F]) device tensors: the amplitude (or its logarithm) of every channel at every frequency, column j C + c,
+        and the share of each window inside its sequence (tmjx_spectrogram).  `out`: a device tensor [n, F C] to write into (a row stride is fine)."""
+        import torch
+        n, Cn = x.shape
+        seq, seq_p, S = self._seq(seq_start)
+        off, rad = np.ascontiguousarray(offset, np.int32), np.ascontiguousarray(radius, np.int32)
+        F, i32p = rad.shape[0], C.POINTER(C.c_int32)
+        bk, floats = self._dev(bank), C.c_int64(0)
+        _hip.check(self._L.tmjx_spectrogram_workspace(n, Cn, F, S, C.byref(floats)), "tmjx_spectrogram_workspace")
+        ws = torch.empty(int(floats.value), dtype=torch.float32, device=self.device)
+        if out is None:
+            out = torch.empty((n, F * Cn), dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != (n, F * Cn) or out.dtype != torch.float32 or out.stride(1) != 1:
+            raise ValueError(f"out must be a float32 device tensor [{n}, {F * Cn}] with contiguous columns")
+        cov = torch.empty((n, F), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _hip.check(self._L.tmjx_spectrogram(x.data_ptr(), n, Cn, x.stride(0), seq_p, S, bk.data_ptr(), off.ctypes.data_as(i32p), rad.ctypes.data_as(i32p), F,
+                                                int(bool(detrend)), _hip.SPECTROGRAM_LOG if log else _hip.SPECTROGRAM_AMPLITUDE, float(floor), out.data_ptr(),
+                                                out.stride(0), cov.data_ptr(), ws.data_ptr(), self._stream()), "tmjx_spectrogram")
+            torch.cuda.current_stream(self.device).synchronize()      # (the host offsets must outlive the queued copies)
+        return out, cov
 
     def strips(self, proj, k, frame_idx, flags, ymin, ymax, window, style, width, height):
         """One tmjx_plot_strips call: proj from asarray, frame_idx / flags numpy -> rgba uint8 numpy [F, H, W, 4]."""

@@ -15,7 +15,7 @@ _PKG = Path(__file__).resolve().parent
 SO_PATH = Path(os.environ.get("TMJX_SO", str(_PKG / "libtmjx_hip.so")))  # TMJX_SO: alternative build (profiling)
 CSRC = _PKG / "csrc"
 SOURCES = (CSRC / "tmjx_hip.hip", CSRC / "tmjx_bf16.hip", CSRC / "tmjx_wave.hip", CSRC / "tmjx_chain.hip", CSRC / "tmjx_lstm.hip",
-           CSRC / "tmjx_rollout.hip", CSRC / "tmjx_wave_sensors.hip", CSRC / "tmjx_wave_align.hip", CSRC / "tmjx_wave_rand.hip", CSRC / "tmjx_render.hip", CSRC / "tmjx_act.hip", CSRC / "tmjx_pca.hip", CSRC / "tmjx_pca_wide.hip", CSRC / "tmjx_readout.hip", CSRC / "tmjx_intervene.hip", CSRC / "tmjx_kmeans.hip", CSRC / "tmjx_hmm.hip")
+           CSRC / "tmjx_rollout.hip", CSRC / "tmjx_wave_sensors.hip", CSRC / "tmjx_wave_align.hip", CSRC / "tmjx_wave_rand.hip", CSRC / "tmjx_render.hip", CSRC / "tmjx_act.hip", CSRC / "tmjx_pca.hip", CSRC / "tmjx_pca_wide.hip", CSRC / "tmjx_readout.hip", CSRC / "tmjx_intervene.hip", CSRC / "tmjx_kmeans.hip", CSRC / "tmjx_hmm.hip", CSRC / "tmjx_spectrogram.hip")
 # per-source compiler flags: the physics kernel's unit is built without machine LICM (csrc/tmjx_wave.hip says why)
 SOURCE_FLAGS = {"tmjx_wave.hip": ("-mllvm", "-disable-machine-licm"),
                 "tmjx_wave_sensors.hip": ("-mllvm", "-disable-machine-licm"),      # (the recording kernel: the same loop body)
@@ -54,6 +54,7 @@ EXPORTS = ("tmjx_model_create", "tmjx_model_destroy", "tmjx_layout", "tmjx_clips
            "tmjx_intervene_ok", "tmjx_intervene",
            "tmjx_kmeans_workspace", "tmjx_kmeans_assign", "tmjx_kmeans_update", "tmjx_kmeans_seed", "tmjx_kmeans_fit",
            "tmjx_hmm_workspace", "tmjx_hmm_emission", "tmjx_hmm_forward_backward", "tmjx_hmm_mstep", "tmjx_hmm_transitions", "tmjx_hmm_viterbi", "tmjx_hmm_fit",
+           "tmjx_wavelet_bank_size", "tmjx_wavelet_bank", "tmjx_spectrogram_workspace", "tmjx_spectrogram",
            "tmjx_debug_rows", "tmjx_last_error", "tmjx_version")
 
 
@@ -209,6 +210,8 @@ class KMeansInfo(C.Structure):
 
 
 HMM_MAX_D, HMM_MAX_K = 1024, 128      # csrc/hmm_core.h
+SPECTROGRAM_MAX_C, SPECTROGRAM_MAX_F, SPECTROGRAM_MAX_R = 1024, 64, 4096      # csrc/spectrogram_core.h
+SPECTROGRAM_AMPLITUDE, SPECTROGRAM_LOG = 0, 1      # TMJX_SPECTROGRAM_* (include/tmjx.h)
 
 
 class HmmInfo(C.Structure):
@@ -491,6 +494,12 @@ def load(path: Path):
     sig.setdefault("tmjx_hmm_viterbi", [None, None])[0] = [fp, C.c_int, C.c_int, i32p, C.c_int, fp, fp, C.c_int, vp, vp, fp, vp]
     sig.setdefault("tmjx_hmm_fit", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, i32p, C.c_int, C.c_int, fp, fp, fp, fp, fp, vp, C.c_int, dbl, dbl, dbl, dbl,
                                                        dbl, C.POINTER(HmmInfo), fp, vp]
+    dblp = C.POINTER(C.c_double)
+    sig.setdefault("tmjx_wavelet_bank_size", [None, None])[0] = [dbl, dblp, C.c_int, dbl, dbl, C.POINTER(C.c_int64)]
+    sig.setdefault("tmjx_wavelet_bank", [None, None])[0] = [dbl, dblp, C.c_int, dbl, dbl, vp, i32p, i32p]
+    sig.setdefault("tmjx_spectrogram_workspace", [None, None])[0] = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+    sig.setdefault("tmjx_spectrogram", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, i32p, C.c_int, fp, i32p, i32p, C.c_int, C.c_int, C.c_int, C.c_float, fp,
+                                                           C.c_int64, fp, fp, vp]
     sig.setdefault("tmjx_plot_strips", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, vp, vp, C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(StripStyle),
                                                            C.c_int, C.c_int, vp, vp]
     sig.setdefault("tmjx_debug_rows", [None, None])[0] = [vp, C.c_char_p, ip, ip]
