@@ -1,6 +1,6 @@
 """The float64 reference of the hidden-Markov-model kernels, a float32 numpy restatement of them, the case generators and the checkers that
-tests/test_hmm_cpu.py (the host emulation) and tests/test_gpu_hmm.py (the C-ABI) share.  A `backend` is analysis.pca.HipBackend or
-tests/hostemu/hmm_emu.EmuHmmBackend.
+tests/test_hmm_cpu.py (the host emulation) and tests/test_gpu_hmm.py (the C-ABI) share.  A `backend` is analysis.pca.HipBackend or the same backend on numpy arrays,
+tests/hostemu/analysis_emu.B.
 
 Emission and M-step cases (n, d, k): one row; one row past a 256-row block; the intention's width; odd tile edges; both limits.  Sequence cases
 (lengths, k): a single row; sequences of one and two rows; short, long and odd; eight full clips and a stub; the state limit.

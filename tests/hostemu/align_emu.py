@@ -2,12 +2,11 @@
 from __future__ import annotations
 
 import ctypes as C
-import subprocess
-from pathlib import Path
 
 import numpy as np
 
-_HERE = Path(__file__).resolve().parent
+from tests.hostemu import loader
+
 _FP, _IP = C.POINTER(C.c_float), C.POINTER(C.c_int)
 DONE_NONE, DONE_RESET, DONE_ALIGN = 0, 1, 2
 CLIP_KEYS = ("position", "quaternion", "joints", "body_positions", "angular_velocity")
@@ -15,11 +14,7 @@ VEL_KEYS = ("velocity", "joints_velocity")
 
 
 def _lib():
-    src = [_HERE / "align_emu.cpp", *sorted((_HERE.parents[1] / "track_mjx_amd" / "csrc").glob("*.h"))]
-    so = _HERE / "libalign_emu.so"
-    if not so.exists() or so.stat().st_mtime < max(p.stat().st_mtime for p in src):
-        subprocess.run(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-o", str(so), str(_HERE / "align_emu.cpp")], check=True, capture_output=True)
-    L = C.CDLL(str(so))
+    L = loader.load("align_emu.cpp")
     L.align_model_create.restype = C.c_void_p
     L.align_model_create.argtypes = [C.c_char_p, C.c_size_t]
     L.align_last_error.restype = C.c_char_p

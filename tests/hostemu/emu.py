@@ -2,18 +2,12 @@
 from __future__ import annotations
 
 import ctypes as C
-import subprocess
-from pathlib import Path
 
 import numpy as np
 
-_HERE = Path(__file__).resolve().parent
+from tests.hostemu import loader
+
 _FP, _IP = C.POINTER(C.c_float), C.POINTER(C.c_int)
-
-
-def build():
-    subprocess.run(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-o", str(_HERE / "libhostemu.so"),
-                    str(_HERE / "hostemu.cpp")], check=True, capture_output=True)
 
 
 def _f(a):
@@ -26,11 +20,7 @@ def _i(a):
 
 class Emu:
     def __init__(self, blob: bytes, n_env: int):
-        src = [_HERE / "hostemu.cpp", *sorted((_HERE.parents[1] / "track_mjx_amd" / "csrc").glob("*.h"))]
-        so = _HERE / "libhostemu.so"
-        if not so.exists() or so.stat().st_mtime < max(p.stat().st_mtime for p in src):
-            build()
-        self.L = L = C.CDLL(str(so))
+        self.L = L = C.CDLL(str(loader.build("hostemu.cpp")))
         L.emu_model_create.restype = C.c_void_p
         L.emu_model_create.argtypes = [C.c_char_p, C.c_size_t]
         L.emu_last_error.restype = C.c_char_p

@@ -3,6 +3,7 @@
 // csrc/hmm_host.h compiled with g++, one loop iteration where the GPU has one workgroup, in the order of the launches of csrc/tmjx_hmm.hip.  It
 // includes kmeans_emu.cpp for the column sums it shares with the k-means.  With -DHMM_EMU_MAIN it is a stand-alone program (for sanitizer builds):
 //   hmm_emu [d k len...] — fits one planted problem (3 features, 2 states, sequences of 1, 2 and 40 rows by default, strided) and prints a checksum.
+#pragma once
 #ifdef HMM_EMU_MAIN
 #undef KMEANS_EMU_MAIN
 #undef PCA_WIDE_EMU_MAIN
@@ -64,50 +65,50 @@ static const int32_t *hemu_seq(const int32_t *seq_start, int S, float *workspace
 }
 
 extern "C" {
-int hemu_workspace(int n, int d, int k, int S, int64_t *floats) {
+int tmjx_hmm_workspace(int n, int d, int k, int S, int64_t *floats) {
   EMU_TRY(hmm_check_workspace(n, d, k, S, floats));
   *floats = hmm_workspace(n, d, k).floats;
   return 0;
 }
 
-int hemu_emission(const float *x, int n, int d, int64_t ldx, const float *means, const float *vars, int k, float *logb, float *workspace) {
+int tmjx_hmm_emission(const float *x, int n, int d, int64_t ldx, const float *means, const float *vars, int k, float *logb, float *workspace, void *) {
   EMU_TRY(hmm_check_emission(x, n, d, ldx, means, vars, k, logb, workspace));
   hemu_emission_run(x, n, d, ldx, means, vars, k, logb, workspace + hmm_workspace(n, d, k).cj);
   return 0;
 }
 
-int hemu_forward_backward(const float *logb, int n, int k, const int32_t *seq_start, int S, const float *transmat, const float *startprob, float *gamma,
-                          double *xi, double *start, double *loglik, double *total, float *workspace) {
+int tmjx_hmm_forward_backward(const float *logb, int n, int k, const int32_t *seq_start, int S, const float *transmat, const float *startprob, float *gamma,
+                              double *xi, double *start, double *loglik, double *total, float *workspace, void *) {
   EMU_TRY(hmm_check_fb(logb, n, k, seq_start, S, transmat, startprob, gamma, xi, start, loglik, total, workspace));
   const HmmWorkspace w = hmm_workspace(n, 1, k);
   hemu_fb_run(logb, n, k, hemu_seq(seq_start, S, workspace, w), S, transmat, startprob, gamma, xi, start, loglik, total, workspace, w);
   return 0;
 }
 
-int hemu_mstep(const float *x, int n, int d, int64_t ldx, const float *gamma, int k, double min_var, double min_weight, float *means, float *vars,
-               double *weight, float *workspace) {
+int tmjx_hmm_mstep(const float *x, int n, int d, int64_t ldx, const float *gamma, int k, double min_var, double min_weight, float *means, float *vars,
+                   double *weight, float *workspace, void *) {
   EMU_TRY(hmm_check_mstep(x, n, d, ldx, gamma, k, min_var, min_weight, means, vars, weight, workspace));
   hemu_mstep_run(x, n, d, ldx, gamma, k, min_var, min_weight, means, vars, weight, workspace, hmm_workspace(n, d, k));
   return 0;
 }
 
-int hemu_transitions(const double *xi, const double *start, int k, double prior, double kappa, float *transmat, float *startprob) {
+int tmjx_hmm_transitions(const double *xi, const double *start, int k, double prior, double kappa, float *transmat, float *startprob, void *) {
   EMU_TRY(hmm_check_transitions(xi, start, k, prior, kappa, transmat, startprob));
   hmm_transitions_wg(xi, start, k, prior, kappa, transmat, startprob);
   return 0;
 }
 
-int hemu_viterbi(const float *logb, int n, int k, const int32_t *seq_start, int S, const float *transmat, const float *startprob, int logspace, int32_t *labels,
-                 double *path_logprob, float *workspace) {
+int tmjx_hmm_viterbi(const float *logb, int n, int k, const int32_t *seq_start, int S, const float *transmat, const float *startprob, int logspace,
+                     int32_t *labels, double *path_logprob, float *workspace, void *) {
   EMU_TRY(hmm_check_viterbi(logb, n, k, seq_start, S, transmat, startprob, labels, path_logprob, workspace));
   const HmmWorkspace w = hmm_workspace(n, 1, k);
   hemu_viterbi_run(logb, k, hemu_seq(seq_start, S, workspace, w), S, transmat, startprob, logspace, labels, path_logprob, workspace, w);
   return 0;
 }
 
-int hemu_fit(const float *x, int n, int d, int64_t ldx, const int32_t *seq_start, int S, int k, float *means, float *vars, float *transmat, float *startprob,
-             float *gamma, int32_t *labels, int max_iter, double tol, double prior, double kappa, double min_var, double min_weight, tmjx_hmm_info_t *info,
-             float *workspace) {
+int tmjx_hmm_fit(const float *x, int n, int d, int64_t ldx, const int32_t *seq_start, int S, int k, float *means, float *vars, float *transmat,
+                 float *startprob, float *gamma, int32_t *labels, int max_iter, double tol, double prior, double kappa, double min_var, double min_weight,
+                 tmjx_hmm_info_t *info, float *workspace, void *) {
   EMU_TRY(hmm_check_fit(x, n, d, ldx, seq_start, S, k, means, vars, transmat, startprob, labels, max_iter, tol, prior, kappa, min_var, min_weight, info,
                         workspace));
   const HmmWorkspace w = hmm_workspace(n, d, k);
@@ -155,21 +156,21 @@ int main(int argc, char **argv) {
   std::vector<float> gamma((size_t)n * k);
   std::vector<int32_t> labels(n);
   int64_t floats = 0;
-  if (hemu_workspace(n, d, k, S, &floats)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
+  if (tmjx_hmm_workspace(n, d, k, S, &floats)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
   std::vector<double> ws((size_t)floats / 2 + 2);      // exactly the size asked for (rounded up to a double), so a sanitizer sees any overrun
   float *wsa = (float *)ws.data();
   tmjx_hmm_info_t info;
-  if (hemu_fit(x.data(), n, d, ldx, seq.data(), S, k, mu.data(), var.data(), A.data(), pi.data(), gamma.data(), labels.data(), 20, 1e-6, 0.1, 0.0, 1e-3, 1e-3, &info,
-               wsa)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
+  if (tmjx_hmm_fit(x.data(), n, d, ldx, seq.data(), S, k, mu.data(), var.data(), A.data(), pi.data(), gamma.data(), labels.data(), 20, 1e-6, 0.1, 0.0, 1e-3, 1e-3, &info,
+                   wsa, nullptr)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
   std::vector<float> logb((size_t)n * k);
   std::vector<double> xi((size_t)k * k), start(k), ll(S), path(S), weight(k);
   double total = 0.0;
   std::vector<int32_t> again(n);
-  if (hemu_emission(x.data(), n, d, ldx, mu.data(), var.data(), k, logb.data(), wsa) ||
-      hemu_forward_backward(logb.data(), n, k, seq.data(), S, A.data(), pi.data(), gamma.data(), xi.data(), start.data(), ll.data(), &total, wsa) ||
-      hemu_viterbi(logb.data(), n, k, seq.data(), S, A.data(), pi.data(), 0, again.data(), path.data(), wsa) ||
-      hemu_mstep(x.data(), n, d, ldx, gamma.data(), k, 1e-3, 1e-3, mu.data(), var.data(), weight.data(), wsa) ||
-      hemu_transitions(xi.data(), start.data(), k, 0.1, 0.0, A.data(), pi.data())) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
+  if (tmjx_hmm_emission(x.data(), n, d, ldx, mu.data(), var.data(), k, logb.data(), wsa, nullptr) ||
+      tmjx_hmm_forward_backward(logb.data(), n, k, seq.data(), S, A.data(), pi.data(), gamma.data(), xi.data(), start.data(), ll.data(), &total, wsa, nullptr) ||
+      tmjx_hmm_viterbi(logb.data(), n, k, seq.data(), S, A.data(), pi.data(), 0, again.data(), path.data(), wsa, nullptr) ||
+      tmjx_hmm_mstep(x.data(), n, d, ldx, gamma.data(), k, 1e-3, 1e-3, mu.data(), var.data(), weight.data(), wsa, nullptr) ||
+      tmjx_hmm_transitions(xi.data(), start.data(), k, 0.1, 0.0, A.data(), pi.data(), nullptr)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
   double sum = total;
   for (float v : mu) sum += fabs(v);
   for (float v : A) sum += v;

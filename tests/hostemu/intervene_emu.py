@@ -8,10 +8,10 @@ from pathlib import Path
 
 import numpy as np
 
+from tests.hostemu import loader
 from track_mjx_amd.hip import INTERVENE_SUBSPACE, INTERVENE_UNITS, Intervene
 
 _HERE = Path(__file__).resolve().parent
-_CSRC = _HERE.parents[1] / "track_mjx_amd" / "csrc"
 _lib_cache = None
 
 
@@ -19,11 +19,7 @@ def _lib():
     global _lib_cache
     if _lib_cache is not None:
         return _lib_cache
-    src = [_HERE / "intervene_emu.cpp", _HERE.parents[1] / "include" / "tmjx.h", _CSRC / "intervene_core.h", _CSRC / "intervene_host.h"]
-    so = _HERE / "libintervene_emu.so"
-    if not so.exists() or so.stat().st_mtime < max(p.stat().st_mtime for p in src):
-        subprocess.run(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-o", str(so), str(_HERE / "intervene_emu.cpp")], check=True, capture_output=True)
-    L = C.CDLL(str(so))
+    L = loader.load("intervene_emu.cpp")
     L.ivemu_last_error.restype = C.c_char_p
     L.ivemu_intervene_ok.argtypes = [C.POINTER(Intervene)]
     L.ivemu_intervene.argtypes = [C.POINTER(Intervene), C.c_int]

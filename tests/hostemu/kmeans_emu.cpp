@@ -3,6 +3,7 @@
 // one loop iteration where the GPU has one workgroup, in the order of the launches of csrc/tmjx_kmeans.hip.  It includes pca_wide_emu.cpp for the
 // column sums it shares with the wide PCA.  With -DKMEANS_EMU_MAIN it is a stand-alone program (for sanitizer builds):
 //   kmeans_emu [n d k] — seeds, fits and re-assigns one blob problem (257 x 3 into 2 by default, strided) and prints a checksum.
+#pragma once
 #ifdef KMEANS_EMU_MAIN
 #undef PCA_WIDE_EMU_MAIN
 #undef PCA_EMU_MAIN
@@ -41,26 +42,26 @@ static void kemu_update_run(const float *x, int n, int d, int64_t ldx, const int
 }
 
 extern "C" {
-int kemu_workspace(int n, int d, int k, int64_t *floats) {
+int tmjx_kmeans_workspace(int n, int d, int k, int64_t *floats) {
   EMU_TRY(kmeans_check_workspace(n, d, k, floats));
   *floats = kmeans_workspace(n, d, k).floats;
   return 0;
 }
 
-int kemu_assign(const float *x, int n, int d, int64_t ldx, const float *centroids, int k, const int32_t *labels_prev, int32_t *labels, float *dist2,
-                double *inertia, int32_t *changed, float *workspace) {
+int tmjx_kmeans_assign(const float *x, int n, int d, int64_t ldx, const float *centroids, int k, const int32_t *labels_prev, int32_t *labels, float *dist2,
+                       double *inertia, int32_t *changed, float *workspace, void *) {
   EMU_TRY(kmeans_check_assign(x, n, d, ldx, centroids, k, labels, inertia, workspace));
   kemu_assign_run(x, n, d, ldx, centroids, k, labels_prev, labels, dist2, inertia, changed, workspace);
   return 0;
 }
 
-int kemu_update(const float *x, int n, int d, int64_t ldx, const int32_t *labels, int k, float *centroids, int32_t *counts, float *workspace) {
+int tmjx_kmeans_update(const float *x, int n, int d, int64_t ldx, const int32_t *labels, int k, float *centroids, int32_t *counts, float *workspace, void *) {
   EMU_TRY(kmeans_check_update(x, n, d, ldx, labels, k, centroids, counts, workspace));
   kemu_update_run(x, n, d, ldx, labels, k, centroids, counts, workspace);
   return 0;
 }
 
-int kemu_seed(const float *x, int n, int d, int64_t ldx, int k, const double *u, float *centroids, int32_t *index, float *workspace) {
+int tmjx_kmeans_seed(const float *x, int n, int d, int64_t ldx, int k, const double *u, float *centroids, int32_t *index, float *workspace, void *) {
   EMU_TRY(kmeans_check_seed(x, n, d, ldx, k, u, centroids, index, workspace));
   const KmeansWorkspace w = kmeans_workspace(n, d, k);
   float *d2 = workspace + w.d2;
@@ -78,8 +79,8 @@ int kemu_seed(const float *x, int n, int d, int64_t ldx, int k, const double *u,
   return 0;
 }
 
-int kemu_fit(const float *x, int n, int d, int64_t ldx, int k, float *centroids, int32_t *labels, float *dist2, int max_iter, double tol,
-             tmjx_kmeans_info_t *info, float *workspace) {
+int tmjx_kmeans_fit(const float *x, int n, int d, int64_t ldx, int k, float *centroids, int32_t *labels, float *dist2, int max_iter, double tol,
+                    tmjx_kmeans_info_t *info, float *workspace, void *) {
   EMU_TRY(kmeans_check_fit(x, n, d, ldx, k, centroids, labels, max_iter, tol, info, workspace));
   const KmeansWorkspace w = kmeans_workspace(n, d, k);
   int32_t *buf[2] = {labels, (int32_t *)(workspace + w.labels2)}, *counts = (int32_t *)(workspace + w.picks);
@@ -122,16 +123,19 @@ int main(int argc, char **argv) {
   for (double &v : u) v = (double)klcg(seed) + 0.5;
   std::vector<int32_t> index(k), labels(n), again(n), counts(k);
   int64_t floats = 0;
-  if (kemu_workspace(n, d, k, &floats)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
+  if (tmjx_kmeans_workspace(n, d, k, &floats)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
   std::vector<double> ws((size_t)floats / 2 + 2);      // exactly the size asked for (rounded up to a double), so a sanitizer sees any overrun
   float *wsa = (float *)ws.data();
   tmjx_kmeans_info_t info;
-  if (kemu_seed(x.data(), n, d, ldx, k, u.data(), c.data(), index.data(), wsa)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
-  if (kemu_fit(x.data(), n, d, ldx, k, c.data(), labels.data(), dist2.data(), 50, 0.0, &info, wsa)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
+  if (tmjx_kmeans_seed(x.data(), n, d, ldx, k, u.data(), c.data(), index.data(), wsa, nullptr)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
+  if (tmjx_kmeans_fit(x.data(), n, d, ldx, k, c.data(), labels.data(), dist2.data(), 50, 0.0, &info, wsa, nullptr)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
   double inertia = 0.0;
   int32_t changed = -1;
-  if (kemu_assign(x.data(), n, d, ldx, c.data(), k, labels.data(), again.data(), nullptr, &inertia, &changed, wsa)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
-  if (kemu_update(x.data(), n, d, ldx, again.data(), k, c.data(), counts.data(), wsa)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
+  if (tmjx_kmeans_assign(x.data(), n, d, ldx, c.data(), k, labels.data(), again.data(), nullptr, &inertia, &changed, wsa, nullptr)) {
+    fprintf(stderr, "%s\n", g_err.c_str());
+    return 1;
+  }
+  if (tmjx_kmeans_update(x.data(), n, d, ldx, again.data(), k, c.data(), counts.data(), wsa, nullptr)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
   double sum = inertia;
   for (float v : c) sum += fabs(v);
   for (int32_t v : counts) sum += v;

@@ -2,6 +2,7 @@
 // csrc/pca_core.h and the argument checks of csrc/pca_host.h compiled with g++, one loop iteration where the GPU has one thread or workgroup.
 // Built like the other emulations; nothing in track_mjx_amd/ loads it.  With -DPCA_EMU_MAIN it is a stand-alone program (for sanitizer builds):
 //   pca_emu — fits, transforms and draws a few small problems (odd d, a row stride, a scrolling panel with a NaN) and prints a checksum.
+#pragma once
 #define TM_HOST_EMU 1
 #define TM_DEV static inline
 #include <math.h>
@@ -20,16 +21,17 @@ static int fail(int code, const std::string &e) { g_err = e; return code; }
 #define EMU_TRY(expr) do { const std::string e_ = (expr); if (!e_.empty()) return fail(TMJX_EINVAL, e_); } while (0)
 
 extern "C" {
-const char *pemu_last_error() { return g_err.c_str(); }
+const char *tmjx_last_error(void) { return g_err.c_str(); }
 
-int pemu_workspace(int n, int d, int64_t *floats) {
+// (static: the wide PCA forwards d <= 128 here, and no call inside the library goes through an exported name)
+static int pemu_workspace(int n, int d, int64_t *floats) {
   if (!floats) return fail(TMJX_EINVAL, "null argument");
   EMU_TRY(pca_check_shape(n, d, d));
   *floats = pca_workspace(n, d).floats;
   return 0;
 }
 
-int pemu_fit(const float *x, int n, int d, int64_t ldx, float *mean, float *components, float *variance, float *workspace, tmjx_pca_info_t *info) {
+static int pemu_fit(const float *x, int n, int d, int64_t ldx, float *mean, float *components, float *variance, float *workspace, tmjx_pca_info_t *info) {
   EMU_TRY(pca_check_fit(x, n, d, ldx, mean, components, variance, workspace, info));
   const PcaWorkspace w = pca_workspace(n, d);
   double *colsum = (double *)(workspace + w.colsum);
@@ -55,7 +57,7 @@ int pemu_fit(const float *x, int n, int d, int64_t ldx, float *mean, float *comp
   return 0;
 }
 
-int pemu_transform(const float *x, int n, int d, int64_t ldx, const float *mean, const float *components, int k, float *out, int64_t ldo) {
+static int pemu_transform(const float *x, int n, int d, int64_t ldx, const float *mean, const float *components, int k, float *out, int64_t ldo) {
   EMU_TRY(pca_check_transform(x, n, d, ldx, mean, components, k, out, ldo));
   std::vector<float> xc(d);
   for (int r = 0; r < n; r++) {
@@ -65,8 +67,18 @@ int pemu_transform(const float *x, int n, int d, int64_t ldx, const float *mean,
   return 0;
 }
 
-int pemu_strips(const float *proj, int T, int k, int64_t ldp, const int32_t *frame_idx, const uint8_t *flags, int F, float ymin, float ymax, int window,
-                const tmjx_strip_style_t *style, int W, int H, uint8_t *rgba) {
+int tmjx_pca_workspace(int n, int d, int64_t *floats) { return pemu_workspace(n, d, floats); }
+
+int tmjx_pca_fit(const float *x, int n, int d, int64_t ldx, float *mean, float *components, float *variance, float *workspace, tmjx_pca_info_t *info, void *) {
+  return pemu_fit(x, n, d, ldx, mean, components, variance, workspace, info);
+}
+
+int tmjx_pca_transform(const float *x, int n, int d, int64_t ldx, const float *mean, const float *components, int k, float *out, int64_t ldo, void *) {
+  return pemu_transform(x, n, d, ldx, mean, components, k, out, ldo);
+}
+
+int tmjx_plot_strips(const float *proj, int T, int k, int64_t ldp, const int32_t *frame_idx, const uint8_t *flags, int F, float ymin, float ymax, int window,
+                     const tmjx_strip_style_t *style, int W, int H, uint8_t *rgba, void *) {
   PcaStrip s;
   EMU_TRY(pca_check_strips(proj, T, k, ldp, frame_idx, F, ymin, ymax, window, style, W, H, rgba, s));
   for (int f = 0; f < F; f++)
@@ -91,12 +103,12 @@ int main() {
     for (float &v : x) v = lcg(seed) + 3.f;
     for (int r = 0; r < n; r++) x[(size_t)r * ldx] += 2.f * lcg(seed);
     int64_t floats = 0;
-    if (pemu_workspace(n, d, &floats)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
+    if (tmjx_pca_workspace(n, d, &floats)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
     std::vector<double> ws((size_t)floats / 2 + 2);
     float *wsa = (float *)(((uintptr_t)ws.data() + 15) & ~(uintptr_t)15);
     tmjx_pca_info_t info;
-    if (pemu_fit(x.data(), n, d, ldx, mean.data(), comp.data(), var.data(), wsa, &info)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
-    if (pemu_transform(x.data(), n, d, ldx, mean.data(), comp.data(), k, out.data(), k)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
+    if (tmjx_pca_fit(x.data(), n, d, ldx, mean.data(), comp.data(), var.data(), wsa, &info, nullptr)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
+    if (tmjx_pca_transform(x.data(), n, d, ldx, mean.data(), comp.data(), k, out.data(), k, nullptr)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
     for (float v : var) sum += v;
     for (float v : out) sum += fabs(v);
     printf("pca_emu: %d x %d (ld %d): %d sweeps, off / norm %.2e, largest variance %.6f\n", n, d, ldx, info.sweeps, info.off_rel, var[0]);
@@ -115,7 +127,7 @@ int main() {
   st.terminated[0] = 255;
   std::vector<uint8_t> rgba((size_t)F * W * H * 4);
   for (int window : {5, 530}) {
-    if (pemu_strips(proj.data(), T, k, k, idx, flags, F, -2.2f, 2.2f, window, &st, W, H, rgba.data())) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
+    if (tmjx_plot_strips(proj.data(), T, k, k, idx, flags, F, -2.2f, 2.2f, window, &st, W, H, rgba.data(), nullptr)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
     for (uint8_t v : rgba) sum += v;
   }
   printf("pca_emu: checksum %.6f\n", sum);

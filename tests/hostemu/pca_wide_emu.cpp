@@ -3,6 +3,7 @@
 // the GPU has one workgroup, in the order of the launches of csrc/tmjx_pca_wide.hip.  It includes pca_emu.cpp, so the library also has the narrow
 // entry points (d <= 128 forwards to them) and the panel.  With -DPCA_WIDE_EMU_MAIN it is a stand-alone program (for sanitizer builds):
 //   pca_wide_emu [n d] — fits and transforms one problem (130 x 192 by default) and prints a checksum.
+#pragma once
 #ifdef PCA_WIDE_EMU_MAIN
 #undef PCA_EMU_MAIN
 #endif
@@ -13,7 +14,8 @@
 #include "../../track_mjx_amd/csrc/pca_wide_host.h"
 
 extern "C" {
-int pwemu_workspace(int n, int d, int64_t *floats) {
+// (static: the readout's fit is this fit)
+static int pwemu_workspace(int n, int d, int64_t *floats) {
   if (d >= 1 && d <= PCA_MAX_D) return pemu_workspace(n, d, floats);
   if (!floats) return fail(TMJX_EINVAL, "null argument");
   EMU_TRY(pca_wide_check_shape(n, d, d));
@@ -29,7 +31,7 @@ static void pwemu_norms(float *ws, const PcaWideWorkspace &w, int d, double *nor
   norms[0] = out[0]; norms[1] = out[1];
 }
 
-int pwemu_fit(const float *x, int n, int d, int64_t ldx, float *mean, float *components, float *variance, float *workspace, tmjx_pca_info_t *info) {
+static int pwemu_fit(const float *x, int n, int d, int64_t ldx, float *mean, float *components, float *variance, float *workspace, tmjx_pca_info_t *info) {
   if (d >= 1 && d <= PCA_MAX_D) return pemu_fit(x, n, d, ldx, mean, components, variance, workspace, info);
   EMU_TRY(pca_wide_check_fit(x, n, d, ldx, mean, components, variance, workspace, info));
   const PcaWideWorkspace w = pca_wide_workspace(n, d);
@@ -77,7 +79,14 @@ int pwemu_fit(const float *x, int n, int d, int64_t ldx, float *mean, float *com
   return 0;
 }
 
-int pwemu_transform(const float *x, int n, int d, int64_t ldx, const float *mean, const float *components, int k, float *out, int64_t ldo) {
+int tmjx_pca_wide_workspace(int n, int d, int64_t *floats) { return pwemu_workspace(n, d, floats); }
+
+int tmjx_pca_fit_wide(const float *x, int n, int d, int64_t ldx, float *mean, float *components, float *variance, float *workspace, tmjx_pca_info_t *info,
+                      void *) {
+  return pwemu_fit(x, n, d, ldx, mean, components, variance, workspace, info);
+}
+
+int tmjx_pca_transform_wide(const float *x, int n, int d, int64_t ldx, const float *mean, const float *components, int k, float *out, int64_t ldo, void *) {
   if (d >= 1 && d <= PCA_MAX_D) return pemu_transform(x, n, d, ldx, mean, components, k, out, ldo);
   EMU_TRY(pca_wide_check_transform(x, n, d, ldx, mean, components, k, out, ldo));
   std::vector<float> s_x(PCA_WIDE_TK * PCA_WIDE_TLD), s_c(PCA_WIDE_TK * PCA_WIDE_TLD);
@@ -101,14 +110,14 @@ int main(int argc, char **argv) {
   for (int r = 0; r < n; r++)
     for (int j = 0; j < 6 && j < d; j++) x[(size_t)r * ldx + j * 7 % d] += (float)(6 - j) * wlcg(seed);
   int64_t floats = 0;
-  if (pwemu_workspace(n, d, &floats)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
+  if (tmjx_pca_wide_workspace(n, d, &floats)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
   std::vector<double> ws((size_t)floats / 2 + 2);
   float *wsa = (float *)(((uintptr_t)ws.data() + 15) & ~(uintptr_t)15);
   tmjx_pca_info_t info;
-  if (pwemu_fit(x.data(), n, d, ldx, mean.data(), comp.data(), var.data(), wsa, &info)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
+  if (tmjx_pca_fit_wide(x.data(), n, d, ldx, mean.data(), comp.data(), var.data(), wsa, &info, nullptr)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
   double sum = 0.0;
   for (int kk : {4, k}) {
-    if (pwemu_transform(x.data(), n, d, ldx, mean.data(), comp.data(), kk, out.data(), ldo)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
+    if (tmjx_pca_transform_wide(x.data(), n, d, ldx, mean.data(), comp.data(), kk, out.data(), ldo, nullptr)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
     for (int r = 0; r < n; r++)
       for (int c = 0; c < kk; c++) sum += fabs(out[(size_t)r * ldo + c]);
   }

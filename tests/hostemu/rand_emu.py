@@ -2,21 +2,16 @@
 from __future__ import annotations
 
 import ctypes as C
-import subprocess
-from pathlib import Path
 
 import numpy as np
 
-_HERE = Path(__file__).resolve().parent
+from tests.hostemu import loader
+
 _FP = C.POINTER(C.c_float)
 
 
 def _lib():
-    src = [_HERE / "rand_emu.cpp", *sorted((_HERE.parents[1] / "track_mjx_amd" / "csrc").glob("*.h"))]
-    so = _HERE / "librand_emu.so"
-    if not so.exists() or so.stat().st_mtime < max(p.stat().st_mtime for p in src):
-        subprocess.run(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-o", str(so), str(_HERE / "rand_emu.cpp")], check=True, capture_output=True)
-    L = C.CDLL(str(so))
+    L = loader.load("rand_emu.cpp")
     L.rand_model_create.restype = C.c_void_p
     L.rand_model_create.argtypes = [C.c_char_p, C.c_size_t]
     L.rand_last_error.restype = C.c_char_p

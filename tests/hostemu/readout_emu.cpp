@@ -4,6 +4,7 @@
 // pca_wide_emu.cpp, so the library also has the PCA entry points, whose fit the readout calls.  With -DREADOUT_EMU_MAIN it is a stand-alone
 // program (for sanitizer builds):
 //   readout_emu [n d m] — fits, weighs, predicts and scores one problem (300 x 140 -> 70 by default, strided) and prints a checksum.
+#pragma once
 #ifdef READOUT_EMU_MAIN
 #undef PCA_WIDE_EMU_MAIN
 #undef PCA_EMU_MAIN
@@ -13,7 +14,7 @@
 #include "../../track_mjx_amd/csrc/readout_host.h"
 
 extern "C" {
-int remu_workspace(int n, int d, int m, int n_lambda, int64_t *floats) {
+int tmjx_readout_workspace(int n, int d, int m, int n_lambda, int64_t *floats) {
   EMU_TRY(readout_check_workspace(n, d, m, n_lambda, floats));
   int64_t pca = 0, pca_widest = 0;
   int rc = pwemu_workspace(n, d, &pca);
@@ -23,8 +24,8 @@ int remu_workspace(int n, int d, int m, int n_lambda, int64_t *floats) {
   return 0;
 }
 
-// The floats a fit (*fit) and a score (*score) of exactly n rows touch from the start of the workspace: the ends of the layouts remu_fit and
-// remu_score use (for the test that tmjx_readout_workspace of n rows covers every n' <= n).
+// The floats a fit (*fit) and a score (*score) of exactly n rows touch from the start of the workspace: the ends of the layouts tmjx_readout_fit and
+// tmjx_readout_score use (for the test that tmjx_readout_workspace of n rows covers every n' <= n).
 int remu_extents(int n, int d, int m, int n_lambda, int64_t *fit, int64_t *score) {
   EMU_TRY(readout_check_workspace(n, d, m, n_lambda, fit));
   int64_t pca = 0;
@@ -36,8 +37,8 @@ int remu_extents(int n, int d, int m, int n_lambda, int64_t *fit, int64_t *score
   return 0;
 }
 
-int remu_fit(const float *x, int n, int d, int64_t ldx, const float *y, int m, int64_t ldy, float *mean_x, float *components, float *variance, float *mean_y,
-             float *z, float *workspace, tmjx_pca_info_t *info) {
+int tmjx_readout_fit(const float *x, int n, int d, int64_t ldx, const float *y, int m, int64_t ldy, float *mean_x, float *components, float *variance,
+                     float *mean_y, float *z, float *workspace, tmjx_pca_info_t *info, void *) {
   EMU_TRY(readout_check_fit(x, n, d, ldx, y, m, ldy, mean_x, components, variance, mean_y, z, workspace, info));
   int64_t pca = 0;
   int rc = pwemu_workspace(n, d, &pca);
@@ -61,7 +62,7 @@ int remu_fit(const float *x, int n, int d, int64_t ldx, const float *y, int m, i
   return 0;
 }
 
-int remu_weights(const float *components, const float *variance, const float *z, int d, int m, const double *lambdas, int n_lambda, float *w) {
+int tmjx_readout_weights(const float *components, const float *variance, const float *z, int d, int m, const double *lambdas, int n_lambda, float *w, void *) {
   EMU_TRY(readout_check_weights(components, variance, z, d, m, lambdas, n_lambda, w));
   std::vector<float> s_a(PCA_KB * READOUT_LD), s_b(PCA_KB * READOUT_LD);
   for (int l = 0; l < n_lambda; l++)
@@ -71,7 +72,8 @@ int remu_weights(const float *components, const float *variance, const float *z,
   return 0;
 }
 
-int remu_predict(const float *x, int n, int d, int64_t ldx, const float *mean_x, const float *w, const float *mean_y, int m, float *out, int64_t ldo) {
+int tmjx_readout_predict(const float *x, int n, int d, int64_t ldx, const float *mean_x, const float *w, const float *mean_y, int m, float *out, int64_t ldo,
+                         void *) {
   EMU_TRY(readout_check_predict(x, n, d, ldx, mean_x, w, mean_y, m, out, ldo));
   std::vector<float> s_x(PCA_WIDE_TK * READOUT_LD), s_w(PCA_WIDE_TK * READOUT_LD);
   for (int64_t r0 = 0; r0 < n; r0 += READOUT_ROWS)
@@ -80,8 +82,8 @@ int remu_predict(const float *x, int n, int d, int64_t ldx, const float *mean_x,
   return 0;
 }
 
-int remu_score(const float *x, int n, int d, int64_t ldx, const float *y, int m, int64_t ldy, const float *mean_x, const float *w, const float *mean_y,
-               int n_lambda, double *sse, double *sst, float *workspace) {
+int tmjx_readout_score(const float *x, int n, int d, int64_t ldx, const float *y, int m, int64_t ldy, const float *mean_x, const float *w, const float *mean_y,
+                       int n_lambda, double *sse, double *sst, float *workspace, void *) {
   EMU_TRY(readout_check_score(x, n, d, ldx, y, m, ldy, mean_x, w, mean_y, n_lambda, sse, sst, workspace));
   const ReadoutScoreWorkspace ws = readout_score_workspace(n, m, n_lambda);
   double *ysum = (double *)(workspace + ws.ysum), *sstp = (double *)(workspace + ws.sst), *ssep = (double *)(workspace + ws.sse);
@@ -115,23 +117,26 @@ int main(int argc, char **argv) {
   for (int r = 0; r < n; r++)
     for (int c = 0; c < m; c++) y[(size_t)r * ldy + c] = x[(size_t)r * ldx + c % d] - 0.5f * x[(size_t)r * ldx + (c + 1) % d] + 0.1f * rlcg(seed) + 7.f;
   int64_t floats = 0;
-  if (remu_workspace(n, d, m, L, &floats)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
+  if (tmjx_readout_workspace(n, d, m, L, &floats)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
   std::vector<double> ws((size_t)floats / 2 + 2);
   float *wsa = (float *)(((uintptr_t)ws.data() + 15) & ~(uintptr_t)15);
   tmjx_pca_info_t info;
-  if (remu_fit(x.data(), n, d, ldx, y.data(), m, ldy, mean_x.data(), comp.data(), var.data(), mean_y.data(), z.data(), wsa, &info)) {
+  if (tmjx_readout_fit(x.data(), n, d, ldx, y.data(), m, ldy, mean_x.data(), comp.data(), var.data(), mean_y.data(), z.data(), wsa, &info, nullptr)) {
     fprintf(stderr, "%s\n", g_err.c_str());
     return 1;
   }
   double total = 0.0;
   for (float v : var) total += v;
   const double lambdas[L] = {1e-3 * total / d, 1e-1 * total / d, 10.0 * total / d};
-  if (remu_weights(comp.data(), var.data(), z.data(), d, m, lambdas, L, w.data())) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
+  if (tmjx_readout_weights(comp.data(), var.data(), z.data(), d, m, lambdas, L, w.data(), nullptr)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
   std::vector<double> sse((size_t)L * m), sst(m);
   // the score and the predictions on the last nt rows (a ragged block)
   const float *xt = x.data() + (size_t)(n - nt) * ldx, *yt = y.data() + (size_t)(n - nt) * ldy;
-  if (remu_score(xt, nt, d, ldx, yt, m, ldy, mean_x.data(), w.data(), mean_y.data(), L, sse.data(), sst.data(), wsa)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
-  if (remu_predict(xt, nt, d, ldx, mean_x.data(), w.data(), mean_y.data(), m, out.data(), ldo)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
+  if (tmjx_readout_score(xt, nt, d, ldx, yt, m, ldy, mean_x.data(), w.data(), mean_y.data(), L, sse.data(), sst.data(), wsa, nullptr)) {
+    fprintf(stderr, "%s\n", g_err.c_str());
+    return 1;
+  }
+  if (tmjx_readout_predict(xt, nt, d, ldx, mean_x.data(), w.data(), mean_y.data(), m, out.data(), ldo, nullptr)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
   double sum = 0.0, r2 = 0.0;
   for (int c = 0; c < m; c++) r2 += 1.0 - sse[c] / sst[c];
   for (int r = 0; r < nt; r++)

@@ -8,19 +8,15 @@ from pathlib import Path
 
 import numpy as np
 
+from tests.hostemu import loader
 from track_mjx_amd.hip import Camera, RenderInfo
 
 _HERE = Path(__file__).resolve().parent
-_CSRC = _HERE.parents[1] / "track_mjx_amd" / "csrc"
 _FP = C.POINTER(C.c_float)
 
 
 def _lib():
-    src = [_HERE / "render_emu.cpp", _CSRC / "render_core.h", _CSRC / "render_host.h", _CSRC / "model_host.h", _HERE.parents[1] / "include" / "tmjx.h"]
-    so = _HERE / "librender_emu.so"
-    if not so.exists() or so.stat().st_mtime < max(p.stat().st_mtime for p in src):
-        subprocess.run(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-o", str(so), str(_HERE / "render_emu.cpp")], check=True, capture_output=True)
-    L = C.CDLL(str(so))
+    L = loader.load("render_emu.cpp")
     vp = C.c_void_p
     L.remu_create.restype = vp
     L.remu_create.argtypes = [C.c_char_p, C.c_size_t]

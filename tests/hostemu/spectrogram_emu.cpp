@@ -4,6 +4,7 @@
 // a stand-alone program (for sanitizer builds):
 //   spectrogram_emu [C F detrend log len...] — transforms one planted signal (3 channels, 5 frequencies, sequences of 1, 2, 5 and 70 rows by
 //   default, strided input and output) with exactly sized buffers and prints a checksum.
+#pragma once
 #ifdef SPECTROGRAM_EMU_MAIN
 #undef HMM_EMU_MAIN
 #undef KMEANS_EMU_MAIN
@@ -15,28 +16,28 @@
 #include "../../track_mjx_amd/csrc/spectrogram_host.h"
 
 extern "C" {
-int semu_bank_size(double rate, const double *freqs, int F, double omega0, double support, int64_t *floats) {
+int tmjx_wavelet_bank_size(double rate, const double *freqs, int F, double omega0, double support, int64_t *floats) {
   EMU_TRY(spec_check_bank(rate, freqs, F, omega0, support));
   if (!floats) return fail(TMJX_EINVAL, "null argument");
   *floats = spec_bank_floats(rate, freqs, F, omega0, support);
   return 0;
 }
 
-int semu_bank(double rate, const double *freqs, int F, double omega0, double support, float *bank, int32_t *offset, int32_t *radius) {
+int tmjx_wavelet_bank(double rate, const double *freqs, int F, double omega0, double support, float *bank, int32_t *offset, int32_t *radius) {
   EMU_TRY(spec_check_bank(rate, freqs, F, omega0, support));
   if (!bank || !offset || !radius) return fail(TMJX_EINVAL, "null argument");
   spec_build_bank(rate, freqs, F, omega0, support, bank, offset, radius);
   return 0;
 }
 
-int semu_workspace(int n, int C, int F, int S, int64_t *floats) {
+int tmjx_spectrogram_workspace(int n, int C, int F, int S, int64_t *floats) {
   EMU_TRY(spec_check_workspace(n, C, F, S, floats));
   *floats = spec_workspace(C, F, S).floats;
   return 0;
 }
 
-int semu_spectrogram(const float *x, int n, int C, int64_t ldx, const int32_t *seq_start, int S, const float *bank, const int32_t *offset, const int32_t *radius,
-                     int F, int detrend, int output_kind, float log_floor, float *out, int64_t ldo, float *coverage, float *workspace) {
+int tmjx_spectrogram(const float *x, int n, int C, int64_t ldx, const int32_t *seq_start, int S, const float *bank, const int32_t *offset, const int32_t *radius,
+                     int F, int detrend, int output_kind, float log_floor, float *out, int64_t ldo, float *coverage, float *workspace, void *) {
   EMU_TRY(spec_check(x, n, C, ldx, seq_start, S, bank, offset, radius, F, output_kind, log_floor, out, ldo, coverage, workspace));
   const SpecWorkspace w = spec_workspace(C, F, S);
   const SpecGeom g = spec_geom(C, spec_max_radius(radius, F));
@@ -76,18 +77,18 @@ int main(int argc, char **argv) {
   std::vector<double> freqs(F);
   for (int j = 0; j < F; j++) freqs[j] = F > 1 ? pow(25.0, (double)j / (F - 1)) : 5.0;      // 1 .. 25 Hz at rate 50
   int64_t bank_floats = 0, floats = 0;
-  if (semu_bank_size(50.0, freqs.data(), F, 5.0, 4.0, &bank_floats)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
+  if (tmjx_wavelet_bank_size(50.0, freqs.data(), F, 5.0, 4.0, &bank_floats)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
   std::vector<float> bank((size_t)bank_floats);      // exactly the sizes asked for, so a sanitizer sees any overrun
   std::vector<int32_t> offset(F + 1), radius(F);
-  if (semu_bank(50.0, freqs.data(), F, 5.0, 4.0, bank.data(), offset.data(), radius.data())) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
+  if (tmjx_wavelet_bank(50.0, freqs.data(), F, 5.0, 4.0, bank.data(), offset.data(), radius.data())) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
   uint32_t seed = 7;
   std::vector<float> x((size_t)(n - 1) * ldx + C), out((size_t)(n - 1) * ldo + (size_t)F * C, -7.25f), cov((size_t)n * F, -7.25f);
   for (int r = 0; r < n; r++)
     for (int c = 0; c < C; c++) x[(size_t)r * ldx + c] = 3.f + sinf(0.7f * r + c) + 0.1f * slcg(seed);
-  if (semu_workspace(n, C, F, S, &floats)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
+  if (tmjx_spectrogram_workspace(n, C, F, S, &floats)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
   std::vector<double> ws((size_t)floats / 2 + 2);
-  if (semu_spectrogram(x.data(), n, C, ldx, seq.data(), S, bank.data(), offset.data(), radius.data(), F, detrend, kind, 1e-3f, out.data(), ldo, cov.data(),
-                       (float *)ws.data())) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
+  if (tmjx_spectrogram(x.data(), n, C, ldx, seq.data(), S, bank.data(), offset.data(), radius.data(), F, detrend, kind, 1e-3f, out.data(), ldo, cov.data(),
+                       (float *)ws.data(), nullptr)) { fprintf(stderr, "%s\n", g_err.c_str()); return 1; }
   double sum = 0.0;
   int bad = 0;
   for (int r = 0; r < n; r++) {

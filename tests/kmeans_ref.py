@@ -1,5 +1,5 @@
 """The float64 reference of the k-means kernels, the case generator and the checkers that tests/test_kmeans_cpu.py (the host emulation) and
-tests/test_gpu_kmeans.py (the C-ABI) share.  A `backend` is analysis.pca.HipBackend or tests/hostemu/kmeans_emu.EmuKMeansBackend.
+tests/test_gpu_kmeans.py (the C-ABI) share.  A `backend` is analysis.pca.HipBackend or tests/hostemu/analysis_emu.B.
 
 Blob cases (n, d, k): one row; one row past a 256-row block; the intention's width; odd tile edges; both limits.  The assign bounds are the
 worst-case error of comparing two d-term float32 FMA chains on data centred at the column mean mu:

@@ -25,6 +25,30 @@ def test_header_symbols_are_exported():
     assert set(hip.EXPORTS) <= exported
 
 
+def _ctype_kind(t):
+    """A ctypes argument type as the header would spell its kind: "pointer", or (class, bytes) of a scalar."""
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or not isinstance(getattr(t, "_type_", ""), str):
+        return "pointer"
+    return ("float" if t._type_ in "fd" else "int", ctypes.sizeof(t))
+
+
+def test_signature_table_agrees_with_the_header():
+    """hip.SIGNATURES against the prototypes of include/tmjx.h, every tmjx_* function: the number of arguments, a pointer exactly where the header
+    has one, the size and the integer / floating class of every scalar, and the return type.  No allow-list."""
+    from tests.abi_header import SCALARS, prototypes
+    protos = prototypes()
+    assert sorted(protos) == _declared() and set(protos) == set(hip.SIGNATURES) and len(protos) >= 148
+    returns = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "char*": ctypes.c_char_p, "void": None}
+    for name, (ret, args) in protos.items():
+        argtypes, restype = hip.SIGNATURES[name]
+        assert len(argtypes) == len(args), f"{name}: {len(argtypes)} argument types for {len(args)} parameters"
+        for i, ((ctype, pname), t) in enumerate(zip(args, argtypes)):
+            want = "pointer" if ctype.endswith("*") else SCALARS[ctype]
+            assert _ctype_kind(t) == want, f"{name}: argument {i} ({ctype} {pname}) is declared {t.__name__}"
+        same = restype is returns[ret] or (ret == "long long" and restype is not None and _ctype_kind(restype) == ("int", 8))      # (c_int64 is c_long)
+        assert same, f"{name}: returns {ret}, declared {restype}"
+
+
 def test_library_loads_and_reports_errors_without_gpu():
     L = hip.lib()
     assert b"gfx950" in L.tmjx_version()

@@ -1,4 +1,5 @@
-"""CPU: the k-means kernel bodies (csrc/kmeans_core.h) compiled into the host emulation (tests/hostemu/kmeans_emu.cpp) against the float64
+"""CPU: the k-means kernel bodies (csrc/kmeans_core.h) compiled into the host emulation (tests/hostemu/kmeans_emu.cpp),
+called through the shared analysis backend (tests/hostemu/analysis_emu.py), against the float64
 reference (tests/kmeans_ref.py): assign, update, the teacher-forced seeding and the fit at the five blob cases, the integer grids where every
 output is exact, the refusals, `KMeans`, `segment_summary`, the command-line tool, and the emulation as a stand-alone program under
 AddressSanitizer and UBSan.  tests/test_gpu_kmeans.py runs the same checks through the C-ABI."""
@@ -10,11 +11,11 @@ import numpy as np
 import pytest
 
 from tests import kmeans_ref as K
-from tests.hostemu import kmeans_emu as E
+from tests.hostemu import analysis_emu as E
 from track_mjx_amd import hip
 from track_mjx_amd.analysis import cluster as CL
 
-B = E.EmuKMeansBackend
+B = E.B
 
 
 def test_limits_are_exported_and_the_entry_points_declared():
@@ -34,10 +35,10 @@ def test_inputs_have_clear_margins(case):
 def test_assign_against_float64(case):
     x, c, _ = K.case_data(case)
     prev = np.random.default_rng(3).integers(0, case[2], case[0]).astype(np.int32)
-    labels, dist2, inertia, changed = E.kmeans_assign(x, c, prev)
+    labels, dist2, inertia, changed = B.kmeans_assign(x, c, prev)
     K.check_assign(x, c, K.case_dist(case), labels, dist2, inertia, changed, prev, "emulation")
     if case == K.MID:
-        again = E.kmeans_assign(x, c, None)
+        again = B.kmeans_assign(x, c, None)
         np.testing.assert_array_equal(again[0], labels)
         assert again[3] == case[0] and again[2] == inertia
 
@@ -46,7 +47,7 @@ def test_assign_against_float64(case):
 def test_update_against_float64(case):
     x, c, _ = K.case_data(case)
     labels = K.case_dist(case).argmin(1).astype(np.int32)
-    out, counts = E.kmeans_update(x, labels, c)
+    out, counts = B.kmeans_update(x, labels, c)
     K.check_update(x, labels, c, out, counts, "emulation")
 
 
@@ -55,7 +56,7 @@ def test_update_leaves_empty_clusters_alone():
     labels = K.case_dist(K.MID).argmin(1).astype(np.int32)
     labels[labels == 2] = 0
     labels[labels == 5] = 6
-    out, counts = E.kmeans_update(x, labels, c)
+    out, counts = B.kmeans_update(x, labels, c)
     assert counts[2] == 0 and counts[5] == 0
     K.check_update(x, labels, c, out, counts, "emulation, two empty")
 
@@ -63,7 +64,7 @@ def test_update_leaves_empty_clusters_alone():
 @pytest.mark.parametrize("case", K.CASES)
 def test_seed_teacher_forced(case):
     x, _, u = K.case_data(case)
-    cen, index = E.kmeans_seed(x, case[2], u)
+    cen, index = B.kmeans_seed(x, case[2], u)
     assert K.check_seed(x, u, cen, index, "emulation") == 0
 
 
@@ -71,7 +72,7 @@ def test_seed_with_fewer_distinct_rows_than_centres():
     rows = np.float32(np.random.default_rng(2).standard_normal((5, 9)) + 3)
     x = np.ascontiguousarray(rows[np.random.default_rng(4).integers(0, 5, 300)])
     u = np.random.default_rng(7).random(8)
-    cen, index = E.kmeans_seed(x, 8, u)
+    cen, index = B.kmeans_seed(x, 8, u)
     assert K.check_seed(x, u, cen, index, "emulation, 5 distinct rows") == 3
     assert len({x[i].tobytes() for i in index[:5]}) == 5
 
@@ -85,7 +86,7 @@ def test_exact_on_the_small_grid_and_ties_go_to_the_lowest_index():
     x, c = K.grid_small()
     assert K.check_exact(x, c, B, min_ties=0.1) >= 0.1
     u = np.random.default_rng(7).random(12)
-    np.testing.assert_array_equal(E.kmeans_seed(x, 12, u)[1], K.seed64(x, u))
+    np.testing.assert_array_equal(B.kmeans_seed(x, 12, u)[1], K.seed64(x, u))
 
 
 def test_exact_on_the_large_grid():
@@ -99,34 +100,34 @@ def test_strided_rows_give_the_dense_bits():
     buf[:, 3:3 + x.shape[1]] = x
     xs = buf[:, 3:3 + x.shape[1]]
     assert B.asarray(xs) is xs
-    for a, b in zip(E.kmeans_assign(xs, c), E.kmeans_assign(x, c)):
+    for a, b in zip(B.kmeans_assign(xs, c), B.kmeans_assign(x, c)):
         np.testing.assert_array_equal(a, b)
     labels = K.case_dist(K.MID).argmin(1)
-    for a, b in zip(E.kmeans_update(xs, labels, c), E.kmeans_update(x, labels, c)):
+    for a, b in zip(B.kmeans_update(xs, labels, c), B.kmeans_update(x, labels, c)):
         np.testing.assert_array_equal(a, b)
-    for a, b in zip(E.kmeans_seed(xs, 7, u), E.kmeans_seed(x, 7, u)):
+    for a, b in zip(B.kmeans_seed(xs, 7, u), B.kmeans_seed(x, 7, u)):
         np.testing.assert_array_equal(a, b)
 
 
 def test_refusals():
     x, c, u = K.case_data(K.CASES[1])
     for kw, word in ((dict(n=100, k=101), "k <= n"), (dict(k=0), "k must be >= 1"), (dict(n=400, k=257), "limit of 256"), (dict(d=1025, ldx=2000), "limit of 1024"),
-                     (dict(n=0), "n must be >= 1"), (dict(ldx=2), "ldx = 2"), (dict(null=("labels",)), "null"), (dict(null=("inertia",)), "null"),
+                     (dict(n=0), "n must be >= 1"), (dict(ldx=2), "ldx = 2"), (dict(labels=None), "null"), (dict(inertia=None), "null"),
                      (dict(misalign=True), "16-byte")):
         with pytest.raises(ValueError, match=word):
-            E.kmeans_assign(x, c, **kw)
+            E.over("tmjx_kmeans_assign", **kw).kmeans_assign(x, c)
     with pytest.raises(ValueError, match="null"):
-        E.kmeans_update(x, np.zeros(257, np.int32), c, null=("counts",))
+        E.over("tmjx_kmeans_update", counts=None).kmeans_update(x, np.zeros(257, np.int32), c)
     with pytest.raises(ValueError, match="k <= n"):
-        E.kmeans_seed(x, 2, u, n=1)
+        E.over("tmjx_kmeans_seed", n=1).kmeans_seed(x, 2, u[:2])
     with pytest.raises(ValueError, match="uniform"):
-        E.kmeans_seed(x, 2, [0.5, 1.0])
+        B.kmeans_seed(x, 2, [0.5, 1.0])
     with pytest.raises(ValueError, match="max_iter"):
-        E.kmeans_fit(x, c, 0, 0.0)
+        B.kmeans_fit(x, c, 0, 0.0)
     with pytest.raises(ValueError, match="limit of 256"):
-        E.workspace(1000, 4, 257)
-    labels, dist2, _, changed = E.kmeans_assign(x, c, null=("dist2", "changed"))      # the two optional outputs
-    assert (dist2 == -1).all() and changed == -1 and (labels >= 0).all()
+        E.workspace("tmjx_kmeans_workspace", 1000, 4, 257)
+    labels, dist2, _, changed = E.over("tmjx_kmeans_assign", dist2=None, changed=None).kmeans_assign(x, c)      # the two optional outputs
+    assert (dist2 == E.sentinel(np.float32)).all() and changed == E.sentinel(np.int32) and (labels >= 0).all()
 
 
 def test_workspace_does_not_scale_with_n_k_d():
@@ -135,7 +136,7 @@ def test_workspace_does_not_scale_with_n_k_d():
     for n in (8192, 210000, 4000000):
         chunks = -(-n // 256)
         for d, k in ((1024, 256), (60, 16), (512, 64)):
-            assert E.workspace(n, d, k) <= 2 * max(2 ** 23, 32 * k * d) + 2 * chunks * d + 6 * n + 1024 * k + 8 * d + 4096, (n, d, k)
+            assert E.workspace("tmjx_kmeans_workspace", n, d, k) <= 2 * max(2 ** 23, 32 * k * d) + 2 * chunks * d + 6 * n + 1024 * k + 8 * d + 4096, (n, d, k)
 
 
 def test_kmeans_class():
@@ -147,7 +148,7 @@ def test_kmeans_class():
     np.testing.assert_array_equal(km.predict(x), km.labels_)
     # the restart with the lowest inertia, the earlier one on a tie
     u = np.random.default_rng(0).random((3, 7))
-    inertias = [float(E.kmeans_fit(x, E.kmeans_seed(x, 7, u[r])[0], 100, 1e-4)[3].inertia) for r in range(3)]
+    inertias = [float(B.kmeans_fit(x, B.kmeans_seed(x, 7, u[r])[0], 100, 1e-4)[3].inertia) for r in range(3)]
     assert km.inertia_ == min(inertias) and km.best_init_ == int(np.argmin(inertias))
     np.testing.assert_array_equal(CL.KMeans(7, n_init=3, seed=0, backend=B).fit_predict(x), km.labels_)
     with pytest.raises(ValueError, match="exceeds the 3 rows"):
@@ -204,7 +205,7 @@ def test_cli_round_trip(tmp_path, capsys):
 
 
 def test_emulation_runs_clean_under_sanitizers(tmp_path):
-    exe = E.build_main(tmp_path / "kmeans_emu_san", ("-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
+    exe = E.build_main("kmeans", tmp_path / "kmeans_emu_san", ("-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
     for args in ((), ("4099", "129", "33")):
         res = subprocess.run([str(exe), *args], capture_output=True, text=True)
         assert res.returncode == 0 and "checksum" in res.stdout and not res.stderr, res.stdout + res.stderr

@@ -1,23 +1,25 @@
 """PCA and the progression panel on the CPU: the float64 reference's own preconditions (eigengaps, the share of panel pixels it excludes), the host
-emulation of the kernel bodies (tests/hostemu/pca_emu.cpp) under the checks tests/test_gpu_pca.py applies to the kernels at the same shapes, every
+emulation of the kernel bodies (tests/hostemu/pca_emu.cpp),
+called through the shared analysis backend (tests/hostemu/analysis_emu.py), under the checks tests/test_gpu_pca.py applies to the kernels at the same shapes, every
 refusal, analysis.pca / analysis.render on the emulation, both command-line tools on synthetic clip_<i>.h5 files, and sklearn where it imports."""
 from __future__ import annotations
 
 import ctypes as C
 import subprocess
+import types
 from pathlib import Path
 
 import numpy as np
 import pytest
 
 from tests import pca_ref as R
-from tests.hostemu import pca_emu as E
+from tests.hostemu import analysis_emu as E
 from track_mjx_amd import hip
 from track_mjx_amd.analysis import pca as P
 
 ROOT = Path(__file__).resolve().parents[1]
 CASES = R.fit_cases(hip.PCA_ROWS_PER_WG)
-B = E.EmuBackend()
+B = E.B
 
 
 # ------------------------------------------------------------------------------------------------------------------ 1. the reference alone
@@ -60,9 +62,9 @@ def test_one_pass_variance_fails_the_offset_case():
 @pytest.mark.parametrize("case", CASES)
 def test_emu_fit_and_transform(case):
     x = R.case_data(*case)
-    mean, comp, var, info = E.fit(x)
+    mean, comp, var, info = B.fit(x)
     assert info.converged == 1 and info.sweeps <= 15
-    R.check_fit(x, mean, comp, var, E.transform(x, mean, comp[:R.top_k(*x.shape)]), case, "emulation")
+    R.check_fit(x, mean, comp, var, B.transform(x, mean, comp[:R.top_k(*x.shape)]), case, "emulation")
 
 
 def test_emu_row_stride():
@@ -72,57 +74,58 @@ def test_emu_row_stride():
     wide[:, 3:68] = x
     view = wide[:, 3:68]
     assert view.strides[0] == 4 * (65 + 5)
-    a, b = E.fit(view), E.fit(x)
+    a, b = B.fit(view), B.fit(x)
     for u, v in zip(a[:3], b[:3]):
         np.testing.assert_array_equal(u, v)
-    np.testing.assert_array_equal(E.transform(view, a[0], a[1][:4]), E.transform(x, b[0], b[1][:4]))
+    np.testing.assert_array_equal(B.transform(view, a[0], a[1][:4]), B.transform(x, b[0], b[1][:4]))
 
 
 def test_emu_degenerate_and_repeatable():
     x = np.tile(np.float32([1.5, -2.0, 7.0]), (10, 1))
-    mean, comp, var, info = E.fit(x)
+    mean, comp, var, info = B.fit(x)
     np.testing.assert_array_equal(var, 0)
     np.testing.assert_array_equal(comp, np.eye(3, dtype=np.float32))
     np.testing.assert_array_equal(mean, x[0])
-    assert np.isfinite(E.transform(x, mean, comp)).all()
+    assert np.isfinite(B.transform(x, mean, comp)).all()
     n, d = 5, 9                                        # n < d: d - n + 1 variances vanish
     x = R.make_data(n, d, 3.0, 2)
-    a, b = E.fit(x), E.fit(x.copy())
+    a, b = B.fit(x), B.fit(x.copy())
     assert (a[2][n - 1:] <= R.bound(d) * a[2][0]).all() and a[2][n - 2] > 1e-3 * a[2][0]
     for u, v in zip(a[:3], b[:3]):
         np.testing.assert_array_equal(u.view(np.uint32), v.view(np.uint32))
     bad = R.make_data(20, 4).copy()
     bad[3, 1] = np.nan
     with pytest.raises(ValueError, match="did not converge"):
-        E.fit(bad)
+        B.fit(bad)
 
 
 def test_emu_refusals():
     x = R.make_data(8, 4)
     with pytest.raises(ValueError, match="d = 129 exceeds the PCA limit of 128"):
-        E.fit(np.zeros((4, 129), np.float32))
+        B.fit(np.zeros((4, 129), np.float32))
     with pytest.raises(ValueError, match="n >= 2 rows .got 1."):
-        E.fit(x[:1])
+        B.fit(x[:1])
     with pytest.raises(ValueError, match="ldx = 3 is smaller than d = 4"):
-        E.fit(x, ldx=3)
-    mean, comp, _, _ = E.fit(x)
+        E.over("tmjx_pca_fit", ldx=3).fit(x)
+    mean, comp, _, _ = B.fit(x)
     with pytest.raises(ValueError, match="k = 5 components asked of d = 4"):
-        E.transform(x, mean, np.zeros((5, 4), np.float32))
+        B.transform(x, mean, np.zeros((5, 4), np.float32))
     with pytest.raises(ValueError, match="ldo = 1 is smaller than k = 2"):
-        E.transform(x, mean, comp[:2], ldo=1)
+        E.over("tmjx_pca_transform", ldo=1).transform(x, mean, comp[:2])
     with pytest.raises(ValueError, match="d = 129"):
-        E.workspace(10, 129)
+        E.workspace("tmjx_pca_workspace", 10, 129)
     p, st = R.panel_projections(), R.panel_style(96, 64)
     ok = dict(proj=p, k=3, frame_idx=[1], flags=[0], ymin=-1.0, ymax=1.0, window=5, style=st, width=96, height=64)
-    assert E.strips(**ok).shape == (1, 64, 96, 4)
+    assert B.strips(**ok).shape == (1, 64, 96, 4)
     for over, word in ((dict(k=9), "k = 9 curves"), (dict(k=0), "k = 0 curves"), (dict(ldp=2), "ldp = 2"), (dict(window=0), "window must be >= 1"),
                        (dict(ymax=-1.0), "ymax > ymin"), (dict(ymax=float("inf")), "finite"), (dict(width=0), "W and H"), (dict(T=0), "T must be >= 1"),
                        (dict(frame_idx=[]), "F must be >= 1"), (dict(width=12), "smaller than 3 x 3")):
+        args = {k: over.pop(k) for k in list(over) if k in ("ldp", "T")}      # (not arguments of the method: substituted in tmjx_plot_strips)
         with pytest.raises(ValueError, match=word):
-            E.strips(**dict(ok, **over))
+            E.over("tmjx_plot_strips", **args).strips(**dict(ok, **over))
     thin = P.strip_style(96, 64, line_half_width=0.0)
     with pytest.raises(ValueError, match="line_half_width"):
-        E.strips(**dict(ok, style=thin))
+        B.strips(**dict(ok, style=thin))
 
 
 def test_library_refuses_before_any_launch():
@@ -135,7 +138,7 @@ def test_library_refuses_before_any_launch():
     assert L.tmjx_pca_transform(one, 10, 4, 4, one, one, 5, one, 5, None) == -22 and b"k = 5" in L.tmjx_last_error()
     assert L.tmjx_pca_transform(one, 10, 4, 3, one, one, 2, one, 2, None) == -22 and b"ldx = 3" in L.tmjx_last_error()
     assert L.tmjx_pca_workspace(1, 4, C.byref(floats)) == -22 and L.tmjx_pca_workspace(10, 129, C.byref(floats)) == -22
-    assert L.tmjx_pca_workspace(2 * hip.PCA_ROWS_PER_WG + 1, 128, C.byref(floats)) == 0 and floats.value == E.workspace(2 * hip.PCA_ROWS_PER_WG + 1, 128)
+    assert L.tmjx_pca_workspace(2 * hip.PCA_ROWS_PER_WG + 1, 128, C.byref(floats)) == 0 and floats.value == E.workspace("tmjx_pca_workspace", 2 * hip.PCA_ROWS_PER_WG + 1, 128)
     st = R.panel_style(96, 64)
     assert L.tmjx_plot_strips(one, 12, 9, 9, one, one, 1, -1.0, 1.0, 5, C.byref(st), 96, 64, one, None) == -22 and b"k = 9" in L.tmjx_last_error()
     assert L.tmjx_plot_strips(one, 12, 3, 3, one, one, 1, 1.0, 1.0, 5, C.byref(st), 96, 64, one, None) == -22 and b"ymax > ymin" in L.tmjx_last_error()
@@ -160,7 +163,7 @@ def test_abi_declares_pca():
 def test_emu_panel(size, k, window):
     flags = np.zeros(len(R.PANEL_FRAMES), np.uint8)
     flags[-1] = 1
-    got = E.strips(R.panel_projections(), k, R.PANEL_FRAMES, flags, *R.PANEL_YLIM, window, R.panel_style(*size), *size)
+    got = B.strips(R.panel_projections(), k, R.PANEL_FRAMES, flags, *R.PANEL_YLIM, window, R.panel_style(*size), *size)
     R.check_panel(got, size, k, window, "emulation")
 
 
@@ -190,8 +193,9 @@ def test_pca_class_on_the_emulation():
         p.transform(x[:, :59])
     with pytest.raises(ValueError, match="2-D"):
         p.fit(x[0])
+    narrow = types.SimpleNamespace(asarray=B.asarray, to_numpy=B.to_numpy, fit=B.fit, transform=B.transform)      # a backend without the wide methods
     with pytest.raises(ValueError, match="d = 129"):
-        P.PCA(backend=B).fit(np.zeros((4, 129), np.float32))
+        P.PCA(backend=narrow).fit(np.zeros((4, 129), np.float32))
 
 
 def _rollouts(n_clips=3, T=9, Z=6, seed=3):
@@ -251,7 +255,7 @@ def test_progression_functions_on_the_emulation():
     panel = Rn.plot_pca_progression(proj, idx, n_components=3, window_size=5, size=(48, 32), terminated=term, backend=B)
     assert panel.shape == (70, 32, 48, 3) and panel.dtype == np.uint8 and Rn.MAX_FRAMES_PER_CALL == 64
     lo, hi = np.nanmin(proj[:, :3]) - 0.2, np.nanmax(proj[:, :3]) + 0.2      # the reference's y limits
-    one = E.strips(proj, 3, idx[60:], term[60:].astype(np.uint8), float(lo), float(hi), 5, P.strip_style(48, 32), 48, 32)[..., :3]
+    one = B.strips(proj, 3, idx[60:], term[60:].astype(np.uint8), float(lo), float(hi), 5, P.strip_style(48, 32), 48, 32)[..., :3]
     np.testing.assert_array_equal(panel[60:], one)
     np.testing.assert_array_equal(panel[13:26], panel[:13])
     with pytest.raises(ValueError, match="n_components = 9"):
@@ -332,7 +336,7 @@ def test_against_sklearn():
 
 def test_emulation_as_a_stand_alone_program_under_sanitizers(tmp_path):
     """The emulation's own main, built with AddressSanitizer and UBSan (a host program: no preload, no Python), runs clean."""
-    exe = E.build_main(tmp_path / "pca_emu", flags=("-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"))
+    exe = E.build_main("pca", tmp_path / "pca_emu", flags=("-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"))
     out = subprocess.run([str(exe)], capture_output=True, text=True)
     assert out.returncode == 0 and "checksum" in out.stdout and "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stdout + out.stderr
     assert out.stdout.count("sweeps") == 6

@@ -1,4 +1,5 @@
-"""Wide PCA (129 <= d <= 1024, block Jacobi) on the CPU: the host emulation of the kernel bodies (tests/hostemu/pca_wide_emu.cpp) under the
+"""Wide PCA (129 <= d <= 1024, block Jacobi) on the CPU: the host emulation of the kernel bodies (tests/hostemu/pca_wide_emu.cpp),
+called through the shared analysis backend (tests/hostemu/analysis_emu.py), under the
 checks tests/test_gpu_pca_wide.py applies to the kernels at the same shapes, the product library's refusals (no GPU is touched), forwarding of
 d <= 128 to the narrow path, repeatability, degenerate inputs, analysis.pca and both command-line tools on wide features, and the emulation as a
 stand-alone program under the sanitizers."""
@@ -6,14 +7,14 @@ from __future__ import annotations
 
 import ctypes as C
 import subprocess
+import types
 from pathlib import Path
 
 import numpy as np
 import pytest
 
 from tests import pca_ref as R
-from tests.hostemu import pca_emu as E
-from tests.hostemu import pca_wide_emu as W
+from tests.hostemu import analysis_emu as E
 from track_mjx_amd import hip
 from track_mjx_amd.analysis import pca as P
 
@@ -21,16 +22,16 @@ ROOT = Path(__file__).resolve().parents[1]
 # (n, d, offset, seed): the first wide size (a 1-column block and a bye); n < d (3 blocks and a bye); an uneven last block with a bye; an odd
 # count of full blocks; the offset-100 case a one-pass variance fails
 CASES = ((300, 129, 3.0, 0), (130, 192, 3.0, 0), (513, 257, 3.0, 0), (700, 320, 3.0, 0), (1500, 512, 100.0, 0))
-B = W.EmuWideBackend()
+B = E.B
 
 
 @pytest.mark.parametrize("case", CASES)
 def test_emu_fit_and_transform(case):
     x = R.case_data(*case)
-    mean, comp, var, info = W.fit_wide(x)
+    mean, comp, var, info = B.fit_wide(x)
     print(case, f"{info.sweeps} block sweeps, off / norm {info.off_rel:.2e}")
     assert info.converged == 1 and 1 <= info.sweeps <= 15
-    R.check_fit(x, mean, comp, var, W.transform_wide(x, mean, comp[:R.top_k(*x.shape)]), case, "emulation")
+    R.check_fit(x, mean, comp, var, B.transform_wide(x, mean, comp[:R.top_k(*x.shape)]), case, "emulation")
 
 
 def test_emu_transform_many_components_and_row_stride():
@@ -42,19 +43,18 @@ def test_emu_transform_many_components_and_row_stride():
     wide[:, 3:3 + d] = x
     view = wide[:, 3:3 + d]
     assert view.strides[0] == 4 * (d + 5)
-    a, b = W.fit_wide(view), W.fit_wide(x)
+    a, b = B.fit_wide(view), B.fit_wide(x)
     for u, v in zip(a[:3], b[:3]):
         np.testing.assert_array_equal(u.view(np.uint32), v.view(np.uint32))
     for k in (4, 16, 17, 70, d):
-        got = W.transform_wide(view, a[0], a[1][:k])
-        np.testing.assert_array_equal(got, W.transform_wide(x, a[0], a[1][:k]))
+        got = B.transform_wide(view, a[0], a[1][:k])
+        np.testing.assert_array_equal(got, B.transform_wide(x, a[0], a[1][:k]))
         want = R.transform(x, a[0], a[1][:k])
         assert np.abs(got - want).max() <= R.bound(d) * np.abs(want).max()
-    out = W._aligned(n * 9).reshape(n, 9)
-    out[:] = -5.0
+    out = np.full((n, 9), -5.0, np.float32)
     m, c = a[0], np.ascontiguousarray(a[1][:4])
-    assert W._lib().pwemu_transform(x.ctypes.data, n, d, d, m.ctypes.data, c.ctypes.data, 4, out.ctypes.data, 9) == 0
-    np.testing.assert_array_equal(out[:, :4], W.transform_wide(x, m, c))
+    E.over("tmjx_pca_transform_wide", out=out, ldo=9).transform_wide(x, m, c)
+    np.testing.assert_array_equal(out[:, :4], B.transform_wide(x, m, c))
     assert (out[:, 4:] == -5.0).all()
 
 
@@ -87,49 +87,49 @@ def test_workspace_grows_with_d_squared_only():
     assert L.tmjx_pca_wide_workspace(210_000, 1024, C.byref(floats)) == 0
     big = floats.value
     print(f"workspace of 210 000 x 1024: {4 * big / 2 ** 20:.1f} MiB")
-    assert 4 * big <= 256 * 2 ** 20 and big == W.workspace(210_000, 1024)
+    assert 4 * big <= 256 * 2 ** 20 and big == E.workspace("tmjx_pca_wide_workspace", 210_000, 1024)
     for n in (16 * hip.PCA_ROWS_PER_WG, 420_000, 2 ** 30):                 # the row count does not enter once there are 16 super-chunks
         assert L.tmjx_pca_wide_workspace(n, 1024, C.byref(floats)) == 0 and floats.value == big
     assert L.tmjx_pca_wide_workspace(210_000, 512, C.byref(floats)) == 0 and 3.9 < big / floats.value < 4.1
     for n, d in ((2, 129), (300, 129), (130, 192), (4097, 257)):
-        assert L.tmjx_pca_wide_workspace(n, d, C.byref(floats)) == 0 and floats.value == W.workspace(n, d)
-    assert L.tmjx_pca_wide_workspace(600, 128, C.byref(floats)) == 0 and floats.value == E.workspace(600, 128)      # d <= 128: the narrow layout
+        assert L.tmjx_pca_wide_workspace(n, d, C.byref(floats)) == 0 and floats.value == E.workspace("tmjx_pca_wide_workspace", n, d)
+    assert L.tmjx_pca_wide_workspace(600, 128, C.byref(floats)) == 0 and floats.value == E.workspace("tmjx_pca_workspace", 600, 128)      # d <= 128: the narrow layout
 
 
 def test_emu_refusals():
     x = R.make_data(8, 130)
     with pytest.raises(ValueError, match="d = 1025 exceeds the wide PCA limit of 1024"):
-        W.fit_wide(np.zeros((4, 1025), np.float32))
+        B.fit_wide(np.zeros((4, 1025), np.float32))
     with pytest.raises(ValueError, match="n >= 2 rows .got 1."):
-        W.fit_wide(x[:1])
+        B.fit_wide(x[:1])
     with pytest.raises(ValueError, match="ldx = 129 is smaller than d = 130"):
-        W.fit_wide(x, ldx=129)
+        E.over("tmjx_pca_fit_wide", ldx=129).fit_wide(x)
     mean = np.zeros(130, np.float32)
     with pytest.raises(ValueError, match="k = 131 components asked of d = 130"):
-        W.transform_wide(x, mean, np.zeros((131, 130), np.float32))
+        B.transform_wide(x, mean, np.zeros((131, 130), np.float32))
     with pytest.raises(ValueError, match="ldo = 1 is smaller than k = 2"):
-        W.transform_wide(x, mean, np.zeros((2, 130), np.float32), ldo=1)
+        E.over("tmjx_pca_transform_wide", ldo=1).transform_wide(x, mean, np.zeros((2, 130), np.float32))
     with pytest.raises(ValueError, match="d = 1025"):
-        W.workspace(10, 1025)
+        E.workspace("tmjx_pca_wide_workspace", 10, 1025)
 
 
 def test_narrow_forwarding_gives_the_narrow_bits():
     case = (129, 65, 3.0, 0)
     x = R.case_data(*case)
-    a, b = W.fit_wide(x), E.fit(x)
+    a, b = B.fit_wide(x), B.fit(x)
     for u, v in zip(a[:3], b[:3]):
         np.testing.assert_array_equal(u.view(np.uint32), v.view(np.uint32))
-    assert a[3].sweeps == b[3].sweeps and W.workspace(129, 65) == E.workspace(129, 65)
-    np.testing.assert_array_equal(W.transform_wide(x, a[0], a[1][:4]).view(np.uint32), E.transform(x, b[0], b[1][:4]).view(np.uint32))
+    assert a[3].sweeps == b[3].sweeps and E.workspace("tmjx_pca_wide_workspace", 129, 65) == E.workspace("tmjx_pca_workspace", 129, 65)
+    np.testing.assert_array_equal(B.transform_wide(x, a[0], a[1][:4]).view(np.uint32), B.transform(x, b[0], b[1][:4]).view(np.uint32))
 
 
 def test_two_calls_give_the_same_bits():
     x = R.case_data(*CASES[2])
-    a, b = W.fit_wide(x), W.fit_wide(x.copy())
+    a, b = B.fit_wide(x), B.fit_wide(x.copy())
     for u, v in zip(a[:3], b[:3]):
         np.testing.assert_array_equal(u.view(np.uint32), v.view(np.uint32))
     assert a[3].sweeps == b[3].sweeps
-    p = [W.transform_wide(x, a[0], a[1][:4]) for _ in range(2)]
+    p = [B.transform_wide(x, a[0], a[1][:4]) for _ in range(2)]
     np.testing.assert_array_equal(p[0].view(np.uint32), p[1].view(np.uint32))
 
 
@@ -137,21 +137,21 @@ def test_degenerate_inputs():
     d = 130
     row = np.linspace(-3.0, 7.0, d).astype(np.float32)
     x = np.tile(row, (10, 1))
-    mean, comp, var, info = W.fit_wide(x)
+    mean, comp, var, info = B.fit_wide(x)
     np.testing.assert_array_equal(var, 0)
     np.testing.assert_array_equal(comp, np.eye(d, dtype=np.float32))
     np.testing.assert_array_equal(mean, row)
     assert info.converged == 1 and info.sweeps == 0
-    assert np.isfinite(W.transform_wide(x, mean, comp)).all()
+    assert np.isfinite(B.transform_wide(x, mean, comp)).all()
     p = P.PCA(2, backend=B).fit(x)
     np.testing.assert_array_equal(p.explained_variance_ratio_, 0)
     bad = R.make_data(40, d).copy()
     bad[3, 77] = np.nan
     with pytest.raises(ValueError, match="non-finite"):
-        W.fit_wide(bad)
+        B.fit_wide(bad)
     bad[3, 77] = np.inf
     with pytest.raises(ValueError, match="non-finite"):
-        W.fit_wide(bad)
+        B.fit_wide(bad)
 
 
 # ------------------------------------------------------------------------------------------------------------------ Python and the tools
@@ -181,7 +181,7 @@ def test_pca_class_on_a_strided_wide_slice():
 
 
 def test_a_backend_without_the_wide_methods_behaves_as_before():
-    old = E.EmuBackend()
+    old = types.SimpleNamespace(asarray=B.asarray, to_numpy=B.to_numpy, fit=B.fit, transform=B.transform)
     assert not hasattr(old, "fit_wide")
     with pytest.raises(ValueError, match="d = 129 exceeds the PCA limit of 128"):
         P.PCA(backend=old).fit(np.zeros((4, 129), np.float32))
@@ -250,7 +250,7 @@ def test_abi_declares_the_wide_entry_points():
 
 def test_emulation_as_a_stand_alone_program_under_sanitizers(tmp_path):
     """The emulation's own main, built with AddressSanitizer and UBSan (a host program: no preload, no Python), runs clean at 130 x 192."""
-    exe = W.build_main(tmp_path / "pca_wide_emu", flags=("-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"))
+    exe = E.build_main("pca_wide", tmp_path / "pca_wide_emu", flags=("-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"))
     out = subprocess.run([str(exe), "130", "192"], capture_output=True, text=True)
     assert out.returncode == 0 and "checksum" in out.stdout and "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stdout + out.stderr
     assert "130 x 192" in out.stdout and "block sweeps" in out.stdout

@@ -1,4 +1,5 @@
-"""The linear readout on the CPU: the host emulation of the kernel bodies (tests/hostemu/readout_emu.cpp) under the checks tests/test_gpu_readout.py
+"""The linear readout on the CPU: the host emulation of the kernel bodies (tests/hostemu/readout_emu.cpp),
+called through the shared analysis backend (tests/hostemu/analysis_emu.py), under the checks tests/test_gpu_readout.py
 applies to the kernels (the float64 reference of tests/readout_ref.py at the first four cases, the bit-level properties, the refusals), the product
 library's refusals (no GPU is touched), analysis.readout on synthetic roll-outs through the emulation backend, the command-line tool, and the
 emulation as a stand-alone program under the sanitizers."""
@@ -14,13 +15,12 @@ import pytest
 
 from tests import pca_ref as PR
 from tests import readout_ref as R
-from tests.hostemu import pca_emu as NE
-from tests.hostemu import readout_emu as E
+from tests.hostemu import analysis_emu as E
 from track_mjx_amd import hip
 from track_mjx_amd.analysis import readout as RO
 
 ROOT = Path(__file__).resolve().parents[1]
-B = E.EmuReadoutBackend()
+B = E.B
 MID = R.CPU_CASES[1]      # 513 + 129 rows, 129 -> 38, three penalties: the case of the bit-level checks
 
 
@@ -39,11 +39,11 @@ def test_emu_against_float64(case):
     (mean_x, comp, var, mean_y, z), w, preds, r2, _ = run(case)
     R.check_case(case, w, preds, r2, "emulation")
     xtr, ytr = R.case_data(case)[:2]
-    pm, pc, pv, _ = E.pca_fit_wide(xtr)                               # the PCA part: tmjx_pca_fit_wide's bits
+    pm, pc, pv, _ = B.fit_wide(xtr)                               # the PCA part: tmjx_pca_fit_wide's bits
     for u, v in ((mean_x, pm), (comp, pc), (var, pv)):
         np.testing.assert_array_equal(bits(u), bits(v))
     if case[2] <= hip.PCA_MAX_D:                                     # and, up to 128 features, the narrow fit's
-        for u, v in zip((mean_x, comp, var), NE.fit(xtr)[:3]):
+        for u, v in zip((mean_x, comp, var), B.fit(xtr)[:3]):
             np.testing.assert_array_equal(bits(u), bits(v))
     m64 = ytr.astype(np.float64).mean(0)
     assert (np.abs(mean_y - m64) <= 2.0 ** -24 * np.abs(m64)).all()  # float64 sums, rounded once
@@ -52,11 +52,11 @@ def test_emu_against_float64(case):
 def test_two_calls_give_the_same_bits():
     xtr, ytr, xte, yte = R.case_data(MID)
     (mean_x, comp, var, mean_y, z), w, _, _, (sse, sst) = run(MID)
-    again = E.readout_fit(xtr.copy(), ytr.copy())
+    again = B.readout_fit(xtr.copy(), ytr.copy())
     np.testing.assert_array_equal(bits(again[4]), bits(z))
-    w2 = E.readout_weights(comp, var, z, R.lambdas_of(var, R.CASES[MID]))
+    w2 = B.readout_weights(comp, var, z, R.lambdas_of(var, R.CASES[MID]))
     np.testing.assert_array_equal(bits(w2), bits(w))
-    sse2, sst2 = E.readout_score(xte, yte, mean_x, w, mean_y)
+    sse2, sst2 = B.readout_score(xte, yte, mean_x, w, mean_y)
     np.testing.assert_array_equal(bits(sse2), bits(sse))
     np.testing.assert_array_equal(bits(sst2), bits(sst))
 
@@ -72,15 +72,15 @@ def test_row_strides_give_the_dense_bits_and_ldo_is_respected():
     (mean_x, comp, var, mean_y, z), w, preds, _, (sse, sst) = run(MID)
     xs, ys, xts, yts = strided(xtr, 3, 2), strided(ytr, 1, 6), strided(xte, 4, 1), strided(yte, 2, 2)
     assert B.asarray(xs) is xs and xs.strides[0] == 4 * (MID[2] + 5)               # no copy
-    got = E.readout_fit(xs, ys)
+    got = B.readout_fit(xs, ys)
     for u, v in zip(got[:5], (mean_x, comp, var, mean_y, z)):
         np.testing.assert_array_equal(bits(u), bits(v))
-    sse2, sst2 = E.readout_score(xts, yts, mean_x, w, mean_y)
+    sse2, sst2 = B.readout_score(xts, yts, mean_x, w, mean_y)
     np.testing.assert_array_equal(bits(sse2), bits(sse))
     np.testing.assert_array_equal(bits(sst2), bits(sst))
     m = MID[3]
     out = np.full((xte.shape[0], m + 3), -5.0, np.float32)
-    E.readout_predict(xts, mean_x, w[1], mean_y, out=out[:, :m])
+    E.over("tmjx_readout_predict", out=out[:, :m], ldo=m + 3).readout_predict(xts, mean_x, w[1], mean_y)
     np.testing.assert_array_equal(bits(out[:, :m]), bits(preds[1]))
     assert (out[:, m:] == -5.0).all()
 
@@ -92,7 +92,7 @@ def test_predict_reproduces_the_score_and_one_penalty_equals_its_row():
         host_sse, host_sst = R.sse_sst(yte, preds[i])
         assert (np.abs(sse[i] - host_sse) <= R.FLOOR * host_sse).all(), np.abs(sse[i] / host_sse - 1).max()
         assert (np.abs(sst - host_sst) <= R.FLOOR * host_sst).all()
-        one = E.readout_score(xte, yte, mean_x, w[i:i + 1], mean_y)
+        one = B.readout_score(xte, yte, mean_x, w[i:i + 1], mean_y)
         np.testing.assert_array_equal(bits(one[0][0]), bits(sse[i]))
         np.testing.assert_array_equal(bits(one[1]), bits(sst))
 
@@ -111,40 +111,48 @@ REFUSALS_FIT = (({"d": 0}, "d must be >= 1 .got 0."), ({"d": 1025, "ldx": 1025},
                 ({"ldy": 2}, "ldy = 2 is smaller than m = 3"), ({"misalign": True}, "16-byte aligned"))
 
 
-def test_emu_refusals():
+@pytest.mark.parametrize("library", ["emulation", "product"])
+def test_fit_refusals_of_both_libraries(library):
+    """The same marshalling and the same substitutes against the emulation and against the product library (which refuses before any launch)."""
     x, y = PR.make_data(8, 12), PR.make_data(8, 3, seed=1)
+    on = B if library == "emulation" else E.product()
     for over, msg in REFUSALS_FIT:
         with pytest.raises(ValueError, match=msg):
-            E.readout_fit(x, y, **over)
-    mean_x, comp, var, mean_y, z, _ = E.readout_fit(x, y)
+            E.over("tmjx_readout_fit", on=on, **over).readout_fit(x, y)
+
+
+def test_emu_refusals():
+    x, y = PR.make_data(8, 12), PR.make_data(8, 3, seed=1)
+    mean_x, comp, var, mean_y, z, _ = B.readout_fit(x, y)
     for lam, msg in (([0.0], r"lambda\[0\] = 0"), ([1.0, -2.0], r"lambda\[1\] = -2"), ([float("nan")], r"lambda\[0\] = .*nan"), ([float("inf")], r"lambda\[0\] = inf")):
         with pytest.raises(ValueError, match=msg + ".* must be finite and > 0"):
-            E.readout_weights(comp, var, z, lam)
+            B.readout_weights(comp, var, z, lam)
     with pytest.raises(ValueError, match="n_lambda = 0 penalties: a call takes 1 .. 16"):
-        E.readout_weights(comp, var, z, [])
+        B.readout_weights(comp, var, z, [])
     with pytest.raises(ValueError, match="n_lambda = 17 penalties"):
-        E.readout_weights(comp, var, z, np.ones(17))
-    w = E.readout_weights(comp, var, z, [0.1, 1.0])
+        B.readout_weights(comp, var, z, np.ones(17))
+    w = B.readout_weights(comp, var, z, [0.1, 1.0])
     with pytest.raises(ValueError, match="a prediction needs n >= 1 rows .got 0."):
-        E.readout_predict(x, mean_x, w[0], mean_y, n=0)
+        E.over("tmjx_readout_predict", n=0).readout_predict(x, mean_x, w[0], mean_y)
     with pytest.raises(ValueError, match="ldo = 2 is smaller than m = 3"):
-        E.readout_predict(x, mean_x, w[0], mean_y, ldo=2)
+        E.over("tmjx_readout_predict", ldo=2).readout_predict(x, mean_x, w[0], mean_y)
     with pytest.raises(ValueError, match="ldx = 11 is smaller than d = 12"):
-        E.readout_predict(x, mean_x, w[0], mean_y, ldx=11)
+        E.over("tmjx_readout_predict", ldx=11).readout_predict(x, mean_x, w[0], mean_y)
     with pytest.raises(ValueError, match="a readout score needs n >= 2 rows .got 1."):
-        E.readout_score(x, y, mean_x, w, mean_y, n=1)
+        E.over("tmjx_readout_score", n=1).readout_score(x, y, mean_x, w, mean_y)
     with pytest.raises(ValueError, match="ldy = 2 is smaller than m = 3"):
-        E.readout_score(x, y, mean_x, w, mean_y, ldy=2)
+        E.over("tmjx_readout_score", ldy=2).readout_score(x, y, mean_x, w, mean_y)
     with pytest.raises(ValueError, match="n_lambda = 17"):
-        E.readout_score(x, y, mean_x, w, mean_y, n_lambda=17)
+        E.over("tmjx_readout_score", n_lambda=17).readout_score(x, y, mean_x, w, mean_y)
     with pytest.raises(ValueError, match="16-byte aligned"):
-        E.readout_score(x, y, mean_x, w, mean_y, misalign=True)
+        E.over("tmjx_readout_score", misalign=True).readout_score(x, y, mean_x, w, mean_y)
     with pytest.raises(ValueError, match="n_lambda = 0 penalties"):
-        E.readout_score(x, y, mean_x, w, mean_y, n_lambda=0)
+        E.over("tmjx_readout_score", n_lambda=0).readout_score(x, y, mean_x, w, mean_y)
     with pytest.raises(ValueError, match="ldx = 11 is smaller than d = 12"):
-        E.readout_score(x, y, mean_x, w, mean_y, ldx=11)
-    for call in (lambda **k: E.readout_predict(x, mean_x, w[0], mean_y, **k), lambda **k: E.readout_score(x, y, mean_x, w, mean_y, **k),
-                 lambda **k: E.readout_weights(comp, var, z, [0.1, 1.0], **k)):
+        E.over("tmjx_readout_score", ldx=11).readout_score(x, y, mean_x, w, mean_y)
+    for call in (lambda **k: E.over("tmjx_readout_predict", **k).readout_predict(x, mean_x, w[0], mean_y),
+                 lambda **k: E.over("tmjx_readout_score", **k).readout_score(x, y, mean_x, w, mean_y),
+                 lambda **k: E.over("tmjx_readout_weights", **k).readout_weights(comp, var, z, [0.1, 1.0])):
         with pytest.raises(ValueError, match="d must be >= 1 .got 0."):
             call(d=0)
         with pytest.raises(ValueError, match="d = 1025 exceeds the readout limit of 1024"):
@@ -154,22 +162,22 @@ def test_emu_refusals():
         with pytest.raises(ValueError, match="m = 513 exceeds the readout limit of 512"):
             call(m=513)
     with pytest.raises(ValueError, match=r"lambda\[0\] = 1e-50 must be finite and > 0 as a float32"):      # (it is rounded to float32: 0)
-        E.readout_weights(comp, var, z, [1e-50])
+        B.readout_weights(comp, var, z, [1e-50])
     with pytest.raises(ValueError, match=r"lambda\[0\] = 1e\+39 must be finite and > 0 as a float32"):
-        E.readout_weights(comp, var, z, [1e39])
-    L, info, p = E._lib(), hip.PcaInfo(), x.ctypes.data
-    assert L.remu_fit(p, 8, 12, 12, None, 3, 3, p, p, p, p, p, p, C.byref(info)) != 0 and b"null argument" in L.pemu_last_error()
-    assert L.remu_predict(p, 8, 12, 12, p, None, p, 3, p, 3) != 0 and b"null argument" in L.pemu_last_error()
-    assert L.remu_score(p, 8, 12, 12, p, 3, 3, p, p, p, 2, None, p, p) != 0 and b"null argument" in L.pemu_last_error()
-    assert L.remu_workspace(8, 12, 3, 2, None) != 0 and b"null argument" in L.pemu_last_error()
+        B.readout_weights(comp, var, z, [1e39])
+    L, info, p = E.lib(), hip.PcaInfo(), x.ctypes.data
+    assert L.tmjx_readout_fit(p, 8, 12, 12, None, 3, 3, p, p, p, p, p, p, C.byref(info), None) != 0 and b"null argument" in L.tmjx_last_error()
+    assert L.tmjx_readout_predict(p, 8, 12, 12, p, None, p, 3, p, 3, None) != 0 and b"null argument" in L.tmjx_last_error()
+    assert L.tmjx_readout_score(p, 8, 12, 12, p, 3, 3, p, p, p, 2, None, p, p, None) != 0 and b"null argument" in L.tmjx_last_error()
+    assert L.tmjx_readout_workspace(8, 12, 3, 2, None) != 0 and b"null argument" in L.tmjx_last_error()
     bad = x.copy()
     bad[3, 5] = np.nan
     with pytest.raises(ValueError, match="did not converge|non-finite"):       # the PCA part's refusal passes through
-        E.readout_fit(bad, y)
+        B.readout_fit(bad, y)
     wide_bad = PR.make_data(40, 130).copy()
     wide_bad[3, 77] = np.nan
     with pytest.raises(ValueError, match="tmjx_pca_fit_wide: the covariance is non-finite"):
-        E.readout_fit(wide_bad, PR.make_data(40, 3, seed=1))
+        B.readout_fit(wide_bad, PR.make_data(40, 3, seed=1))
 
 
 def test_library_refuses_before_any_launch():
@@ -215,7 +223,7 @@ def test_library_refuses_before_any_launch():
         assert L.tmjx_readout_workspace(*args, C.byref(floats)) == -22 and word in L.tmjx_last_error()
     assert L.tmjx_readout_workspace(8, 12, 3, 2, None) == -22
     for args in ((8, 12, 3, 2), (300, 60, 5, 1), (513, 129, 38, 3), (4200, 257, 130, 2), (210_000, 1024, 74, 8), (1_000_000, 1024, 512, 16)):
-        assert L.tmjx_readout_workspace(*args, C.byref(floats)) == 0 and floats.value == E.workspace(*args) and floats.value % 4 == 0
+        assert L.tmjx_readout_workspace(*args, C.byref(floats)) == 0 and floats.value == E.workspace("tmjx_readout_workspace", *args) and floats.value % 4 == 0
     print(f"workspace of 1 000 000 x 1024 -> 512 under 16 penalties: {4 * floats.value / 2 ** 20:.0f} MiB")
     assert 4 * floats.value <= 512 * 2 ** 20
 
@@ -229,14 +237,14 @@ def test_workspace_of_n_rows_covers_every_smaller_call():
     ns = (2, 255, 256, 257, 4095, 4096, 4097, 4352, 4353, 8192, 8193, 8448, 12_289, 57_600, 57_601)
     smaller = sorted({2, *(256 * k for k in range(1, 227)), *(256 * k + 1 for k in range(1, 226))})
     for d, m, nl in ((1, 512, 1), (4, 512, 1), (25, 512, 16), (128, 74, 8), (129, 38, 3), (1024, 74, 8), (1024, 512, 16)):
-        ends = [(n2, max(E.extents(n2, d, m, nl))) for n2 in smaller]
+        ends = [(n2, max(E.readout_extents(n2, d, m, nl))) for n2 in smaller]
         for n in ns:
-            have = E.workspace(n, d, m, nl)
+            have = E.workspace("tmjx_readout_workspace", n, d, m, nl)
             assert L.tmjx_readout_workspace(n, d, m, nl, C.byref(floats)) == 0 and floats.value == have
             worst = max((e, n2) for n2, e in ends if n2 <= n)
             assert have >= worst[0], f"workspace({n}, {d}, {m}, {nl}) = {have} floats, a call of {worst[1]} rows reaches {worst[0]}"
-    fit_end, score_end = E.extents(4096, 1, 512, 1)      # the case that showed it: 17 chunks sized, 16 scored
-    assert E.workspace(4352, 1, 512, 1) >= score_end > E.extents(4352, 1, 512, 1)[0] and fit_end <= score_end
+    fit_end, score_end = E.readout_extents(4096, 1, 512, 1)      # the case that showed it: 17 chunks sized, 16 scored
+    assert E.workspace("tmjx_readout_workspace", 4352, 1, 512, 1) >= score_end > E.readout_extents(4352, 1, 512, 1)[0] and fit_end <= score_end
 
 
 @pytest.mark.parametrize("d", (1, 4, 130))
@@ -246,19 +254,19 @@ def test_calls_of_fewer_rows_stay_inside_a_workspace_of_more(d):
     m, rng = 512 if d < 130 else 40, np.random.default_rng(5)
     x = PR.make_data(4096, d, 3.0, 4)
     y = (x[:, :1] * rng.standard_normal(m) + rng.standard_normal((4096, m))).astype(np.float32)
-    own = E.readout_fit(x, y)
-    got = E.readout_fit(x, y, ws_rows=4352)
+    own = B.readout_fit(x, y)
+    got = E.over("tmjx_readout_fit", ws_rows=4352).readout_fit(x, y)
     for u, v in zip(got[:5], own[:5]):
         np.testing.assert_array_equal(bits(u), bits(v))
     mean_x, comp, var, mean_y, z, _ = own
-    w = E.readout_weights(comp, var, z, [float(var.sum()) / d])
-    sse, sst = E.readout_score(x, y, mean_x, w, mean_y)
-    sse2, sst2 = E.readout_score(x, y, mean_x, w, mean_y, ws_rows=4352)
+    w = B.readout_weights(comp, var, z, [float(var.sum()) / d])
+    sse, sst = B.readout_score(x, y, mean_x, w, mean_y)
+    sse2, sst2 = E.over("tmjx_readout_score", ws_rows=4352).readout_score(x, y, mean_x, w, mean_y)
     np.testing.assert_array_equal(bits(sse2), bits(sse))
     np.testing.assert_array_equal(bits(sst2), bits(sst))
     if d < 130:      # the guard does see a buffer that is too small (at d = 130 the fit's part is the larger one even for 256 rows)
         with pytest.raises(AssertionError, match="wrote behind its workspace"):
-            E.readout_score(x, y, mean_x, w, mean_y, ws_rows=256)
+            E.over("tmjx_readout_score", ws_rows=256).readout_score(x, y, mean_x, w, mean_y)
 
 
 def test_abi_declares_the_readout_entry_points():
@@ -277,7 +285,7 @@ def test_abi_declares_the_readout_entry_points():
 def test_emulation_as_a_stand_alone_program_under_sanitizers(tmp_path):
     """The emulation's own main, built with AddressSanitizer and UBSan (a host program: no preload, no Python), runs clean on a strided 300 x 140 -> 70
     problem with a ragged score block."""
-    exe = E.build_main(tmp_path / "readout_emu", flags=("-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"))
+    exe = E.build_main("readout", tmp_path / "readout_emu", flags=("-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"))
     out = subprocess.run([str(exe)], capture_output=True, text=True)
     assert out.returncode == 0 and "checksum" in out.stdout and "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stdout + out.stderr
     assert "300 x 140 -> 70" in out.stdout

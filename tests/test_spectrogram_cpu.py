@@ -1,4 +1,5 @@
-"""CPU: the spectrogram kernel bodies (csrc/spectrogram_core.h) compiled into the host emulation (tests/hostemu/spectrogram_emu.cpp) against the
+"""CPU: the spectrogram kernel bodies (csrc/spectrogram_core.h) compiled into the host emulation (tests/hostemu/spectrogram_emu.cpp),
+called through the shared analysis backend (tests/hostemu/analysis_emu.py), against the
 float64 reference (tests/spectrogram_ref.py): the reference against analysis first, the float32 numpy restatement alone against the derived bound
 (and three wrong variants of it that must break it), the emulation at every case, the bit-level properties, the refusals, the planted rhythm, the
 command-line tool, and the emulation as a stand-alone program under AddressSanitizer and UBSan.  tests/test_gpu_spectrogram.py runs the same checks
@@ -11,10 +12,10 @@ import numpy as np
 import pytest
 
 from tests import spectrogram_ref as R
-from tests.hostemu import spectrogram_emu as E
+from tests.hostemu import analysis_emu as E
 from track_mjx_amd import hip
 
-B = E.EmuSpectrogramBackend
+B = E.B
 CASES = [pytest.param(R.EDGE, True, False, id="edge"), pytest.param(R.EDGE, False, False, id="edge-no-detrend"), pytest.param(R.EDGE, True, True, id="edge-log"),
          pytest.param(R.F1, True, False, id="F1"), pytest.param(R.F64, True, False, id="F64"), pytest.param(R.PRODUCT, True, False, id="product")]
 
@@ -93,31 +94,32 @@ def test_refusals_leave_out_untouched():
 
     def call(**kw):
         a = dict(seq_start=seq, offset=offset, radius=radius)
-        a.update({k: kw.pop(k) for k in list(kw) if k in a})
-        return E.spectrogram(x, a["seq_start"], bank, a["offset"], a["radius"], out=out, **kw)
+        a.update({k: kw.pop(k) for k in list(kw) if k in a and kw[k] is not None})      # (None: a null pointer, substituted below)
+        own = {k: kw.pop(k) for k in list(kw) if k in ("log", "floor")}      # (the method's own arguments; the rest substitutes tmjx_spectrogram's)
+        return E.over("tmjx_spectrogram", **kw).spectrogram(x, a["seq_start"], bank, a["offset"], a["radius"], out=out, **own)
     big = np.array(radius)
     big[0] = 4097
     off2 = np.array(offset)
     off2[1] += 3
-    for kw, word in ((dict(n=0), "n must be >= 1"), (dict(Cn=0), "C must be >= 1"), (dict(Cn=1025, ldx=1025), "limit of 1024"), (dict(F=0), "F must be >= 1"),
+    for kw, word in ((dict(n=0), "n must be >= 1"), (dict(C=0), "C must be >= 1"), (dict(C=1025, ldx=1025), "limit of 1024"), (dict(F=0), "F must be >= 1"),
                      (dict(F=65), "limit of 64"), (dict(S=0), "S must be >= 1"), (dict(ldx=2), "ldx = 2"), (dict(ldo=5), "ldo = 5"),
                      (dict(radius=big), "outside 0 .. 4096"), (dict(offset=off2), "does not follow"), (dict(seq_start=[1, 37, 187]), r"seq_start\[0\] = 1"),
-                     (dict(seq_start=[0, 37, 37]), "strictly increasing"), (dict(seq_start=[0, 37, 186]), r"seq_start\[S\] = 186"), (dict(kind=2), "output_kind = 2"),
+                     (dict(seq_start=[0, 37, 37]), "strictly increasing"), (dict(seq_start=[0, 37, 186]), r"seq_start\[S\] = 186"), (dict(output_kind=2), "output_kind = 2"),
                      (dict(log=True, floor=0.0), "log_floor"), (dict(log=True, floor=float("nan")), "log_floor"), (dict(misalign=True), "16-byte"),
-                     *[(dict(null=(name,)), "null") for name in ("x", "seq_start", "bank", "offset", "radius", "out", "coverage", "workspace")]):
+                     *[({name: None}, "null") for name in ("x", "seq_start", "bank", "offset", "radius", "out", "coverage", "workspace")]):
         with pytest.raises(ValueError, match=word):
             call(**kw)
         assert (out == -7.25).all(), kw
     for kw, word in ((dict(freqs=[26.0]), "rate / 2"), (dict(freqs=[0.0]), "rate / 2"), (dict(freqs=[float("nan")]), "rate / 2"), (dict(freqs=[0.02]), "limit of 4096"),
                      (dict(freqs=[5.0], omega0=0.0), "omega0"), (dict(freqs=[5.0], support=-1.0), "support"), (dict(freqs=[5.0], rate=0.0), "rate"),
-                     (dict(freqs=[5.0] * 65), "limit of 64"), (dict(freqs=[5.0], F=0), "F must be >= 1"), (dict(freqs=[5.0], null=True), "null")):
+                     (dict(freqs=[5.0] * 65), "limit of 64"), (dict(freqs=[5.0], over=dict(F=0)), "F must be >= 1"), (dict(freqs=[5.0], over=dict(freqs=None)), "null")):
         kw = dict(kw)
         with pytest.raises(ValueError, match=word):
-            E.wavelet_bank(kw.pop("rate", 50.0), kw.pop("freqs"), **kw)
+            E.over("tmjx_wavelet_bank_size", **kw.pop("over", {})).wavelet_bank(kw.pop("rate", 50.0), kw.pop("freqs"), **kw)
 
 
 def test_workspace_does_not_scale_with_n():
-    assert E.workspace(210000, 67, 25, 840) == E.workspace(1000, 67, 25, 840) <= 840 * 67 + 2 * 25 * 8194 + 4096
+    assert E.workspace("tmjx_spectrogram_workspace", 210000, 67, 25, 840) == E.workspace("tmjx_spectrogram_workspace", 1000, 67, 25, 840) <= 840 * 67 + 2 * 25 * 8194 + 4096
 
 
 def test_spectrogram_class_argument_checks():
@@ -146,7 +148,7 @@ def test_cli_round_trip(tmp_path, capsys):
 
 
 def test_emulation_runs_clean_under_sanitizers(tmp_path):
-    exe = E.build_main(tmp_path / "spectrogram_emu_san", ("-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
+    exe = E.build_main("spectrogram", tmp_path / "spectrogram_emu_san", ("-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
     for args in ((), ("1", "1", "1", "0", "1"), ("67", "3", "0", "1", "249", "5"), ("130", "2", "1", "0", "1", "64", "65"), ("4", "64", "1", "0", "300")):
         res = subprocess.run([str(exe), *args], capture_output=True, text=True)
         assert res.returncode == 0 and "checksum" in res.stdout and not res.stderr, res.stdout + res.stderr

@@ -1,0 +1,348 @@
+"""The analysis entry points of the C-ABI (include/tmjx.h: tmjx_pca_*, tmjx_plot_strips, tmjx_readout_*, tmjx_kmeans_*, tmjx_hmm_*,
+tmjx_wavelet_bank*, tmjx_spectrogram*) as methods on arrays.
+
+`Backend` marshals every call once, against a small provider of arrays: what differs between the device and a host is how an array is uploaded,
+allocated, addressed and read back, not which arguments go where.  `HipBackend` is the backend on torch device tensors (`TorchArrays`), the one
+the product uses; the CPU tests run the same methods on numpy arrays against the host emulation of the kernels (tests/hostemu/), so the
+marshalling below is executed without a GPU.
+
+A provider has: `lib` (the library handle), `check(rc, what)` (raises on a non-zero return code), `rows(x)` (a 2-D float32 array whose columns are
+contiguous, a row stride kept), `upload(a, dtype, copy=False)`, `empty(shape, dtype, zero=False)`, `host_empty(shape, dtype)` (for what a host
+function fills), `workspace(floats)`, `ptr(a)`, `ld(a)` (the row stride in elements), `dense_columns(a)`, `stream()`, `guard()` (a context manager
+around a launch), `to_numpy(a)` and `sync()`."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from .. import hip as _hip
+
+_I32P, _F64P = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+f32, f64, i32 = np.float32, np.float64, np.int32
+
+
+class Backend:
+    """x (and y, proj) come from `asarray`; every other input is a numpy array.  Which outputs are numpy and which stay the provider's arrays is
+    said per method."""
+
+    def __init__(self, arrays):
+        self._p = arrays
+
+    def _call(self, name, *args):
+        with self._p.guard():
+            self._p.check(getattr(self._p.lib, name)(*args), name)
+
+    def _workspace(self, name, *dims):
+        """The workspace `name` (a tmjx_*_workspace entry) reports for `dims`."""
+        floats = C.c_int64(0)
+        self._p.check(getattr(self._p.lib, name)(*dims, C.byref(floats)), name)
+        return self._p.workspace(int(floats.value))
+
+    def asarray(self, x):
+        """A 2-D float32 array of the provider whose columns are contiguous; a row stride (a column slice of a wider buffer) is kept."""
+        shape = tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
+        if len(shape) != 2:
+            raise ValueError(f"expected a 2-D array [n, d], got shape {shape}")
+        return self._p.rows(x)
+
+    def to_numpy(self, t):
+        return self._p.to_numpy(t)
+
+    # PCA (analysis/pca.py; tmjx_pca_*)
+    def fit(self, x):
+        """x from asarray -> (mean [d], components [d, d], variance [d]) float32 numpy, and the call's hip.PcaInfo."""
+        return self._fit(x, "tmjx_pca_workspace", "tmjx_pca_fit")
+
+    def _fit(self, x, workspace_entry, fit_entry):
+        p = self._p
+        n, d = x.shape
+        ws, info = self._workspace(workspace_entry, n, d), _hip.PcaInfo()
+        mean, comp, var = (p.empty(s, f32) for s in ((d,), (d, d), (d,)))
+        self._call(fit_entry, p.ptr(x), n, d, p.ld(x), p.ptr(mean), p.ptr(comp), p.ptr(var), p.ptr(ws), C.byref(info), p.stream())
+        return p.to_numpy(mean), p.to_numpy(comp), p.to_numpy(var), info
+
+    def transform(self, x, mean, components):
+        """(x - mean) . components^T as the provider's array [n, k]; mean [d] and components [k, d] numpy."""
+        return self._transform(x, mean, components, "tmjx_pca_transform")
+
+    def _transform(self, x, mean, components, entry):
+        p = self._p
+        n, d = x.shape
+        k = components.shape[0]
+        m, c = p.upload(mean, f32), p.upload(components, f32)
+        out = p.empty((n, k), f32)
+        self._call(entry, p.ptr(x), n, d, p.ld(x), p.ptr(m), p.ptr(c), k, p.ptr(out), k, p.stream())
+        return out
+
+    def fit_wide(self, x):
+        """`fit` for d <= 1024 (tmjx_pca_fit_wide: block Jacobi above 128 features, the narrow fit's bits up to 128); info.sweeps: block sweeps."""
+        return self._fit(x, "tmjx_pca_wide_workspace", "tmjx_pca_fit_wide")
+
+    def transform_wide(self, x, mean, components):
+        """`transform` for d <= 1024 (tmjx_pca_transform_wide)."""
+        return self._transform(x, mean, components, "tmjx_pca_transform_wide")
+
+    # the linear readout (analysis/readout.py; tmjx_readout_*): x and y from asarray, everything else float32 numpy
+    def readout_fit(self, x, y):
+        """-> (mean_x [d], components [d, d], variance [d], mean_y [m], z [d, m]) float32 numpy and the PCA part's hip.PcaInfo (tmjx_readout_fit)."""
+        p = self._p
+        (n, d), m = x.shape, y.shape[1]
+        ws, info = self._workspace("tmjx_readout_workspace", n, d, m, 1), _hip.PcaInfo()
+        mean_x, comp, var, mean_y, z = (p.empty(s, f32) for s in ((d,), (d, d), (d,), (m,), (d, m)))
+        self._call("tmjx_readout_fit", p.ptr(x), n, d, p.ld(x), p.ptr(y), m, p.ld(y), p.ptr(mean_x), p.ptr(comp), p.ptr(var), p.ptr(mean_y), p.ptr(z),
+                   p.ptr(ws), C.byref(info), p.stream())
+        return (*(p.to_numpy(t) for t in (mean_x, comp, var, mean_y, z)), info)
+
+    def readout_weights(self, components, variance, z, lambdas):
+        """lambdas: absolute penalties [L] -> w [L, d, m] float32 numpy (tmjx_readout_weights)."""
+        p = self._p
+        d, m = z.shape
+        lam = np.ascontiguousarray(lambdas, f64)
+        comp, var, zz = p.upload(components, f32), p.upload(variance, f32), p.upload(z, f32)
+        w = p.empty((max(lam.shape[0], 1), d, m), f32)
+        self._call("tmjx_readout_weights", p.ptr(comp), p.ptr(var), p.ptr(zz), d, m, lam.ctypes.data_as(_F64P), lam.shape[0], p.ptr(w), p.stream())
+        return p.to_numpy(w)
+
+    def readout_predict(self, x, mean_x, w, mean_y):
+        """w [d, m] -> (x - mean_x) w + mean_y as the provider's array [n, m] (tmjx_readout_predict)."""
+        p = self._p
+        (n, d), m = x.shape, w.shape[1]
+        mx, ww, my = p.upload(mean_x, f32), p.upload(w, f32), p.upload(mean_y, f32)
+        out = p.empty((n, m), f32)
+        self._call("tmjx_readout_predict", p.ptr(x), n, d, p.ld(x), p.ptr(mx), p.ptr(ww), p.ptr(my), m, p.ptr(out), m, p.stream())
+        return out
+
+    def readout_score(self, x, y, mean_x, w, mean_y):
+        """w [L, d, m] -> (sse [L, m], sst [m]) float64 numpy over the rows given (tmjx_readout_score)."""
+        p = self._p
+        (n, d), (L, _, m) = x.shape, w.shape
+        mx, ww, my = p.upload(mean_x, f32), p.upload(w, f32), p.upload(mean_y, f32)
+        ws = self._workspace("tmjx_readout_workspace", n, d, m, L)
+        sse, sst = p.empty((L, m), f64), p.empty((m,), f64)
+        self._call("tmjx_readout_score", p.ptr(x), n, d, p.ld(x), p.ptr(y), m, p.ld(y), p.ptr(mx), p.ptr(ww), p.ptr(my), L, p.ptr(sse), p.ptr(sst),
+                   p.ptr(ws), p.stream())
+        return p.to_numpy(sse), p.to_numpy(sst)
+
+    # k-means (analysis/cluster.py; tmjx_kmeans_*): x from asarray, centroids float32 numpy [k, d], labels int32 numpy (copied: read-only is fine)
+    def kmeans_seed(self, x, k, u):
+        """k-means++ with the uniforms u [k] -> (centroids [k, d] float32, index [k] int32: the rows chosen) numpy (tmjx_kmeans_seed)."""
+        p = self._p
+        n, d = x.shape
+        uu = np.ascontiguousarray(u, f64)
+        if uu.shape != (k,):
+            raise ValueError(f"expected {k} uniforms, got shape {uu.shape}")
+        ws, index = self._workspace("tmjx_kmeans_workspace", n, d, k), p.host_empty((k,), i32)
+        cen = p.empty((k, d), f32)
+        self._call("tmjx_kmeans_seed", p.ptr(x), n, d, p.ld(x), k, uu.ctypes.data_as(_F64P), p.ptr(cen), index.ctypes.data_as(_I32P), p.ptr(ws), p.stream())
+        return p.to_numpy(cen), index
+
+    def kmeans_assign(self, x, centroids, labels_prev=None):
+        """-> (labels [n] int32, dist2 [n] float32, inertia float, changed int: the rows whose label differs from labels_prev, n without one)
+        (tmjx_kmeans_assign)."""
+        p = self._p
+        (n, d), k = x.shape, centroids.shape[0]
+        cen, ws = p.upload(centroids, f32, copy=True), self._workspace("tmjx_kmeans_workspace", n, d, k)
+        prev = None if labels_prev is None else p.upload(labels_prev, i32, copy=True)
+        labels, dist2 = p.empty((n,), i32), p.empty((n,), f32)
+        inertia, changed = p.empty((1,), f64, zero=True), p.empty((1,), i32, zero=True)
+        self._call("tmjx_kmeans_assign", p.ptr(x), n, d, p.ld(x), p.ptr(cen), k, None if prev is None else p.ptr(prev), p.ptr(labels), p.ptr(dist2),
+                   p.ptr(inertia), p.ptr(changed), p.ptr(ws), p.stream())
+        return p.to_numpy(labels), p.to_numpy(dist2), float(inertia.item()), int(changed.item())
+
+    def kmeans_update(self, x, labels, centroids):
+        """-> (centroids [k, d] float32: the mean of each cluster's rows, an empty cluster's row as given; counts [k] int32) (tmjx_kmeans_update)."""
+        p = self._p
+        (n, d), k = x.shape, centroids.shape[0]
+        cen, lab, ws = p.upload(centroids, f32, copy=True), p.upload(labels, i32, copy=True), self._workspace("tmjx_kmeans_workspace", n, d, k)
+        counts = p.empty((k,), i32)
+        self._call("tmjx_kmeans_update", p.ptr(x), n, d, p.ld(x), p.ptr(lab), k, p.ptr(cen), p.ptr(counts), p.ptr(ws), p.stream())
+        return p.to_numpy(cen), p.to_numpy(counts)
+
+    def kmeans_fit(self, x, centroids, max_iter=100, tol=1e-4):
+        """Lloyd's iteration from `centroids` -> (centroids, labels int32 [n], dist2 float32 [n]) numpy and the call's hip.KMeansInfo (tmjx_kmeans_fit)."""
+        p = self._p
+        (n, d), k = x.shape, centroids.shape[0]
+        cen, ws, info = p.upload(centroids, f32, copy=True), self._workspace("tmjx_kmeans_workspace", n, d, k), _hip.KMeansInfo()
+        labels, dist2 = p.empty((n,), i32), p.empty((n,), f32)
+        self._call("tmjx_kmeans_fit", p.ptr(x), n, d, p.ld(x), k, p.ptr(cen), p.ptr(labels), p.ptr(dist2), int(max_iter), float(tol), C.byref(info),
+                   p.ptr(ws), p.stream())
+        return p.to_numpy(cen), p.to_numpy(labels), p.to_numpy(dist2), info
+
+    # the hidden Markov model (analysis/hmm.py; tmjx_hmm_*): x from asarray; logb, gamma and the parameters float32 numpy (copied: read-only is
+    # fine, and the in-place entry points never touch the caller's); seq_start int32 [S + 1]
+    @staticmethod
+    def _seq(seq_start):
+        seq = np.ascontiguousarray(seq_start, i32)
+        return seq, seq.ctypes.data_as(_I32P), seq.shape[0] - 1
+
+    def hmm_emission(self, x, means, vars):
+        """-> logb [n, k] float32: the log density of every row under every state's diagonal Gaussian (tmjx_hmm_emission)."""
+        p = self._p
+        (n, d), k = x.shape, means.shape[0]
+        mu, var, ws = p.upload(means, f32, copy=True), p.upload(vars, f32, copy=True), self._workspace("tmjx_hmm_workspace", n, d, k, 1)
+        logb = p.empty((n, k), f32)
+        self._call("tmjx_hmm_emission", p.ptr(x), n, d, p.ld(x), p.ptr(mu), p.ptr(var), k, p.ptr(logb), p.ptr(ws), p.stream())
+        return p.to_numpy(logb)
+
+    def hmm_forward_backward(self, logb, seq_start, transmat, startprob):
+        """-> (gamma [n, k] float32, xi [k, k] float64, start [k] float64, loglik [S] float64, their total) (tmjx_hmm_forward_backward)."""
+        p = self._p
+        n, k = logb.shape
+        seq, seq_p, S = self._seq(seq_start)
+        lb, A, pi = (p.upload(a, f32, copy=True) for a in (logb, transmat, startprob))
+        ws = self._workspace("tmjx_hmm_workspace", n, 1, k, S)
+        gamma = p.empty((n, k), f32)
+        xi, start, loglik, total = p.empty((k, k), f64), p.empty((k,), f64), p.empty((S,), f64), p.empty((1,), f64)
+        self._call("tmjx_hmm_forward_backward", p.ptr(lb), n, k, seq_p, S, p.ptr(A), p.ptr(pi), p.ptr(gamma), p.ptr(xi), p.ptr(start), p.ptr(loglik),
+                   p.ptr(total), p.ptr(ws), p.stream())
+        return p.to_numpy(gamma), p.to_numpy(xi), p.to_numpy(start), p.to_numpy(loglik), float(total.item())
+
+    def hmm_mstep(self, x, gamma, means, vars, min_var=0.0, min_weight=0.0):
+        """-> (means, vars [k, d] float32, weight [k] float64): the weighted moments of every state; one below min_weight as given (tmjx_hmm_mstep)."""
+        p = self._p
+        (n, d), k = x.shape, means.shape[0]
+        g, mu, var = (p.upload(a, f32, copy=True) for a in (gamma, means, vars))
+        ws, weight = self._workspace("tmjx_hmm_workspace", n, d, k, 1), p.empty((k,), f64)
+        self._call("tmjx_hmm_mstep", p.ptr(x), n, d, p.ld(x), p.ptr(g), k, float(min_var), float(min_weight), p.ptr(mu), p.ptr(var), p.ptr(weight),
+                   p.ptr(ws), p.stream())
+        return p.to_numpy(mu), p.to_numpy(var), p.to_numpy(weight)
+
+    def hmm_transitions(self, xi, start, prior, kappa, transmat, startprob):
+        """-> (transmat [k, k], startprob [k]) float32 from expected counts and Dirichlet pseudo-counts; a row without mass as given (tmjx_hmm_transitions)."""
+        p = self._p
+        k = len(start)
+        xx, st = p.upload(xi, f64), p.upload(start, f64)
+        A, pi = p.upload(transmat, f32, copy=True), p.upload(startprob, f32, copy=True)
+        self._call("tmjx_hmm_transitions", p.ptr(xx), p.ptr(st), k, float(prior), float(kappa), p.ptr(A), p.ptr(pi), p.stream())
+        return p.to_numpy(A), p.to_numpy(pi)
+
+    def hmm_viterbi(self, logb, seq_start, transmat, startprob, logspace=False):
+        """-> (labels [n] int32: the best path of every sequence, path_logprob [S] float64); logspace: the parameters hold logarithms (tmjx_hmm_viterbi)."""
+        p = self._p
+        n, k = logb.shape
+        seq, seq_p, S = self._seq(seq_start)
+        lb, A, pi = (p.upload(a, f32, copy=True) for a in (logb, transmat, startprob))
+        ws = self._workspace("tmjx_hmm_workspace", n, 1, k, S)
+        labels, path = p.empty((n,), i32), p.empty((S,), f64)
+        self._call("tmjx_hmm_viterbi", p.ptr(lb), n, k, seq_p, S, p.ptr(A), p.ptr(pi), int(bool(logspace)), p.ptr(labels), p.ptr(path), p.ptr(ws),
+                   p.stream())
+        return p.to_numpy(labels), p.to_numpy(path)
+
+    def hmm_fit(self, x, seq_start, means, vars, transmat, startprob, max_iter=50, tol=1e-4, prior=0.0, kappa=0.0, min_var=0.0, min_weight=0.0):
+        """EM from the parameters given -> (means, vars, transmat, startprob, gamma [n, k], labels [n] int32) numpy and the call's hip.HmmInfo
+        (tmjx_hmm_fit)."""
+        p = self._p
+        (n, d), k = x.shape, means.shape[0]
+        seq, seq_p, S = self._seq(seq_start)
+        mu, var, A, pi = (p.upload(a, f32, copy=True) for a in (means, vars, transmat, startprob))
+        ws, info = self._workspace("tmjx_hmm_workspace", n, d, k, S), _hip.HmmInfo()
+        gamma, labels = p.empty((n, k), f32), p.empty((n,), i32)
+        self._call("tmjx_hmm_fit", p.ptr(x), n, d, p.ld(x), seq_p, S, k, p.ptr(mu), p.ptr(var), p.ptr(A), p.ptr(pi), p.ptr(gamma), p.ptr(labels),
+                   int(max_iter), float(tol), float(prior), float(kappa), float(min_var), float(min_weight), C.byref(info), p.ptr(ws), p.stream())
+        return (*(p.to_numpy(t) for t in (mu, var, A, pi, gamma, labels)), info)
+
+    # the wavelet spectrogram (analysis/spectrogram.py; tmjx_wavelet_bank*, tmjx_spectrogram*): x from asarray, the bank as wavelet_bank returns it
+    def wavelet_bank(self, rate, freqs, omega0=5.0, support=4.0):
+        """-> (bank float32, offset int32 [F + 1], radius int32 [F]) numpy: the Morlet tables of every frequency (tmjx_wavelet_bank, a host function)."""
+        p = self._p
+        fr = np.ascontiguousarray(freqs, f64).reshape(-1)
+        F, floats, dp = fr.shape[0], C.c_int64(0), fr.ctypes.data_as(_F64P)
+        p.check(p.lib.tmjx_wavelet_bank_size(float(rate), dp, F, float(omega0), float(support), C.byref(floats)), "tmjx_wavelet_bank_size")
+        bank, offset, radius = p.host_empty((int(floats.value),), f32), p.host_empty((F + 1,), i32), p.host_empty((F,), i32)
+        p.check(p.lib.tmjx_wavelet_bank(float(rate), dp, F, float(omega0), float(support), bank.ctypes.data, offset.ctypes.data_as(_I32P),
+                                        radius.ctypes.data_as(_I32P)), "tmjx_wavelet_bank")
+        return bank, offset, radius
+
+    def spectrogram(self, x, seq_start, bank, offset, radius, detrend=True, log=False, floor=1e-3, out=None):
+        """-> (out [n, F C], coverage [n, F]) arrays of the provider: the amplitude (or its logarithm) of every channel at every frequency, column
+        j C + c, and the share of each window inside its sequence (tmjx_spectrogram).  `out`: an array of the provider [n, F C] to write into (a row
+        stride is fine)."""
+        p = self._p
+        n, Cn = x.shape
+        seq, seq_p, S = self._seq(seq_start)
+        off, rad = np.ascontiguousarray(offset, i32), np.ascontiguousarray(radius, i32)
+        F = rad.shape[0]
+        bk, ws = p.upload(bank, f32), self._workspace("tmjx_spectrogram_workspace", n, Cn, F, S)
+        if out is None:
+            out = p.empty((n, F * Cn), f32)
+        elif tuple(out.shape) != (n, F * Cn) or not p.dense_columns(out):
+            raise ValueError(f"out must be a float32 device tensor [{n}, {F * Cn}] with contiguous columns")
+        cov = p.empty((n, F), f32)
+        with p.guard():
+            p.check(p.lib.tmjx_spectrogram(p.ptr(x), n, Cn, p.ld(x), seq_p, S, p.ptr(bk), off.ctypes.data_as(_I32P), rad.ctypes.data_as(_I32P), F,
+                                           int(bool(detrend)), _hip.SPECTROGRAM_LOG if log else _hip.SPECTROGRAM_AMPLITUDE, float(floor), p.ptr(out), p.ld(out),
+                                           p.ptr(cov), p.ptr(ws), p.stream()), "tmjx_spectrogram")
+            p.sync()      # (the host offsets must outlive the queued copies)
+        return out, cov
+
+    def strips(self, proj, k, frame_idx, flags, ymin, ymax, window, style, width, height):
+        """One tmjx_plot_strips call: proj from asarray, frame_idx / flags numpy -> rgba uint8 numpy [F, H, W, 4]."""
+        p = self._p
+        fi, fl = p.upload(frame_idx, i32), p.upload(flags, np.uint8)
+        F = fi.shape[0]
+        out = p.empty((F, max(height, 0), max(width, 0), 4), np.uint8)
+        self._call("tmjx_plot_strips", p.ptr(proj), proj.shape[0], k, p.ld(proj), p.ptr(fi), p.ptr(fl), F, ymin, ymax, window, C.byref(style), width, height,
+                   p.ptr(out), p.stream())
+        return p.to_numpy(out)
+
+
+class TorchArrays:
+    """The provider of torch tensors on one device, for the product library."""
+
+    def __init__(self, device="cuda", lib=None):
+        import torch
+        self._t, self.device = torch, torch.device(device)
+        self.lib = _hip.lib() if lib is None else lib
+        self.check = _hip.check
+
+    def rows(self, x):
+        t = x if isinstance(x, self._t.Tensor) else self._t.from_numpy(np.array(x, dtype=np.float32, order="C"))      # (a copy: read-only arrays are fine)
+        t = t.to(device=self.device, dtype=self._t.float32)
+        return t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.contiguous()
+
+    def upload(self, a, dtype, copy=False):
+        return self._t.as_tensor(np.ascontiguousarray(np.array(a, dtype=dtype) if copy else a, dtype), device=self.device)
+
+    def empty(self, shape, dtype, zero=False):
+        return (self._t.zeros if zero else self._t.empty)(shape, dtype=getattr(self._t, np.dtype(dtype).name), device=self.device)
+
+    @staticmethod
+    def host_empty(shape, dtype):
+        return np.zeros(shape, dtype)
+
+    def workspace(self, floats):
+        return self._t.empty(floats, dtype=self._t.float32, device=self.device)
+
+    @staticmethod
+    def ptr(t):
+        return t.data_ptr()
+
+    @staticmethod
+    def ld(t):
+        return t.stride(0)
+
+    def dense_columns(self, t):
+        return t.dtype == self._t.float32 and t.stride(1) == 1
+
+    def stream(self):
+        return C.c_void_p(self._t.cuda.current_stream(self.device).cuda_stream)
+
+    def guard(self):
+        return self._t.cuda.device(self.device)
+
+    @staticmethod
+    def to_numpy(t):
+        return t.cpu().numpy()
+
+    def sync(self):
+        self._t.cuda.current_stream(self.device).synchronize()
+
+
+class HipBackend(Backend):
+    """The analysis entry points on torch device tensors.  A stand-in with the same methods is accepted wherever a `backend` is; one without
+    `fit_wide` / `transform_wide` serves features up to 128 wide only."""
+
+    def __init__(self, device="cuda", lib=None):
+        super().__init__(TorchArrays(device, lib))
+        self.device = self._p.device

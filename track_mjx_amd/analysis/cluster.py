@@ -11,13 +11,13 @@ commonest.  `python -m track_mjx_amd.analysis.rollout ... intervene_centroids=<c
 from __future__ import annotations
 
 import os
-import re
 import sys
 
 import numpy as np
 
 from .. import hip as _hip
 from . import pca as _pca
+from .utils import rollout_features
 
 CLI_OPTIONS = ("rollouts", "out", "feature", "k", "seed", "n_init", "max_iter", "tol")
 
@@ -96,23 +96,7 @@ def fit_rollouts(rollouts, feature: str = "intention", k: int = 32, n_init: int 
                  backend=None):
     """Cluster `feature` (up to 1024 wide) over every roll-out.  `rollouts`: a directory of clip_<i>.h5, or a list of roll-out dicts.
     -> (kmeans, labels, distances): labels[j] int32 [T_j] and distances[j] float32 [T_j] of roll-out j; kmeans.clips_ are the clip numbers."""
-    if isinstance(rollouts, (str, os.PathLike)):
-        from .. import h5lite
-        ids = sorted(int(m.group(1)) for m in (re.fullmatch(r"clip_(\d+)\.h5", f) for f in os.listdir(rollouts)) if m)
-        if not ids:
-            raise ValueError(f"no clip_<i>.h5 in {rollouts}")
-        feats = []
-        for c in ids:
-            with h5lite.File(os.path.join(rollouts, f"clip_{c}.h5")) as h:
-                feats.append(_pca._feature_of(h, feature, f"clip_{c}.h5"))
-    else:
-        ids = list(range(len(rollouts)))
-        if not ids:
-            raise ValueError("no roll-outs to cluster")
-        feats = [_pca._feature_of(r, feature, f"roll-out {j}") for j, r in enumerate(rollouts)]
-    widths = {f.shape[1] for f in feats}
-    if len(widths) != 1:
-        raise ValueError(f"{feature} has different widths across roll-outs: {sorted(widths)}")
+    ids, feats = rollout_features(rollouts, lambda r, _, where: _pca._feature_of(r, feature, where), feature, "cluster")
     km = KMeans(k, n_init=n_init, max_iter=max_iter, tol=tol, seed=seed, device=device, backend=backend)
     km.fit(km._b.asarray(np.concatenate(feats, 0)))
     km.clips_, km.feature_ = ids, feature

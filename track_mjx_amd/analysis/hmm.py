@@ -16,7 +16,6 @@ the commonest.
 from __future__ import annotations
 
 import os
-import re
 import sys
 
 import numpy as np
@@ -24,6 +23,7 @@ import numpy as np
 from .. import hip as _hip
 from . import cluster as _cluster
 from . import pca as _pca
+from .utils import rollout_features
 
 CLI_OPTIONS = ("rollouts", "out", "feature", "k", "kappa", "prior", "seed", "n_init", "max_iter", "tol", "holdout", "posteriors")
 MIN_WEIGHT = 1e-3      # a state holding less than this many expected rows keeps its emission parameters
@@ -123,23 +123,7 @@ def fit_rollouts(rollouts, feature: str = "intention", k: int = 32, max_iter: in
     holdout = int(holdout)
     if holdout < 0 or holdout == 1:
         raise ValueError(f"holdout must be 0 (no clip held out) or >= 2 (got {holdout})")
-    if isinstance(rollouts, (str, os.PathLike)):
-        from .. import h5lite
-        ids = sorted(int(m.group(1)) for m in (re.fullmatch(r"clip_(\d+)\.h5", f) for f in os.listdir(rollouts)) if m)
-        if not ids:
-            raise ValueError(f"no clip_<i>.h5 in {rollouts}")
-        feats = []
-        for c in ids:
-            with h5lite.File(os.path.join(rollouts, f"clip_{c}.h5")) as h:
-                feats.append(_pca._feature_of(h, feature, f"clip_{c}.h5"))
-    else:
-        ids = list(range(len(rollouts)))
-        if not ids:
-            raise ValueError("no roll-outs to fit")
-        feats = [_pca._feature_of(r, feature, f"roll-out {j}") for j, r in enumerate(rollouts)]
-    widths = {f.shape[1] for f in feats}
-    if len(widths) != 1:
-        raise ValueError(f"{feature} has different widths across roll-outs: {sorted(widths)}")
+    ids, feats = rollout_features(rollouts, lambda r, _, where: _pca._feature_of(r, feature, where), feature, "fit")
     held = [p for p in range(len(ids)) if holdout and p % holdout == holdout - 1]
     train = [p for p in range(len(ids)) if p not in held]
     if not train or (holdout and not held):

@@ -20,6 +20,7 @@ import numpy as np
 
 from .. import hip as _hip
 from . import pca as _pca
+from .utils import rollout_features
 
 CLI_OPTIONS = ("rollouts", "out", "feature", "target", "target_cols", "alphas", "holdout", "lag")
 DEFAULT_ALPHAS = (1e-3, 1e-2, 1e-1, 1.0, 10.0)
@@ -147,16 +148,7 @@ def fit_rollouts(rollouts, feature: str, target: str, alphas=DEFAULT_ALPHAS, hol
         raise ValueError(f"holdout must be >= 2 (got {holdout})")
     if lag not in (0, 1):
         raise ValueError(f"lag must be 0 or 1 (got {lag})")
-    if isinstance(rollouts, (str, os.PathLike)):
-        from .. import h5lite
-        ids = sorted(int(m.group(1)) for m in (re.fullmatch(r"clip_(\d+)\.h5", f) for f in os.listdir(rollouts)) if m)
-        pairs = []
-        for c in ids:
-            with h5lite.File(os.path.join(rollouts, f"clip_{c}.h5")) as h:
-                pairs.append((_pca._feature_of(h, feature, f"clip_{c}.h5"), _target_of(h, target, f"clip_{c}.h5")))
-    else:
-        ids = list(range(len(rollouts)))
-        pairs = [(_pca._feature_of(r, feature, f"roll-out {j}"), _target_of(r, target, f"roll-out {j}")) for j, r in enumerate(rollouts)]
+    ids, pairs = rollout_features(rollouts, lambda r, _, where: (_pca._feature_of(r, feature, where), _target_of(r, target, where)))
     if len(ids) < 2:
         raise ValueError(f"a held-out score needs at least two clips (got {len(ids)})")
     if len({f.shape[1] for f, _ in pairs}) != 1 or len({t.shape[1] for _, t in pairs}) != 1:

@@ -20,7 +20,6 @@ components of a wide layer).  rate is the control rate of the roll-out in Hz and
 from __future__ import annotations
 
 import os
-import re
 import sys
 
 import numpy as np
@@ -29,6 +28,7 @@ from .. import hip as _hip
 from . import hmm as _hmm
 from . import pca as _pca
 from . import readout as _readout
+from .utils import rollout_features
 
 CLI_OPTIONS = ("rollouts", "out", "source", "cols", "rate", "f_min", "f_max", "n_freqs", "omega0", "support", "detrend", "output", "floor", "projections")
 MAX_TOOL_WIDTH = 1024      # analysis.cluster, analysis.hmm and the wide PCA stop here
@@ -127,24 +127,13 @@ def _signals(rollouts, source: str, cols, projections):
             raise ValueError(str(e).replace("target_cols", "cols")) from None
         return np.ascontiguousarray(a[:, sl], np.float32)
 
-    if isinstance(rollouts, (str, os.PathLike)):
-        ids = sorted(int(m.group(1)) for m in (re.fullmatch(r"clip_(\d+)\.h5", f) for f in os.listdir(rollouts)) if m)
-        if not ids:
-            raise ValueError(f"no clip_<i>.h5 in {rollouts}")
-        sigs, metas = [], []
-        for c in ids:
-            with h5lite.File(os.path.join(rollouts, f"clip_{c}.h5")) as h:
-                sigs.append(one(h, c, f"clip_{c}.h5"))
-                metas.append(_tree(h["meta"]) if "meta" in h else None)
-    else:
-        ids = list(range(len(rollouts)))
-        if not ids:
-            raise ValueError("no roll-outs to transform")
-        sigs = [one(r, j, f"roll-out {j}") for j, r in enumerate(rollouts)]
-        metas = [r.get("meta") if hasattr(r, "get") else None for r in rollouts]
-    widths = {s.shape[1] for s in sigs}
-    if len(widths) != 1:
-        raise ValueError(f"{source} has different widths across roll-outs: {sorted(widths)}")
+    def meta(r):
+        if isinstance(r, h5lite.File):
+            return _tree(r["meta"]) if "meta" in r else None
+        return r.get("meta") if hasattr(r, "get") else None
+
+    ids, items = rollout_features(rollouts, lambda r, clip, where: (one(r, clip, where), meta(r)), source, "transform")
+    sigs, metas = [s for s, _ in items], [m for _, m in items]
     if any(s.ndim != 2 or s.shape[0] < 1 for s in sigs):
         raise ValueError(f"{source}: expected [T, C] with T >= 1")
     return ids, sigs, metas

@@ -5,11 +5,38 @@ Mapping (recursive_dict_to_h5py): dict -> group, list / tuple -> group with memb
 dataset, None -> skipped.  Loading turns a group whose members are all digits back into a list (an empty group too, as the reference does)."""
 from __future__ import annotations
 
+import os
+import re
 from pathlib import Path
 
 import numpy as np
 
 from .. import h5lite
+
+
+def rollout_features(rollouts, read, name=None, verb=None):
+    """What the analysis tools take of a set of roll-outs.  `rollouts`: a directory of clip_<i>.h5 (read in numeric order), or a list of roll-out
+    dicts; `read(rollout, clip, where)` -> the [T, D] feature of one (an open h5lite file or a dict), or a tuple that starts with it.
+    -> (clip numbers: the list positions for dicts, [what `read` returned]).  With `verb` ("fit", "cluster", ...) an empty set is an error; with
+    `name` the features must all have one width."""
+    if isinstance(rollouts, (str, os.PathLike)):
+        ids = sorted(int(m.group(1)) for m in (re.fullmatch(r"clip_(\d+)\.h5", f) for f in os.listdir(rollouts)) if m)
+        if verb is not None and not ids:
+            raise ValueError(f"no clip_<i>.h5 in {rollouts}")
+        items = []
+        for c in ids:
+            with h5lite.File(os.path.join(rollouts, f"clip_{c}.h5")) as h:
+                items.append(read(h, c, f"clip_{c}.h5"))
+    else:
+        ids = list(range(len(rollouts)))
+        if verb is not None and not ids:
+            raise ValueError(f"no roll-outs to {verb}")
+        items = [read(r, j, f"roll-out {j}") for j, r in enumerate(rollouts)]
+    if name is not None:
+        widths = {(i[0] if isinstance(i, tuple) else i).shape[1] for i in items}
+        if len(widths) != 1:
+            raise ValueError(f"{name} has different widths across roll-outs: {sorted(widths)}")
+    return ids, items
 
 
 def _to_tree(data):

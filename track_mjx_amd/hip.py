@@ -34,30 +34,6 @@ class Layout(C.Structure):
         "i_clip_idx", "i_start_frame", "i_buffer_index", "i_nan_count", "istate_rows", "ws_rows")]
 
 
-EXPORTS = ("tmjx_model_create", "tmjx_model_destroy", "tmjx_layout", "tmjx_clips_upload", "tmjx_reset", "tmjx_step",
-           "tmjx_physics", "tmjx_physics_step", "tmjx_forward", "tmjx_reward_obs", "tmjx_reward_frame", "tmjx_gae", "tmjx_ppo_scratch_floats", "tmjx_ppo_loss", "tmjx_ppo_loss_phases",
-           "tmjx_silu_ln_partial_floats", "tmjx_silu_ln_fwd", "tmjx_silu_ln_bwd", "tmjx_silu_ln_fwd_bf16", "tmjx_silu_ln_bwd_bf16", "tmjx_minibatch_begin_bf16", "tmjx_gather_normalize", "tmjx_latent_concat", "tmjx_latent_concat_bwd", "tmjx_latent_concat_bwd_add", "tmjx_sample_action", "tmjx_linear_nolds", "tmjx_linear_act", "tmjx_linear_act_ok", "tmjx_linear_nolds_norm", "tmjx_linear_nolds_bf16", "tmjx_adam_clip", "tmjx_adam_clip_norm", "tmjx_adam_clip_norm_frozen", "tmjx_adam_norm_floats", "tmjx_colsum_scratch_floats", "tmjx_colsum",
-           "tmjx_gather_minibatch", "tmjx_minibatch_begin", "tmjx_philox4x32_10", "tmjx_gemm_nt", "tmjx_gemm_nt_silu_ln", "tmjx_gemm_nt_silu_ln_ok", "tmjx_gemm_nn", "tmjx_colsum_grouped", "tmjx_gemm_nn_ln_bwd", "tmjx_gemm_nn_ln_bwd_ok", "tmjx_gemm_nn_ln_bwd_partial_floats", "tmjx_gemm_dw", "tmjx_gemm_dw_grouped", "tmjx_gemm_dw_scratch_floats", "tmjx_set_wrappers", "tmjx_set_action_repeat", "tmjx_stats_scratch_floats", "tmjx_stats_sums", "tmjx_stats_apply", "tmjx_stats_apply_pinned",
-           "tmjx_rollout_store", "tmjx_clips_share", "tmjx_gemm_nt_silu", "tmjx_gemm_nt_silu_ok", "tmjx_silu_fwd", "tmjx_silu_bwd", "tmjx_gemm_nn_silu_bwd_ok", "tmjx_gemm_nn_silu_bwd", "tmjx_silu_bwd_rank1", "tmjx_head_dw_scratch_floats", "tmjx_head_dw", "tmjx_head_fwd_ok", "tmjx_head_fwd", "tmjx_bf16_shadow", "tmjx_bgemm_nt", "tmjx_bgemm_dw", "tmjx_bgemm_dw_grouped", "tmjx_bgemm_dw_scratch_floats", "tmjx_bgemm_row_tile_ok", "tmjx_bf16_z_bytes", "tmjx_bgemm_partial_floats",
-           "tmjx_bgemm_ln_fwd", "tmjx_bgemm_ln_bwd", "tmjx_bgemm_silu_fwd", "tmjx_bgemm_silu_bwd", "tmjx_bf_silu_bwd", "tmjx_bf_silu_bwd_rank1",
-           "tmjx_chain_rows", "tmjx_chain_fwd_ok", "tmjx_chain_fwd", "tmjx_chain_bwd_ok", "tmjx_chain_bwd",
-           "tmjx_lstm_hidden_ok", "tmjx_lstm_seq_fwd", "tmjx_lstm_seq_bwd",
-           "tmjx_record_check", "tmjx_record_step", "tmjx_latent_concat_det", "tmjx_action_mode",
-           "tmjx_decoder_input", "tmjx_decoder_act_ok", "tmjx_decoder_act", "tmjx_lstm_decoder_act_ok", "tmjx_lstm_decoder_act",
-           "tmjx_policy_act_ok", "tmjx_policy_act",
-           "tmjx_sensor_info", "tmjx_physics_sensors", "tmjx_step_sensors",
-           "tmjx_set_done_policy", "tmjx_clips_upload_velocities", "tmjx_set_env_scales", "tmjx_set_env_gravity",
-           "tmjx_render_info", "tmjx_render_camera", "tmjx_render_pose", "tmjx_render_prims", "tmjx_render",
-           "tmjx_pca_workspace", "tmjx_pca_fit", "tmjx_pca_transform", "tmjx_plot_strips",
-           "tmjx_pca_wide_workspace", "tmjx_pca_fit_wide", "tmjx_pca_transform_wide",
-           "tmjx_readout_workspace", "tmjx_readout_fit", "tmjx_readout_weights", "tmjx_readout_predict", "tmjx_readout_score",
-           "tmjx_intervene_ok", "tmjx_intervene",
-           "tmjx_kmeans_workspace", "tmjx_kmeans_assign", "tmjx_kmeans_update", "tmjx_kmeans_seed", "tmjx_kmeans_fit",
-           "tmjx_hmm_workspace", "tmjx_hmm_emission", "tmjx_hmm_forward_backward", "tmjx_hmm_mstep", "tmjx_hmm_transitions", "tmjx_hmm_viterbi", "tmjx_hmm_fit",
-           "tmjx_wavelet_bank_size", "tmjx_wavelet_bank", "tmjx_spectrogram_workspace", "tmjx_spectrogram",
-           "tmjx_debug_rows", "tmjx_last_error", "tmjx_version")
-
-
 class Minibatch(C.Structure):
     """tmjx_minibatch_t (include/tmjx.h)."""
     _fields_ = ([(k, C.c_void_p) for k in ("obs", "next_last", "raw_action", "log_prob", "reward", "discount", "truncation", "perm", "mean", "std", "obs_n", "next_n",
@@ -248,7 +224,176 @@ class PpoCfg(C.Structure):
                 ("discounting", C.c_float), ("gae_lambda", C.c_float), ("clip_eps", C.c_float), ("entropy_cost", C.c_float),
                 ("kl_weight", C.c_float), ("normalize_advantage", C.c_int32), ("accumulate", C.c_int32)]
 
+
+_i, _i64, _u64, _f, _d, _vp, _s, _P = C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_void_p, C.c_char_p, C.POINTER
+# entry point -> (argument types, return type), one for one with the prototypes of include/tmjx.h (tests/test_abi.py compares the two).  Data
+# pointers are void pointers (tensor addresses are passed as integers); a pointer the host fills or reads keeps its type
+SIGNATURES = {
+    "tmjx_model_create": ([_s, C.c_size_t, _P(_vp)], _i),
+    "tmjx_model_destroy": ([_vp], None),
+    "tmjx_layout": ([_vp, _P(Layout)], _i),
+    "tmjx_clips_upload": ([_vp] * 6 + [_i, _i], _i),
+    "tmjx_reset": ([_vp] * 9 + [_i, _vp], _i),
+    "tmjx_step": ([_vp] * 10 + [_i, _vp], _i),
+    "tmjx_physics": ([_vp, _vp, _vp, _i, _vp, _i, _vp], _i),
+    "tmjx_physics_step": ([_vp] * 4 + [_i, _vp], _i),
+    "tmjx_forward": ([_vp, _vp, _vp, _i, _vp], _i),
+    "tmjx_reward_obs": ([_vp] * 10 + [_i, _vp], _i),
+    "tmjx_reward_frame": ([_vp] * 14 + [_i, _vp], _i),
+    "tmjx_gae": ([_vp] * 5 + [_f, _f, _vp, _vp, _i, _i, _vp], _i),
+    "tmjx_ppo_scratch_floats": ([_i, _i], _i),
+    "tmjx_ppo_loss": ([_P(PpoCfg)] + [_vp] * 16, _i),
+    "tmjx_ppo_loss_phases": ([_P(PpoCfg)] + [_vp] * 15 + [_i, _vp], _i),
+    "tmjx_silu_ln_partial_floats": ([_i, _i], _i),
+    "tmjx_silu_ln_fwd": ([_vp] * 6 + [_i, _i, _f, _vp], _i),
+    "tmjx_silu_ln_bwd": ([_vp] * 8 + [_i, _i, _vp], _i),
+    "tmjx_silu_ln_fwd_bf16": ([_vp] * 5 + [_i, _vp, _i, _i, _f, _vp], _i),
+    "tmjx_silu_ln_bwd_bf16": ([_vp] * 6 + [_i, _vp, _vp, _i, _i, _vp], _i),
+    "tmjx_minibatch_begin_bf16": ([_P(Minibatch), _vp, _i, _vp], _i),
+    "tmjx_gather_normalize": ([_vp] * 5 + [_i] * 4 + [_vp], _i),
+    "tmjx_latent_concat": ([_vp] * 4 + [_i] * 4 + [_i64, _i64, _vp, _vp, _i, _u64, _vp, _vp], _i),
+    "tmjx_latent_concat_bwd": ([_vp] * 4 + [_i, _i, _i, _vp], _i),
+    "tmjx_latent_concat_bwd_add": ([_vp] * 5 + [_i, _i, _i, _vp], _i),
+    "tmjx_sample_action": ([_vp] * 5 + [_i, _i, _u64, _vp, _vp], _i),
+    "tmjx_linear_nolds": ([_vp, _i64, _i64, _vp, _vp, _vp, _i, _i, _i, _vp], _i),
+    "tmjx_linear_act": ([_vp, _i64, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp], _i),
+    "tmjx_linear_act_ok": ([_vp, _i64, _vp, _i, _i], _i),
+    "tmjx_linear_nolds_norm": ([_vp, _i64, _i64, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp], _i),
+    "tmjx_linear_nolds_bf16": ([_vp, _i64, _i64, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp], _i),
+    "tmjx_adam_clip": ([_vp] * 5 + [_i64] + [_f] * 7 + [_vp], _i),
+    "tmjx_adam_clip_norm": ([_vp] * 6 + [_i64] + [_f] * 7 + [_vp], _i),
+    "tmjx_adam_clip_norm_frozen": ([_vp] * 6 + [_i64, _i64, _i64] + [_f] * 7 + [_vp], _i),
+    "tmjx_adam_norm_floats": ([], _i),
+    "tmjx_colsum_scratch_floats": ([_i], _i),
+    "tmjx_colsum": ([_vp, _vp, _vp, _i, _i, _vp], _i),
+    "tmjx_gather_minibatch": ([_vp] * 14 + [_i] * 5 + [_vp], _i),
+    "tmjx_minibatch_begin": ([_P(Minibatch), _vp], _i),
+    "tmjx_philox4x32_10": ([_vp, _vp, _vp], _i),
+    "tmjx_gemm_nt": ([_vp, _i, _vp, _i, _vp, _vp] + [_i] * 4 + [_vp], _i),
+    "tmjx_gemm_nt_silu_ln": ([_vp, _i, _vp, _i] + [_vp] * 5 + [_i, _vp, _i, _i, _i, _f, _vp], _i),
+    "tmjx_gemm_nt_silu_ln_ok": ([_vp, _i, _vp, _i, _i], _i),
+    "tmjx_gemm_nn": ([_vp, _i, _vp, _i, _vp] + [_i] * 4 + [_vp], _i),
+    "tmjx_colsum_grouped": ([_P(ColsumProblem), _i, _vp], _i),
+    "tmjx_gemm_nn_ln_bwd": ([_vp, _i, _vp, _i] + [_vp] * 6 + [_i, _i, _i, _vp], _i),
+    "tmjx_gemm_nn_ln_bwd_ok": ([_vp, _i, _vp, _i, _i], _i),
+    "tmjx_gemm_nn_ln_bwd_partial_floats": ([_i, _i], _i64),
+    "tmjx_gemm_dw": ([_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp], _i),
+    "tmjx_gemm_dw_grouped": ([_P(DwProblem), _i, _vp], _i),
+    "tmjx_gemm_dw_scratch_floats": ([_i, _i, _i], _i64),
+    "tmjx_set_wrappers": ([_vp, _i, _i], _i),
+    "tmjx_set_action_repeat": ([_vp, _i], _i),
+    "tmjx_stats_scratch_floats": ([_i], _i),
+    "tmjx_stats_sums": ([_vp] * 4 + [_i64, _i, _vp], _i),
+    "tmjx_stats_apply": ([_vp, _f] + [_vp] * 4 + [_i, _f, _f, _vp], _i),
+    "tmjx_stats_apply_pinned": ([_vp, _f] + [_vp] * 4 + [_i, _i, _f, _f, _vp], _i),
+    "tmjx_rollout_store": ([_P(RolloutStore), _vp], _i),
+    "tmjx_clips_share": ([_vp, _vp], _i),
+    "tmjx_gemm_nt_silu": ([_vp, _i, _vp, _i, _vp, _vp, _vp] + [_i] * 4 + [_vp], _i),
+    "tmjx_gemm_nt_silu_ok": ([_vp, _i, _vp, _i], _i),
+    "tmjx_silu_fwd": ([_vp, _vp, _vp, _i64, _i, _vp], _i),
+    "tmjx_silu_bwd": ([_vp] * 4 + [_i64, _i, _vp], _i),
+    "tmjx_gemm_nn_silu_bwd_ok": ([_vp, _i, _vp, _i], _i),
+    "tmjx_gemm_nn_silu_bwd": ([_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp], _i),
+    "tmjx_silu_bwd_rank1": ([_vp] * 5 + [_i64, _i, _vp], _i),
+    "tmjx_head_dw_scratch_floats": ([_i, _i], _i64),
+    "tmjx_head_dw": ([_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp], _i),
+    "tmjx_head_fwd_ok": ([_vp, _i, _vp, _i], _i),
+    "tmjx_head_fwd": ([_vp, _i, _vp, _vp, _vp, _i, _i, _vp], _i),
+    "tmjx_bf16_shadow": ([_P(Bf16Shadow), _i, _vp], _i),
+    "tmjx_bgemm_nt": ([_vp, _i, _i, _vp, _i, _vp, _vp] + [_i] * 4 + [_vp], _i),
+    "tmjx_bgemm_dw": ([_vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp], _i),
+    "tmjx_bgemm_dw_grouped": ([_P(BdwProblem), _i, _i, _vp], _i),
+    "tmjx_bgemm_dw_scratch_floats": ([_i, _i, _i], _i64),
+    "tmjx_bgemm_row_tile_ok": ([_i], _i),
+    "tmjx_bf16_z_bytes": ([], _i),
+    "tmjx_bgemm_partial_floats": ([_i, _i, _i], _i64),
+    "tmjx_bgemm_ln_fwd": ([_vp, _i, _i, _vp, _i] + [_vp] * 4 + [_i, _vp, _i, _vp, _i, _i, _i, _f, _vp], _i),
+    "tmjx_bgemm_ln_bwd": ([_vp, _i, _i, _vp, _i, _vp, _i] + [_vp] * 4 + [_i, _vp, _i, _i, _i, _vp], _i),
+    "tmjx_bgemm_silu_fwd": ([_vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp] + [_i] * 4 + [_vp], _i),
+    "tmjx_bgemm_silu_bwd": ([_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _vp], _i),
+    "tmjx_bf_silu_bwd": ([_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp], _i),
+    "tmjx_bf_silu_bwd_rank1": ([_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp], _i),
+    "tmjx_chain_rows": ([_i], _i),
+    "tmjx_chain_fwd_ok": ([_P(ChainFwd)], _i),
+    "tmjx_chain_fwd": ([_P(ChainFwd), _vp], _i),
+    "tmjx_chain_bwd_ok": ([_P(ChainBwd)], _i),
+    "tmjx_chain_bwd": ([_P(ChainBwd), _vp], _i),
+    "tmjx_lstm_hidden_ok": ([_i], _i),
+    "tmjx_lstm_seq_fwd": ([_P(LstmFwd), _vp], _i),
+    "tmjx_lstm_seq_bwd": ([_P(LstmBwd), _vp], _i),
+    "tmjx_record_check": ([_P(RecordStream), _i, _i, _i], _i),
+    "tmjx_record_step": ([_vp] + [_i] * 4 + [_vp], _i),
+    "tmjx_latent_concat_det": ([_vp, _i, _vp, _i64, _i64, _vp, _vp, _vp, _i, _vp] + [_i] * 5 + [_vp], _i),
+    "tmjx_action_mode": ([_vp, _i, _vp, _vp, _i, _i, _vp], _i),
+    "tmjx_decoder_input": ([_vp, _i, _vp, _i64, _i64, _vp, _vp, _vp] + [_i] * 5 + [_vp], _i),
+    "tmjx_decoder_act_ok": ([_P(DecoderAct)], _i),
+    "tmjx_decoder_act": ([_P(DecoderAct), _vp], _i),
+    "tmjx_lstm_decoder_act_ok": ([_P(LstmDecoderAct)], _i),
+    "tmjx_lstm_decoder_act": ([_P(LstmDecoderAct), _vp], _i),
+    "tmjx_policy_act_ok": ([_P(PolicyAct)], _i),
+    "tmjx_policy_act": ([_P(PolicyAct), _vp], _i),
+    "tmjx_sensor_info": ([_vp, _P(_i), _P(_i)], _i),
+    "tmjx_physics_sensors": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp], _i),
+    "tmjx_step_sensors": ([_vp] * 12 + [_i, _vp], _i),
+    "tmjx_set_done_policy": ([_vp, _i], _i),
+    "tmjx_clips_upload_velocities": ([_vp, _vp, _vp, _i, _i], _i),
+    "tmjx_set_env_scales": ([_vp, _vp, _i], _i),
+    "tmjx_set_env_gravity": ([_vp, _vp, _i], _i),
+    "tmjx_render_info": ([_vp, _i, _i, _P(RenderInfo)], _i),
+    "tmjx_render_camera": ([_vp, _s, _P(Camera)], _i),
+    "tmjx_render_pose": ([_vp, _vp, _vp, _i, _i, _P(Camera), _vp, _vp], _i),
+    "tmjx_render_prims": ([_vp, _vp] + [_i] * 4 + [_vp] * 4, _i),
+    "tmjx_render": ([_vp, _vp, _vp, _i, _i, _P(Camera), _i, _i] + [_vp] * 5, _i),
+    "tmjx_pca_workspace": ([_i, _i, _P(_i64)], _i),
+    "tmjx_pca_fit": ([_vp, _i, _i, _i64] + [_vp] * 4 + [_P(PcaInfo), _vp], _i),
+    "tmjx_pca_transform": ([_vp, _i, _i, _i64, _vp, _vp, _i, _vp, _i64, _vp], _i),
+    "tmjx_plot_strips": ([_vp, _i, _i, _i64, _vp, _vp, _i, _f, _f, _i, _P(StripStyle), _i, _i, _vp, _vp], _i),
+    "tmjx_pca_wide_workspace": ([_i, _i, _P(_i64)], _i),
+    "tmjx_pca_fit_wide": ([_vp, _i, _i, _i64] + [_vp] * 4 + [_P(PcaInfo), _vp], _i),
+    "tmjx_pca_transform_wide": ([_vp, _i, _i, _i64, _vp, _vp, _i, _vp, _i64, _vp], _i),
+    "tmjx_readout_workspace": ([_i] * 4 + [_P(_i64)], _i),
+    "tmjx_readout_fit": ([_vp, _i, _i, _i64, _vp, _i, _i64] + [_vp] * 6 + [_P(PcaInfo), _vp], _i),
+    "tmjx_readout_weights": ([_vp, _vp, _vp, _i, _i, _P(_d), _i, _vp, _vp], _i),
+    "tmjx_readout_predict": ([_vp, _i, _i, _i64, _vp, _vp, _vp, _i, _vp, _i64, _vp], _i),
+    "tmjx_readout_score": ([_vp, _i, _i, _i64, _vp, _i, _i64, _vp, _vp, _vp, _i] + [_vp] * 4, _i),
+    "tmjx_intervene_ok": ([_P(Intervene)], _i),
+    "tmjx_intervene": ([_P(Intervene), _i, _vp], _i),
+    "tmjx_kmeans_workspace": ([_i, _i, _i, _P(_i64)], _i),
+    "tmjx_kmeans_assign": ([_vp, _i, _i, _i64, _vp, _i] + [_vp] * 7, _i),
+    "tmjx_kmeans_update": ([_vp, _i, _i, _i64, _vp, _i] + [_vp] * 4, _i),
+    "tmjx_kmeans_seed": ([_vp, _i, _i, _i64, _i, _P(_d), _vp, _P(_i), _vp, _vp], _i),
+    "tmjx_kmeans_fit": ([_vp, _i, _i, _i64, _i, _vp, _vp, _vp, _i, _d, _P(KMeansInfo), _vp, _vp], _i),
+    "tmjx_hmm_workspace": ([_i] * 4 + [_P(_i64)], _i),
+    "tmjx_hmm_emission": ([_vp, _i, _i, _i64, _vp, _vp, _i, _vp, _vp, _vp], _i),
+    "tmjx_hmm_forward_backward": ([_vp, _i, _i, _P(_i), _i] + [_vp] * 9, _i),
+    "tmjx_hmm_mstep": ([_vp, _i, _i, _i64, _vp, _i, _d, _d] + [_vp] * 5, _i),
+    "tmjx_hmm_transitions": ([_vp, _vp, _i, _d, _d, _vp, _vp, _vp], _i),
+    "tmjx_hmm_viterbi": ([_vp, _i, _i, _P(_i), _i, _vp, _vp, _i] + [_vp] * 4, _i),
+    "tmjx_hmm_fit": ([_vp, _i, _i, _i64, _P(_i), _i, _i] + [_vp] * 6 + [_i] + [_d] * 5 + [_P(HmmInfo), _vp, _vp], _i),
+    "tmjx_wavelet_bank_size": ([_d, _P(_d), _i, _d, _d, _P(_i64)], _i),
+    "tmjx_wavelet_bank": ([_d, _P(_d), _i, _d, _d, _vp, _P(_i), _P(_i)], _i),
+    "tmjx_spectrogram_workspace": ([_i] * 4 + [_P(_i64)], _i),
+    "tmjx_spectrogram": ([_vp, _i, _i, _i64, _P(_i), _i, _vp, _P(_i), _P(_i), _i, _i, _i, _f, _vp, _i64, _vp, _vp, _vp], _i),
+    "tmjx_debug_rows": ([_vp, _s, _P(_i), _P(_i)], _i),
+    "tmjx_last_error": ([], _s),
+    "tmjx_version": ([], _s),
+}
+EXPORTS = tuple(SIGNATURES)
+
 _lib = None
+
+
+def include_closure(path: Path, seen: dict | None = None) -> dict:
+    """{file: text} of a source and every file it includes with quotes, recursively (what a rebuild of it depends on)."""
+    import re
+    seen = {} if seen is None else seen
+    path = Path(path).resolve()
+    if path in seen or not path.exists():
+        return seen
+    seen[path] = text = path.read_text()
+    for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', text, re.M):
+        include_closure(path.parent / inc, seen)
+    return seen
 
 
 def build(verbose: bool = False, out: Path | None = None, defines: tuple = ()) -> Path:
@@ -261,19 +406,9 @@ def build(verbose: bool = False, out: Path | None = None, defines: tuple = ()) -
     # Objects are cached next to the library, keyed by a hash of the flags and of the source with every header it includes (recursively):
     # editing one kernel family recompiles one unit
     import hashlib
-    import re
     from concurrent.futures import ThreadPoolExecutor
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-fPIC", "-Wno-unused-value", *[f"-D{d}" for d in defines],
              *os.environ.get("TMJX_EXTRA_HIPCC_FLAGS", "").split()]          # (tuning experiments: A/B builds with extra compiler flags)
-
-    def closure(path: Path, seen: dict) -> dict:
-        if path in seen or not path.exists():
-            return seen
-        text = path.read_text()
-        seen[path] = text
-        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', text, re.M):
-            closure((path.parent / inc).resolve(), seen)
-        return seen
 
     cache = out.parent / ".build"
     cache.mkdir(exist_ok=True)
@@ -283,7 +418,7 @@ def build(verbose: bool = False, out: Path | None = None, defines: tuple = ()) -
 
     for src in SOURCES:
         h = hashlib.sha256(" ".join(flags_of(src)).encode())
-        for pth, text in sorted(closure(src.resolve(), {}).items()):
+        for pth, text in sorted(include_closure(src).items()):
             h.update(str(pth.name).encode()); h.update(text.encode())
         objs.append(cache / f"{src.stem}.{h.hexdigest()[:16]}.o")
 
@@ -336,6 +471,16 @@ def lib():
     return _lib
 
 
+def declare(L, names=None):
+    """Give the entry points of SIGNATURES (or `names` of them) that library `L` exports their argument and return types.  A library may export a
+    subset (the oracle's ABI twin has no learner kernels, the tests' host emulation only the analyses): calling a missing one raises."""
+    for name in SIGNATURES if names is None else names:
+        fn = getattr(L, name, None)
+        if fn is not None:
+            fn.argtypes, fn.restype = SIGNATURES[name]
+    return L
+
+
 def load(path: Path):
     """dlopen a build of the library and declare its entry points (lib() = the product build; tests load the lane cross-check build)."""
     path = Path(path)
@@ -346,174 +491,7 @@ def load(path: Path):
         L = C.CDLL(str(path))
     except OSError as e:  # e.g. no ROCm runtime on this machine
         raise TmjxError(f"cannot load {path}: {e}") from e
-    vp, ip, fp = C.c_void_p, C.POINTER(C.c_int32), C.c_void_p
-    sig: dict = {}      # entry point -> (argtypes, restype or None for the default int return code)
-    sig.setdefault("tmjx_model_create", [None, None])[0] = [C.c_char_p, C.c_size_t, C.POINTER(vp)]
-    sig.setdefault("tmjx_model_destroy", [None, None])[0] = [vp]
-    sig.setdefault("tmjx_model_destroy", [None, None])[1] = None
-    sig.setdefault("tmjx_layout", [None, None])[0] = [vp, C.POINTER(Layout)]
-    sig.setdefault("tmjx_clips_upload", [None, None])[0] = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int]
-    sig.setdefault("tmjx_reset", [None, None])[0] = [vp, fp, vp, vp, vp, fp, fp, fp, fp, C.c_int, vp]
-    sig.setdefault("tmjx_step", [None, None])[0] = [vp, fp, vp, fp, fp, fp, fp, fp, fp, fp, C.c_int, vp]
-    sig.setdefault("tmjx_physics", [None, None])[0] = [vp, fp, fp, C.c_int, fp, C.c_int, vp]
-    sig.setdefault("tmjx_physics_step", [None, None])[0] = [vp, fp, fp, fp, C.c_int, vp]
-    sig.setdefault("tmjx_sensor_info", [None, None])[0] = [vp, ip, ip]
-    sig.setdefault("tmjx_physics_sensors", [None, None])[0] = [vp, fp, fp, C.c_int, fp, fp, fp, C.c_int, vp]
-    sig.setdefault("tmjx_step_sensors", [None, None])[0] = [vp, fp, vp, fp, fp, fp, fp, fp, fp, fp, fp, fp, C.c_int, vp]
-    sig.setdefault("tmjx_forward", [None, None])[0] = [vp, fp, fp, C.c_int, vp]
-    sig.setdefault("tmjx_reward_obs", [None, None])[0] = [vp, fp, vp, fp, fp, fp, fp, fp, fp, fp, C.c_int, vp]
-    sig.setdefault("tmjx_reward_frame", [None, None])[0] = [vp, fp, vp, fp] + [fp] * 5 + [fp] * 5 + [C.c_int, vp]
-    sig.setdefault("tmjx_gae", [None, None])[0] = [fp, fp, fp, fp, fp, C.c_float, C.c_float, fp, fp, C.c_int, C.c_int, vp]
-    sig.setdefault("tmjx_ppo_scratch_floats", [None, None])[0] = [C.c_int, C.c_int]
-    sig.setdefault("tmjx_ppo_loss", [None, None])[0] = [C.POINTER(PpoCfg)] + [fp] * 15 + [vp]
-    sig.setdefault("tmjx_ppo_loss_phases", [None, None])[0] = [C.POINTER(PpoCfg)] + [fp] * 15 + [C.c_int, vp]
-    sig.setdefault("tmjx_silu_ln_partial_floats", [None, None])[0] = [C.c_int, C.c_int]
-    sig.setdefault("tmjx_silu_ln_fwd", [None, None])[0] = [fp] * 6 + [C.c_int, C.c_int, C.c_float, vp]
-    sig.setdefault("tmjx_silu_ln_bwd", [None, None])[0] = [fp] * 8 + [C.c_int, C.c_int, vp]
-    sig.setdefault("tmjx_silu_ln_fwd_bf16", [None, None])[0] = [fp] * 5 + [C.c_int, fp, C.c_int, C.c_int, C.c_float, vp]
-    sig.setdefault("tmjx_silu_ln_bwd_bf16", [None, None])[0] = [fp] * 6 + [C.c_int, fp, fp, C.c_int, C.c_int, vp]
-    sig.setdefault("tmjx_gather_normalize", [None, None])[0] = [fp] * 5 + [C.c_int] * 4 + [vp]
-    sig.setdefault("tmjx_gather_minibatch", [None, None])[0] = [fp] * 14 + [C.c_int] * 5 + [vp]
-    sig.setdefault("tmjx_minibatch_begin", [None, None])[0] = [C.POINTER(Minibatch), vp]
-    sig.setdefault("tmjx_minibatch_begin_bf16", [None, None])[0] = [C.POINTER(Minibatch), fp, C.c_int, vp]
-    sig.setdefault("tmjx_philox4x32_10", [None, None])[0] = [fp, fp, vp]
-    sig.setdefault("tmjx_latent_concat", [None, None])[0] = [fp] * 4 + [C.c_int] * 4 + [C.c_int64, C.c_int64, fp, fp, C.c_int, C.c_uint64, fp, vp]
-    sig.setdefault("tmjx_latent_concat_bwd", [None, None])[0] = [fp] * 4 + [C.c_int] * 3 + [vp]
-    sig.setdefault("tmjx_latent_concat_bwd_add", [None, None])[0] = [fp] * 5 + [C.c_int] * 3 + [vp]
-    sig.setdefault("tmjx_sample_action", [None, None])[0] = [fp] * 5 + [C.c_int, C.c_int, C.c_uint64, fp, vp]
-    sig.setdefault("tmjx_linear_nolds", [None, None])[0] = [fp, C.c_int64, C.c_int64, fp, fp, fp, C.c_int, C.c_int, C.c_int, vp]
-    sig.setdefault("tmjx_linear_act", [None, None])[0] = [fp, C.c_int64, fp, C.c_int, fp, fp, C.c_int, C.c_int, C.c_int, fp, fp, vp]
-    sig.setdefault("tmjx_linear_act_ok", [None, None])[0] = [fp, C.c_int64, fp, C.c_int, C.c_int]
-    sig.setdefault("tmjx_linear_nolds_norm", [None, None])[0] = [fp, C.c_int64, C.c_int64, fp, fp, fp, C.c_int, C.c_int, C.c_int, fp, fp, vp]
-    sig.setdefault("tmjx_linear_nolds_bf16", [None, None])[0] = [fp, C.c_int64, C.c_int64, fp, C.c_int, fp, fp, C.c_int, C.c_int, C.c_int, fp, fp, vp]
-    sig.setdefault("tmjx_colsum_scratch_floats", [None, None])[0] = [C.c_int]
-    sig.setdefault("tmjx_colsum", [None, None])[0] = [fp, fp, fp, C.c_int, C.c_int, vp]
-    sig.setdefault("tmjx_adam_clip", [None, None])[0] = [fp] * 5 + [C.c_longlong] + [C.c_float] * 7 + [vp]
-    sig.setdefault("tmjx_adam_clip_norm", [None, None])[0] = [fp] * 6 + [C.c_longlong] + [C.c_float] * 7 + [vp]
-    sig.setdefault("tmjx_adam_clip_norm_frozen", [None, None])[0] = [fp] * 6 + [C.c_longlong] * 3 + [C.c_float] * 7 + [vp]
-    sig.setdefault("tmjx_gemm_nt", [None, None])[0] = [fp, C.c_int, fp, C.c_int, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
-    sig.setdefault("tmjx_gemm_nt_silu_ln_ok", [None, None])[0] = [fp, C.c_int, fp, C.c_int, C.c_int]
-    sig.setdefault("tmjx_gemm_nt_silu_ln", [None, None])[0] = [fp, C.c_int, fp, C.c_int, fp, fp, fp, fp, fp, C.c_int, fp, C.c_int, C.c_int, C.c_int, C.c_float, vp]
-    sig.setdefault("tmjx_colsum_grouped", [None, None])[0] = [C.POINTER(ColsumProblem), C.c_int, vp]
-    sig.setdefault("tmjx_gemm_nn_ln_bwd_ok", [None, None])[0] = [fp, C.c_int, fp, C.c_int, C.c_int]
-    sig.setdefault("tmjx_gemm_nn_ln_bwd_partial_floats", [None, None])[0] = [C.c_int, C.c_int]
-    sig.setdefault("tmjx_gemm_nn_ln_bwd_partial_floats", [None, None])[1] = C.c_longlong
-    sig.setdefault("tmjx_gemm_nn_ln_bwd", [None, None])[0] = [fp, C.c_int, fp, C.c_int, fp, fp, fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, vp]
-    sig.setdefault("tmjx_gemm_nn", [None, None])[0] = [fp, C.c_int, fp, C.c_int, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
-    sig.setdefault("tmjx_gemm_dw_scratch_floats", [None, None])[0] = [C.c_int, C.c_int, C.c_int]
-    sig.setdefault("tmjx_gemm_dw_scratch_floats", [None, None])[1] = C.c_longlong
-    sig.setdefault("tmjx_gemm_dw", [None, None])[0] = [fp, C.c_int, fp, C.c_int, fp, fp, fp, C.c_int, C.c_int, C.c_int, vp]
-    sig.setdefault("tmjx_gemm_dw_grouped", [None, None])[0] = [C.POINTER(DwProblem), C.c_int, vp]
-    sig.setdefault("tmjx_gemm_nt_silu_ok", [None, None])[0] = [fp, C.c_int, fp, C.c_int]
-    sig.setdefault("tmjx_gemm_nt_silu", [None, None])[0] = [fp, C.c_int, fp, C.c_int, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
-    sig.setdefault("tmjx_silu_fwd", [None, None])[0] = [fp, fp, fp, C.c_longlong, C.c_int, vp]
-    sig.setdefault("tmjx_silu_bwd", [None, None])[0] = [fp, fp, fp, fp, C.c_longlong, C.c_int, vp]
-    sig.setdefault("tmjx_gemm_nn_silu_bwd_ok", [None, None])[0] = [fp, C.c_int, fp, C.c_int]
-    sig.setdefault("tmjx_gemm_nn_silu_bwd", [None, None])[0] = [fp, C.c_int, fp, C.c_int, fp, fp, fp, C.c_int, C.c_int, C.c_int, vp]
-    sig.setdefault("tmjx_silu_bwd_rank1", [None, None])[0] = [fp, fp, fp, fp, fp, C.c_longlong, C.c_int, vp]
-    sig.setdefault("tmjx_head_dw_scratch_floats", [None, None])[0] = [C.c_int, C.c_int]
-    sig.setdefault("tmjx_head_dw_scratch_floats", [None, None])[1] = C.c_longlong
-    sig.setdefault("tmjx_head_dw", [None, None])[0] = [fp, fp, C.c_int, fp, fp, fp, C.c_int, C.c_int, vp]
-    sig.setdefault("tmjx_head_fwd_ok", [None, None])[0] = [fp, C.c_int, fp, C.c_int]
-    sig.setdefault("tmjx_head_fwd", [None, None])[0] = [fp, C.c_int, fp, fp, fp, C.c_int, C.c_int, vp]
-    sig.setdefault("tmjx_rollout_store", [None, None])[0] = [C.POINTER(RolloutStore), vp]
-    sig.setdefault("tmjx_clips_share", [None, None])[0] = [vp, vp]
-    sig.setdefault("tmjx_bf16_shadow", [None, None])[0] = [C.POINTER(Bf16Shadow), C.c_int, vp]
-    sig.setdefault("tmjx_bgemm_nt", [None, None])[0] = [fp, C.c_int, C.c_int, fp, C.c_int, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
-    sig.setdefault("tmjx_bgemm_row_tile_ok", [None, None])[0] = [C.c_int]
-    sig.setdefault("tmjx_bgemm_partial_floats", [None, None])[0] = [C.c_int, C.c_int, C.c_int]
-    sig.setdefault("tmjx_bgemm_partial_floats", [None, None])[1] = C.c_longlong
-    sig.setdefault("tmjx_bgemm_ln_fwd", [None, None])[0] = [fp, C.c_int, C.c_int, fp, C.c_int, fp, fp, fp, fp, C.c_int, fp, C.c_int, fp, C.c_int, C.c_int, C.c_int, C.c_float, vp]
-    sig.setdefault("tmjx_bgemm_ln_bwd", [None, None])[0] = [fp, C.c_int, C.c_int, fp, C.c_int, fp, C.c_int, fp, fp, fp, fp, C.c_int, fp, C.c_int, C.c_int, C.c_int, vp]
-    sig.setdefault("tmjx_bgemm_silu_fwd", [None, None])[0] = [fp, C.c_int, C.c_int, fp, C.c_int, fp, fp, C.c_int, fp, C.c_int, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
-    sig.setdefault("tmjx_bgemm_silu_bwd", [None, None])[0] = [fp, C.c_int, C.c_int, fp, C.c_int, fp, C.c_int, fp, fp, C.c_int, fp, C.c_int, C.c_int, C.c_int, vp]
-    sig.setdefault("tmjx_bf_silu_bwd", [None, None])[0] = [fp, C.c_int, fp, C.c_int, fp, fp, C.c_int, fp, C.c_int, C.c_int, vp]
-    sig.setdefault("tmjx_bf_silu_bwd_rank1", [None, None])[0] = [fp, fp, fp, C.c_int, fp, fp, C.c_int, fp, C.c_int, C.c_int, vp]
-    sig.setdefault("tmjx_bgemm_dw_scratch_floats", [None, None])[0] = [C.c_int, C.c_int, C.c_int]
-    sig.setdefault("tmjx_bgemm_dw_scratch_floats", [None, None])[1] = C.c_longlong
-    sig.setdefault("tmjx_bgemm_dw", [None, None])[0] = [fp, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, C.c_int, fp, fp, C.c_int, C.c_int, C.c_int, vp]
-    sig.setdefault("tmjx_bgemm_dw_grouped", [None, None])[0] = [C.POINTER(BdwProblem), C.c_int, C.c_int, vp]
-    sig.setdefault("tmjx_set_wrappers", [None, None])[0] = [vp, C.c_int, C.c_int]
-    sig.setdefault("tmjx_set_action_repeat", [None, None])[0] = [vp, C.c_int]
-    sig.setdefault("tmjx_set_done_policy", [None, None])[0] = [vp, C.c_int]
-    sig.setdefault("tmjx_set_env_scales", [None, None])[0] = [vp, fp, C.c_int]
-    sig.setdefault("tmjx_set_env_gravity", [None, None])[0] = [vp, fp, C.c_int]
-    sig.setdefault("tmjx_clips_upload_velocities", [None, None])[0] = [vp, vp, vp, C.c_int, C.c_int]
-    sig.setdefault("tmjx_stats_scratch_floats", [None, None])[0] = [C.c_int]
-    sig.setdefault("tmjx_stats_sums", [None, None])[0] = [fp, fp, fp, fp, C.c_longlong, C.c_int, vp]
-    sig.setdefault("tmjx_stats_apply", [None, None])[0] = [fp, C.c_float, fp, fp, fp, fp, C.c_int, C.c_float, C.c_float, vp]
-    sig.setdefault("tmjx_stats_apply_pinned", [None, None])[0] = [fp, C.c_float, fp, fp, fp, fp, C.c_int, C.c_int, C.c_float, C.c_float, vp]
-    sig.setdefault("tmjx_chain_rows", [None, None])[0] = [C.c_int]
-    sig.setdefault("tmjx_chain_fwd_ok", [None, None])[0] = [C.POINTER(ChainFwd)]
-    sig.setdefault("tmjx_chain_fwd", [None, None])[0] = [C.POINTER(ChainFwd), vp]
-    sig.setdefault("tmjx_chain_bwd_ok", [None, None])[0] = [C.POINTER(ChainBwd)]
-    sig.setdefault("tmjx_chain_bwd", [None, None])[0] = [C.POINTER(ChainBwd), vp]
-    sig.setdefault("tmjx_lstm_hidden_ok", [None, None])[0] = [C.c_int]
-    sig.setdefault("tmjx_lstm_seq_fwd", [None, None])[0] = [C.POINTER(LstmFwd), vp]
-    sig.setdefault("tmjx_lstm_seq_bwd", [None, None])[0] = [C.POINTER(LstmBwd), vp]
-    sig.setdefault("tmjx_record_check", [None, None])[0] = [C.POINTER(RecordStream), C.c_int, C.c_int, C.c_int]
-    sig.setdefault("tmjx_record_step", [None, None])[0] = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
-    sig.setdefault("tmjx_latent_concat_det", [None, None])[0] = [fp, C.c_int, fp, C.c_int64, C.c_int64, fp, fp, fp, C.c_int, fp, C.c_int] + [C.c_int] * 4 + [vp]
-    sig.setdefault("tmjx_action_mode", [None, None])[0] = [fp, C.c_int, fp, fp, C.c_int, C.c_int, vp]
-    sig.setdefault("tmjx_decoder_input", [None, None])[0] = [fp, C.c_int, fp, C.c_int64, C.c_int64, fp, fp, fp, C.c_int] + [C.c_int] * 4 + [vp]
-    sig.setdefault("tmjx_decoder_act_ok", [None, None])[0] = [C.POINTER(DecoderAct)]
-    sig.setdefault("tmjx_decoder_act", [None, None])[0] = [C.POINTER(DecoderAct), vp]
-    sig.setdefault("tmjx_lstm_decoder_act_ok", [None, None])[0] = [C.POINTER(LstmDecoderAct)]
-    sig.setdefault("tmjx_lstm_decoder_act", [None, None])[0] = [C.POINTER(LstmDecoderAct), vp]
-    sig.setdefault("tmjx_policy_act_ok", [None, None])[0] = [C.POINTER(PolicyAct)]
-    sig.setdefault("tmjx_policy_act", [None, None])[0] = [C.POINTER(PolicyAct), vp]
-    sig.setdefault("tmjx_render_info", [None, None])[0] = [vp, C.c_int, C.c_int, C.POINTER(RenderInfo)]
-    sig.setdefault("tmjx_render_camera", [None, None])[0] = [vp, C.c_char_p, C.POINTER(Camera)]
-    sig.setdefault("tmjx_render_pose", [None, None])[0] = [vp, fp, fp, C.c_int, C.c_int, C.POINTER(Camera), fp, vp]
-    sig.setdefault("tmjx_render_prims", [None, None])[0] = [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp, fp, vp, vp]
-    sig.setdefault("tmjx_render", [None, None])[0] = [vp, fp, fp, C.c_int, C.c_int, C.POINTER(Camera), C.c_int, C.c_int, fp, vp, fp, vp, vp]
-    sig.setdefault("tmjx_pca_workspace", [None, None])[0] = [C.c_int, C.c_int, C.POINTER(C.c_int64)]
-    sig.setdefault("tmjx_pca_fit", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, fp, fp, fp, fp, C.POINTER(PcaInfo), vp]
-    sig.setdefault("tmjx_pca_transform", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, fp, fp, C.c_int, fp, C.c_int64, vp]
-    sig.setdefault("tmjx_pca_wide_workspace", [None, None])[0] = [C.c_int, C.c_int, C.POINTER(C.c_int64)]
-    sig.setdefault("tmjx_pca_fit_wide", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, fp, fp, fp, fp, C.POINTER(PcaInfo), vp]
-    sig.setdefault("tmjx_pca_transform_wide", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, fp, fp, C.c_int, fp, C.c_int64, vp]
-    sig.setdefault("tmjx_readout_workspace", [None, None])[0] = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
-    sig.setdefault("tmjx_readout_fit", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, fp, C.c_int, C.c_int64, fp, fp, fp, fp, fp, fp, C.POINTER(PcaInfo), vp]
-    sig.setdefault("tmjx_readout_weights", [None, None])[0] = [fp, fp, fp, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, fp, vp]
-    sig.setdefault("tmjx_readout_predict", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, fp, fp, fp, C.c_int, fp, C.c_int64, vp]
-    sig.setdefault("tmjx_readout_score", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, fp, C.c_int, C.c_int64, fp, fp, fp, C.c_int, fp, fp, fp, vp]
-    sig.setdefault("tmjx_intervene_ok", [None, None])[0] = [C.POINTER(Intervene)]
-    sig.setdefault("tmjx_intervene", [None, None])[0] = [C.POINTER(Intervene), C.c_int, vp]
-    sig.setdefault("tmjx_kmeans_workspace", [None, None])[0] = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
-    sig.setdefault("tmjx_kmeans_assign", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, fp, C.c_int, vp, vp, fp, vp, vp, fp, vp]
-    sig.setdefault("tmjx_kmeans_update", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, vp, C.c_int, fp, vp, fp, vp]
-    sig.setdefault("tmjx_kmeans_seed", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_double), fp, C.POINTER(C.c_int32), fp, vp]
-    sig.setdefault("tmjx_kmeans_fit", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, C.c_int, fp, vp, fp, C.c_int, C.c_double, C.POINTER(KMeansInfo), fp, vp]
-    i32p, dbl = C.POINTER(C.c_int32), C.c_double
-    sig.setdefault("tmjx_hmm_workspace", [None, None])[0] = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
-    sig.setdefault("tmjx_hmm_emission", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, fp, fp, C.c_int, fp, fp, vp]
-    sig.setdefault("tmjx_hmm_forward_backward", [None, None])[0] = [fp, C.c_int, C.c_int, i32p, C.c_int, fp, fp, fp, vp, vp, vp, vp, fp, vp]
-    sig.setdefault("tmjx_hmm_mstep", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, fp, C.c_int, dbl, dbl, fp, fp, vp, fp, vp]
-    sig.setdefault("tmjx_hmm_transitions", [None, None])[0] = [vp, vp, C.c_int, dbl, dbl, fp, fp, vp]
-    sig.setdefault("tmjx_hmm_viterbi", [None, None])[0] = [fp, C.c_int, C.c_int, i32p, C.c_int, fp, fp, C.c_int, vp, vp, fp, vp]
-    sig.setdefault("tmjx_hmm_fit", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, i32p, C.c_int, C.c_int, fp, fp, fp, fp, fp, vp, C.c_int, dbl, dbl, dbl, dbl,
-                                                       dbl, C.POINTER(HmmInfo), fp, vp]
-    dblp = C.POINTER(C.c_double)
-    sig.setdefault("tmjx_wavelet_bank_size", [None, None])[0] = [dbl, dblp, C.c_int, dbl, dbl, C.POINTER(C.c_int64)]
-    sig.setdefault("tmjx_wavelet_bank", [None, None])[0] = [dbl, dblp, C.c_int, dbl, dbl, vp, i32p, i32p]
-    sig.setdefault("tmjx_spectrogram_workspace", [None, None])[0] = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
-    sig.setdefault("tmjx_spectrogram", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, i32p, C.c_int, fp, i32p, i32p, C.c_int, C.c_int, C.c_int, C.c_float, fp,
-                                                           C.c_int64, fp, fp, vp]
-    sig.setdefault("tmjx_plot_strips", [None, None])[0] = [fp, C.c_int, C.c_int, C.c_int64, vp, vp, C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(StripStyle),
-                                                           C.c_int, C.c_int, vp, vp]
-    sig.setdefault("tmjx_debug_rows", [None, None])[0] = [vp, C.c_char_p, ip, ip]
-    sig.setdefault("tmjx_last_error", [None, None])[1] = C.c_char_p
-    sig.setdefault("tmjx_version", [None, None])[1] = C.c_char_p
-    restype_set = {"tmjx_model_destroy"}
-    for name, (argtypes, restype) in sig.items():
-        fn = getattr(L, name, None)      # a library may export a subset (the oracle's ABI twin has no learner kernels): calling a missing one raises
-        if fn is None:
-            continue
-        if argtypes is not None:
-            fn.argtypes = argtypes
-        if restype is not None or name in restype_set:
-            fn.restype = restype
+    declare(L)
     return L
 
 
