@@ -934,6 +934,51 @@ int tmjx_hmm_fit(const float *x, int n, int d, int64_t ldx, const int32_t *seq_s
                  float *startprob, float *gamma, int32_t *labels, int max_iter, double tol, double prior, double kappa, double min_var, double min_weight,
                  tmjx_hmm_info_t *info, float *workspace, void *stream);
 
+/* ---- An autoregressive hidden Markov model over recorded signals x [n][d] (1 <= d <= 32): every one of 1 <= k <= 128 states is its own linear
+ * law x_t ~ A_j x_(t-1) + .. + b_j with diagonal noise (csrc/tmjx_arhmm.hip, csrc/arhmm_core.h; DESIGN.md "Autoregressive sequence model").  The
+ * conventions of tmjx_hmm_*: no model handle; all device memory is the caller's; everything runs on the caller's stream; ldx >= d; seq_start
+ * [S + 1] is a HOST array, checked there and copied to the workspace on the stream (it must stay valid until the queued work has run;
+ * tmjx_arhmm_fit waits itself); fixed-order arithmetic, no floating-point atomics: the same bits on every run and at every row stride.
+ *   Rows and scoring: 0 <= lags <= 4, lags d <= 128, warmup >= lags.  Row t of a sequence starting at t0 is SCORED when t - t0 >= warmup.  An
+ *     unscored row has logb = 0 for every state and adds nothing to the moments: the model conditions on it, the chain still runs through it.  No
+ *     lag reads across a sequence boundary; a sequence of `warmup` rows or fewer is entirely unscored (a defined result).
+ *   Coordinates: xc = x - center in float32, rounded once; center [d] (device) may be null: zeros.
+ *   Regressor: phi_t = [xc_(t-1); ..; xc_(t-lags); 1], p = lags d + 1 columns: column l d + c multiplies feature c at lag l + 1, the last column is
+ *     the intercept.  psi_t = [phi_t; xc_t], q = p + d columns.
+ *   Parameters (device float32): weights [k][d][p], vars [k][d], center [d].
+ *   tmjx_arhmm_workspace: *floats = the scratch of every call below for these n, d, lags, k, S, with what the reused tmjx_hmm_* steps take
+ *     (tmjx_hmm_workspace(n, 1, k, S)).  The row split of the moment sums depends on n, k and q only.
+ *   tmjx_arhmm_emission: logb [n][k].  Per (row, state), the features c in ascending order: pred = the intercept, one fmaf per regressor column in
+ *     ascending column order, r = xc - pred, q = fmaf(r, r (1 / var), q); logb = fmaf(-1/2, q, c_j), c_j = -1/2 sum_c log(2 pi var_jc) in float64
+ *     rounded once.  With lags = 0, warmup = 0, a null center and the intercepts as means this gives the bits of tmjx_hmm_emission.
+ *   tmjx_arhmm_moments: moments [k][q][q] (device float64) = sum over the scored rows of gamma_tj psi_t psi_t^T, weight [k] (device float64) =
+ *     sum over the scored rows of gamma_tj.  Float64 from the first product (gamma psi_a in double, one fma with psi_b), summed in row order over
+ *     fixed row parts, the parts in part order; both triangles are written and hold the same bits.
+ *   tmjx_arhmm_solve: per state, in float64: G = M[:p,:p] + ridge diag(1, .., 1, 0) (the intercept is not penalised), C = M[p:, :p]; Cholesky in a
+ *     fixed order, W = C G^-1, var_c = max((M_xx[c][c] - W_c . C_c) / w, min_var), means_j = center + C[:, p - 1] / w (the state's weighted mean of
+ *     x; means [k][d] is optional); everything rounded once.  status [k] (device int32): 0 updated, 1 light (w < min_weight or w <= 0), 2 a
+ *     pivot <= 0.  A state with status 1 or 2 keeps the bits of its weights, vars and means.
+ *   tmjx_arhmm_fit: EM exactly as tmjx_hmm_fit runs it (the same stopping rule, one read-back per iteration, the final emission, forward-backward
+ *     and Viterbi), with tmjx_arhmm_emission where the Gaussian emission stood and tmjx_arhmm_moments + tmjx_arhmm_solve where the M-step stood.
+ *     The parameters are updated in place; gamma [n][k] and status [k] are optional; info->n_singular counts the states the last M-step found
+ *     singular.  It WAITS for the stream.
+ * Each returns TMJX_EINVAL before any launch, with a message that names the value, for n < 1, d, lags, lags d or k outside the limits,
+ * warmup < lags, S < 1 or S > n, a seq_start that breaks the rules, ldx < d, a null required pointer, a workspace that is not 16-byte aligned,
+ * max_iter < 1, or a tol, prior, kappa, ridge, min_var or min_weight that is negative or NaN. */
+#define ARHMM_MAX_D 32
+#define ARHMM_MAX_LAGS 4
+typedef struct { int32_t n_iter, converged; double loglik; float emission_ms, fb_ms, mstep_ms, viterbi_ms; int32_t n_singular, pad_; } tmjx_arhmm_info_t;
+int tmjx_arhmm_workspace(int n, int d, int lags, int k, int S, int64_t *floats);
+int tmjx_arhmm_emission(const float *x, int n, int d, int64_t ldx, const int32_t *seq_start, int S, int lags, int warmup, const float *center,
+                        const float *weights, const float *vars, int k, float *logb, float *workspace, void *stream);
+int tmjx_arhmm_moments(const float *x, int n, int d, int64_t ldx, const int32_t *seq_start, int S, int lags, int warmup, const float *center,
+                       const float *gamma, int k, double *moments, double *weight, float *workspace, void *stream);
+int tmjx_arhmm_solve(const double *moments, const double *weight, int k, int d, int lags, const float *center, double ridge, double min_var, double min_weight,
+                     float *weights, float *vars, float *means, int32_t *status, float *workspace, void *stream);
+int tmjx_arhmm_fit(const float *x, int n, int d, int64_t ldx, const int32_t *seq_start, int S, int lags, int warmup, const float *center, int k, float *weights,
+                   float *vars, float *transmat, float *startprob, float *gamma, int32_t *labels, int32_t *status, int max_iter, double tol, double prior,
+                   double kappa, double ridge, double min_var, double min_weight, tmjx_arhmm_info_t *info, float *workspace, void *stream);
+
 /* ---- Morlet wavelet spectrograms of recorded signals x [n][C] (1 <= C <= 1024) at 1 <= F <= 64 centre frequencies (csrc/tmjx_spectrogram.hip,
  * csrc/spectrogram_core.h; DESIGN.md "Spectrogram").  The conventions of tmjx_hmm_*: no model handle; all device memory is the caller's; everything
  * runs on the caller's stream; x is float32 and may be a column slice of a wider buffer (ldx >= C); the rows form S sequences given by

@@ -1,4 +1,4 @@
-"""The analysis entry points of the C-ABI (include/tmjx.h: tmjx_pca_*, tmjx_plot_strips, tmjx_readout_*, tmjx_kmeans_*, tmjx_hmm_*,
+"""The analysis entry points of the C-ABI (include/tmjx.h: tmjx_pca_*, tmjx_plot_strips, tmjx_readout_*, tmjx_kmeans_*, tmjx_hmm_*, tmjx_arhmm_*,
 tmjx_wavelet_bank*, tmjx_spectrogram*) as methods on arrays.
 
 `Backend` marshals every call once, against a small provider of arrays: what differs between the device and a host is how an array is uploaded,
@@ -241,6 +241,67 @@ class Backend:
         self._call("tmjx_hmm_fit", p.ptr(x), n, d, p.ld(x), seq_p, S, k, p.ptr(mu), p.ptr(var), p.ptr(A), p.ptr(pi), p.ptr(gamma), p.ptr(labels),
                    int(max_iter), float(tol), float(prior), float(kappa), float(min_var), float(min_weight), C.byref(info), p.ptr(ws), p.stream())
         return (*(p.to_numpy(t) for t in (mu, var, A, pi, gamma, labels)), info)
+
+    # the autoregressive HMM (analysis/arhmm.py; tmjx_arhmm_*): x from asarray; center [d], weights [k, d, p], vars [k, d] float32 numpy (copied);
+    # center=None is the null pointer (zeros)
+    def arhmm_emission(self, x, seq_start, lags, warmup, center, weights, vars):
+        """-> logb [n, k] float32: the log density of every scored row under every state's linear law, 0 in the unscored rows (tmjx_arhmm_emission)."""
+        p = self._p
+        (n, d), k = x.shape, vars.shape[0]
+        seq, seq_p, S = self._seq(seq_start)
+        cen = None if center is None else p.upload(center, f32, copy=True)
+        W, var = p.upload(weights, f32, copy=True), p.upload(vars, f32, copy=True)
+        ws, logb = self._workspace("tmjx_arhmm_workspace", n, d, int(lags), k, S), p.empty((n, k), f32)
+        with p.guard():
+            p.check(p.lib.tmjx_arhmm_emission(p.ptr(x), n, d, p.ld(x), seq_p, S, int(lags), int(warmup), None if cen is None else p.ptr(cen), p.ptr(W), p.ptr(var),
+                                              k, p.ptr(logb), p.ptr(ws), p.stream()), "tmjx_arhmm_emission")
+            p.sync()      # (the host offsets must outlive the queued copy)
+        return p.to_numpy(logb)
+
+    def arhmm_moments(self, x, seq_start, lags, warmup, center, gamma):
+        """-> (moments [k, q, q], weight [k]) float64: the weighted Gram matrices of psi = [phi; xc] over the scored rows (tmjx_arhmm_moments)."""
+        p = self._p
+        (n, d), k = x.shape, gamma.shape[1]
+        seq, seq_p, S = self._seq(seq_start)
+        q = (int(lags) + 1) * d + 1
+        cen = None if center is None else p.upload(center, f32, copy=True)
+        g, ws = p.upload(gamma, f32, copy=True), self._workspace("tmjx_arhmm_workspace", n, d, int(lags), k, S)
+        moments, weight = p.empty((k, q, q), f64), p.empty((k,), f64)
+        with p.guard():
+            p.check(p.lib.tmjx_arhmm_moments(p.ptr(x), n, d, p.ld(x), seq_p, S, int(lags), int(warmup), None if cen is None else p.ptr(cen), p.ptr(g), k,
+                                             p.ptr(moments), p.ptr(weight), p.ptr(ws), p.stream()), "tmjx_arhmm_moments")
+            p.sync()
+        return p.to_numpy(moments), p.to_numpy(weight)
+
+    def arhmm_solve(self, moments, weight, d, lags, center, weights, vars, ridge=0.0, min_var=0.0, min_weight=0.0, means=None):
+        """-> (weights [k, d, p], vars [k, d], means [k, d] float32, status [k] int32): every state's ridge regression from its moments; a light
+        (status 1) or singular (2) state as given, its row of `means` (zeros without one) too (tmjx_arhmm_solve)."""
+        p = self._p
+        k = vars.shape[0]
+        cen = None if center is None else p.upload(center, f32, copy=True)
+        M, w = p.upload(moments, f64), p.upload(weight, f64)
+        W, var = p.upload(weights, f32, copy=True), p.upload(vars, f32, copy=True)
+        mu = p.upload(np.zeros((k, d), f32) if means is None else means, f32, copy=True)
+        status, ws = p.empty((k,), i32), self._workspace("tmjx_arhmm_workspace", 1, d, int(lags), k, 1)
+        self._call("tmjx_arhmm_solve", p.ptr(M), p.ptr(w), k, d, int(lags), None if cen is None else p.ptr(cen), float(ridge), float(min_var), float(min_weight),
+                   p.ptr(W), p.ptr(var), p.ptr(mu), p.ptr(status), p.ptr(ws), p.stream())
+        return p.to_numpy(W), p.to_numpy(var), p.to_numpy(mu), p.to_numpy(status)
+
+    def arhmm_fit(self, x, seq_start, lags, warmup, center, weights, vars, transmat, startprob, max_iter=50, tol=1e-4, prior=0.0, kappa=0.0, ridge=0.0,
+                  min_var=0.0, min_weight=0.0):
+        """EM from the parameters given -> (weights, vars, transmat, startprob, gamma [n, k], labels [n] int32, status [k] int32) numpy and the call's
+        hip.ArhmmInfo (tmjx_arhmm_fit)."""
+        p = self._p
+        (n, d), k = x.shape, vars.shape[0]
+        seq, seq_p, S = self._seq(seq_start)
+        cen = None if center is None else p.upload(center, f32, copy=True)
+        W, var, A, pi = (p.upload(a, f32, copy=True) for a in (weights, vars, transmat, startprob))
+        ws, info = self._workspace("tmjx_arhmm_workspace", n, d, int(lags), k, S), _hip.ArhmmInfo()
+        gamma, labels, status = p.empty((n, k), f32), p.empty((n,), i32), p.empty((k,), i32)
+        self._call("tmjx_arhmm_fit", p.ptr(x), n, d, p.ld(x), seq_p, S, int(lags), int(warmup), None if cen is None else p.ptr(cen), k, p.ptr(W), p.ptr(var),
+                   p.ptr(A), p.ptr(pi), p.ptr(gamma), p.ptr(labels), p.ptr(status), int(max_iter), float(tol), float(prior), float(kappa), float(ridge),
+                   float(min_var), float(min_weight), C.byref(info), p.ptr(ws), p.stream())
+        return (*(p.to_numpy(t) for t in (W, var, A, pi, gamma, labels, status)), info)
 
     # the wavelet spectrogram (analysis/spectrogram.py; tmjx_wavelet_bank*, tmjx_spectrogram*): x from asarray, the bank as wavelet_bank returns it
     def wavelet_bank(self, rate, freqs, omega0=5.0, support=4.0):
