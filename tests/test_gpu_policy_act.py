@@ -140,19 +140,24 @@ def test_equal_to_the_old_launches_with_the_callers_draws(M):
     assert_same(run_new(N, M, eps, noise), run_old(N, M, eps, noise), f"M = {M}")
 
 
-@pytest.mark.parametrize("M", ROWS)
-def test_equal_to_the_old_launches_with_the_device_stream(M):
-    """Philox streams 2 / 3 on the device: the same draws, the same advance of the draw counter, and fresh noise on the next call."""
+# (the cases at counter 5 keep the ids they had before the counter became a parameter)
+@pytest.mark.parametrize("M,ctr", [(M, c) for c in (5, 2 ** 32 + 5) for M in ROWS], ids=[f"{M}" if c == 5 else f"{M}-high-counter" for c in (5, 2 ** 32 + 5) for M in ROWS])
+def test_equal_to_the_old_launches_with_the_device_stream(M, ctr):
+    """Philox streams 2 / 3 on the device: the same draws, the same advance of the draw counter, and fresh noise on the next call; from a counter with
+    its high word clear and set (tests/test_gpu_noise_gather.py states what the launch sequence draws, element for element)."""
     N = nets()
     seed = 0x1234567887654321
-    st_new, st_old = (torch.tensor([5, 0], dtype=torch.long, device=DEV) for _ in range(2))
+    st_new, st_old = (torch.tensor([ctr, 0], dtype=torch.long, device=DEV) for _ in range(2))
     new, old = run_new(N, M, seed=seed, rng_state=st_new), run_old(N, M, seed=seed, rng_state=st_old)
     assert_same(new, old, f"M = {M}, first call")
-    assert st_new.tolist() == [6, 0] and torch.equal(st_new, st_old)
+    assert st_new.tolist() == [ctr + 1, 0] and torch.equal(st_new, st_old)
     new2, old2 = run_new(N, M, seed=seed, rng_state=st_new), run_old(N, M, seed=seed, rng_state=st_old)
     assert_same(new2, old2, f"M = {M}, second call")
-    assert st_new.tolist() == [7, 0] and torch.equal(st_new, st_old)
+    assert st_new.tolist() == [ctr + 2, 0] and torch.equal(st_new, st_old)
     assert torch.equal(new2["fc2"], new["fc2"]) and not torch.equal(new2["raw"], new["raw"])      # same nets and observation, different noise
+    if ctr >> 32:      # the counter's high word is part of the draw: the same low word alone gives other noise
+        low = run_new(N, M, seed=seed, rng_state=torch.tensor([ctr & 0xFFFFFFFF, 0], dtype=torch.long, device=DEV))
+        assert torch.equal(low["fc2"], new["fc2"]) and not torch.equal(low["raw"], new["raw"])
 
 
 def test_whole_policy_against_float64_torch():

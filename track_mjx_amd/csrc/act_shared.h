@@ -25,7 +25,7 @@ __device__ __forceinline__ void tm_philox4x32_10(unsigned c0, unsigned c1, unsig
   }
   out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
-// four N(0, 1) draws for elements 4 q .. 4 q + 3 of stream `sid` at draw counter `ctr` (Box-Muller on 24-bit uniforms in (0, 1))
+// four N(0, 1) draws for elements 4 q .. 4 q + 3 of stream `sid` at draw counter `ctr` (Box-Muller on 24-bit uniforms in (0, 1]: from 2^23 up + 0.5f rounds to even, the top value gives 1.0 and a radius of 0)
 __device__ __forceinline__ void tm_normal4(unsigned long long seed, unsigned long long ctr, unsigned sid, unsigned q, float *n) {
   unsigned x[4];
   tm_philox4x32_10(q, sid, (unsigned)ctr, (unsigned)(ctr >> 32), (unsigned)seed, (unsigned)(seed >> 32), x);
