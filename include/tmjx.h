@@ -979,6 +979,62 @@ int tmjx_arhmm_fit(const float *x, int n, int d, int64_t ldx, const int32_t *seq
                    float *vars, float *transmat, float *startprob, float *gamma, int32_t *labels, int32_t *status, int max_iter, double tol, double prior,
                    double kappa, double ridge, double min_var, double min_weight, tmjx_arhmm_info_t *info, float *workspace, void *stream);
 
+/* ---- A behaviour map of recorded features: exact k nearest neighbours, perplexity-calibrated affinities, an exact t-SNE embedding in two
+ * dimensions and the placement of further rows on it (csrc/tmjx_tsne.hip, csrc/tsne_core.h; DESIGN.md "Behaviour map").  The conventions of
+ * tmjx_kmeans_*: no model handle; all device memory is the caller's; everything runs on the caller's stream; rows of x and q are float32 and may
+ * carry a stride (ldx, ldq >= d); fixed-order arithmetic, every division correctly rounded, every sum across points, tiles or workgroups float64
+ * in a fixed order, no floating-point or integer atomics: the same bits on every run.  Limits: 1 <= d <= 1024, 2 <= n <= 65536 reference or
+ * training rows, 1 <= k <= 128 neighbours, m >= 1 queries.
+ *   tmjx_tsne_workspace: *floats = the scratch every call below takes for these n, m, d, k; one sized for (n, m, d, k) also serves the calls that
+ *     know n only.  It scales with n + m + n d / 256, never with n n or m n.
+ *   tmjx_knn: idx [m][k] (int32), dist2 [m][k] = the k nearest rows of x [n][d] to every row of q [m][d].  With mean = the float64 column mean of
+ *     x rounded to float32 (as tmjx_kmeans_assign forms it), qc = q - mean, xc_j = x_j - mean: score_j = ||xc_j||^2 - 2 qc . xc_j, the dot product
+ *     one fmaf chain per pair in ascending feature order, dist2 = max(0, ||qc||^2 + score_j).  Every list is sorted ascending by (dist2, index):
+ *     ties go to the lowest index.  The pass is fused: a workgroup owns 128 queries, walks the reference tiles staged in LDS and keeps every
+ *     query's running k best in LDS; the [m][n] distances are never written.  Row i is left out of query i's list when exclude_self != 0 AND the
+ *     search is of x against itself (q == x, m == n, ldq == ldx): then k <= n - 1; otherwise k <= n and exclude_self changes nothing.
+ *   tmjx_tsne_affinities: per row of dist2 [m][k], a bisection on beta of 100 iterations from beta = 1, so that the entropy of
+ *     p_j ~ exp(-beta (dist2_j - min_j dist2_j)) equals log(perplexity); float32 exponentials, float64 sums in list order; p [m][k] rounded once,
+ *     beta [m].  A row whose distances are all equal is the uniform row with beta = 1; a row whose entropy cannot fall to the target (too many
+ *     zeros) ends at beta = 2^100 and is uniform over its nearest.  1 <= perplexity < k.
+ *   tmjx_tsne_gradient: P is a symmetric CSR (row_ptr [n + 1] HOST int32: row_ptr[0] = 0, non-decreasing, row_ptr[n] = nnz, checked there and
+ *     copied to the workspace on the stream, so it must stay valid until the queued work has run; col [nnz] int32 ascending in a row, val [nnz]
+ *     float32, both on the device; a column outside [0, n) is skipped).  With dx, dy = y_i - y_j, q_ij = fma(dy, dy, fma(dx, dx, 1)) and
+ *     w_ij = 1 / q_ij in float32:  rep_i = sum_{j != i} (w w) (dx, dy) and Z = sum_{i != j} w, float32 products summed in float64 in index order
+ *     over fixed parts of the walk, the parts in part order, the points in point order (an all-pairs kernel: a workgroup owns 256 points and
+ *     walks tiles of 256 points staged in LDS);  attr_i = sum_j (P_ij w) (dx, dy) over the row in order, float64 sums;
+ *     grad_i = 4 (exaggeration attr_i - rep_i / Z) in float64, rounded once; *kl = sum P_ij log(P_ij Z / w_ij) over the stored entries with
+ *     P_ij > 0, float64, the unexaggerated P; *z = Z.  z and kl are device float64.
+ *   tmjx_tsne_update: delta-bar-delta.  Per component: gain += 0.2 where sign(grad) != sign(velocity), gain *= 0.8 where they agree, then
+ *     gain = max(gain, min_gain); velocity = momentum velocity - (eta gain) grad; y += velocity: single float32 operations, none fused.  y is then
+ *     recentred: its float64 column means (block sums in point order, blocks in block order) are subtracted in float64, rounded once.
+ *   tmjx_tsne_fit: n_iter iterations of gradient then update on the host side of the ABI: the first exaggeration_iters with `exaggeration`
+ *     and momentum_early, the rest with exaggeration 1 and momentum_late; then one more gradient at exaggeration 1, whose kl and z describe the y
+ *     returned (info->kl, info->z).  y, velocity and gains [n][2] are updated in place.  It equals its own steps bit for bit.  It WAITS for the
+ *     stream.
+ *   tmjx_tsne_place: y_out_i = sum_j p_ij y_train[idx_ij] in list order, a float32 product and a float32 add per term, none fused; an index
+ *     outside [0, n) is skipped.
+ * Each returns TMJX_EINVAL before any launch, with a message that names the value, for n, m, d or k outside the limits, k above the candidate
+ * rows, ldx or ldq < d, a perplexity outside [1, k), a row_ptr that breaks the rules or disagrees with nnz, an exaggeration or eta that is not
+ * positive and finite, a momentum outside [0, 1), a negative min_gain, n_iter outside 0 .. 100000, a null required pointer, a workspace that is
+ * not 16-byte aligned, or a misaligned array. */
+#define TSNE_MAX_D 1024
+#define TSNE_MAX_N 65536
+#define TSNE_MAX_K 128
+typedef struct { int32_t n_iter, pad_; double kl, z; float gradient_ms, update_ms; } tmjx_tsne_info_t;
+int tmjx_tsne_workspace(int n, int64_t m, int d, int k, int64_t *floats);
+int tmjx_knn(const float *x, int n, int d, int64_t ldx, const float *q, int64_t m, int64_t ldq, int exclude_self, int k, int32_t *idx, float *dist2,
+             float *workspace, void *stream);
+int tmjx_tsne_affinities(const float *dist2, int64_t m, int k, double perplexity, float *p, float *beta, void *stream);
+int tmjx_tsne_gradient(const float *y, int n, const int32_t *row_ptr, const int32_t *col, const float *val, int64_t nnz, double exaggeration, float *grad,
+                       double *z, double *kl, float *workspace, void *stream);
+int tmjx_tsne_update(float *y, const float *grad, float *velocity, float *gains, int n, float momentum, float eta, float min_gain, float *workspace,
+                     void *stream);
+int tmjx_tsne_fit(float *y, int n, const int32_t *row_ptr, const int32_t *col, const float *val, int64_t nnz, int n_iter, double exaggeration,
+                  int exaggeration_iters, float momentum_early, float momentum_late, float eta, float min_gain, float *velocity, float *gains,
+                  tmjx_tsne_info_t *info, float *workspace, void *stream);
+int tmjx_tsne_place(const int32_t *idx, const float *p, int64_t m, int k, const float *y_train, int n, float *y_out, void *stream);
+
 /* ---- Morlet wavelet spectrograms of recorded signals x [n][C] (1 <= C <= 1024) at 1 <= F <= 64 centre frequencies (csrc/tmjx_spectrogram.hip,
  * csrc/spectrogram_core.h; DESIGN.md "Spectrogram").  The conventions of tmjx_hmm_*: no model handle; all device memory is the caller's; everything
  * runs on the caller's stream; x is float32 and may be a column slice of a wider buffer (ldx >= C); the rows form S sequences given by

@@ -1,5 +1,5 @@
 """The analysis entry points of the C-ABI (include/tmjx.h: tmjx_pca_*, tmjx_plot_strips, tmjx_readout_*, tmjx_kmeans_*, tmjx_hmm_*, tmjx_arhmm_*,
-tmjx_wavelet_bank*, tmjx_spectrogram*) as methods on arrays.
+tmjx_wavelet_bank*, tmjx_spectrogram*, tmjx_knn, tmjx_tsne_*) as methods on arrays.
 
 `Backend` marshals every call once, against a small provider of arrays: what differs between the device and a host is how an array is uploaded,
 allocated, addressed and read back, not which arguments go where.  `HipBackend` is the backend on torch device tensors (`TorchArrays`), the one
@@ -302,6 +302,81 @@ class Backend:
                    p.ptr(A), p.ptr(pi), p.ptr(gamma), p.ptr(labels), p.ptr(status), int(max_iter), float(tol), float(prior), float(kappa), float(ridge),
                    float(min_var), float(min_weight), C.byref(info), p.ptr(ws), p.stream())
         return (*(p.to_numpy(t) for t in (W, var, A, pi, gamma, labels, status)), info)
+
+    # the behaviour map (analysis/embed.py; tmjx_knn, tmjx_tsne_*): x and q from asarray; idx int32 / dist2, p float32 numpy [m, k]; the CSR of P as
+    # (row_ptr int32 [n + 1], col int32 [nnz], val float32 [nnz]) numpy; y, velocity, gains float32 numpy [n, 2] (copied: the caller's stay)
+    def knn(self, x, q=None, k=1, exclude_self=False):
+        """-> (idx [m, k] int32, dist2 [m, k] float32): the k nearest rows of x to every row of q, sorted by (dist2, index).  q=None searches x
+        against itself; exclude_self then leaves row i out of query i's list (tmjx_knn)."""
+        p = self._p
+        q = x if q is None else q
+        (n, d), m = x.shape, q.shape[0]
+        if q.shape[1] != d:
+            raise ValueError(f"queries of {q.shape[1]} features against references of {d}")
+        ws = self._workspace("tmjx_tsne_workspace", n, m, d, int(k))
+        idx, dist2 = p.empty((m, max(int(k), 1)), i32), p.empty((m, max(int(k), 1)), f32)
+        self._call("tmjx_knn", p.ptr(x), n, d, p.ld(x), p.ptr(q), m, p.ld(q), int(bool(exclude_self)), int(k), p.ptr(idx), p.ptr(dist2), p.ptr(ws), p.stream())
+        return p.to_numpy(idx), p.to_numpy(dist2)
+
+    def tsne_affinities(self, dist2, perplexity):
+        """-> (p [m, k] float32: every row's conditional probabilities at the beta whose entropy is log(perplexity); beta [m] float32)
+        (tmjx_tsne_affinities)."""
+        p = self._p
+        m, k = dist2.shape
+        dd = p.upload(dist2, f32, copy=True)
+        out, beta = p.empty((m, k), f32), p.empty((m,), f32)
+        self._call("tmjx_tsne_affinities", p.ptr(dd), m, k, float(perplexity), p.ptr(out), p.ptr(beta), p.stream())
+        return p.to_numpy(out), p.to_numpy(beta)
+
+    def _csr(self, csr):
+        p = self._p
+        row_ptr, col, val = np.ascontiguousarray(csr[0], i32), p.upload(csr[1], i32, copy=True), p.upload(csr[2], f32, copy=True)
+        return row_ptr, row_ptr.ctypes.data_as(_I32P), col, val, int(np.shape(csr[1])[0])
+
+    def tsne_gradient(self, y, csr, exaggeration=1.0):
+        """-> (grad [n, 2] float32, Z, kl): one gradient of the t-SNE objective at y for the symmetric P = csr (tmjx_tsne_gradient)."""
+        p = self._p
+        n = y.shape[0]
+        row_ptr, rp, col, val, nnz = self._csr(csr)
+        yy, ws = p.upload(y, f32, copy=True), self._workspace("tmjx_tsne_workspace", n, 1, 1, 1)
+        grad, z, kl = p.empty((n, 2), f32), p.empty((1,), f64), p.empty((1,), f64)
+        with p.guard():
+            p.check(p.lib.tmjx_tsne_gradient(p.ptr(yy), n, rp, p.ptr(col), p.ptr(val), nnz, float(exaggeration), p.ptr(grad), p.ptr(z), p.ptr(kl), p.ptr(ws),
+                                             p.stream()), "tmjx_tsne_gradient")
+            p.sync()      # (the host offsets must outlive the queued copy)
+        return p.to_numpy(grad), float(z.item()), float(kl.item())
+
+    def tsne_update(self, y, grad, velocity, gains, momentum, eta, min_gain=0.01):
+        """-> (y, velocity, gains) [n, 2] float32: one delta-bar-delta step, y recentred (tmjx_tsne_update)."""
+        p = self._p
+        n = y.shape[0]
+        yy, g, v, ga = (p.upload(a, f32, copy=True) for a in (y, grad, velocity, gains))
+        ws = self._workspace("tmjx_tsne_workspace", n, 1, 1, 1)
+        self._call("tmjx_tsne_update", p.ptr(yy), p.ptr(g), p.ptr(v), p.ptr(ga), n, float(momentum), float(eta), float(min_gain), p.ptr(ws), p.stream())
+        return p.to_numpy(yy), p.to_numpy(v), p.to_numpy(ga)
+
+    def tsne_fit(self, y, csr, n_iter, exaggeration, exaggeration_iters, momentum_early, momentum_late, eta, min_gain=0.01, velocity=None, gains=None):
+        """The schedule from y (velocity zeros, gains ones unless given) -> (y, velocity, gains) [n, 2] float32 numpy and the call's hip.TsneInfo
+        (tmjx_tsne_fit)."""
+        p = self._p
+        n = y.shape[0]
+        row_ptr, rp, col, val, nnz = self._csr(csr)
+        yy = p.upload(y, f32, copy=True)
+        v = p.upload(np.zeros((n, 2), f32) if velocity is None else velocity, f32, copy=True)
+        ga = p.upload(np.ones((n, 2), f32) if gains is None else gains, f32, copy=True)
+        ws, info = self._workspace("tmjx_tsne_workspace", n, 1, 1, 1), _hip.TsneInfo()
+        self._call("tmjx_tsne_fit", p.ptr(yy), n, rp, p.ptr(col), p.ptr(val), nnz, int(n_iter), float(exaggeration), int(exaggeration_iters), float(momentum_early),
+                   float(momentum_late), float(eta), float(min_gain), p.ptr(v), p.ptr(ga), C.byref(info), p.ptr(ws), p.stream())
+        return p.to_numpy(yy), p.to_numpy(v), p.to_numpy(ga), info
+
+    def tsne_place(self, idx, p_rows, y_train):
+        """-> y_out [m, 2] float32: every query at the p-weighted mean of its neighbours' positions (tmjx_tsne_place)."""
+        p = self._p
+        (m, k), n = idx.shape, y_train.shape[0]
+        ii, pp, yt = p.upload(idx, i32, copy=True), p.upload(p_rows, f32, copy=True), p.upload(y_train, f32, copy=True)
+        out = p.empty((m, 2), f32)
+        self._call("tmjx_tsne_place", p.ptr(ii), p.ptr(pp), m, k, p.ptr(yt), n, p.ptr(out), p.stream())
+        return p.to_numpy(out)
 
     # the wavelet spectrogram (analysis/spectrogram.py; tmjx_wavelet_bank*, tmjx_spectrogram*): x from asarray, the bank as wavelet_bank returns it
     def wavelet_bank(self, rate, freqs, omega0=5.0, support=4.0):

@@ -15,7 +15,7 @@ _PKG = Path(__file__).resolve().parent
 SO_PATH = Path(os.environ.get("TMJX_SO", str(_PKG / "libtmjx_hip.so")))  # TMJX_SO: alternative build (profiling)
 CSRC = _PKG / "csrc"
 SOURCES = (CSRC / "tmjx_hip.hip", CSRC / "tmjx_bf16.hip", CSRC / "tmjx_wave.hip", CSRC / "tmjx_chain.hip", CSRC / "tmjx_lstm.hip",
-           CSRC / "tmjx_rollout.hip", CSRC / "tmjx_wave_sensors.hip", CSRC / "tmjx_wave_align.hip", CSRC / "tmjx_wave_rand.hip", CSRC / "tmjx_render.hip", CSRC / "tmjx_act.hip", CSRC / "tmjx_pca.hip", CSRC / "tmjx_pca_wide.hip", CSRC / "tmjx_readout.hip", CSRC / "tmjx_intervene.hip", CSRC / "tmjx_kmeans.hip", CSRC / "tmjx_hmm.hip", CSRC / "tmjx_spectrogram.hip", CSRC / "tmjx_arhmm.hip")
+           CSRC / "tmjx_rollout.hip", CSRC / "tmjx_wave_sensors.hip", CSRC / "tmjx_wave_align.hip", CSRC / "tmjx_wave_rand.hip", CSRC / "tmjx_render.hip", CSRC / "tmjx_act.hip", CSRC / "tmjx_pca.hip", CSRC / "tmjx_pca_wide.hip", CSRC / "tmjx_readout.hip", CSRC / "tmjx_intervene.hip", CSRC / "tmjx_kmeans.hip", CSRC / "tmjx_hmm.hip", CSRC / "tmjx_spectrogram.hip", CSRC / "tmjx_arhmm.hip", CSRC / "tmjx_tsne.hip")
 # per-source compiler flags: the physics kernel's unit is built without machine LICM (csrc/tmjx_wave.hip says why)
 SOURCE_FLAGS = {"tmjx_wave.hip": ("-mllvm", "-disable-machine-licm"),
                 "tmjx_wave_sensors.hip": ("-mllvm", "-disable-machine-licm"),      # (the recording kernel: the same loop body)
@@ -204,6 +204,14 @@ class ArhmmInfo(C.Structure):
     _fields_ = HmmInfo._fields_ + [("n_singular", C.c_int32), ("pad_", C.c_int32)]
 
 
+TSNE_MAX_D, TSNE_MAX_N, TSNE_MAX_K = 1024, 65536, 128      # csrc/tsne_core.h
+
+
+class TsneInfo(C.Structure):
+    """tmjx_tsne_info_t (include/tmjx.h)."""
+    _fields_ = [("n_iter", C.c_int32), ("pad_", C.c_int32), ("kl", C.c_double), ("z", C.c_double), ("gradient_ms", C.c_float), ("update_ms", C.c_float)]
+
+
 INTERVENE_SUBSPACE, INTERVENE_UNITS, INTERVENE_MAX_W, INTERVENE_MAX_K = 0, 1, 1024, 16      # include/tmjx.h, csrc/intervene_core.h
 
 
@@ -383,6 +391,13 @@ SIGNATURES = {
     "tmjx_arhmm_moments": ([_vp, _i, _i, _i64, _P(_i), _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp], _i),
     "tmjx_arhmm_solve": ([_vp, _vp, _i, _i, _i, _vp, _d, _d, _d] + [_vp] * 6, _i),
     "tmjx_arhmm_fit": ([_vp, _i, _i, _i64, _P(_i), _i, _i, _i, _vp, _i] + [_vp] * 7 + [_i] + [_d] * 6 + [_P(ArhmmInfo), _vp, _vp], _i),
+    "tmjx_tsne_workspace": ([_i, _i64, _i, _i, _P(_i64)], _i),
+    "tmjx_knn": ([_vp, _i, _i, _i64, _vp, _i64, _i64, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "tmjx_tsne_affinities": ([_vp, _i64, _i, _d, _vp, _vp, _vp], _i),
+    "tmjx_tsne_gradient": ([_vp, _i, _P(_i), _vp, _vp, _i64, _d, _vp, _vp, _vp, _vp, _vp], _i),
+    "tmjx_tsne_update": ([_vp, _vp, _vp, _vp, _i, _f, _f, _f, _vp, _vp], _i),
+    "tmjx_tsne_fit": ([_vp, _i, _P(_i), _vp, _vp, _i64, _i, _d, _i, _f, _f, _f, _f, _vp, _vp, _P(TsneInfo), _vp, _vp], _i),
+    "tmjx_tsne_place": ([_vp, _vp, _i64, _i, _vp, _i, _vp, _vp], _i),
     "tmjx_wavelet_bank_size": ([_d, _P(_d), _i, _d, _d, _P(_i64)], _i),
     "tmjx_wavelet_bank": ([_d, _P(_d), _i, _d, _d, _vp, _P(_i), _P(_i)], _i),
     "tmjx_spectrogram_workspace": ([_i] * 4 + [_P(_i64)], _i),
