@@ -1035,6 +1035,59 @@ int tmjx_tsne_fit(float *y, int n, const int32_t *row_ptr, const int32_t *col, c
                   tmjx_tsne_info_t *info, float *workspace, void *stream);
 int tmjx_tsne_place(const int32_t *idx, const float *p, int64_t m, int k, const float *y_train, int n, float *y_out, void *stream);
 
+/* ---- How two representations of the same n time steps relate: linear CKA, the correlation of two dissimilarity matrices and canonical
+ * correlations (csrc/tmjx_compare.hip, csrc/compare_core.h; DESIGN.md "Representation comparison").  The conventions of tmjx_knn: no model handle;
+ * all device memory is the caller's; everything runs on the caller's stream; x [n][d1] and y [n][d2] are float32 and may be column slices of wider
+ * buffers (ldx >= d1, ldy >= d2), and may be the same buffer; fixed-order arithmetic, every sum across rows, pairs, tiles or workgroups float64 in
+ * a fixed order, no atomics of any kind: the same bits on every run.  Limits: n >= 3, 1 <= d1, d2 <= 1024, n <= 32768 for tmjx_rdm_corr.  Both
+ * sides are centred by the float64 column means (rounded once to float32, as tmjx_readout_fit forms them) before anything else.
+ *   tmjx_compare_workspace: *floats = the scratch every call below takes at these sizes.
+ *   tmjx_cka_linear: out[0..2] (device float64) = ||Cxy||_F^2, ||Cxx||_F^2, ||Cyy||_F^2 of the centred covariances (divisor n - 1).  The moments
+ *     are split by rows as tmjx_readout_fit's cross moment: float32 FMAs inside a chunk of 256 rows, float64 across chunks and super-chunks; a
+ *     row of a moment is squared and summed in float64 by one workgroup (a fixed tree), the rows in row order.  No [d1][d2] matrix leaves the
+ *     device.  Linear CKA = out[0] / sqrt(out[1] out[2]) is the caller's; a side without variance gives out[1] or out[2] = 0.
+ *   tmjx_rdm_corr: over every pair i < j of the n rows, with Dx_ij and Dy_ij the dissimilarities of rows i, j of x and of y:
+ *     sums[0..4] (device float64) = sum Dx, sum Dy, sum Dx^2, sum Dy^2, sum Dx Dy; the Pearson correlation of the two matrices' upper triangles
+ *     is the caller's.  Metrics: 0 squared Euclidean, 1 Euclidean, 2 correlation distance (1 - the Pearson correlation of the two column-centred
+ *     rows across the features; a row whose centred norm is 0 is at distance 1 from every other row; d >= 2), 3 label mismatch (d = 1: the
+ *     column holds integers stored as floats, read as it is; D = 0 where equal, else 1).  A row is staged as ((x - mean) - shift) scale (metric
+ *     2: shift its mean across the features, scale 1 / its centred norm, both from float64 sums; else 0 and 1), and a pair is the chain
+ *     s = fmaf(a_f - b_f, a_f - b_f, s) over the features in ascending order: D = s, sqrt(s) or s / 2, in float64.  Duplicate rows are at
+ *     distance exactly 0.  An all-pairs kernel: a workgroup owns 128 rows i and 64 rows j, stages both in LDS, first for x, then for y, and
+ *     leaves five float64 sums (a fixed tree over its threads); the tiles are added in a fixed order.  Neither n x n matrix is ever written.
+ *   tmjx_cca: tmjx_pca_fit_wide of both sides as it is; on each side the leading components whose cumulative variance first reaches var_keep,
+ *     at least 1, at most max_rank <= 128, never one whose eigenvalue is <= 2^-20 of the largest (info->kx, ky); the whitened cross matrix
+ *     M = Wx Cxy Wy^T [kx][ky] in float64 (Cxy: the moment above); its singular value decomposition by tmjx_compare_svd's kernel.  The PCA's
+ *     float32 eigenvalues pick the components and do not scale them: with E the kept rows of the components, S = E Cxx E^T [k][k] (float64,
+ *     the moment above) = Q diag(s) Q^T by the same kernel and W = diag(s)^-1/2 Q^T E, which has the singular values of
+ *     Lx^-1/2 Ux Cxy Uy^T Ly^-1/2 in exact arithmetic and whitens the kept span to float64.  Where a side drops components (k < d), the cut is
+ *     sharpened first: the window of at most 128 components around it (64 to each side where there is room) is re-diagonalised against the
+ *     float64 Cxx by the same kernel, and its leading Ritz vectors replace the kept rows of the window.  info->converged covers every
+ *     decomposition of the call (up to five).
+ *     rho [r] (r = min(kx, ky)), descending; a [r][d1], b [r][d2]: the canonical directions in feature space, (x - mean) . a_i of unit variance;
+ *     the caller's buffers hold min(max_rank, d1, d2) rows.  It WAITS for the stream.  The PCA's refusals and TMJX_ENOCONV (the PCA's or the
+ *     decomposition's) pass through; a side without variance is TMJX_EINVAL.
+ *   tmjx_compare_svd: a [rows][cols] float64 (device, row stride lda), rows, cols <= 128 -> sigma [r] descending, u [r][rows], v [r][cols]
+ *     (rows: the singular vectors), r = min(rows, cols), all device float64.  One-sided (Hestenes) Jacobi in ONE workgroup, the matrix in LDS in
+ *     float64 (transposed when rows < cols), the accumulated rotations in the workspace (2 r^2 + 4 floats; a tmjx_compare_workspace buffer
+ *     serves); pairs in round-robin order, four threads a pair; a pair turns while |g_p . g_q| > 2^-40 ||g_p|| ||g_q||, a sweep without a turn ends
+ *     it, 60 sweeps without one are TMJX_ENOCONV.  The vector of the longer side that belongs to sigma = 0 is zero.  *sweeps (host): the sweeps
+ *     run.  It WAITS for the stream.
+ * Each returns TMJX_EINVAL before any launch, with a message that names the value, for n < 3, n > 32768 (tmjx_rdm_corr), d1 or d2 outside
+ * 1 .. 1024, ldx < d1 or ldy < d2, a metric outside 0 .. 3, metric 3 with d != 1, metric 2 with d < 2, var_keep outside (0, 1], max_rank outside
+ * 1 .. 128, rows or cols outside 1 .. 128, a null pointer, a workspace that is not 16-byte aligned, or a misaligned array. */
+#define COMPARE_MAX_D 1024
+#define COMPARE_MAX_N 32768
+#define COMPARE_MAX_RANK 128
+typedef struct { int32_t kx, ky, sweeps, converged; float pca_ms, cross_ms, svd_ms, pad_; } tmjx_cca_info_t;
+int tmjx_compare_workspace(int n, int d1, int d2, int64_t *floats);
+int tmjx_cka_linear(const float *x, int n, int d1, int64_t ldx, const float *y, int d2, int64_t ldy, double *out, float *workspace, void *stream);
+int tmjx_rdm_corr(const float *x, int n, int d1, int64_t ldx, int metric_x, const float *y, int d2, int64_t ldy, int metric_y, double *sums, float *workspace,
+                  void *stream);
+int tmjx_cca(const float *x, int n, int d1, int64_t ldx, const float *y, int d2, int64_t ldy, double var_keep, int max_rank, float *rho, float *a, float *b,
+             tmjx_cca_info_t *info, float *workspace, void *stream);
+int tmjx_compare_svd(const double *a, int rows, int cols, int64_t lda, double *sigma, double *u, double *v, int32_t *sweeps, float *workspace, void *stream);
+
 /* ---- Morlet wavelet spectrograms of recorded signals x [n][C] (1 <= C <= 1024) at 1 <= F <= 64 centre frequencies (csrc/tmjx_spectrogram.hip,
  * csrc/spectrogram_core.h; DESIGN.md "Spectrogram").  The conventions of tmjx_hmm_*: no model handle; all device memory is the caller's; everything
  * runs on the caller's stream; x is float32 and may be a column slice of a wider buffer (ldx >= C); the rows form S sequences given by

@@ -1,5 +1,5 @@
 """The analysis entry points of the C-ABI (include/tmjx.h: tmjx_pca_*, tmjx_plot_strips, tmjx_readout_*, tmjx_kmeans_*, tmjx_hmm_*, tmjx_arhmm_*,
-tmjx_wavelet_bank*, tmjx_spectrogram*, tmjx_knn, tmjx_tsne_*) as methods on arrays.
+tmjx_wavelet_bank*, tmjx_spectrogram*, tmjx_knn, tmjx_tsne_*, tmjx_cka_linear, tmjx_rdm_corr, tmjx_cca, tmjx_compare_svd) as methods on arrays.
 
 `Backend` marshals every call once, against a small provider of arrays: what differs between the device and a host is how an array is uploaded,
 allocated, addressed and read back, not which arguments go where.  `HipBackend` is the backend on torch device tensors (`TorchArrays`), the one
@@ -377,6 +377,55 @@ class Backend:
         out = p.empty((m, 2), f32)
         self._call("tmjx_tsne_place", p.ptr(ii), p.ptr(pp), m, k, p.ptr(yt), n, p.ptr(out), p.stream())
         return p.to_numpy(out)
+
+    # representation comparison (analysis/compare.py; tmjx_cka_linear, tmjx_rdm_corr, tmjx_cca, tmjx_compare_svd): x and y from asarray, the same rows
+    def _pair(self, x, y):
+        (n, d1), (ny, d2) = x.shape, y.shape
+        if ny != n:
+            raise ValueError(f"the two sides have {n} and {ny} rows: they must be the same time steps")
+        return n, d1, d2
+
+    def cka_linear(self, x, y):
+        """-> float64 numpy [3]: ||Cxy||_F^2, ||Cxx||_F^2, ||Cyy||_F^2 of the centred covariances (tmjx_cka_linear)."""
+        p = self._p
+        n, d1, d2 = self._pair(x, y)
+        ws, out = self._workspace("tmjx_compare_workspace", n, d1, d2), p.empty((3,), f64)
+        self._call("tmjx_cka_linear", p.ptr(x), n, d1, p.ld(x), p.ptr(y), d2, p.ld(y), p.ptr(out), p.ptr(ws), p.stream())
+        return p.to_numpy(out)
+
+    def rdm_corr(self, x, metric_x, y, metric_y):
+        """-> float64 numpy [5]: sum Dx, sum Dy, sum Dx^2, sum Dy^2, sum Dx Dy over the pairs i < j of rows (tmjx_rdm_corr); the metrics are
+        hip.COMPARE_SQEUCLIDEAN, _EUCLIDEAN, _CORRELATION, _LABEL."""
+        p = self._p
+        n, d1, d2 = self._pair(x, y)
+        ws, sums = self._workspace("tmjx_compare_workspace", n, d1, d2), p.empty((5,), f64)
+        self._call("tmjx_rdm_corr", p.ptr(x), n, d1, p.ld(x), int(metric_x), p.ptr(y), d2, p.ld(y), int(metric_y), p.ptr(sums), p.ptr(ws), p.stream())
+        return p.to_numpy(sums)
+
+    def cca(self, x, y, var_keep=0.99, max_rank=_hip.COMPARE_MAX_RANK):
+        """-> (rho [r], a [r, d1], b [r, d2]) float32 numpy and the call's hip.CcaInfo: the canonical correlations, descending, and the directions in
+        feature space (tmjx_cca)."""
+        p = self._p
+        n, d1, d2 = self._pair(x, y)
+        ws, info = self._workspace("tmjx_compare_workspace", n, d1, d2), _hip.CcaInfo()
+        cap = max(1, min(int(max_rank), d1, d2, _hip.COMPARE_MAX_RANK))
+        rho, a, b = p.empty((cap,), f32), p.empty((cap, d1), f32), p.empty((cap, d2), f32)
+        self._call("tmjx_cca", p.ptr(x), n, d1, p.ld(x), p.ptr(y), d2, p.ld(y), float(var_keep), int(max_rank), p.ptr(rho), p.ptr(a), p.ptr(b), C.byref(info),
+                   p.ptr(ws), p.stream())
+        r = min(info.kx, info.ky)
+        return p.to_numpy(rho)[:r], p.to_numpy(a)[:r], p.to_numpy(b)[:r], info
+
+    def compare_svd(self, m):
+        """m float64 numpy [rows, cols], both <= 128 -> (sigma [r] descending, u [r, rows], v [r, cols]) float64 numpy and the sweeps run: the kernel
+        behind tmjx_cca on its own (tmjx_compare_svd)."""
+        p = self._p
+        m = np.ascontiguousarray(m, f64)
+        rows, cols = m.shape
+        r, sweeps = max(min(rows, cols), 1), C.c_int32(0)
+        a, ws = p.upload(m, f64), p.workspace(2 * r * r + 4)
+        sigma, u, v = p.empty((r,), f64), p.empty((r, rows), f64), p.empty((r, cols), f64)
+        self._call("tmjx_compare_svd", p.ptr(a), rows, cols, cols, p.ptr(sigma), p.ptr(u), p.ptr(v), C.byref(sweeps), p.ptr(ws), p.stream())
+        return p.to_numpy(sigma), p.to_numpy(u), p.to_numpy(v), int(sweeps.value)
 
     # the wavelet spectrogram (analysis/spectrogram.py; tmjx_wavelet_bank*, tmjx_spectrogram*): x from asarray, the bank as wavelet_bank returns it
     def wavelet_bank(self, rate, freqs, omega0=5.0, support=4.0):

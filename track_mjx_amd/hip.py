@@ -15,7 +15,7 @@ _PKG = Path(__file__).resolve().parent
 SO_PATH = Path(os.environ.get("TMJX_SO", str(_PKG / "libtmjx_hip.so")))  # TMJX_SO: alternative build (profiling)
 CSRC = _PKG / "csrc"
 SOURCES = (CSRC / "tmjx_hip.hip", CSRC / "tmjx_bf16.hip", CSRC / "tmjx_wave.hip", CSRC / "tmjx_chain.hip", CSRC / "tmjx_lstm.hip",
-           CSRC / "tmjx_rollout.hip", CSRC / "tmjx_wave_sensors.hip", CSRC / "tmjx_wave_align.hip", CSRC / "tmjx_wave_rand.hip", CSRC / "tmjx_render.hip", CSRC / "tmjx_act.hip", CSRC / "tmjx_pca.hip", CSRC / "tmjx_pca_wide.hip", CSRC / "tmjx_readout.hip", CSRC / "tmjx_intervene.hip", CSRC / "tmjx_kmeans.hip", CSRC / "tmjx_hmm.hip", CSRC / "tmjx_spectrogram.hip", CSRC / "tmjx_arhmm.hip", CSRC / "tmjx_tsne.hip")
+           CSRC / "tmjx_rollout.hip", CSRC / "tmjx_wave_sensors.hip", CSRC / "tmjx_wave_align.hip", CSRC / "tmjx_wave_rand.hip", CSRC / "tmjx_render.hip", CSRC / "tmjx_act.hip", CSRC / "tmjx_pca.hip", CSRC / "tmjx_pca_wide.hip", CSRC / "tmjx_readout.hip", CSRC / "tmjx_intervene.hip", CSRC / "tmjx_kmeans.hip", CSRC / "tmjx_hmm.hip", CSRC / "tmjx_spectrogram.hip", CSRC / "tmjx_arhmm.hip", CSRC / "tmjx_tsne.hip", CSRC / "tmjx_compare.hip")
 # per-source compiler flags: the physics kernel's unit is built without machine LICM (csrc/tmjx_wave.hip says why)
 SOURCE_FLAGS = {"tmjx_wave.hip": ("-mllvm", "-disable-machine-licm"),
                 "tmjx_wave_sensors.hip": ("-mllvm", "-disable-machine-licm"),      # (the recording kernel: the same loop body)
@@ -212,6 +212,15 @@ class TsneInfo(C.Structure):
     _fields_ = [("n_iter", C.c_int32), ("pad_", C.c_int32), ("kl", C.c_double), ("z", C.c_double), ("gradient_ms", C.c_float), ("update_ms", C.c_float)]
 
 
+COMPARE_MAX_D, COMPARE_MAX_N, COMPARE_MAX_RANK = 1024, 32768, 128      # csrc/compare_core.h
+COMPARE_SQEUCLIDEAN, COMPARE_EUCLIDEAN, COMPARE_CORRELATION, COMPARE_LABEL = 0, 1, 2, 3      # the metrics of tmjx_rdm_corr (include/tmjx.h)
+
+
+class CcaInfo(C.Structure):
+    """tmjx_cca_info_t (include/tmjx.h)."""
+    _fields_ = [(k, C.c_int32) for k in ("kx", "ky", "sweeps", "converged")] + [(k, C.c_float) for k in ("pca_ms", "cross_ms", "svd_ms", "pad_")]
+
+
 INTERVENE_SUBSPACE, INTERVENE_UNITS, INTERVENE_MAX_W, INTERVENE_MAX_K = 0, 1, 1024, 16      # include/tmjx.h, csrc/intervene_core.h
 
 
@@ -398,6 +407,11 @@ SIGNATURES = {
     "tmjx_tsne_update": ([_vp, _vp, _vp, _vp, _i, _f, _f, _f, _vp, _vp], _i),
     "tmjx_tsne_fit": ([_vp, _i, _P(_i), _vp, _vp, _i64, _i, _d, _i, _f, _f, _f, _f, _vp, _vp, _P(TsneInfo), _vp, _vp], _i),
     "tmjx_tsne_place": ([_vp, _vp, _i64, _i, _vp, _i, _vp, _vp], _i),
+    "tmjx_compare_workspace": ([_i, _i, _i, _P(_i64)], _i),
+    "tmjx_cka_linear": ([_vp, _i, _i, _i64, _vp, _i, _i64, _vp, _vp, _vp], _i),
+    "tmjx_rdm_corr": ([_vp, _i, _i, _i64, _i, _vp, _i, _i64, _i, _vp, _vp, _vp], _i),
+    "tmjx_cca": ([_vp, _i, _i, _i64, _vp, _i, _i64, _d, _i, _vp, _vp, _vp, _P(CcaInfo), _vp, _vp], _i),
+    "tmjx_compare_svd": ([_vp, _i, _i, _i64, _vp, _vp, _vp, _P(_i), _vp, _vp], _i),
     "tmjx_wavelet_bank_size": ([_d, _P(_d), _i, _d, _d, _P(_i64)], _i),
     "tmjx_wavelet_bank": ([_d, _P(_d), _i, _d, _d, _vp, _P(_i), _P(_i)], _i),
     "tmjx_spectrogram_workspace": ([_i] * 4 + [_P(_i64)], _i),
