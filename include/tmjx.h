@@ -1088,6 +1088,43 @@ int tmjx_cca(const float *x, int n, int d1, int64_t ldx, const float *y, int d2,
              tmjx_cca_info_t *info, float *workspace, void *stream);
 int tmjx_compare_svd(const double *a, int rows, int cols, int64_t lda, double *sigma, double *u, double *v, int32_t *sweeps, float *workspace, void *stream);
 
+/* ---- The decoder's Jacobian at recorded steps: the local linearisation of ctrl = tanh(loc) with respect to columns of the decoder's input row
+ * (csrc/tmjx_jacobian.hip, csrc/jacobian_core.h; DESIGN.md "Decoder Jacobian").  The conventions of tmjx_knn: no model handle; all device memory
+ * is the caller's; everything runs on the caller's stream; fixed-order arithmetic, no atomics: the same bits on every run, and the bits of a row's
+ * outputs depend neither on m nor on where the row stands in the list.
+ *   The descriptor: L blocks Dense -> SiLU -> LayerNorm (1 <= L <= 8; layer l: W [width][K] with row stride ldw >= K, K = d_in for the first and
+ *     the width before it otherwise, b, gamma, beta [width], 1 <= width <= 1024; eps of the LayerNorm, biased variance), the head Wh [2A][H_L]
+ *     with row stride ldwh whose first A rows are loc (1 <= A <= 64; only they are read), bh, and the differentiated input columns
+ *     [wrt_col0, wrt_col0 + wrt_cols), 1 <= wrt_cols <= 128 inside d_in.
+ *   tmjx_jacobian_workspace: *floats = the scratch a call with this descriptor and m rows takes (it stops growing at 1024 rows: the list is worked
+ *     through in passes of 1024).
+ *   tmjx_decoder_jacobian: x [n][d_in] float32 (row stride ldx); row_index: device int32 [m], the rows to evaluate in that order (null: 0 .. m - 1,
+ *     which needs m <= n; an index outside 0 .. n - 1 reads as a row of zeros); mode 0: d ctrl / d x, 1: d loc / d x; scale (optional) [n][wrt_cols]
+ *     with row stride ld_scale: the standard deviation of each differentiated input at that row.  Outputs, each optional by null except sums, per-row
+ *     ones at position i of the list: ctrl_out [m][A] = tanh(loc), jac [m][A][wrt_cols], gain [m] = ||J_i||_F^2, col2 [m][wrt_cols] = sum_a J_aj^2,
+ *     row2 [m][A] = sum_j J_aj^2, action_var [m][A] = sum_j (J_aj scale_j)^2 (needs scale); sums: device float64 [A wrt_cols | wrt_cols^2 | A^2] =
+ *     the sums over the m rows of J, J^T J and J J^T (per row float32 chains, across rows float64: groups of 32 rows in row order, the groups in
+ *     order).  Forward: u = W h + b (the chain fmaf(W_jk, h_k, .) from 0 in ascending k, then the bias), s = u / (1 + expf(-u)), the LayerNorm by
+ *     two fixed trees; reverse for the A rows at once: G = diag(1 - ctrl^2) Wh[:A], per block q = g gamma, du = r (q - mean(q) - xhat mean(q xhat))
+ *     silu'(u), g = du W, at the first layer over the wrt columns of W only.
+ * Each returns TMJX_EINVAL before any launch, with a message that names the value, for a limit above exceeded, a null required pointer, ldx < d_in,
+ * a weight stride below its width, ld_scale < wrt_cols, m < 1, n < 1, m > n without row_index, a mode outside 0 .. 1, action_var without scale, a
+ * workspace that is not 16-byte aligned, or a misaligned array. */
+#define TMJX_JACOBIAN_MAX_LAYERS 8
+typedef struct { const float *W, *b, *gamma, *beta; int32_t width, ldw; } tmjx_jacobian_layer_t;
+typedef struct {
+  int32_t L, d_in;
+  tmjx_jacobian_layer_t layer[TMJX_JACOBIAN_MAX_LAYERS];
+  float eps;
+  int32_t A;
+  const float *Wh, *bh;
+  int32_t ldwh, wrt_col0, wrt_cols, pad_;
+} tmjx_jacobian_desc_t;
+int tmjx_jacobian_workspace(const tmjx_jacobian_desc_t *desc, int m, int64_t *floats);
+int tmjx_decoder_jacobian(const tmjx_jacobian_desc_t *desc, const float *x, int n, int64_t ldx, const int32_t *row_index, int m, const float *scale,
+                          int64_t ld_scale, int mode, float *ctrl_out, float *jac, float *gain, float *col2, float *row2, float *action_var, double *sums,
+                          float *workspace, void *stream);
+
 /* ---- Morlet wavelet spectrograms of recorded signals x [n][C] (1 <= C <= 1024) at 1 <= F <= 64 centre frequencies (csrc/tmjx_spectrogram.hip,
  * csrc/spectrogram_core.h; DESIGN.md "Spectrogram").  The conventions of tmjx_hmm_*: no model handle; all device memory is the caller's; everything
  * runs on the caller's stream; x is float32 and may be a column slice of a wider buffer (ldx >= C); the rows form S sequences given by

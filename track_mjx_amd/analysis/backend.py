@@ -1,5 +1,6 @@
 """The analysis entry points of the C-ABI (include/tmjx.h: tmjx_pca_*, tmjx_plot_strips, tmjx_readout_*, tmjx_kmeans_*, tmjx_hmm_*, tmjx_arhmm_*,
-tmjx_wavelet_bank*, tmjx_spectrogram*, tmjx_knn, tmjx_tsne_*, tmjx_cka_linear, tmjx_rdm_corr, tmjx_cca, tmjx_compare_svd) as methods on arrays.
+tmjx_wavelet_bank*, tmjx_spectrogram*, tmjx_knn, tmjx_tsne_*, tmjx_cka_linear, tmjx_rdm_corr, tmjx_cca, tmjx_compare_svd, tmjx_decoder_jacobian) as methods on
+arrays.
 
 `Backend` marshals every call once, against a small provider of arrays: what differs between the device and a host is how an array is uploaded,
 allocated, addressed and read back, not which arguments go where.  `HipBackend` is the backend on torch device tensors (`TorchArrays`), the one
@@ -426,6 +427,46 @@ class Backend:
         sigma, u, v = p.empty((r,), f64), p.empty((r, rows), f64), p.empty((r, cols), f64)
         self._call("tmjx_compare_svd", p.ptr(a), rows, cols, cols, p.ptr(sigma), p.ptr(u), p.ptr(v), C.byref(sweeps), p.ptr(ws), p.stream())
         return p.to_numpy(sigma), p.to_numpy(u), p.to_numpy(v), int(sweeps.value)
+
+    # the decoder's Jacobian (analysis/jacobian.py; tmjx_jacobian_workspace, tmjx_decoder_jacobian): x from asarray, the weights float32 numpy
+    def decoder_jacobian(self, x, layers, head, wrt, eps=1e-6, row_index=None, scale=None, mode=0, want=("ctrl", "jac", "gain", "col2", "row2")):
+        """The Jacobian of ctrl = tanh(loc) (mode 0) or of loc (mode 1) with respect to the columns wrt = (col0, cols) of the rows of x [n, d_in].
+        layers: [(W [H, K], b, gamma, beta)] of the Dense -> SiLU -> LayerNorm blocks; head: (Wh [>= A, H_L], bh, A); row_index: int32 [m], the rows to
+        evaluate in that order (None: every row); scale: from asarray [n, cols], the standard deviation of each differentiated input (adds
+        action_var).  -> a dict of numpy arrays: those of `want` (ctrl [m, A], jac [m, A, cols], gain [m], col2 [m, cols], row2 [m, A]),
+        action_var [m, A] with a scale, and the float64 sums over the rows mean_sum [A, cols], gram_in [cols, cols], gram_out [A, A]."""
+        p = self._p
+        n, d_in = x.shape
+        (col0, cols), (wh, bh, A) = (int(v) for v in wrt), head
+        desc, keep = _hip.JacobianDesc(), []
+
+        def up(a):
+            keep.append(p.upload(a, f32))
+            return keep[-1]
+        desc.L, desc.d_in, desc.eps, desc.A, desc.wrt_col0, desc.wrt_cols = len(layers), d_in, float(eps), int(A), col0, cols
+        if len(layers) > _hip.JACOBIAN_MAX_LAYERS:
+            raise ValueError(f"{len(layers)} decoder blocks: the Jacobian takes up to {_hip.JACOBIAN_MAX_LAYERS}")
+        for slot, (W, b, gamma, beta) in zip(desc.layer, layers):
+            w = up(W)
+            slot.W, slot.b, slot.gamma, slot.beta, slot.width, slot.ldw = p.ptr(w), p.ptr(up(b)), p.ptr(up(gamma)), p.ptr(up(beta)), w.shape[0], p.ld(w)
+        w = up(wh)
+        desc.Wh, desc.bh, desc.ldwh = p.ptr(w), p.ptr(up(bh)), p.ld(w)
+        idx = None if row_index is None else p.upload(row_index, i32, copy=True)
+        m = n if idx is None else int(idx.shape[0])
+        ws = self._workspace("tmjx_jacobian_workspace", C.byref(desc), m)
+        shapes = {"ctrl": (m, A), "jac": (m, A, cols), "gain": (m,), "col2": (m, cols), "row2": (m, A)}
+        out = {k: p.empty(shapes[k], f32) for k in shapes if k in want}
+        if scale is not None:
+            out["action_var"] = p.empty((m, A), f32)
+        sums = p.empty((A * cols + cols * cols + A * A,), f64)
+        arg = lambda k: p.ptr(out[k]) if k in out else None      # noqa: E731
+        self._call("tmjx_decoder_jacobian", C.byref(desc), p.ptr(x), n, p.ld(x), None if idx is None else p.ptr(idx), m, None if scale is None else p.ptr(scale),
+                   0 if scale is None else p.ld(scale), int(mode), arg("ctrl"), arg("jac"), arg("gain"), arg("col2"), arg("row2"), arg("action_var"), p.ptr(sums),
+                   p.ptr(ws), p.stream())
+        res = {k: p.to_numpy(v) for k, v in out.items()}
+        s = p.to_numpy(sums)
+        res["mean_sum"], res["gram_in"], res["gram_out"] = s[:A * cols].reshape(A, cols), s[A * cols:A * cols + cols * cols].reshape(cols, cols), s[A * cols + cols * cols:].reshape(A, A)
+        return res
 
     # the wavelet spectrogram (analysis/spectrogram.py; tmjx_wavelet_bank*, tmjx_spectrogram*): x from asarray, the bank as wavelet_bank returns it
     def wavelet_bank(self, rate, freqs, omega0=5.0, support=4.0):

@@ -1,0 +1,274 @@
+"""The decoder's Jacobian at recorded steps on the GPU (csrc/tmjx_jacobian.hip; DESIGN.md "Decoder Jacobian"): sensitivity.  At every recorded
+step the decoder's input row [intention | normalised proprioception] is in the roll-out; this tool recomputes the decoder there and differentiates
+ctrl = tanh(loc) (or loc) with respect to the intention (or any 128 columns of the input): how strongly each latent dimension drives each
+actuator, which latent directions matter for action and which are slack, and how much of the stochastic encoder's noise reaches the muscles.
+
+    python -m track_mjx_amd.analysis.jacobian checkpoint=<run dir | step dir> rollouts=<dir of clip_<i>.h5> [wrt=intention | input:a:b] [mode=ctrl|loc]
+                                              [max_rows=0] [seed=0] [labels=<clusters.h5>] [store=false] [features_out=<dir>] out=<jacobian.h5>
+
+writes gain/clip_<i> [T-1] (the squared Frobenius norm of J), latent_sensitivity/clip_<i> [T-1, Z] (sum over actuators of J_aj^2),
+actuator_sensitivity/clip_<i> [T-1, A] (sum over inputs) and, where the roll-out recorded encoder/logvar and the differentiated columns are
+intention columns, action_var/clip_<i> [T-1, A] (sum_j J_aj^2 exp(logvar_j): the variance the encoder's noise puts on each actuator, to first
+order); mean_jacobian [A, Z], gram_in [Z, Z] (the mean of J^T J) and gram_out [A, A] (of J J^T); the eigen-decomposition of gram_in as `feature`,
+`mean`, `components` [Z, Z], `explained_variance`, `explained_variance_ratio`, the layout of analysis.pca, so that `python -m
+track_mjx_amd.analysis.rollout ... intervene_pca=<jacobian.h5> intervene_components=0:3` projects out the latent directions the decoder listens to
+most (the trailing components are the slack ones); forward_mismatch, the largest |recomputed ctrl - recorded ctrl| (a warning above 1e-3: a
+checkpoint that did not make these roll-outs differs at O(0.1), and so does an intervention downstream of the intention); rows, wrt, mode, clips.
+max_rows= evaluates a sorted random sample (the other rows of the per-clip series are NaN); labels= (a clusters.h5, hmm.h5, arhmm.h5 or map.h5)
+adds motif_mean_jacobian [K, A, Z], motif_gram_in [K, Z, Z], motif_gain [K] and motif_rows [K]; store=true adds jacobian/clip_<i> [T-1, A, Z]
+(refused above 2^31 bytes); features_out= writes a directory of clip_<i>.h5 with activations/latent_sensitivity, activations/actuator_sensitivity,
+activations/jacobian_gain [T-1, 1] and the clip's meta, which analysis.cluster, hmm, pca, readout, spectrogram and embed take like a roll-out
+directory.  Limits: the MLP decoder only (a use_lstm checkpoint is refused: the recurrent decoder's Jacobian is not built), up to 8 blocks of up to
+1024 units, 64 actuators, 128 differentiated columns a call."""
+from __future__ import annotations
+
+import os
+import sys
+
+import numpy as np
+
+from .. import hip as _hip
+from . import pca as _pca
+from .utils import rollout_features
+
+CLI_OPTIONS = ("checkpoint", "rollouts", "wrt", "mode", "max_rows", "seed", "labels", "store", "out", "features_out")
+USAGE = ("usage: python -m track_mjx_amd.analysis.jacobian checkpoint=<run dir | step dir> rollouts=<dir of clip_<i>.h5> [wrt=intention | input:a:b] "
+         "[mode=ctrl|loc] [max_rows=0] [seed=0] [labels=<clusters.h5>] [store=false] [features_out=<dir>] out=<jacobian.h5>")
+MODES = {"ctrl": _hip.JACOBIAN_CTRL, "loc": _hip.JACOBIAN_LOC}
+MISMATCH_WARN = 1e-3
+STORE_MAX_BYTES = 2 ** 31
+LSTM_REFUSAL = ("the checkpoint holds an LSTM decoder (train_config.use_lstm): the Jacobian is built for the MLP decoder (Dense -> SiLU -> LayerNorm blocks) "
+                "only; the recurrent decoder's Jacobian is not built")
+
+
+def decoder_weights(source):
+    """-> (layers [(W [H, K], b, gamma, beta)], (Wh [2A, H_L], bh, A), eps) as float32 numpy.  `source`: a checkpoint (a run directory, a step directory
+    or a .npz: loaded as the decoder policy loads it, agent/checkpoint.py), or a module with `.decoder` blocks and a `.head` (DecoderNet,
+    IntentionPolicy), or a DecoderPolicy (its `.net`)."""
+    if isinstance(source, (str, os.PathLike)):
+        from ..agent import checkpoint as ckpt
+        try:
+            source = ckpt.make_decoder_policy_fn(source, device="cpu")
+        except NotImplementedError:
+            raise ValueError(LSTM_REFUSAL) from None
+    net = getattr(source, "net", source)
+    if not hasattr(net, "decoder") or not hasattr(net, "head") or hasattr(net, "hidden_layer_num"):
+        raise ValueError(LSTM_REFUSAL if hasattr(net, "hidden_layer_num") or hasattr(net, "w_hh") else
+                         f"{type(net).__name__} has no decoder blocks and head: expected a DecoderNet, an IntentionPolicy or a checkpoint of one")
+    num = lambda t: np.ascontiguousarray(t.detach().cpu().numpy(), np.float32)      # noqa: E731
+    blocks = list(net.decoder)
+    if not blocks:
+        raise ValueError("the decoder has no hidden block")
+    eps = {float(b.norm.eps) for b in blocks}
+    if len(eps) != 1:
+        raise ValueError(f"the decoder's LayerNorms have different eps: {sorted(eps)}")
+    layers = [(num(b.dense.weight), num(b.dense.bias), num(b.norm.weight), num(b.norm.bias)) for b in blocks]
+    wh, bh = num(net.head.weight), num(net.head.bias)
+    return layers, (wh, bh, wh.shape[0] // 2), eps.pop()
+
+
+def _read_clip(r, clip, where):
+    z, prop = _pca._feature_of(r, "intention", where), _pca._feature_of(r, "egocentric_obs", where)
+    if z.shape[0] != prop.shape[0]:
+        raise ValueError(f"{where}: intention has {z.shape[0]} rows, egocentric_obs {prop.shape[0]}")
+    try:
+        logvar = _pca._feature_of(r, "encoder/logvar", where)
+    except KeyError:
+        logvar = None
+    try:
+        ctrl = _pca._feature_of(r, "ctrl", where)[:z.shape[0]]
+    except KeyError:
+        ctrl = None
+    from .. import h5lite
+    from .spectrogram import _tree
+    if isinstance(r, h5lite.File):
+        meta = _tree(r["meta"]) if "meta" in r else None
+    else:
+        meta = r.get("meta") if hasattr(r, "get") else None
+    return np.concatenate([z, prop], 1), z.shape[1], logvar, ctrl, meta
+
+
+def _parse_wrt(wrt: str, Z: int, d_in: int) -> tuple:
+    if wrt == "intention":
+        a, b = 0, Z
+    else:
+        parts = str(wrt).split(":")
+        if len(parts) != 3 or parts[0] != "input":
+            raise ValueError(f"wrt = {wrt!r}: expected intention or input:a:b")
+        try:
+            a, b = int(parts[1]), int(parts[2])
+        except ValueError:
+            raise ValueError(f"wrt = {wrt!r}: expected intention or input:a:b with integers a < b") from None
+    if not 0 <= a < b <= d_in:
+        raise ValueError(f"wrt = {wrt}: the columns {a}:{b} do not lie inside the decoder's {d_in} inputs")
+    if b - a > _hip.JACOBIAN_MAX_WRT:
+        raise ValueError(f"wrt = {wrt}: {b - a} columns exceed the {_hip.JACOBIAN_MAX_WRT} one call differentiates; pick a range with wrt=input:a:b")
+    return a, b - a
+
+
+def _labels_file(path):
+    from .. import h5lite
+    with h5lite.File(str(path)) as h:
+        if "labels" not in h:
+            raise KeyError(f"{path} has no labels group (write it with analysis.cluster, hmm, arhmm or embed)")
+        return {int(k.split("_", 1)[1]): np.asarray(h["labels"][k][()]).reshape(-1) for k in h["labels"].keys()}
+
+
+def eigen(gram, backend):
+    """The eigen-decomposition of a symmetric positive semi-definite [Z, Z] float64 matrix by the backend's one-sided Jacobi kernel (its singular
+    values are the eigenvalues): -> (values [Z] descending, vectors [Z, Z] rows, the largest-magnitude coefficient of each positive)."""
+    sigma, _, v, _ = backend.compare_svd(np.ascontiguousarray(gram, np.float64))
+    v = np.array(v, np.float64)
+    lead = np.abs(v).argmax(1)
+    v *= np.where(v[np.arange(v.shape[0]), lead] < 0.0, -1.0, 1.0)[:, None]
+    return np.array(sigma, np.float64), v
+
+
+def jacobian_rollouts(checkpoint, rollouts, wrt="intention", mode="ctrl", max_rows=0, seed=0, labels=None, store=False, features=False, device="cuda",
+                      backend=None) -> dict:
+    """The tool as a function (the module's text says what the result holds): `checkpoint` as decoder_weights takes it, `rollouts` a directory of
+    clip_<i>.h5 or a list of roll-out dicts, `labels` a file or {clip: int labels}.  features=True adds "features": per clip the tree features_out=
+    writes.  -> the dict the command line writes."""
+    if mode not in MODES:
+        raise ValueError(f"mode = {mode!r}: ctrl (through the tanh) or loc")
+    layers, head, eps = decoder_weights(checkpoint)
+    d_in, A = layers[0][0].shape[1], head[2]
+    ids, items = rollout_features(rollouts, _read_clip, "the decoder's input", "differentiate")
+    width = items[0][0].shape[1]
+    if width != d_in:
+        raise ValueError(f"the roll-outs' decoder input [intention | egocentric_obs] is {width} wide, the checkpoint's decoder takes {d_in}: "
+                         "this checkpoint did not make these roll-outs")
+    Z = items[0][1]
+    col0, cols = _parse_wrt(wrt, Z, d_in)
+    lens = [it[0].shape[0] for it in items]
+    n = int(sum(lens))
+    if n < 1:
+        raise ValueError("the roll-outs hold no recorded step")
+    x = np.ascontiguousarray(np.concatenate([it[0] for it in items], 0), np.float32)
+    scale = None
+    if all(it[2] is not None for it in items) and col0 + cols <= Z:
+        lv = np.concatenate([it[2] for it in items], 0)[:, col0:col0 + cols]
+        scale = np.ascontiguousarray(np.exp(0.5 * lv.astype(np.float64)), np.float32)
+    recorded = np.concatenate([it[3] for it in items], 0) if all(it[3] is not None and it[3].shape[1] == A for it in items) else None
+    max_rows = int(max_rows)
+    if max_rows < 0:
+        raise ValueError(f"max_rows must be >= 0 (got {max_rows})")
+    # a row that is not finite (a roll-out whose physics diverged is recorded to its end) is never evaluated: its series stay NaN
+    finite = np.flatnonzero(np.isfinite(x).all(1) & (np.isfinite(scale).all(1) if scale is not None else True))
+    if finite.shape[0] < 1:
+        raise ValueError("no recorded step has a finite decoder input")
+    sampled = 0 < max_rows < finite.shape[0]
+    if sampled and features:
+        raise ValueError("features_out= needs every row: drop max_rows=")
+    index = None
+    if sampled:
+        index = np.sort(np.random.default_rng(int(seed)).choice(finite, size=max_rows, replace=False)).astype(np.int32)
+    elif finite.shape[0] < n:
+        index = finite.astype(np.int32)
+    m = n if index is None else int(index.shape[0])
+    if store and m * A * cols * 4 > STORE_MAX_BYTES:
+        raise ValueError(f"store=true: {m} rows x {A} x {cols} float32 exceed 2^31 bytes; sample with max_rows= or differentiate fewer columns")
+    bk = _pca.HipBackend(device) if backend is None else backend
+    xa, sa = bk.asarray(x), None if scale is None else bk.asarray(scale)
+    want = ("ctrl", "gain", "col2", "row2") + (("jac",) if store else ())
+    try:
+        res = bk.decoder_jacobian(xa, layers, head, (col0, cols), eps, index, sa, MODES[mode], want)
+    except _hip.TmjxError as e:
+        raise ValueError(str(e)) from None
+    rows = np.arange(n) if index is None else index.astype(np.int64)
+    ends = np.cumsum(lens)
+
+    def per_clip(a):
+        full = np.full((n, *a.shape[1:]), np.nan, np.float32)
+        full[rows] = a
+        return {f"clip_{c}": full[e - t:e] for c, e, t in zip(ids, ends, lens)}
+    out = {"gain": per_clip(res["gain"]), "latent_sensitivity": per_clip(res["col2"]), "actuator_sensitivity": per_clip(res["row2"])}
+    if "action_var" in res:
+        out["action_var"] = per_clip(res["action_var"])
+    if store:
+        out["jacobian"] = per_clip(res["jac"])
+    gram_in = res["gram_in"] / m
+    values, vectors = eigen(gram_in, bk)
+    total = float(values.sum())
+    out.update({"mean_jacobian": res["mean_sum"] / m, "gram_in": gram_in, "gram_out": res["gram_out"] / m,
+                "feature": "intention" if (col0, cols) == (0, Z) else f"input:{col0}:{col0 + cols}",
+                "mean": x[rows, col0:col0 + cols].astype(np.float64).mean(0).astype(np.float32), "components": vectors.astype(np.float32),
+                "explained_variance": values.astype(np.float32),
+                "explained_variance_ratio": (values / total if total > 0.0 else np.zeros_like(values)).astype(np.float32),
+                "forward_mismatch": np.float64(np.abs(res["ctrl"].astype(np.float64) - recorded[rows]).max()) if recorded is not None else np.float64(np.nan),
+                "rows": np.int64(m), "wrt": f"{col0}:{col0 + cols}", "mode": mode, "clips": np.asarray(ids, np.int64)})
+    if index is not None:
+        out["row_index"] = index.astype(np.int64)
+    if labels is not None:
+        lab = _labels_file(labels) if isinstance(labels, (str, os.PathLike)) else {int(k): np.asarray(v).reshape(-1) for k, v in dict(labels).items()}
+        flat = np.full(n, -1, np.int64)
+        for c, e, t in zip(ids, ends, lens):
+            if c not in lab:
+                raise KeyError(f"the labels file has no clip_{c}")
+            if lab[c].shape[0] < t:
+                raise ValueError(f"the labels of clip_{c} hold {lab[c].shape[0]} rows, the roll-out {t}")
+            flat[e - t:e] = lab[c][:t]
+        K = int(flat.max()) + 1
+        picked = np.zeros(n, bool)
+        picked[rows] = True
+        mj, mg, gain, count = np.full((K, A, cols), np.nan), np.full((K, cols, cols), np.nan), np.full(K, np.nan), np.zeros(K, np.int64)
+        for k in range(K):
+            mine = np.flatnonzero((flat == k) & picked).astype(np.int32)
+            count[k] = mine.shape[0]
+            if mine.shape[0]:
+                r = bk.decoder_jacobian(xa, layers, head, (col0, cols), eps, mine, None, MODES[mode], ("gain",))
+                mj[k], mg[k], gain[k] = r["mean_sum"] / mine.shape[0], r["gram_in"] / mine.shape[0], float(r["gain"].astype(np.float64).mean())
+        out.update({"motif_mean_jacobian": mj, "motif_gram_in": mg, "motif_gain": gain, "motif_rows": count})
+    if features:
+        out["features"] = {}
+        for j, c in enumerate(ids):
+            tree = {"activations": {"latent_sensitivity": out["latent_sensitivity"][f"clip_{c}"], "actuator_sensitivity": out["actuator_sensitivity"][f"clip_{c}"],
+                                    "jacobian_gain": out["gain"][f"clip_{c}"].reshape(-1, 1)}}
+            if items[j][4] is not None:
+                tree["meta"] = items[j][4]
+            out["features"][c] = tree
+    return out
+
+
+def _flag(opts, name):
+    v = opts.get(name, "false").lower()
+    if v not in ("true", "false"):
+        raise ValueError(f"{name} must be true or false (got {opts[name]})")
+    return v == "true"
+
+
+def main(argv=None, backend=None, policy=None) -> int:
+    """The command line; `policy`: a module in place of checkpoint= (DecoderNet, IntentionPolicy), `backend`: a stand-in for HipBackend."""
+    from .. import h5lite
+    argv = list(sys.argv[1:] if argv is None else argv)
+    opts = dict(a.split("=", 1) for a in argv if "=" in a and a.split("=", 1)[0] in CLI_OPTIONS)
+    if ("checkpoint" not in opts and policy is None) or "rollouts" not in opts or "out" not in opts or len(opts) != len(argv):
+        print(USAGE, file=sys.stderr)
+        return 2
+    try:
+        res = jacobian_rollouts(opts["checkpoint"] if policy is None else policy, opts["rollouts"], opts.get("wrt", "intention"), opts.get("mode", "ctrl"),
+                                int(opts.get("max_rows", 0)), int(opts.get("seed", 0)), opts.get("labels"), _flag(opts, "store"), "features_out" in opts,
+                                backend=backend)
+    except (KeyError, ValueError, OSError) as e:
+        print(f"[jacobian] {e.args[0] if e.args else e}", file=sys.stderr)
+        return 2
+    feats = res.pop("features", None)
+    os.makedirs(os.path.dirname(os.path.abspath(opts["out"])), exist_ok=True)
+    h5lite.write_tree(opts["out"], res)
+    if feats is not None:
+        os.makedirs(opts["features_out"], exist_ok=True)
+        for c, tree in feats.items():
+            h5lite.write_tree(os.path.join(opts["features_out"], f"clip_{c}.h5"), tree)
+    mismatch = float(res["forward_mismatch"])
+    if mismatch > MISMATCH_WARN:
+        print(f"[jacobian] warning: the recomputed ctrl differs from the recorded one by up to {mismatch:.3g} (> {MISMATCH_WARN}): did this checkpoint make "
+              "these roll-outs, and without an intervention downstream of the intention?", file=sys.stderr)
+    ratio = ", ".join(f"{100 * r:.1f}%" for r in res["explained_variance_ratio"][:4])
+    print(f"[jacobian] d {res['mode']} / d input[{res['wrt']}]: {int(res['rows'])} rows of {len(res['clips'])} clips, {res['mean_jacobian'].shape[0]} actuators; "
+          f"mean gain {float(np.trace(res['gram_in'])):.4g}, the leading sensitive directions carry {ratio}; forward mismatch {mismatch:.3g}; wrote {opts['out']}",
+          flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

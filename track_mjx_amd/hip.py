@@ -15,11 +15,12 @@ _PKG = Path(__file__).resolve().parent
 SO_PATH = Path(os.environ.get("TMJX_SO", str(_PKG / "libtmjx_hip.so")))  # TMJX_SO: alternative build (profiling)
 CSRC = _PKG / "csrc"
 SOURCES = (CSRC / "tmjx_hip.hip", CSRC / "tmjx_bf16.hip", CSRC / "tmjx_wave.hip", CSRC / "tmjx_chain.hip", CSRC / "tmjx_lstm.hip",
-           CSRC / "tmjx_rollout.hip", CSRC / "tmjx_wave_sensors.hip", CSRC / "tmjx_wave_align.hip", CSRC / "tmjx_wave_rand.hip", CSRC / "tmjx_render.hip", CSRC / "tmjx_act.hip", CSRC / "tmjx_pca.hip", CSRC / "tmjx_pca_wide.hip", CSRC / "tmjx_readout.hip", CSRC / "tmjx_intervene.hip", CSRC / "tmjx_kmeans.hip", CSRC / "tmjx_hmm.hip", CSRC / "tmjx_spectrogram.hip", CSRC / "tmjx_arhmm.hip", CSRC / "tmjx_tsne.hip", CSRC / "tmjx_compare.hip")
+           CSRC / "tmjx_rollout.hip", CSRC / "tmjx_wave_sensors.hip", CSRC / "tmjx_wave_align.hip", CSRC / "tmjx_wave_rand.hip", CSRC / "tmjx_render.hip", CSRC / "tmjx_act.hip", CSRC / "tmjx_pca.hip", CSRC / "tmjx_pca_wide.hip", CSRC / "tmjx_readout.hip", CSRC / "tmjx_intervene.hip", CSRC / "tmjx_kmeans.hip", CSRC / "tmjx_hmm.hip", CSRC / "tmjx_spectrogram.hip", CSRC / "tmjx_arhmm.hip", CSRC / "tmjx_tsne.hip", CSRC / "tmjx_compare.hip", CSRC / "tmjx_jacobian.hip")
 # per-source compiler flags: the physics kernel's unit is built without machine LICM (csrc/tmjx_wave.hip says why)
 SOURCE_FLAGS = {"tmjx_wave.hip": ("-mllvm", "-disable-machine-licm"),
                 "tmjx_wave_sensors.hip": ("-mllvm", "-disable-machine-licm"),      # (the recording kernel: the same loop body)
-                "tmjx_wave_rand.hip": ("-mllvm", "-disable-machine-licm")}         # (the domain-randomisation kernel: likewise)
+                "tmjx_wave_rand.hip": ("-mllvm", "-disable-machine-licm"),         # (the domain-randomisation kernel: likewise)
+                "tmjx_jacobian.hip": ("-ffp-contract=off",)}      # (the Jacobian states its order: only the fmaf it writes is fused, as on the host)
 
 
 class TmjxError(RuntimeError):
@@ -221,6 +222,21 @@ class CcaInfo(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("kx", "ky", "sweeps", "converged")] + [(k, C.c_float) for k in ("pca_ms", "cross_ms", "svd_ms", "pad_")]
 
 
+JACOBIAN_MAX_LAYERS, JACOBIAN_MAX_WIDTH, JACOBIAN_MAX_A, JACOBIAN_MAX_WRT, JACOBIAN_CHUNK = 8, 1024, 64, 128, 1024      # csrc/jacobian_core.h
+JACOBIAN_CTRL, JACOBIAN_LOC = 0, 1      # the modes of tmjx_decoder_jacobian (include/tmjx.h)
+
+
+class JacobianLayer(C.Structure):
+    """tmjx_jacobian_layer_t (include/tmjx.h)."""
+    _fields_ = [(k, C.c_void_p) for k in ("W", "b", "gamma", "beta")] + [("width", C.c_int32), ("ldw", C.c_int32)]
+
+
+class JacobianDesc(C.Structure):
+    """tmjx_jacobian_desc_t (include/tmjx.h)."""
+    _fields_ = [("L", C.c_int32), ("d_in", C.c_int32), ("layer", JacobianLayer * JACOBIAN_MAX_LAYERS), ("eps", C.c_float), ("A", C.c_int32), ("Wh", C.c_void_p),
+                ("bh", C.c_void_p), ("ldwh", C.c_int32), ("wrt_col0", C.c_int32), ("wrt_cols", C.c_int32), ("pad_", C.c_int32)]
+
+
 INTERVENE_SUBSPACE, INTERVENE_UNITS, INTERVENE_MAX_W, INTERVENE_MAX_K = 0, 1, 1024, 16      # include/tmjx.h, csrc/intervene_core.h
 
 
@@ -412,6 +428,8 @@ SIGNATURES = {
     "tmjx_rdm_corr": ([_vp, _i, _i, _i64, _i, _vp, _i, _i64, _i, _vp, _vp, _vp], _i),
     "tmjx_cca": ([_vp, _i, _i, _i64, _vp, _i, _i64, _d, _i, _vp, _vp, _vp, _P(CcaInfo), _vp, _vp], _i),
     "tmjx_compare_svd": ([_vp, _i, _i, _i64, _vp, _vp, _vp, _P(_i), _vp, _vp], _i),
+    "tmjx_jacobian_workspace": ([_P(JacobianDesc), _i, _P(_i64)], _i),
+    "tmjx_decoder_jacobian": ([_P(JacobianDesc), _vp, _i, _i64, _vp, _i, _vp, _i64, _i] + [_vp] * 9, _i),
     "tmjx_wavelet_bank_size": ([_d, _P(_d), _i, _d, _d, _P(_i64)], _i),
     "tmjx_wavelet_bank": ([_d, _P(_d), _i, _d, _d, _vp, _P(_i), _P(_i)], _i),
     "tmjx_spectrogram_workspace": ([_i] * 4 + [_P(_i64)], _i),
