@@ -153,7 +153,8 @@ def test_abi_declares_pca():
     assert any(p.name == "tmjx_pca.hip" for p in hip.SOURCES) and "tmjx_pca.hip" not in hip.SOURCE_FLAGS
     assert C.sizeof(hip.PcaInfo) == 20 and C.sizeof(hip.StripStyle) == 68
     core = (ROOT / "track_mjx_amd" / "csrc" / "pca_core.h").read_text()
-    assert f"#define PCA_ROWS_PER_WG {hip.PCA_ROWS_PER_WG}" in core and f"#define PCA_MAX_D {hip.PCA_MAX_D}" in core and f"#define PCA_MAX_K {hip.PCA_MAX_K}" in core
+    wg = (ROOT / "track_mjx_amd" / "csrc" / "wg_core.h").read_text()      # (the fixed row split is the discipline's)
+    assert f"#define PCA_ROWS_PER_WG {hip.PCA_ROWS_PER_WG}" in wg and f"#define PCA_MAX_D {hip.PCA_MAX_D}" in core and f"#define PCA_MAX_K {hip.PCA_MAX_K}" in core
 
 
 # ------------------------------------------------------------------------------------------------------------------ 3. the emulation: the panel

@@ -1,11 +1,12 @@
 // csrc/arhmm_core.h — the bodies of the autoregressive hidden-Markov-model kernels (DESIGN.md "Autoregressive sequence model"; include/tmjx.h:
 // tmjx_arhmm_*): K states, each its own linear law x_t ~ W_j phi_t with diagonal noise, phi_t = [xc_(t-1); ...; xc_(t-L); 1] the centred rows
-// before t inside its sequence.  Written with the PCA_WG / PCA_PAR / PCA_SYNC discipline of csrc/pca_core.h, so that they also compile on the host
+// before t inside its sequence.  Written with the PCA_WG / PCA_PAR / PCA_SYNC discipline of csrc/wg_core.h, so that they also compile on the host
 // (tests/hostemu/arhmm_emu.cpp).  Every product of the emission is a chain of float32 FMAs in a fixed order, every moment sum float64 in a fixed
 // order: no floating-point atomics, the same bits on every run.  What does not look at x (forward-backward, transitions, Viterbi) is
 // csrc/hmm_core.h, called as it stands.
 #pragma once
 #include "hmm_core.h"
+#include "moments_core.h"
 
 #define ARHMM_MAX_D 32
 #define ARHMM_MAX_LAGS 4

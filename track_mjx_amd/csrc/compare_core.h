@@ -1,12 +1,12 @@
 // csrc/compare_core.h — the bodies of the representation-comparison kernels (DESIGN.md "Representation comparison"; include/tmjx.h: tmjx_cka_linear,
 // tmjx_rdm_corr, tmjx_cca, tmjx_compare_svd): the Frobenius norms of the centred covariances, the all-pairs pass over two feature sets at once
 // that never writes either distance matrix, the small float64 products of the whitened cross matrix, and a one-sided Jacobi singular value
-// decomposition in one workgroup.  Written with the PCA_WG / PCA_PAR / PCA_SYNC / PCA_PRIVATE discipline of csrc/pca_core.h, so that they also
-// compile on the host (tests/hostemu/compare_emu.cpp).  The moments are the readout's (readout_cross_wg: float32 FMAs inside a chunk of 256 rows,
-// float64 across chunks and super-chunks); every pair of rows is one chain of float32 operations in ascending feature order; every sum across
+// decomposition in one workgroup.  Written with the PCA_WG / PCA_PAR / PCA_SYNC / PCA_PRIVATE discipline of csrc/wg_core.h, so that they also
+// compile on the host (tests/hostemu/compare_emu.cpp).  The moments are csrc/moments_core.h in the readout's tiling (readout_cross_wg: float32
+// FMAs inside a chunk of 256 rows, float64 across chunks and super-chunks); the tournament of the decomposition is pca_pair; every pair of rows is one chain of float32 operations in ascending feature order; every sum across
 // pairs, tiles, rows of a matrix or workgroups is float64 in a fixed order: no atomics of any kind, the same bits on every run.
 #pragma once
-#include "readout_core.h"
+#include "pca_core.h"
 
 #define COMPARE_MAX_D 1024
 #define COMPARE_MAX_N 32768       // rows of the all-pairs entry: 5.4e8 pairs
@@ -33,13 +33,6 @@ static_assert(2 * COMPARE_SVD_PAIRS >= COMPARE_MAX_RANK, "one pass of the workgr
 
 typedef float cmp_f4 __attribute__((vector_size(16)));
 
-// the slot of thread tid in an array declared with PCA_PRIVATE and handed to a function as a pointer
-#ifdef TM_HOST_EMU
-#define COMPARE_SLOT(tid) (tid)
-#else
-#define COMPARE_SLOT(tid) 0
-#endif
-
 // ----------------------------------------------------------------------------------------------- the Frobenius norm of a moment
 // Row `row` of C [d][m] = (the super-chunks' float64 partials added in order) / (n - 1): thread t squares the columns t, t + 256, ... in order and
 // the 256 sums meet in a fixed tree.  rowsum[row] = sum_j C_ij^2.  s_red: [PCA_THREADS] doubles of LDS.
@@ -47,38 +40,23 @@ PCA_WG void compare_frob_row_wg(const double *partial, int S, int d, int m, int 
   PCA_PAR(tid, PCA_THREADS) {
     double s = 0.0;
     for (int j = tid; j < m; j += PCA_THREADS) {
-      double c = 0.0;
-      for (int w = 0; w < S; w++) c += partial[(int64_t)w * d * m + (int64_t)row * m + j];
-      c /= (double)(n - 1);
+      const double c = wg_sum(partial + (int64_t)row * m + j, S, (int64_t)d * m) / (double)(n - 1);
       s = fma(c, c, s);
     }
     s_red[tid] = s;
   }
   PCA_SYNC();
-  for (int half = PCA_THREADS / 2; half >= 1; half >>= 1) {
-    PCA_PAR(tid, PCA_THREADS) {
-      if (tid < half) s_red[tid] += s_red[tid + half];
-    }
-    PCA_SYNC();
-  }
+  wg_tree<1>(s_red);
   PCA_PAR(tid, PCA_THREADS) {
     if (tid == 0) rowsum[row] = s_red[0];
   }
 }
 
 // `count` values in index order
-TM_DEV double compare_total(const double *v, int count) {
-  double s = 0.0;
-  for (int i = 0; i < count; i++) s += v[i];
-  return s;
-}
+TM_DEV double compare_total(const double *v, int count) { return wg_sum(v, count, 1); }
 
 // element e of C [d][m] in float64: the super-chunks' partials added in order, over n - 1
-TM_DEV double compare_cross_reduce(const double *partial, int S, int d, int m, int n, int64_t e) {
-  double s = 0.0;
-  for (int w = 0; w < S; w++) s += partial[(int64_t)w * d * m + e];
-  return s / (double)(n - 1);
-}
+TM_DEV double compare_cross_reduce(const double *partial, int S, int d, int m, int n, int64_t e) { return wg_sum(partial + e, S, (int64_t)d * m) / (double)(n - 1); }
 
 // ----------------------------------------------------------------------------------------------- the rows of a dissimilarity
 // One feature set of the all-pairs pass.  A value is staged as ((x - mean) - shift) scale, three single float32 operations.  Metrics 0 and 1:
@@ -213,14 +191,7 @@ PCA_WG void compare_pairs_wg(const CompareSide &sx, const CompareSide &sy, int n
     s_red[4 * PCA_THREADS + tid] = s4;
   }
   PCA_SYNC();
-  for (int half = PCA_THREADS / 2; half >= 1; half >>= 1) {
-    PCA_PAR(tid, PCA_THREADS) {
-      if (tid < half)
-#pragma unroll
-        for (int k = 0; k < 5; k++) s_red[k * PCA_THREADS + tid] += s_red[k * PCA_THREADS + tid + half];
-    }
-    PCA_SYNC();
-  }
+  wg_tree<5>(s_red);
   PCA_PAR(tid, PCA_THREADS) {
     if (tid < 5) out[tid] = s_red[tid * PCA_THREADS];
   }
@@ -237,14 +208,7 @@ PCA_WG void compare_pairs_total_wg(const double *parts, int64_t tiles, double *s
     for (int k = 0; k < 5; k++) s_red[k * PCA_THREADS + tid] = s[k];
   }
   PCA_SYNC();
-  for (int half = PCA_THREADS / 2; half >= 1; half >>= 1) {
-    PCA_PAR(tid, PCA_THREADS) {
-      if (tid < half)
-#pragma unroll
-        for (int k = 0; k < 5; k++) s_red[k * PCA_THREADS + tid] += s_red[k * PCA_THREADS + tid + half];
-    }
-    PCA_SYNC();
-  }
+  wg_tree<5>(s_red);
   PCA_PAR(tid, PCA_THREADS) {
     if (tid < 5) sums[tid] = s_red[tid * PCA_THREADS];
   }

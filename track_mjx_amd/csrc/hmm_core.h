@@ -1,10 +1,12 @@
 // csrc/hmm_core.h — the bodies of the hidden-Markov-model kernels (DESIGN.md "Sequence model"; include/tmjx.h: tmjx_hmm_*): K states with
 // diagonal-covariance Gaussian emissions over recorded activations x [n][d], the rows split into S sequences.  Written with the PCA_WG / PCA_PAR /
-// PCA_SYNC discipline of csrc/pca_core.h, so that they also compile on the host (tests/hostemu/hmm_emu.cpp): whatever a thread carries from one
+// PCA_SYNC discipline of csrc/wg_core.h, so that they also compile on the host (tests/hostemu/hmm_emu.cpp; the column mean and the row split are
+// csrc/moments_core.h, km_f4 and kmeans_inf the k-means'): whatever a thread carries from one
 // PCA_PAR region to the next lives in LDS.  Every product is a chain of float32 FMAs in a fixed order, every sum across rows or workgroups is
 // float64 in a fixed order: no floating-point atomics, the same bits on every run.
 #pragma once
 #include "kmeans_core.h"
+#include "moments_core.h"
 
 #define HMM_MAX_D 1024
 #define HMM_MAX_K 128

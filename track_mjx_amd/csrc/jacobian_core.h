@@ -2,12 +2,12 @@
 // shared-weight product every matrix of the computation goes through, the Dense -> SiLU -> LayerNorm block forward that keeps what its backward
 // needs, the head (loc, ctrl, the first gradient rows), the LayerNorm / SiLU backward that turns a gradient with respect to a block's output
 // into the left operand of the next product, the per-row outputs and the float64 sums over the rows.  Written with the PCA_WG / PCA_PAR /
-// PCA_SYNC / PCA_PRIVATE discipline of csrc/pca_core.h, so that they also compile on the host (tests/hostemu/jacobian_emu.cpp).  Every number
+// PCA_SYNC / PCA_PRIVATE discipline of csrc/wg_core.h, so that they also compile on the host (tests/hostemu/jacobian_emu.cpp).  Every number
 // is one chain of float32 operations in a stated order (a product: acc = fmaf(a_k, b_k, acc) from 0 in ascending k); a sum across a row of a
 // layer is a fixed tree; the sums across the rows of the call are float64 in row order: no atomics, the same bits on every run, and the bits of
 // a row depend neither on how many rows the call has nor on where the row stands in the list.
 #pragma once
-#include "pca_core.h"
+#include "wg_core.h"
 
 #define JAC_MAX_LAYERS 8
 #define JAC_MAX_WIDTH 1024
@@ -32,15 +32,6 @@ typedef float jac_f4 __attribute__((vector_size(16)));
 
 // the logistic function as the Jacobian has it (csrc/silu_math.h is device-only): differs from the recording kernels' fast form at 1e-6
 TM_DEV float jac_sigmoid(float u) { return 1.f / (1.f + expf(-u)); }
-
-// the sum of s_red [PCA_THREADS] in a fixed tree; the total is s_red[0] behind it
-#define JAC_TREE(s_red)                                        \
-  for (int half_ = PCA_THREADS / 2; half_ >= 1; half_ >>= 1) { \
-    PCA_PAR(tid, PCA_THREADS) {                                \
-      if (tid < half_) s_red[tid] += s_red[tid + half_];       \
-    }                                                          \
-    PCA_SYNC();                                                \
-  }
 
 // ----------------------------------------------------------------------------------------------- the product
 // Tile (tm, tn) of C [M][N] (row stride ldc) = A [M][K] . B: every element is the chain acc = fmaf(A[m][k], B(k, n), acc) from 0 in ascending k.
@@ -130,7 +121,7 @@ PCA_WG void jac_gemm_wg(const float *a, int64_t lda, const int32_t *gather, int 
 
 // ----------------------------------------------------------------------------------------------- a block forward
 // Row `row` of a Dense -> SiLU -> LayerNorm block behind the product: z [rows][H] holds W h and leaves as the block's output.  Thread t owns the
-// columns t, t + 256, ...:  u = z + bias,  sig = 1 / (1 + expf(-u)),  s = u sig;  mean = (the tree over the threads' sums, each in column order) / H;
+// columns t, t + 256, ...:  u = z + bias,  sig = 1 / (1 + expf(-u)),  s = u sig;  mean = (wg_tree over the threads' sums, each in column order) / H;
 // var = (the same tree over (s - mean)^2, one fmaf a term) / H;  r = 1 / sqrtf(var + eps);  xhat = (s - mean) r;  h = fmaf(gamma, xhat, beta).
 // Kept for the backward: xhat, and rs = r silu'(u) with silu'(u) = sig (1 + u (1 - sig)).  s_red: [PCA_THREADS] floats of LDS.
 PCA_WG void jac_block_fwd_wg(float *z, const float *bias, const float *gamma, const float *beta, float eps, int H, int row, float *xhat, float *rs, float *s_red) {
@@ -155,7 +146,7 @@ PCA_WG void jac_block_fwd_wg(float *z, const float *bias, const float *gamma, co
     s_red[tid] = sum;
   }
   PCA_SYNC();
-  JAC_TREE(s_red)
+  wg_tree<1>(s_red);
   const float mean = s_red[0] / (float)H;
   PCA_SYNC();
   PCA_PAR(tid, PCA_THREADS) {
@@ -169,7 +160,7 @@ PCA_WG void jac_block_fwd_wg(float *z, const float *bias, const float *gamma, co
     s_red[tid] = sum;
   }
   PCA_SYNC();
-  JAC_TREE(s_red)
+  wg_tree<1>(s_red);
   const float r = 1.f / sqrtf(s_red[0] / (float)H + eps);
   PCA_SYNC();
   PCA_PAR(tid, PCA_THREADS) {

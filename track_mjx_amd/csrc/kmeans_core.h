@@ -1,9 +1,9 @@
 // csrc/kmeans_core.h — the bodies of the k-means kernels (DESIGN.md "Clustering"; include/tmjx.h: tmjx_kmeans_*): Lloyd's iteration with k-means++
 // seeding on recorded activations x [n][d] against k centroids.  Written with the PCA_WG / PCA_PAR / PCA_SYNC / PCA_PRIVATE discipline of
-// csrc/pca_core.h, so that they also compile on the host (tests/hostemu/kmeans_emu.cpp).  Every product is a chain of float32 FMAs in a fixed
+// csrc/wg_core.h, so that they also compile on the host (tests/hostemu/kmeans_emu.cpp); the column mean and the row split are csrc/moments_core.h.  Every product is a chain of float32 FMAs in a fixed
 // order; every sum across rows or workgroups is float64 in a fixed order: no floating-point atomics, the same bits on every run.
 #pragma once
-#include "pca_wide_core.h"
+#include "moments_core.h"
 
 #define KMEANS_MAX_D 1024
 #define KMEANS_MAX_K 256
@@ -14,56 +14,14 @@
 #define KMEANS_LDC 68            // row stride of the staged centroids  s_c[feature][centroid]: likewise its 4 centroids as one
 #define KMEANS_UTILE 64          // columns of an update workgroup: its LDS image is [k][64] float64, 128 KB at k = 256
 #define KMEANS_UTHREADS 256      // its threads: four waves, wave w owns the clusters j = w (mod 4)
-#define KMEANS_MIN_PART 32       // row parts of the update: the partial sums [P][k][d] float64 take at most 64 MB (2^23 doubles) or, where k d is
-#define KMEANS_PART_DOUBLES (1 << 23)      // large, 32 parts, whatever n is
 #define KMEANS_SEED_ROWS 256     // rows of one workgroup of the seeding distance pass, and of one block of its prefix sum
 
-// the fixed row split of the update: chunks of 256 rows, `per` consecutive chunks to a part, at most max(32, 2^23 / (k d)) parts.  It depends on
-// n, k and d only.
-struct KmeansSplit { int nchunks, per, P; };
-PCA_HD KmeansSplit kmeans_split(int n, int k, int d) {
-  KmeansSplit s;
-  int cap = KMEANS_PART_DOUBLES / (k * d);
-  if (cap < KMEANS_MIN_PART) cap = KMEANS_MIN_PART;
-  s.nchunks = pca_nwg(n);
-  s.per = (s.nchunks + cap - 1) / cap;
-  s.P = (s.nchunks + s.per - 1) / s.per;
-  return s;
-}
 PCA_HD int kmeans_tiles(int v, int tile) { return (v + tile - 1) / tile; }
 PCA_HD float kmeans_inf() { return __builtin_inff(); }
 
 typedef float km_f4 __attribute__((vector_size(16)));
 
 // ----------------------------------------------------------------------------------------------- assign
-// float64 column sums of chunk `chunk` (256 rows) over the columns [128 cb, 128 cb + 128): thread (h, c) sums the rows of parity h in row order,
-// the halves are added in a fixed order.  partial: [chunks][d].  s_sum: [2][128] doubles of LDS.
-PCA_WG void kmeans_colsum_wg(const float *x, int64_t ldx, int n, int d, int chunk, int cb, double *partial, double *s_sum) {
-  const int64_t row0 = (int64_t)chunk * PCA_ROWS_PER_WG;
-  const int rows = n - row0 < PCA_ROWS_PER_WG ? (int)(n - row0) : PCA_ROWS_PER_WG;
-  PCA_PAR(tid, PCA_THREADS) {
-    const int c = cb * PCA_WIDE_TILE + (tid & (PCA_WIDE_TILE - 1)), h = tid / PCA_WIDE_TILE;
-    if (c < d) {
-      double sum = 0.0;
-#pragma unroll 8
-      for (int r = h; r < rows; r += 2) sum += (double)x[(row0 + r) * ldx + c];
-      s_sum[h * PCA_WIDE_TILE + (tid & (PCA_WIDE_TILE - 1))] = sum;
-    }
-  }
-  PCA_SYNC();
-  PCA_PAR(tid, PCA_THREADS) {
-    const int c = cb * PCA_WIDE_TILE + tid;
-    if (tid < PCA_WIDE_TILE && c < d) partial[(int64_t)chunk * d + c] = s_sum[tid] + s_sum[PCA_WIDE_TILE + tid];
-  }
-}
-
-// the mean of column c: the chunks' sums added in chunk order, in float64
-TM_DEV float kmeans_mean_col(const double *partial, int nchunks, int d, int n, int c) {
-  double s = 0.0;
-  for (int w = 0; w < nchunks; w++) s += partial[(int64_t)w * d + c];
-  return (float)(s / (double)n);
-}
-
 // ||c_j - mean||^2 of centroid j: one fmaf chain over the features in ascending order, the centroid centred as the rows are
 TM_DEV float kmeans_cnorm(const float *centroids, const float *mean, int d, int j) {
   float s = 0.f;

@@ -1,75 +1,25 @@
 // csrc/pca_core.h — the bodies of the PCA kernels and of the progression panel (DESIGN.md "PCA"; include/tmjx.h: tmjx_pca_*, tmjx_plot_strips).
-// Like render_core.h they also compile on the host (tests/hostemu/pca_emu.cpp).  Two kinds of function:
-//   TM_DEV  — one thread's work (a projection, a pixel of the panel): the host runs one loop iteration where the GPU has one thread;
-//   PCA_WG  — one workgroup's work, written as PCA_PAR loops (one iteration per thread) between PCA_SYNC barriers.  On the GPU a PCA_PAR body runs
-//             once per thread and PCA_SYNC is __syncthreads; on the host PCA_PAR is a serial loop over the thread ids and PCA_SYNC nothing, which is
-//             the same computation because no PCA_PAR body reads what another iteration of the same loop writes.  State a thread keeps across
-//             a barrier is declared with PCA_PRIVATE (registers on the GPU, one slot per thread id on the host).
+// Like render_core.h they also compile on the host (tests/hostemu/pca_emu.cpp): the discipline is csrc/wg_core.h, the column sums, the mean and
+// the inner step of the Gram tile csrc/moments_core.h.
 #pragma once
-#include <math.h>
-#include <stddef.h>
-#include <stdint.h>
-
-#ifndef TM_DEV
-#define TM_DEV __device__ __forceinline__
-#endif
+#include "moments_core.h"
 
 #define PCA_MAX_D 128          // two [128][129] float images (A and V) are 132 KB of the CU's 160 KB of LDS
-#define PCA_ROWS_PER_WG 256    // rows of one workgroup's partial moments: the fixed split that makes the reduction order independent of the grid
-#define PCA_THREADS 256        // workgroup size of the moment, transform and panel kernels
-#define PCA_KB 16              // rows of x staged in LDS per barrier pair of the Gram kernel
-#define PCA_TILE_LD 128        // row stride of that stage (every lane of a wave reads the same row: the stride does not matter to the banks)
+#define PCA_TILE_LD 128        // row stride of the Gram kernel's stage (every lane of a wave reads the same row: the stride does not matter to the banks)
 #define PCA_TROWS 64           // rows of x per workgroup of the transform kernel
 #define PCA_MAX_K 8            // curves of a panel
 #define PCA_SWEEP_LIMIT 30
 #define PCA_TOL 5.9604645e-8f  // 2^-24: sweeps stop at off(A) <= PCA_TOL * ||A||_F
 
-#ifdef TM_HOST_EMU
-#define PCA_WG static inline
-#define PCA_PAR(tid, nt) for (int tid = 0; tid < (nt); tid++)
-#define PCA_SYNC() ((void)0)
-#define PCA_PRIVATE(T, name, n) T name##_all_[PCA_THREADS][n]
-#define PCA_MINE(name, tid) name##_all_[tid]
-#define PCA_HD static inline
-#else
-#define PCA_HD __host__ __device__ static inline
-#define PCA_WG __device__ __forceinline__
-#define PCA_PAR(tid, nt) for (int tid = threadIdx.x, once_ = 1; once_; once_ = 0)
-#define PCA_SYNC() __syncthreads()
-#define PCA_PRIVATE(T, name, n) T name##_all_[1][n]
-#define PCA_MINE(name, tid) name##_all_[0]
-#endif
+static_assert(PCA_MAX_D == PCA_WIDE_TILE, "the narrow fit's column sums are one tile of moments_colsum_wg");
 
 // what the Jacobi kernel reports (device side of tmjx_pca_info_t)
 struct PcaInfo { int sweeps, converged; float off_rel; int pad_; };
 
-PCA_HD int pca_nwg(int n) { return (n + PCA_ROWS_PER_WG - 1) / PCA_ROWS_PER_WG; }
-
 // ----------------------------------------------------------------------------------------------- moments
-// Pass 1: float64 column sums of the workgroup's rows.  Thread (h, c) = (tid / 128, tid % 128) sums the rows of parity h of column c; the two
-// halves are added in a fixed order.  s_sum: [2][PCA_MAX_D] doubles of LDS.
-PCA_WG void pca_colsum_wg(const float *x, int64_t ldx, int n, int d, int wg, double *partial, double *s_sum) {
-  const int row0 = wg * PCA_ROWS_PER_WG, rows = n - row0 < PCA_ROWS_PER_WG ? n - row0 : PCA_ROWS_PER_WG;
-  PCA_PAR(tid, PCA_THREADS) {
-    const int c = tid & (PCA_MAX_D - 1), h = tid / PCA_MAX_D;
-    if (c < d) {
-      double s = 0.0;
-      for (int r = h; r < rows; r += 2) s += (double)x[(int64_t)(row0 + r) * ldx + c];
-      s_sum[h * PCA_MAX_D + c] = s;
-    }
-  }
-  PCA_SYNC();
-  PCA_PAR(tid, PCA_THREADS) {
-    if (tid < d) partial[(int64_t)wg * d + tid] = s_sum[tid] + s_sum[PCA_MAX_D + tid];
-  }
-}
-
-// the mean of column c: the workgroups' sums added in workgroup order, in float64
-TM_DEV float pca_mean_col(const double *partial, int nwg, int d, int n, int c) {
-  double s = 0.0;
-  for (int w = 0; w < nwg; w++) s += partial[(int64_t)w * d + c];
-  return (float)(s / (double)n);
-}
+// Pass 1: the column sums of the workgroup's PCA_ROWS_PER_WG rows are one chunk and one tile (cb = 0) of csrc/moments_core.h; partial: [nwg][d].
+PCA_WG void pca_colsum_wg(const float *x, int64_t ldx, int n, int d, int wg, double *partial, double *s_sum) { kmeans_colsum_wg(x, ldx, n, d, wg, 0, partial, s_sum); }
+TM_DEV float pca_mean_col(const double *partial, int nwg, int d, int n, int c) { return moments_mean_col(partial, nwg, d, n, c); }
 
 // Pass 2: the workgroup's partial of (x - mean)^T (x - mean), plain float32 FMAs.  256 threads as a 16 x 16 grid; thread (ty, tx) owns the NT x NT
 // elements (ty + 16 a, tx + 16 b), so the 16 lanes of a row read 16 consecutive floats of the staged row and the four ty of a wave broadcast.
@@ -91,21 +41,7 @@ PCA_WG void pca_gram_wg(const float *x, int64_t ldx, int n, int d, const float *
       }
     }
     PCA_SYNC();
-    PCA_PAR(tid, PCA_THREADS) {
-      const int ty = tid >> 4, tx = tid & 15;
-      float *mine = PCA_MINE(acc, tid);
-#pragma unroll 4
-      for (int k = 0; k < PCA_KB; k++) {
-        const float *row = s_tile + k * PCA_TILE_LD;
-        float a[NT], b[NT];
-#pragma unroll
-        for (int u = 0; u < NT; u++) { a[u] = row[ty + 16 * u]; b[u] = row[tx + 16 * u]; }
-#pragma unroll
-        for (int u = 0; u < NT; u++)
-#pragma unroll
-          for (int v = 0; v < NT; v++) mine[u * NT + v] = fmaf(a[u], b[v], mine[u * NT + v]);
-      }
-    }
+    PCA_PAR(tid, PCA_THREADS) { moments_fma_rows<NT, NT>(s_tile, PCA_TILE_LD, s_tile, PCA_TILE_LD, tid >> 4, tid & 15, PCA_MINE(acc, tid)); }
     PCA_SYNC();
   }
   PCA_PAR(tid, PCA_THREADS) {
@@ -122,11 +58,7 @@ PCA_WG void pca_gram_wg(const float *x, int64_t ldx, int n, int d, const float *
 }
 
 // element e of the covariance: the partials added in workgroup order, in float64, over n - 1
-TM_DEV float pca_gram_reduce(const float *partial, int nwg, int d, int n, int e) {
-  double s = 0.0;
-  for (int w = 0; w < nwg; w++) s += (double)partial[(int64_t)w * d * d + e];
-  return (float)(s / (double)(n - 1));
-}
+TM_DEV float pca_gram_reduce(const float *partial, int nwg, int d, int n, int e) { return (float)(wg_sum(partial + e, nwg, (int64_t)d * d) / (double)(n - 1)); }
 
 // ----------------------------------------------------------------------------------------------- Jacobi
 // pair k of step r of the round-robin tournament on m (even) players: player m - 1 stays, the others turn; p < q

@@ -1,139 +1,38 @@
 // csrc/pca_wide_core.h — the bodies of the wide PCA kernels, 129 <= d <= 1024 (DESIGN.md "PCA", wide fit; include/tmjx.h: tmjx_pca_*_wide).
-// Written with the PCA_WG / PCA_PAR / PCA_SYNC / PCA_PRIVATE discipline of csrc/pca_core.h, so that they also compile on the host
-// (tests/hostemu/pca_wide_emu.cpp).  The covariance and V^T live in global memory; the eigen-decomposition is block Jacobi: the columns are cut
-// into blocks of PCA_WIDE_BLOCK, the blocks are paired by the round-robin tournament of pca_pair, and the (at most 128 x 128) sub-matrix of a pair
-// is diagonalised by pca_jacobi_wg, whose sorted unit eigenvector rows J rotate the pair's rows (J A, J V^T) and then its columns (A J^T).
+// Written with the PCA_WG / PCA_PAR / PCA_SYNC / PCA_PRIVATE discipline of csrc/wg_core.h, so that they also compile on the host
+// (tests/hostemu/pca_wide_emu.cpp); the moments are csrc/moments_core.h, the inner solver csrc/pca_core.h.  The covariance and V^T live in
+// global memory; the eigen-decomposition is block Jacobi: the columns are cut into blocks of PCA_WIDE_BLOCK, the blocks are paired by the
+// round-robin tournament of pca_pair, and the (at most 128 x 128) sub-matrix of a pair is diagonalised by pca_jacobi_wg, whose sorted unit eigenvector rows J rotate the pair's rows (J A, J V^T) and then its columns (A J^T).
 #pragma once
 #include "pca_core.h"
 
 #define PCA_WIDE_MAX_D 1024
 #define PCA_WIDE_BLOCK 64        // columns of a Jacobi block: a pair is PCA_MAX_D = 128 wide, the inner solver's limit
-#define PCA_WIDE_TILE 128        // side of a Gram output tile
-#define PCA_WIDE_MAX_SUPER 16    // row super-chunks of the moment passes: the partials are [S][d][d] float64, whatever n is
 #define PCA_WIDE_PASS 64         // columns (row pass) or rows (column pass) of one workgroup of a rotation pass
 #define PCA_WIDE_LDA 129         // row stride of the staged slice of J: 16 consecutive k of one row go to 16 different banks
 #define PCA_WIDE_LDB 65          // row stride of the staged slice of A
 #define PCA_WIDE_TK 64           // features staged per barrier pair of the transform kernel
 #define PCA_WIDE_TLD 65          // row stride of that stage
 
-// the fixed row split of the moment passes: chunks of PCA_ROWS_PER_WG rows, `per` consecutive chunks to a super-chunk, S <= 16 super-chunks.
-// It depends on n only.
-struct PcaWideSplit { int nchunks, per, S; };
-PCA_HD PcaWideSplit pca_wide_split(int n) {
-  PcaWideSplit s;
-  s.nchunks = pca_nwg(n);
-  s.per = (s.nchunks + PCA_WIDE_MAX_SUPER - 1) / PCA_WIDE_MAX_SUPER;
-  s.S = (s.nchunks + s.per - 1) / s.per;
-  return s;
-}
-PCA_HD int pca_wide_tiles(int d) { return (d + PCA_WIDE_TILE - 1) / PCA_WIDE_TILE; }
 PCA_HD int pca_wide_blocks(int d) { return (d + PCA_WIDE_BLOCK - 1) / PCA_WIDE_BLOCK; }
 PCA_HD int pca_wide_players(int d) { return (pca_wide_blocks(d) + 1) & ~1; }      // with the empty "bye" block of an odd count
 
 // ----------------------------------------------------------------------------------------------- moments
-// Pass 1: float64 column sums of super-chunk s over the columns [128 cb, 128 cb + 128).  Thread (h, c) sums the rows of parity h (counted from
-// the super-chunk's first row) in row order; the halves are added in a fixed order.  partial: [S][d].  s_sum: [2][128] doubles of LDS.
-PCA_WG void pca_wide_colsum_wg(const float *x, int64_t ldx, int n, int d, int s, int cb, double *partial, double *s_sum) {
-  const PcaWideSplit sp = pca_wide_split(n);
-  const int64_t row0 = (int64_t)s * sp.per * PCA_ROWS_PER_WG;
-  const int64_t left = (int64_t)n - row0, span = (int64_t)sp.per * PCA_ROWS_PER_WG;
-  const int rows = (int)(left < span ? left : span);
-  PCA_PAR(tid, PCA_THREADS) {
-    const int c = cb * PCA_WIDE_TILE + (tid & (PCA_WIDE_TILE - 1)), h = tid / PCA_WIDE_TILE;
-    if (c < d) {
-      double sum = 0.0;
-      for (int r = h; r < rows; r += 2) sum += (double)x[(row0 + r) * ldx + c];
-      s_sum[h * PCA_WIDE_TILE + (tid & (PCA_WIDE_TILE - 1))] = sum;
-    }
-  }
-  PCA_SYNC();
-  PCA_PAR(tid, PCA_THREADS) {
-    const int c = cb * PCA_WIDE_TILE + tid;
-    if (tid < PCA_WIDE_TILE && c < d) partial[(int64_t)s * d + c] = s_sum[tid] + s_sum[PCA_WIDE_TILE + tid];
-  }
-}
-
-// the mean of column c: the super-chunks' sums added in order, in float64
-TM_DEV float pca_wide_mean_col(const double *partial, int S, int d, int n, int c) {
-  double s = 0.0;
-  for (int w = 0; w < S; w++) s += partial[(int64_t)w * d + c];
-  return (float)(s / (double)n);
-}
-
-// Pass 2: output tile (ti, tj), tj >= ti, of (x - mean)^T (x - mean) over super-chunk s.  Within a chunk of 256 rows the products are float32 FMAs
-// with the thread layout of pca_gram_wg<8>; after each chunk the thread adds its 64 float32 sums into float64 accumulators, in chunk order.
-// partial: [S][d][d] float64, of which only the tiles with tj >= ti are written.  s_tile: [2][PCA_KB][PCA_TILE_LD] floats of LDS.  In a diagonal
+// Pass 1: the float64 column sums of every super-chunk of pca_wide_split(n) and the mean from them (moments_colsum_wg, moments_mean_col).
+// Pass 2: output tile (ti, tj), tj >= ti, of (x - mean)^T (x - mean) over super-chunk s: moments_tile_wg<8, 8> with both sides taken from x.
+// partial: [S][d][d] float64, of which only the tiles with tj >= ti are written.  s_tile: [2][PCA_KB][PCA_WIDE_TILE] floats of LDS.  In a diagonal
 // tile (i, j) and (j, i) see the same products in the same order.
 PCA_WG void pca_wide_gram_wg(const float *x, int64_t ldx, int n, int d, const float *mean, int ti, int tj, int s, double *partial, float *s_tile) {
   const PcaWideSplit sp = pca_wide_split(n);
   const int chunk0 = s * sp.per, chunk1 = chunk0 + sp.per < sp.nchunks ? chunk0 + sp.per : sp.nchunks;
-  const int ci0 = ti * PCA_WIDE_TILE, cj0 = tj * PCA_WIDE_TILE;
-  float *s_i = s_tile, *s_j = s_tile + PCA_KB * PCA_TILE_LD;
-  PCA_PRIVATE(float, acc, 64);
-  PCA_PRIVATE(double, sum, 64);
-  PCA_PAR(tid, PCA_THREADS) {
-#pragma unroll
-    for (int e = 0; e < 64; e++) PCA_MINE(sum, tid)[e] = 0.0;
-  }
-  for (int chunk = chunk0; chunk < chunk1; chunk++) {
-    const int64_t row0 = (int64_t)chunk * PCA_ROWS_PER_WG;
-    const int rows = n - row0 < PCA_ROWS_PER_WG ? (int)(n - row0) : PCA_ROWS_PER_WG;
-    PCA_PAR(tid, PCA_THREADS) {
-#pragma unroll
-      for (int e = 0; e < 64; e++) PCA_MINE(acc, tid)[e] = 0.f;
-    }
-    for (int kb = 0; kb < rows; kb += PCA_KB) {
-      PCA_PAR(tid, PCA_THREADS) {
-        for (int e = tid; e < PCA_KB * PCA_WIDE_TILE; e += PCA_THREADS) {
-          const int r = e / PCA_WIDE_TILE, c = e % PCA_WIDE_TILE;
-          const bool in = kb + r < rows;
-          const float *xr = x + (row0 + kb + r) * ldx;
-          s_i[r * PCA_TILE_LD + c] = (in && ci0 + c < d) ? xr[ci0 + c] - mean[ci0 + c] : 0.f;
-          s_j[r * PCA_TILE_LD + c] = (in && cj0 + c < d) ? xr[cj0 + c] - mean[cj0 + c] : 0.f;
-        }
-      }
-      PCA_SYNC();
-      PCA_PAR(tid, PCA_THREADS) {
-        const int ty = tid >> 4, tx = tid & 15;
-        float *mine = PCA_MINE(acc, tid);
-#pragma unroll 4
-        for (int k = 0; k < PCA_KB; k++) {
-          float a[8], b[8];
-#pragma unroll
-          for (int u = 0; u < 8; u++) { a[u] = s_i[k * PCA_TILE_LD + ty + 16 * u]; b[u] = s_j[k * PCA_TILE_LD + tx + 16 * u]; }
-#pragma unroll
-          for (int u = 0; u < 8; u++)
-#pragma unroll
-            for (int v = 0; v < 8; v++) mine[u * 8 + v] = fmaf(a[u], b[v], mine[u * 8 + v]);
-        }
-      }
-      PCA_SYNC();
-    }
-    PCA_PAR(tid, PCA_THREADS) {
-#pragma unroll
-      for (int e = 0; e < 64; e++) PCA_MINE(sum, tid)[e] += (double)PCA_MINE(acc, tid)[e];
-    }
-  }
-  PCA_PAR(tid, PCA_THREADS) {
-    const int ty = tid >> 4, tx = tid & 15;
-    double *out = partial + (int64_t)s * d * d;
-#pragma unroll
-    for (int u = 0; u < 8; u++)
-#pragma unroll
-      for (int v = 0; v < 8; v++) {
-        const int i = ci0 + ty + 16 * u, j = cj0 + tx + 16 * v;
-        if (i < d && j < d) out[(int64_t)i * d + j] = PCA_MINE(sum, tid)[u * 8 + v];
-      }
-  }
+  moments_tile_wg<8, 8>(x, ldx, mean, d, ti * PCA_WIDE_TILE, x, ldx, mean, d, tj * PCA_WIDE_TILE, n, chunk0, chunk1, partial + (int64_t)s * d * d, d, s_tile,
+                        s_tile + PCA_KB * PCA_WIDE_TILE);
 }
 
 // element (i, j) of the covariance: the super-chunks' partials added in order, in float64, over n - 1; below the diagonal tiles the mirror image
 TM_DEV float pca_wide_gram_reduce(const double *partial, int S, int d, int n, int i, int j) {
   const bool up = i / PCA_WIDE_TILE <= j / PCA_WIDE_TILE;
-  const int64_t e = up ? (int64_t)i * d + j : (int64_t)j * d + i;
-  double s = 0.0;
-  for (int w = 0; w < S; w++) s += partial[(int64_t)w * d * d + e];
-  return (float)(s / (double)(n - 1));
+  return (float)(wg_sum(partial + (up ? (int64_t)i * d + j : (int64_t)j * d + i), S, (int64_t)d * d) / (double)(n - 1));
 }
 
 // ----------------------------------------------------------------------------------------------- norms
@@ -150,23 +49,14 @@ PCA_WG void pca_wide_rownorm_wg(const float *A, int d, int row, double *rowsum, 
     s_red[tid] = s; s_red[PCA_THREADS + tid] = o;
   }
   PCA_SYNC();
-  for (int w = PCA_THREADS / 2; w > 0; w >>= 1) {
-    PCA_PAR(tid, PCA_THREADS) {
-      if (tid < w) { s_red[tid] += s_red[tid + w]; s_red[PCA_THREADS + tid] += s_red[PCA_THREADS + tid + w]; }
-    }
-    PCA_SYNC();
-  }
+  wg_tree<2>(s_red);
   PCA_PAR(tid, PCA_THREADS) {
     if (tid == 0) { rowsum[row] = s_red[0]; rowsum[d + row] = s_red[PCA_THREADS]; }
   }
 }
 
 // which = 0: ||A||_F^2, which = 1: off(A)^2 — the rows' sums added in row order
-TM_DEV double pca_wide_norm_total(const double *rowsum, int d, int which) {
-  double s = 0.0;
-  for (int i = 0; i < d; i++) s += rowsum[which * d + i];
-  return s;
-}
+TM_DEV double pca_wide_norm_total(const double *rowsum, int d, int which) { return wg_sum(rowsum + which * d, d, 1); }
 
 // ----------------------------------------------------------------------------------------------- block Jacobi
 // pair k of round r: the blocks p < q as column ranges [p0, p0 + sp) and [q0, q0 + sq); m = sp + sq <= 128 is the sub-matrix's size, 0 when q is

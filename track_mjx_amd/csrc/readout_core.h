@@ -1,7 +1,8 @@
 // csrc/readout_core.h — the bodies of the linear-readout kernels (DESIGN.md "Readout"; include/tmjx.h: tmjx_readout_*): ridge regression from
 // recorded activations x [n][d] to targets y [n][m] in the eigenbasis the wide PCA leaves on the device.  Written with the PCA_WG / PCA_PAR /
-// PCA_SYNC / PCA_PRIVATE discipline of csrc/pca_core.h, so that they also compile on the host (tests/hostemu/readout_emu.cpp).  Every product is a
-// chain of float32 FMAs in a fixed order; every sum across workgroups is float64 in a fixed order: no atomics, the same bits on every run.
+// PCA_SYNC / PCA_PRIVATE discipline of csrc/wg_core.h, so that they also compile on the host (tests/hostemu/readout_emu.cpp); the moments are
+// csrc/moments_core.h, the eigenbasis and the transform's stage sizes csrc/pca_wide_core.h.  Every product is a chain of float32 FMAs in a fixed
+// order; every sum across workgroups is float64 in a fixed order: no atomics, the same bits on every run.
 #pragma once
 #include "pca_wide_core.h"
 
@@ -19,80 +20,18 @@ PCA_HD int readout_tiles(int v, int tile) { return (v + tile - 1) / tile; }
 
 // ----------------------------------------------------------------------------------------------- cross moment
 // Output tile (ti, tj) of (x - mean_x)^T (y - mean_y) over super-chunk s of pca_wide_split(n): the features [128 ti, 128 ti + 128) against the
-// targets [64 tj, 64 tj + 64), both centred as they are staged, edge tiles masked.  Within a chunk of 256 rows the products are float32 FMAs; after
-// each chunk the thread adds its 32 float32 sums into float64 accumulators, in chunk order.  Thread (ty, tx) owns the features ty + 16 u and the
-// targets tx + 16 v.  partial: [S][d][m] float64.  s_x: [PCA_KB][PCA_WIDE_TILE], s_y: [PCA_KB][READOUT_TILE_M] floats of LDS.
+// targets [64 tj, 64 tj + 64), moments_tile_wg<8, 4>.  partial: [S][d][m] float64.  s_x: [PCA_KB][PCA_WIDE_TILE], s_y: [PCA_KB][READOUT_TILE_M] floats
+// of LDS.
 PCA_WG void readout_cross_wg(const float *x, int64_t ldx, const float *y, int64_t ldy, int n, int d, int m, const float *mean_x, const float *mean_y, int ti,
                              int tj, int s, double *partial, float *s_x, float *s_y) {
   const PcaWideSplit sp = pca_wide_split(n);
   const int chunk0 = s * sp.per, chunk1 = chunk0 + sp.per < sp.nchunks ? chunk0 + sp.per : sp.nchunks;
-  const int ci0 = ti * PCA_WIDE_TILE, cj0 = tj * READOUT_TILE_M;
-  PCA_PRIVATE(float, acc, 32);
-  PCA_PRIVATE(double, sum, 32);
-  PCA_PAR(tid, PCA_THREADS) {
-#pragma unroll
-    for (int e = 0; e < 32; e++) PCA_MINE(sum, tid)[e] = 0.0;
-  }
-  for (int chunk = chunk0; chunk < chunk1; chunk++) {
-    const int64_t row0 = (int64_t)chunk * PCA_ROWS_PER_WG;
-    const int rows = n - row0 < PCA_ROWS_PER_WG ? (int)(n - row0) : PCA_ROWS_PER_WG;
-    PCA_PAR(tid, PCA_THREADS) {
-#pragma unroll
-      for (int e = 0; e < 32; e++) PCA_MINE(acc, tid)[e] = 0.f;
-    }
-    for (int kb = 0; kb < rows; kb += PCA_KB) {
-      PCA_PAR(tid, PCA_THREADS) {
-        for (int e = tid; e < PCA_KB * PCA_WIDE_TILE; e += PCA_THREADS) {
-          const int r = e / PCA_WIDE_TILE, c = e % PCA_WIDE_TILE;
-          s_x[r * PCA_WIDE_TILE + c] = (kb + r < rows && ci0 + c < d) ? x[(row0 + kb + r) * ldx + ci0 + c] - mean_x[ci0 + c] : 0.f;
-        }
-        for (int e = tid; e < PCA_KB * READOUT_TILE_M; e += PCA_THREADS) {
-          const int r = e / READOUT_TILE_M, c = e % READOUT_TILE_M;
-          s_y[r * READOUT_TILE_M + c] = (kb + r < rows && cj0 + c < m) ? y[(row0 + kb + r) * ldy + cj0 + c] - mean_y[cj0 + c] : 0.f;
-        }
-      }
-      PCA_SYNC();
-      PCA_PAR(tid, PCA_THREADS) {
-        const int ty = tid >> 4, tx = tid & 15;
-        float *mine = PCA_MINE(acc, tid);
-#pragma unroll 4
-        for (int k = 0; k < PCA_KB; k++) {
-          float a[8], b[4];
-#pragma unroll
-          for (int u = 0; u < 8; u++) a[u] = s_x[k * PCA_WIDE_TILE + ty + 16 * u];
-#pragma unroll
-          for (int v = 0; v < 4; v++) b[v] = s_y[k * READOUT_TILE_M + tx + 16 * v];
-#pragma unroll
-          for (int u = 0; u < 8; u++)
-#pragma unroll
-            for (int v = 0; v < 4; v++) mine[u * 4 + v] = fmaf(a[u], b[v], mine[u * 4 + v]);
-        }
-      }
-      PCA_SYNC();
-    }
-    PCA_PAR(tid, PCA_THREADS) {
-#pragma unroll
-      for (int e = 0; e < 32; e++) PCA_MINE(sum, tid)[e] += (double)PCA_MINE(acc, tid)[e];
-    }
-  }
-  PCA_PAR(tid, PCA_THREADS) {
-    const int ty = tid >> 4, tx = tid & 15;
-    double *out = partial + (int64_t)s * d * m;
-#pragma unroll
-    for (int u = 0; u < 8; u++)
-#pragma unroll
-      for (int v = 0; v < 4; v++) {
-        const int i = ci0 + ty + 16 * u, j = cj0 + tx + 16 * v;
-        if (i < d && j < m) out[(int64_t)i * m + j] = PCA_MINE(sum, tid)[u * 4 + v];
-      }
-  }
+  moments_tile_wg<8, 4>(x, ldx, mean_x, d, ti * PCA_WIDE_TILE, y, ldy, mean_y, m, tj * READOUT_TILE_M, n, chunk0, chunk1, partial + (int64_t)s * d * m, m, s_x, s_y);
 }
 
 // element e of C [d][m]: the super-chunks' partials added in order, in float64, over n - 1
 TM_DEV float readout_cross_reduce(const double *partial, int S, int d, int m, int n, int e) {
-  double s = 0.0;
-  for (int w = 0; w < S; w++) s += partial[(int64_t)w * d * m + e];
-  return (float)(s / (double)(n - 1));
+  return (float)(wg_sum(partial + e, S, (int64_t)d * m) / (double)(n - 1));
 }
 
 // ----------------------------------------------------------------------------------------------- Z and the weights
@@ -252,43 +191,13 @@ PCA_WG void readout_apply_wg(const float *x, int n, int d, int64_t ldx, const fl
 }
 
 // sse of output column q: the row blocks' partials added in block order
-TM_DEV double readout_sse_col(const double *partial, int nblocks, int Q, int q) {
-  double s = 0.0;
-  for (int b = 0; b < nblocks; b++) s += partial[(int64_t)b * Q + q];
-  return s;
-}
+TM_DEV double readout_sse_col(const double *partial, int nblocks, int Q, int q) { return wg_sum(partial + q, nblocks, Q); }
 
-// The centred sum of squares of y over super-chunk s and the columns [128 cb, 128 cb + 128), by the split and thread layout of pca_wide_colsum_wg;
-// the column mean is float64: colsum's partials [S][m] added in order, over n.  partial: [S][m].  s_sum: [2][128] doubles of LDS.
+// The centred sum of squares of y over super-chunk s and the columns [128 cb, 128 cb + 128): the column-sum body with the term (y - mean)^2, the
+// column mean in float64 from colsum's partials [S][m].  partial: [S][m].  s_sum: [2][128] doubles of LDS.
 PCA_WG void readout_sst_wg(const float *y, int64_t ldy, int n, int m, int s, int cb, const double *colsum, double *partial, double *s_sum) {
-  const PcaWideSplit sp = pca_wide_split(n);
-  const int64_t row0 = (int64_t)s * sp.per * PCA_ROWS_PER_WG;
-  const int64_t left = (int64_t)n - row0, span = (int64_t)sp.per * PCA_ROWS_PER_WG;
-  const int rows = (int)(left < span ? left : span);
-  PCA_PAR(tid, PCA_THREADS) {
-    const int c = cb * PCA_WIDE_TILE + (tid & (PCA_WIDE_TILE - 1)), h = tid / PCA_WIDE_TILE;
-    if (c < m) {
-      double mean = 0.0;
-      for (int w = 0; w < sp.S; w++) mean += colsum[(int64_t)w * m + c];
-      mean /= (double)n;
-      double sum = 0.0;
-      for (int r = h; r < rows; r += 2) {
-        const double e = (double)y[(row0 + r) * ldy + c] - mean;
-        sum += e * e;
-      }
-      s_sum[h * PCA_WIDE_TILE + (tid & (PCA_WIDE_TILE - 1))] = sum;
-    }
-  }
-  PCA_SYNC();
-  PCA_PAR(tid, PCA_THREADS) {
-    const int c = cb * PCA_WIDE_TILE + tid;
-    if (tid < PCA_WIDE_TILE && c < m) partial[(int64_t)s * m + c] = s_sum[tid] + s_sum[PCA_WIDE_TILE + tid];
-  }
+  pca_wide_colsum_wg<true>(y, ldy, n, m, s, cb, partial, s_sum, colsum);
 }
 
 // sst of column c: the super-chunks' partials added in order
-TM_DEV double readout_sst_col(const double *partial, int S, int m, int c) {
-  double s = 0.0;
-  for (int w = 0; w < S; w++) s += partial[(int64_t)w * m + c];
-  return s;
-}
+TM_DEV double readout_sst_col(const double *partial, int S, int m, int c) { return wg_sum(partial + c, S, m); }

@@ -1,6 +1,6 @@
 // csrc/spectrogram_core.h — the bodies of the wavelet-spectrogram kernels (DESIGN.md "Spectrogram"; include/tmjx.h: tmjx_spectrogram): a bank of
 // complex Morlet FIR filters over every channel of a recorded signal x [n][C], the rows split into S sequences; no tap crosses a sequence
-// boundary.  Written with the PCA_WG / PCA_PAR / PCA_SYNC discipline of csrc/pca_core.h, so that they also compile on the host
+// boundary.  Written with the PCA_WG / PCA_PAR / PCA_SYNC discipline of csrc/wg_core.h, so that they also compile on the host
 // (tests/hostemu/spectrogram_emu.cpp): whatever a thread carries from one PCA_PAR region to the next is PCA_PRIVATE or lives in LDS.
 //   re, im   one float32 FMA chain per output in ascending tap order.  Rows outside the sequence are zeros in the LDS image: a zero product leaves
 //            the chain's bits as they are, so the bits of an output depend on its sequence alone, not on the tiling or on what else is in the call.
@@ -8,7 +8,7 @@
 //   mean     float64 sums of four interleaved row classes in row order, the classes added in order, rounded once
 // No atomics: the same bits on every run.
 #pragma once
-#include "kmeans_core.h"
+#include "wg_core.h"
 
 #define SPEC_MAX_C 1024
 #define SPEC_MAX_F 64

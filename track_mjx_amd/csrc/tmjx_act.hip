@@ -10,7 +10,6 @@
 #include "host_launch.h"
 #include "policy_act.h"
 
-static int fail(int code, const std::string &msg) { return tmjx_internal_fail(code, msg.c_str()); }
 static bool rows16(const void *p, long long ld) { return al16(p) && !(ld & 3); }
 
 static_assert(PA_MAX_BLOCKS == TMJX_CHAIN_MAX_HIDDEN, "tmjx_policy_act_t: block arrays");

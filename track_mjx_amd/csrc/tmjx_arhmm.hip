@@ -15,9 +15,6 @@
 #include "host_launch.h"
 #include "arhmm_host.h"
 
-static int fail(int code, const std::string &msg) { return tmjx_internal_fail(code, msg.c_str()); }
-#define ARHMM_TRY(expr) do { const std::string e_ = (expr); if (!e_.empty()) return fail(TMJX_EINVAL, e_); } while (0)
-#define ARHMM_HIP(what, expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(TMJX_EHIP, std::string(what) + ": " + hipGetErrorString(e_)); } while (0)
 using namespace tmjx_host;
 
 // ----------------------------------------------------------------------------------------------- kernels
@@ -67,7 +64,7 @@ __global__ __launch_bounds__(PCA_THREADS) void k_arhmm_solve(const double *__res
 // ----------------------------------------------------------------------------------------------- launches
 // the sequence offsets to the workspace and every row's position from them
 static int launch_pos(const int32_t *seq_start, int S, int n, float *workspace, const ArhmmWorkspace &w, hipStream_t s, const char *what) {
-  ARHMM_HIP(what, hipMemcpyAsync(workspace + w.seq, seq_start, sizeof(int32_t) * (size_t)(S + 1), hipMemcpyHostToDevice, s));
+  TM_HIP(what, hipMemcpyAsync(workspace + w.seq, seq_start, sizeof(int32_t) * (size_t)(S + 1), hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_arhmm_pos, dim3(kmeans_tiles(n, PCA_THREADS)), dim3(PCA_THREADS), 0, s, (const int32_t *)(workspace + w.seq), S, n,
                      (int32_t *)(workspace + w.pos));
   return check_launch(what);
@@ -104,14 +101,14 @@ static int launch_solve(const double *moments, const double *weight, int k, int 
 extern "C" {
 
 int tmjx_arhmm_workspace(int n, int d, int lags, int k, int S, int64_t *floats) {
-  ARHMM_TRY(arhmm_check_workspace(n, d, lags, k, S, floats));
+  TM_TRY(arhmm_check_workspace(n, d, lags, k, S, floats));
   *floats = arhmm_workspace(n, d, lags, k, S).floats;
   return TMJX_OK;
 }
 
 int tmjx_arhmm_emission(const float *x, int n, int d, int64_t ldx, const int32_t *seq_start, int S, int lags, int warmup, const float *center,
                         const float *weights, const float *vars, int k, float *logb, float *workspace, void *stream) {
-  ARHMM_TRY(arhmm_check_emission(x, n, d, ldx, seq_start, S, lags, warmup, weights, vars, k, logb, workspace));
+  TM_TRY(arhmm_check_emission(x, n, d, ldx, seq_start, S, lags, warmup, weights, vars, k, logb, workspace));
   const ArhmmWorkspace w = arhmm_workspace(n, d, lags, k, S);
   const int rc = launch_pos(seq_start, S, n, workspace, w, (hipStream_t)stream, "tmjx_arhmm_emission");
   if (rc) return rc;
@@ -120,7 +117,7 @@ int tmjx_arhmm_emission(const float *x, int n, int d, int64_t ldx, const int32_t
 
 int tmjx_arhmm_moments(const float *x, int n, int d, int64_t ldx, const int32_t *seq_start, int S, int lags, int warmup, const float *center,
                        const float *gamma, int k, double *moments, double *weight, float *workspace, void *stream) {
-  ARHMM_TRY(arhmm_check_moments(x, n, d, ldx, seq_start, S, lags, warmup, gamma, k, moments, weight, workspace));
+  TM_TRY(arhmm_check_moments(x, n, d, ldx, seq_start, S, lags, warmup, gamma, k, moments, weight, workspace));
   const ArhmmWorkspace w = arhmm_workspace(n, d, lags, k, S);
   const int rc = launch_pos(seq_start, S, n, workspace, w, (hipStream_t)stream, "tmjx_arhmm_moments");
   if (rc) return rc;
@@ -129,7 +126,7 @@ int tmjx_arhmm_moments(const float *x, int n, int d, int64_t ldx, const int32_t 
 
 int tmjx_arhmm_solve(const double *moments, const double *weight, int k, int d, int lags, const float *center, double ridge, double min_var, double min_weight,
                      float *weights, float *vars, float *means, int32_t *status, float *workspace, void *stream) {
-  ARHMM_TRY(arhmm_check_solve(moments, weight, k, d, lags, ridge, min_var, min_weight, weights, vars, status, workspace));
+  TM_TRY(arhmm_check_solve(moments, weight, k, d, lags, ridge, min_var, min_weight, weights, vars, status, workspace));
   return launch_solve(moments, weight, k, d, lags, center, ridge, min_var, min_weight, weights, vars, means, status, workspace, arhmm_workspace(1, d, lags, k, 1),
                       (hipStream_t)stream);
 }
@@ -137,7 +134,7 @@ int tmjx_arhmm_solve(const double *moments, const double *weight, int k, int d, 
 int tmjx_arhmm_fit(const float *x, int n, int d, int64_t ldx, const int32_t *seq_start, int S, int lags, int warmup, const float *center, int k, float *weights,
                    float *vars, float *transmat, float *startprob, float *gamma, int32_t *labels, int32_t *status, int max_iter, double tol, double prior,
                    double kappa, double ridge, double min_var, double min_weight, tmjx_arhmm_info_t *info, float *workspace, void *stream) {
-  ARHMM_TRY(arhmm_check_fit(x, n, d, ldx, seq_start, S, lags, warmup, k, weights, vars, transmat, startprob, labels, max_iter, tol, prior, kappa, ridge, min_var,
+  TM_TRY(arhmm_check_fit(x, n, d, ldx, seq_start, S, lags, warmup, k, weights, vars, transmat, startprob, labels, max_iter, tol, prior, kappa, ridge, min_var,
                             min_weight, info, workspace));
   const ArhmmWorkspace w = arhmm_workspace(n, d, lags, k, S);
   const HmmWorkspace hw = hmm_workspace(n, 1, k);
@@ -148,7 +145,7 @@ int tmjx_arhmm_fit(const float *x, int n, int d, int64_t ldx, const int32_t *seq
          *total = (double *)(hws + hw.total), *moments = (double *)(workspace + w.moments), *weight = (double *)(workspace + w.weight);
   int32_t *st = status ? status : (int32_t *)(workspace + w.status);
   hipEvent_t ev[8];
-  for (int i = 0; i < 8; i++) ARHMM_HIP("hipEventCreate", hipEventCreate(&ev[i]));
+  for (int i = 0; i < 8; i++) TM_HIP("hipEventCreate", hipEventCreate(&ev[i]));
   auto finish = [&](int code) { for (int i = 0; i < 8; i++) (void)hipEventDestroy(ev[i]); return code; };
   int rc = launch_pos(seq_start, S, n, workspace, w, s, "tmjx_arhmm_fit");
   if (rc) return finish(rc);

@@ -10,7 +10,6 @@
 #include "gemm_bf16.h"
 #include "host_launch.h"
 
-static int fail(int code, const std::string &msg) { return tmjx_internal_fail(code, msg.c_str()); }
 #define BZ_ALIGN (4 * sizeof(bz_t) - 1)      // a saved pre-activation row is accessed four elements at a time (bz_t: gemm_bf16.h)
 extern "C" int tmjx_bf16_z_bytes(void) { return (int)sizeof(bz_t); }
 

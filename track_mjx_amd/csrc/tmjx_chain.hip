@@ -12,7 +12,6 @@
 #include "decoder_act.h"
 
 extern "C" int tmjx_internal_gemm_mt(int M, int col_tiles);         // tmjx_hip.hip: the row tile (80 / 32 rows) the layer-by-layer kernels take
-static int fail(int code, const std::string &msg) { return tmjx_internal_fail(code, msg.c_str()); }
 static bool rows16(const void *p, long long ld) { return al16(p) && !(ld & 3); }
 
 template <int MT, int EPI, int FIN>

@@ -1,8 +1,8 @@
 // csrc/tmjx_compare.hip — how two representations of the same time steps relate: linear CKA, the correlation of two dissimilarity matrices and
 // canonical correlations (include/tmjx.h: tmjx_compare_workspace, tmjx_cka_linear, tmjx_rdm_corr, tmjx_cca, tmjx_compare_svd; DESIGN.md
 // "Representation comparison").  The bodies are csrc/compare_core.h (they also compile on the host); the argument checks and the workspace layout
-// csrc/compare_host.h.  The moments are the readout's device functions, the eigen-decompositions tmjx_pca_fit_wide's, called as it is.
-//   k_cmp_colsum / k_cmp_mean  float64 column sums by super-chunk, the mean          k_cmp_cross   one workgroup per (128 x 64 of the moment, super-chunk)
+// csrc/compare_host.h.  The moments are csrc/moments_core.h in the readout's tiling, the eigen-decompositions tmjx_pca_fit_wide's, called as it is.
+//   k_moments_colsum / k_moments_mean  the column means by super-chunk               k_cmp_cross   one workgroup per (128 x 64 of the moment, super-chunk)
 //   k_cmp_frob    one workgroup per row of a moment: sum_j C_ij^2                     k_cmp_total   the rows in row order
 //   k_cmp_rowstat shift, scale and ok of every row of a side                          k_cmp_pairs   the all-pairs pass: a (128 x 64) pair tile per workgroup
 //   k_cmp_sums    the tiles' five sums in a fixed order                               k_cmp_c       C in float64
@@ -20,22 +20,9 @@
 #include "host_launch.h"
 #include "compare_host.h"
 
-static int fail(int code, const std::string &msg) { return tmjx_internal_fail(code, msg.c_str()); }
-#define CMP_TRY(expr) do { const std::string e_ = (expr); if (!e_.empty()) return fail(TMJX_EINVAL, e_); } while (0)
-#define CMP_HIP(what, expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(TMJX_EHIP, std::string(what) + ": " + hipGetErrorString(e_)); } while (0)
 using namespace tmjx_host;
 
 // ----------------------------------------------------------------------------------------------- kernels
-__global__ __launch_bounds__(PCA_THREADS) void k_cmp_colsum(const float *__restrict__ x, int64_t ldx, int n, int d, double *__restrict__ partial) {
-  __shared__ double s_sum[2 * PCA_WIDE_TILE];
-  pca_wide_colsum_wg(x, ldx, n, d, blockIdx.y, blockIdx.x, partial, s_sum);
-}
-
-__global__ __launch_bounds__(PCA_THREADS) void k_cmp_mean(const double *__restrict__ partial, int S, int d, int n, float *__restrict__ mean) {
-  const int c = blockIdx.x * PCA_THREADS + threadIdx.x;
-  if (c < d) mean[c] = pca_wide_mean_col(partial, S, d, n, c);
-}
-
 // blockIdx.x: the tile of 128 columns of x; blockIdx.y: the tile of 64 columns of y; blockIdx.z: the super-chunk.  x and y may be the same buffer.
 __global__ __launch_bounds__(PCA_THREADS) void k_cmp_cross(const float *x, int64_t ldx, const float *y, int64_t ldy, int n, int d, int m, const float *mean_x,
                                                            const float *mean_y, double *__restrict__ partial) {
@@ -108,12 +95,8 @@ static inline unsigned blocks_of(int64_t count, int per) { return (unsigned)((co
 
 static void launch_means(const float *x, int n, int d1, int64_t ldx, const float *y, int d2, int64_t ldy, float *workspace, const CompareWorkspace &w,
                          hipStream_t s) {
-  double *xsum = (double *)(workspace + w.xsum), *ysum = (double *)(workspace + w.ysum);
-  const int S = w.split.S;
-  hipLaunchKernelGGL(k_cmp_colsum, dim3(pca_wide_tiles(d1), S), dim3(PCA_THREADS), 0, s, x, ldx, n, d1, xsum);
-  hipLaunchKernelGGL(k_cmp_mean, dim3(blocks_of(d1, PCA_THREADS)), dim3(PCA_THREADS), 0, s, xsum, S, d1, n, workspace + w.mean_x);
-  hipLaunchKernelGGL(k_cmp_colsum, dim3(pca_wide_tiles(d2), S), dim3(PCA_THREADS), 0, s, y, ldy, n, d2, ysum);
-  hipLaunchKernelGGL(k_cmp_mean, dim3(blocks_of(d2, PCA_THREADS)), dim3(PCA_THREADS), 0, s, ysum, S, d2, n, workspace + w.mean_y);
+  moments_launch_mean<false>(x, ldx, n, d1, (double *)(workspace + w.xsum), workspace + w.mean_x, s);
+  moments_launch_mean<false>(y, ldy, n, d2, (double *)(workspace + w.ysum), workspace + w.mean_y, s);
 }
 
 static void launch_cross(const float *x, int64_t ldx, int d, const float *mean_x, const float *y, int64_t ldy, int m, const float *mean_y, int n, float *workspace,
@@ -123,15 +106,8 @@ static void launch_cross(const float *x, int64_t ldx, int d, const float *mean_x
 }
 
 static int launch_svd(const double *a, int ra, int ca, int64_t lda, double *sigma, double *u, double *v, int32_t *info, double *work, hipStream_t s) {
-  const size_t lds = sizeof(double) * (size_t)compare_svd_lds_doubles(ra, ca);
-  static bool attr_set = false;      // more than 64 KiB of dynamic LDS needs the attribute once: set for the largest matrix
-  if (!attr_set) {
-    CMP_HIP("hipFuncSetAttribute(k_cmp_svd)", hipFuncSetAttribute((const void *)k_cmp_svd, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                                  (int)(sizeof(double) * compare_svd_lds_doubles(COMPARE_MAX_RANK, COMPARE_MAX_RANK))));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(k_cmp_svd, dim3(1), dim3(PCA_THREADS), lds, s, a, ra, ca, lda, sigma, u, v, info, work);
-  return check_launch("k_cmp_svd");
+  return launch_lds<k_cmp_svd>("k_cmp_svd", dim3(1), dim3(PCA_THREADS), sizeof(double) * compare_svd_lds_doubles(COMPARE_MAX_RANK, COMPARE_MAX_RANK),
+                               sizeof(double) * (size_t)compare_svd_lds_doubles(ra, ca), s, a, ra, ca, lda, sigma, u, v, info, work);
 }
 
 // The whitening matrix of one side, W [k][d] float64 with W Cxx W^T = I on the span of its k leading components: E = components[:k] in float64,
@@ -159,7 +135,7 @@ static int launch_whitener(const float *x, int64_t ldx, int d, const float *mean
     hipLaunchKernelGGL(k_cmp_gemm<false>, dim3(blocks_of((int64_t)(k - win.lo) * d, PCA_THREADS)), dim3(PCA_THREADS), 0, s, v, (int64_t)nw, ew, (int64_t)d, nw,
                        k - win.lo, d, ritz);
     if ((rc = check_launch("tmjx_cca (window)"))) return rc;
-    CMP_HIP("tmjx_cca (window)", hipMemcpyAsync(ew, ritz, sizeof(double) * (size_t)(k - win.lo) * d, hipMemcpyDeviceToDevice, s));
+    TM_HIP("tmjx_cca (window)", hipMemcpyAsync(ew, ritz, sizeof(double) * (size_t)(k - win.lo) * d, hipMemcpyDeviceToDevice, s));
   }
   hipLaunchKernelGGL(k_cmp_gemm<false>, dim3(blocks_of((int64_t)k * d, PCA_THREADS)), dim3(PCA_THREADS), 0, s, e, (int64_t)d, c, (int64_t)d, d, k, d, t);
   hipLaunchKernelGGL(k_cmp_gemm<true>, dim3(blocks_of((int64_t)k * k, PCA_THREADS)), dim3(PCA_THREADS), 0, s, t, (int64_t)d, e, (int64_t)d, d, k, k, m);
@@ -182,7 +158,7 @@ static int pca_floats_of(int n, int d1, int d2, int64_t *floats) {
 extern "C" {
 
 int tmjx_compare_workspace(int n, int d1, int d2, int64_t *floats) {
-  CMP_TRY(compare_check_workspace(n, d1, d2, floats));
+  TM_TRY(compare_check_workspace(n, d1, d2, floats));
   int64_t pca = 0;
   const int rc = pca_floats_of(n, d1, d2, &pca);
   if (rc) return rc;
@@ -191,7 +167,7 @@ int tmjx_compare_workspace(int n, int d1, int d2, int64_t *floats) {
 }
 
 int tmjx_cka_linear(const float *x, int n, int d1, int64_t ldx, const float *y, int d2, int64_t ldy, double *out, float *workspace, void *stream) {
-  CMP_TRY(compare_check_cka(x, n, d1, ldx, y, d2, ldy, out, workspace));
+  TM_TRY(compare_check_cka(x, n, d1, ldx, y, d2, ldy, out, workspace));
   const CompareWorkspace w = compare_workspace(n, d1, d2, 0);
   hipStream_t s = (hipStream_t)stream;
   const float *mean_x = workspace + w.mean_x, *mean_y = workspace + w.mean_y;
@@ -209,7 +185,7 @@ int tmjx_cka_linear(const float *x, int n, int d1, int64_t ldx, const float *y, 
 
 int tmjx_rdm_corr(const float *x, int n, int d1, int64_t ldx, int metric_x, const float *y, int d2, int64_t ldy, int metric_y, double *sums, float *workspace,
                   void *stream) {
-  CMP_TRY(compare_check_rdm(x, n, d1, ldx, metric_x, y, d2, ldy, metric_y, sums, workspace));
+  TM_TRY(compare_check_rdm(x, n, d1, ldx, metric_x, y, d2, ldy, metric_y, sums, workspace));
   const CompareWorkspace w = compare_workspace(n, d1, d2, 0);
   hipStream_t s = (hipStream_t)stream;
   const int64_t up = (n + 3) & ~3;
@@ -228,14 +204,14 @@ int tmjx_rdm_corr(const float *x, int n, int d1, int64_t ldx, int metric_x, cons
 }
 
 int tmjx_compare_svd(const double *a, int rows, int cols, int64_t lda, double *sigma, double *u, double *v, int32_t *sweeps, float *workspace, void *stream) {
-  CMP_TRY(compare_check_svd(a, rows, cols, lda, sigma, u, v, sweeps, workspace));
+  TM_TRY(compare_check_svd(a, rows, cols, lda, sigma, u, v, sweeps, workspace));
   hipStream_t s = (hipStream_t)stream;
   const int nn = rows < cols ? rows : cols;
   int32_t *dinfo = (int32_t *)(workspace + 2 * (int64_t)nn * nn), host[2] = {0, 0};
   int rc = launch_svd(a, rows, cols, lda, sigma, u, v, dinfo, (double *)workspace, s);
   if (rc) return rc;
-  CMP_HIP("tmjx_compare_svd", hipMemcpyAsync(host, dinfo, sizeof(host), hipMemcpyDeviceToHost, s));
-  CMP_HIP("tmjx_compare_svd", hipStreamSynchronize(s));
+  TM_HIP("tmjx_compare_svd", hipMemcpyAsync(host, dinfo, sizeof(host), hipMemcpyDeviceToHost, s));
+  TM_HIP("tmjx_compare_svd", hipStreamSynchronize(s));
   *sweeps = host[0];
   if (!host[1]) return fail(TMJX_ENOCONV, "tmjx_compare_svd: " + compare_svd_noconv_message(host[0]));
   return TMJX_OK;
@@ -243,7 +219,7 @@ int tmjx_compare_svd(const double *a, int rows, int cols, int64_t lda, double *s
 
 int tmjx_cca(const float *x, int n, int d1, int64_t ldx, const float *y, int d2, int64_t ldy, double var_keep, int max_rank, float *rho, float *a, float *b,
              tmjx_cca_info_t *info, float *workspace, void *stream) {
-  CMP_TRY(compare_check_cca(x, n, d1, ldx, y, d2, ldy, var_keep, max_rank, rho, a, b, info, workspace));
+  TM_TRY(compare_check_cca(x, n, d1, ldx, y, d2, ldy, var_keep, max_rank, rho, a, b, info, workspace));
   int64_t pca = 0;
   int rc = pca_floats_of(n, d1, d2, &pca);
   if (rc) return rc;

@@ -57,10 +57,9 @@ static int launch_wave(const tmjx_model *m, float *state, const float *action, i
                        float *rec = nullptr, float *sensordata = nullptr, float *cfrc_ext = nullptr);
 
 static thread_local std::string g_err;
-static int fail(int code, const std::string &msg) { g_err = msg; return code; }
-// the library's other translation units (tmjx_bf16.hip) record their failures in the same per-thread message
+// every translation unit of the library records its failures in the same per-thread message, through fail() of host_launch.h
 #define TMJX_SMALL_BATCH 8192      // rows up to which the acting-path element-wise kernels launch one-wave blocks
-extern "C" int tmjx_internal_fail(int code, const char *msg) { return fail(code, msg ? msg : ""); }
+extern "C" int tmjx_internal_fail(int code, const char *msg) { g_err = msg ? msg : ""; return code; }
 #define HIP_TRY(expr)                                                                                   \
   do {                                                                                                  \
     hipError_t e_ = (expr);                                                                             \
@@ -1134,15 +1133,8 @@ static int launch_gemm_ln(const float *A, int lda, const float *W, int ldw, cons
 template <bool YVEC, bool XVEC>
 static int launch_gemm_dw(const float *dY, int ldy, const float *X, int ldx, float *scratch, int M, int N, int K, int with_bias, int rps, int S, int ld, hipStream_t s) {
   constexpr size_t lds = 2 * sizeof(float) * 2 * DW_BM * DW_LD;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void *)k_gemm_dw<YVEC, XVEC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(TMJX_EHIP, std::string("hipFuncSetAttribute(k_gemm_dw): ") + hipGetErrorString(e));
-    attr_set = true;
-  }
   dim3 grid((N + DW_BT - 1) / DW_BT, (K + DW_BT - 1) / DW_BT, S);
-  hipLaunchKernelGGL((k_gemm_dw<YVEC, XVEC>), grid, dim3(512), lds, s, dY, ldy, X, ldx, scratch, M, N, K, with_bias, rps, ld);
-  return TMJX_OK;
+  return launch_lds<k_gemm_dw<YVEC, XVEC>>("k_gemm_dw", grid, dim3(512), lds, s, dY, ldy, X, ldx, scratch, M, N, K, with_bias, rps, ld);
 }
 template <int NIW, int MT>
 static int launch_gemm_silu(const float *A, int lda, const float *W, int ldw, const float *bias, float *Z, float *Y, int ldc, int M, int N, int K, hipStream_t s) {
@@ -1342,14 +1334,9 @@ int tmjx_gemm_dw_grouped(const tmjx_dw_problem_t *probs, int n, void *stream) {
     P.red_begin = red; red += (int)(((long long)q.N * (q.K + (q.db ? 1 : 0)) + 255) / 256);
   }
   constexpr size_t lds = 2 * sizeof(float) * 2 * DW_BM * DW_LD;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void *)k_gemm_dw_grouped, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(TMJX_EHIP, std::string("hipFuncSetAttribute(k_gemm_dw_grouped): ") + hipGetErrorString(e));
-    attr_set = true;
-  }
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_gemm_dw_grouped, dim3(wg), dim3(512), lds, s, G);
+  const int rc = launch_lds<k_gemm_dw_grouped>("k_gemm_dw_grouped", dim3(wg), dim3(512), lds, s, G);
+  if (rc) return rc;
   hipLaunchKernelGGL(k_dw_reduce_grouped, dim3(red), dim3(256), 0, s, G);
   return check_launch("k_gemm_dw_grouped");
 }

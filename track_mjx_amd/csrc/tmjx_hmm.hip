@@ -4,7 +4,7 @@
 //   k_hmm_const    c_j, one thread per state                                k_hmm_emission  logb: 128 rows per workgroup walk the state tiles
 //   k_hmm_fb       the scaled recursion, one workgroup per sequence          k_hmm_start     start and the total loglik, in sequence order
 //   k_hmm_outer    float64 outer-product sums per (row part, 64 x 64 tile)   k_hmm_xi        the parts in order, times A
-//   k_hmm_colsum / k_hmm_mean   the column mean of x, as the k-means forms it   k_hmm_mreduce   the M-step from the parts
+//   k_moments_colsum / _mean    the column mean of x, as the k-means forms it   k_hmm_mreduce   the M-step from the parts
 //   k_hmm_trans    transmat and startprob from the counts                    k_hmm_viterbi   one workgroup per sequence
 #include <hip/hip_runtime.h>
 
@@ -16,9 +16,6 @@
 #include "host_launch.h"
 #include "hmm_host.h"
 
-static int fail(int code, const std::string &msg) { return tmjx_internal_fail(code, msg.c_str()); }
-#define HMM_TRY(expr) do { const std::string e_ = (expr); if (!e_.empty()) return fail(TMJX_EINVAL, e_); } while (0)
-#define HMM_HIP(what, expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(TMJX_EHIP, std::string(what) + ": " + hipGetErrorString(e_)); } while (0)
 using namespace tmjx_host;
 
 // ----------------------------------------------------------------------------------------------- kernels
@@ -63,16 +60,6 @@ __global__ __launch_bounds__(PCA_THREADS) void k_hmm_xi(const double *__restrict
   if (e < k * k) hmm_xi_reduce(part, P, k, transmat, xi, e);
 }
 
-__global__ __launch_bounds__(PCA_THREADS) void k_hmm_colsum(const float *__restrict__ x, int64_t ldx, int n, int d, double *__restrict__ partial) {
-  __shared__ double s_sum[2 * PCA_WIDE_TILE];
-  kmeans_colsum_wg(x, ldx, n, d, blockIdx.x, blockIdx.y, partial, s_sum);
-}
-
-__global__ __launch_bounds__(PCA_THREADS) void k_hmm_mean(const double *__restrict__ partial, int nchunks, int d, int n, float *__restrict__ mean) {
-  const int c = blockIdx.x * PCA_THREADS + threadIdx.x;
-  if (c < d) mean[c] = kmeans_mean_col(partial, nchunks, d, n, c);
-}
-
 __global__ __launch_bounds__(PCA_THREADS) void k_hmm_mreduce(const double *__restrict__ part1, const double *__restrict__ part2,
                                                              const double *__restrict__ partw, int P, int k, int d, const float *__restrict__ mean,
                                                              double min_var, double min_weight, float *__restrict__ means, float *__restrict__ vars,
@@ -96,20 +83,8 @@ __global__ __launch_bounds__(HMM_THREADS) void k_hmm_viterbi(const float *__rest
 }
 
 // ----------------------------------------------------------------------------------------------- launches
-// a kernel of HMM_THREADS with dynamic LDS: more than 64 KiB needs the attribute once per kernel, set for the largest k; the launch takes what this k needs
-template <auto Kernel, class... Args>
-static int launch_dyn(const char *what, dim3 grid, size_t lds_max, size_t lds, hipStream_t s, Args... args) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    HMM_HIP(what, hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(Kernel, grid, dim3(HMM_THREADS), lds, s, args...);
-  return check_launch(what);
-}
-
 static int upload_seq(const int32_t *seq_start, int S, float *workspace, const HmmWorkspace &w, hipStream_t s, const char *what) {
-  HMM_HIP(what, hipMemcpyAsync(workspace + w.seq, seq_start, sizeof(int32_t) * (size_t)(S + 1), hipMemcpyHostToDevice, s));
+  TM_HIP(what, hipMemcpyAsync(workspace + w.seq, seq_start, sizeof(int32_t) * (size_t)(S + 1), hipMemcpyHostToDevice, s));
   return TMJX_OK;
 }
 
@@ -125,7 +100,7 @@ static int launch_fb(const float *logb, int n, int k, int S, const float *transm
   const int32_t *seq = (const int32_t *)(workspace + w.seq);
   float *alphahat = workspace + w.alphahat, *vnext = workspace + w.vnext;
   double *xipart = (double *)(workspace + w.xipart);
-  const int rc = launch_dyn<k_hmm_fb>("tmjx_hmm_forward_backward", dim3(S), sizeof(float) * hmm_fb_lds_floats(HMM_MAX_K), sizeof(float) * hmm_fb_lds_floats(k), s,
+  const int rc = launch_lds<k_hmm_fb>("tmjx_hmm_forward_backward", dim3(S), dim3(HMM_THREADS), sizeof(float) * hmm_fb_lds_floats(HMM_MAX_K), sizeof(float) * hmm_fb_lds_floats(k), s,
                                       logb, k, seq, transmat, startprob, workspace + w.mrow, workspace + w.cs, alphahat, vnext, gamma, loglik);
   if (rc) return rc;
   hipLaunchKernelGGL(k_hmm_start, dim3(1), dim3(HMM_THREADS), 0, s, gamma, k, seq, S, loglik, start, total);
@@ -141,10 +116,7 @@ static int launch_mstep(const float *x, int n, int d, int64_t ldx, const float *
   double *colsum = (double *)(workspace + w.colsum), *p1 = (double *)(workspace + w.part1), *p2 = (double *)(workspace + w.part2),
          *pw = (double *)(workspace + w.partw);
   float *mean = workspace + w.mean;
-  if (!have_mean) {      // (a fit forms the column mean of x once)
-    hipLaunchKernelGGL(k_hmm_colsum, dim3(w.nchunks, pca_wide_tiles(d)), dim3(PCA_THREADS), 0, s, x, ldx, n, d, colsum);
-    hipLaunchKernelGGL(k_hmm_mean, dim3(kmeans_tiles(d, PCA_THREADS)), dim3(PCA_THREADS), 0, s, colsum, w.nchunks, d, n, mean);
-  }
+  if (!have_mean) moments_launch_mean<true>(x, ldx, n, d, colsum, mean, s);      // (a fit forms the column mean of x once)
   hipLaunchKernelGGL(k_hmm_outer, dim3(kmeans_tiles(d, HMM_OT), kmeans_tiles(k, HMM_OT), w.msplit.P), dim3(PCA_THREADS), 0, s, gamma, (int64_t)k, k, x, ldx, d,
                      (const float *)mean, n, w.msplit, p1, p2, pw);
   hipLaunchKernelGGL(k_hmm_mreduce, dim3(kmeans_tiles(k * d, PCA_THREADS)), dim3(PCA_THREADS), 0, s, p1, p2, pw, w.msplit.P, k, d, mean, min_var, min_weight, means,
@@ -154,7 +126,7 @@ static int launch_mstep(const float *x, int n, int d, int64_t ldx, const float *
 
 static int launch_viterbi(const float *logb, int k, int S, const float *transmat, const float *startprob, int logspace, int32_t *labels, double *path_logprob,
                           float *workspace, const HmmWorkspace &w, hipStream_t s) {
-  return launch_dyn<k_hmm_viterbi>("tmjx_hmm_viterbi", dim3(S), sizeof(float) * (HMM_MAX_K * hmm_lda(HMM_MAX_K) + 2 * HMM_THREADS),
+  return launch_lds<k_hmm_viterbi>("tmjx_hmm_viterbi", dim3(S), dim3(HMM_THREADS), sizeof(float) * (HMM_MAX_K * hmm_lda(HMM_MAX_K) + 2 * HMM_THREADS),
                                    sizeof(float) * (k * hmm_lda(k) + 2 * HMM_THREADS), s, logb, k, (const int32_t *)(workspace + w.seq), transmat, startprob, logspace, (uint8_t *)(workspace + w.bp), labels, path_logprob);
 }
 
@@ -162,19 +134,19 @@ static int launch_viterbi(const float *logb, int k, int S, const float *transmat
 extern "C" {
 
 int tmjx_hmm_workspace(int n, int d, int k, int S, int64_t *floats) {
-  HMM_TRY(hmm_check_workspace(n, d, k, S, floats));
+  TM_TRY(hmm_check_workspace(n, d, k, S, floats));
   *floats = hmm_workspace(n, d, k).floats;
   return TMJX_OK;
 }
 
 int tmjx_hmm_emission(const float *x, int n, int d, int64_t ldx, const float *means, const float *vars, int k, float *logb, float *workspace, void *stream) {
-  HMM_TRY(hmm_check_emission(x, n, d, ldx, means, vars, k, logb, workspace));
+  TM_TRY(hmm_check_emission(x, n, d, ldx, means, vars, k, logb, workspace));
   return launch_emission(x, n, d, ldx, means, vars, k, logb, workspace + hmm_workspace(n, d, k).cj, (hipStream_t)stream);
 }
 
 int tmjx_hmm_forward_backward(const float *logb, int n, int k, const int32_t *seq_start, int S, const float *transmat, const float *startprob, float *gamma,
                               double *xi, double *start, double *loglik, double *total, float *workspace, void *stream) {
-  HMM_TRY(hmm_check_fb(logb, n, k, seq_start, S, transmat, startprob, gamma, xi, start, loglik, total, workspace));
+  TM_TRY(hmm_check_fb(logb, n, k, seq_start, S, transmat, startprob, gamma, xi, start, loglik, total, workspace));
   const HmmWorkspace w = hmm_workspace(n, 1, k);
   const int rc = upload_seq(seq_start, S, workspace, w, (hipStream_t)stream, "tmjx_hmm_forward_backward");
   if (rc) return rc;
@@ -183,19 +155,19 @@ int tmjx_hmm_forward_backward(const float *logb, int n, int k, const int32_t *se
 
 int tmjx_hmm_mstep(const float *x, int n, int d, int64_t ldx, const float *gamma, int k, double min_var, double min_weight, float *means, float *vars,
                    double *weight, float *workspace, void *stream) {
-  HMM_TRY(hmm_check_mstep(x, n, d, ldx, gamma, k, min_var, min_weight, means, vars, weight, workspace));
+  TM_TRY(hmm_check_mstep(x, n, d, ldx, gamma, k, min_var, min_weight, means, vars, weight, workspace));
   return launch_mstep(x, n, d, ldx, gamma, k, min_var, min_weight, means, vars, weight, workspace, hmm_workspace(n, d, k), (hipStream_t)stream, false);
 }
 
 int tmjx_hmm_transitions(const double *xi, const double *start, int k, double prior, double kappa, float *transmat, float *startprob, void *stream) {
-  HMM_TRY(hmm_check_transitions(xi, start, k, prior, kappa, transmat, startprob));
+  TM_TRY(hmm_check_transitions(xi, start, k, prior, kappa, transmat, startprob));
   hipLaunchKernelGGL(k_hmm_trans, dim3(1), dim3(HMM_THREADS), 0, (hipStream_t)stream, xi, start, k, prior, kappa, transmat, startprob);
   return check_launch("tmjx_hmm_transitions");
 }
 
 int tmjx_hmm_viterbi(const float *logb, int n, int k, const int32_t *seq_start, int S, const float *transmat, const float *startprob, int logspace,
                      int32_t *labels, double *path_logprob, float *workspace, void *stream) {
-  HMM_TRY(hmm_check_viterbi(logb, n, k, seq_start, S, transmat, startprob, labels, path_logprob, workspace));
+  TM_TRY(hmm_check_viterbi(logb, n, k, seq_start, S, transmat, startprob, labels, path_logprob, workspace));
   const HmmWorkspace w = hmm_workspace(n, 1, k);
   const int rc = upload_seq(seq_start, S, workspace, w, (hipStream_t)stream, "tmjx_hmm_viterbi");
   if (rc) return rc;
@@ -205,7 +177,7 @@ int tmjx_hmm_viterbi(const float *logb, int n, int k, const int32_t *seq_start, 
 int tmjx_hmm_fit(const float *x, int n, int d, int64_t ldx, const int32_t *seq_start, int S, int k, float *means, float *vars, float *transmat,
                  float *startprob, float *gamma, int32_t *labels, int max_iter, double tol, double prior, double kappa, double min_var, double min_weight,
                  tmjx_hmm_info_t *info, float *workspace, void *stream) {
-  HMM_TRY(hmm_check_fit(x, n, d, ldx, seq_start, S, k, means, vars, transmat, startprob, labels, max_iter, tol, prior, kappa, min_var, min_weight, info,
+  TM_TRY(hmm_check_fit(x, n, d, ldx, seq_start, S, k, means, vars, transmat, startprob, labels, max_iter, tol, prior, kappa, min_var, min_weight, info,
                         workspace));
   const HmmWorkspace w = hmm_workspace(n, d, k);
   hipStream_t s = (hipStream_t)stream;
@@ -213,7 +185,7 @@ int tmjx_hmm_fit(const float *x, int n, int d, int64_t ldx, const int32_t *seq_s
   double *xi = (double *)(workspace + w.xi), *start = (double *)(workspace + w.start), *weight = (double *)(workspace + w.weight),
          *loglik = (double *)(workspace + w.loglik), *path = (double *)(workspace + w.path), *total = (double *)(workspace + w.total);
   hipEvent_t ev[8];
-  for (int i = 0; i < 8; i++) HMM_HIP("hipEventCreate", hipEventCreate(&ev[i]));
+  for (int i = 0; i < 8; i++) TM_HIP("hipEventCreate", hipEventCreate(&ev[i]));
   auto finish = [&](int code) { for (int i = 0; i < 8; i++) (void)hipEventDestroy(ev[i]); return code; };
   int rc = upload_seq(seq_start, S, workspace, w, s, "tmjx_hmm_fit");
   if (rc) return finish(rc);

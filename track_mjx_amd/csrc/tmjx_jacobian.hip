@@ -18,8 +18,6 @@
 #include "host_launch.h"
 #include "jacobian_host.h"
 
-static int fail(int code, const std::string &msg) { return tmjx_internal_fail(code, msg.c_str()); }
-#define JAC_TRY(expr) do { const std::string e_ = (expr); if (!e_.empty()) return fail(TMJX_EINVAL, e_); } while (0)
 using namespace tmjx_host;
 
 // ----------------------------------------------------------------------------------------------- kernels
@@ -78,7 +76,7 @@ __global__ __launch_bounds__(PCA_THREADS) void k_jac_sum_add(const double *__res
 extern "C" {
 
 int tmjx_jacobian_workspace(const tmjx_jacobian_desc_t *desc, int m, int64_t *floats) {
-  JAC_TRY(jac_check_workspace(desc, m, floats));
+  TM_TRY(jac_check_workspace(desc, m, floats));
   *floats = jac_workspace(desc, m).floats;
   return TMJX_OK;
 }
@@ -86,7 +84,7 @@ int tmjx_jacobian_workspace(const tmjx_jacobian_desc_t *desc, int m, int64_t *fl
 int tmjx_decoder_jacobian(const tmjx_jacobian_desc_t *desc, const float *x, int n, int64_t ldx, const int32_t *row_index, int m, const float *scale,
                           int64_t ld_scale, int mode, float *ctrl_out, float *jac, float *gain, float *col2, float *row2, float *action_var, double *sums,
                           float *workspace, void *stream) {
-  JAC_TRY(jac_check_call(desc, x, n, ldx, row_index, m, scale, ld_scale, mode, ctrl_out, jac, gain, col2, row2, action_var, sums, workspace));
+  TM_TRY(jac_check_call(desc, x, n, ldx, row_index, m, scale, ld_scale, mode, ctrl_out, jac, gain, col2, row2, action_var, sums, workspace));
   const tmjx_jacobian_desc_t d = *desc;
   const JacWorkspace w = jac_workspace(&d, m);
   hipStream_t s = (hipStream_t)stream;

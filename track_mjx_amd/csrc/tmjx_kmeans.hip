@@ -1,7 +1,7 @@
 // csrc/tmjx_kmeans.hip — k-means of recorded activations: Lloyd's iteration with k-means++ seeding (include/tmjx.h: tmjx_kmeans_workspace,
 // tmjx_kmeans_assign, tmjx_kmeans_update, tmjx_kmeans_seed, tmjx_kmeans_fit; DESIGN.md "Clustering").  The bodies are csrc/kmeans_core.h (they also
 // compile on the host); the argument checks and the workspace layout csrc/kmeans_host.h.
-//   k_km_colsum   one workgroup per (chunk of 256 rows, 128 columns): float64 column sums     k_km_mean     the sums added in chunk order
+//   k_moments_colsum, k_moments_mean   the column mean of x by chunk of 256 rows (csrc/moments_core.h)
 //   k_km_cnorm    ||c_j - mean||^2, one thread per centroid                                    k_km_assign   the fused pass: 128 rows per workgroup
 //   k_km_totals   inertia and changed: the workgroups' partials added in order                 k_km_update   four waves per (row part, 64 columns)
 //   k_km_reduce   the parts' sums over the parts' counts                                       k_km_dist / k_km_pick   one k-means++ step
@@ -15,22 +15,9 @@
 #include "host_launch.h"
 #include "kmeans_host.h"
 
-static int fail(int code, const std::string &msg) { return tmjx_internal_fail(code, msg.c_str()); }
-#define KM_TRY(expr) do { const std::string e_ = (expr); if (!e_.empty()) return fail(TMJX_EINVAL, e_); } while (0)
-#define KM_HIP(what, expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(TMJX_EHIP, std::string(what) + ": " + hipGetErrorString(e_)); } while (0)
 using namespace tmjx_host;
 
 // ----------------------------------------------------------------------------------------------- kernels
-__global__ __launch_bounds__(PCA_THREADS) void k_km_colsum(const float *__restrict__ x, int64_t ldx, int n, int d, double *__restrict__ partial) {
-  __shared__ double s_sum[2 * PCA_WIDE_TILE];
-  kmeans_colsum_wg(x, ldx, n, d, blockIdx.x, blockIdx.y, partial, s_sum);
-}
-
-__global__ __launch_bounds__(PCA_THREADS) void k_km_mean(const double *__restrict__ partial, int nchunks, int d, int n, float *__restrict__ mean) {
-  const int c = blockIdx.x * PCA_THREADS + threadIdx.x;
-  if (c < d) mean[c] = kmeans_mean_col(partial, nchunks, d, n, c);
-}
-
 __global__ __launch_bounds__(PCA_THREADS) void k_km_cnorm(const float *__restrict__ centroids, const float *__restrict__ mean, int d, int k,
                                                           float *__restrict__ cnorm) {
   const int j = blockIdx.x * PCA_THREADS + threadIdx.x;
@@ -87,10 +74,7 @@ static int launch_assign(const float *x, int n, int d, int64_t ldx, const float 
   double *colsum = (double *)(workspace + w.colsum), *pin = (double *)(workspace + w.part_inertia);
   float *mean = workspace + w.mean, *cnorm = workspace + w.cnorm;
   int32_t *pch = (int32_t *)(workspace + w.part_changed);
-  if (!have_mean) {      // (a fit forms the column mean of x once: the rows do not change between its assigns)
-    hipLaunchKernelGGL(k_km_colsum, dim3(w.split.nchunks, pca_wide_tiles(d)), dim3(PCA_THREADS), 0, s, x, ldx, n, d, colsum);
-    hipLaunchKernelGGL(k_km_mean, dim3(kmeans_tiles(d, PCA_THREADS)), dim3(PCA_THREADS), 0, s, colsum, w.split.nchunks, d, n, mean);
-  }
+  if (!have_mean) moments_launch_mean<true>(x, ldx, n, d, colsum, mean, s);      // (a fit forms the column mean of x once: the rows do not change between its assigns)
   hipLaunchKernelGGL(k_km_cnorm, dim3(kmeans_tiles(k, PCA_THREADS)), dim3(PCA_THREADS), 0, s, centroids, mean, d, k, cnorm);
   hipLaunchKernelGGL(k_km_assign, dim3(w.nwg_assign), dim3(PCA_THREADS), 0, s, x, n, d, ldx, centroids, k, mean, cnorm, labels_prev, labels, dist2, pin, pch);
   hipLaunchKernelGGL(k_km_totals, dim3(1), dim3(PCA_THREADS), 0, s, pin, pch, w.nwg_assign, inertia, changed);
@@ -102,14 +86,9 @@ static int launch_update(const float *x, int n, int d, int64_t ldx, const int32_
   const KmeansWorkspace w = kmeans_workspace(n, d, k);
   double *psum = (double *)(workspace + w.part_sum);
   int32_t *pcnt = (int32_t *)(workspace + w.part_cnt);
-  static bool attr_set = false;      // more than 64 KiB of dynamic LDS needs the attribute once: set for the largest k
-  if (!attr_set) {
-    KM_HIP("hipFuncSetAttribute(k_km_update)", hipFuncSetAttribute((const void *)k_km_update, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                                   KMEANS_MAX_K * (KMEANS_UTILE * 8 + 4)));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(k_km_update, dim3(kmeans_tiles(d, KMEANS_UTILE), w.split.P), dim3(KMEANS_UTHREADS), (size_t)k * (KMEANS_UTILE * 8 + 4), s, x, n, d, ldx, labels,
-                     k, psum, pcnt);
+  const int rc = launch_lds<k_km_update>("k_km_update", dim3(kmeans_tiles(d, KMEANS_UTILE), w.split.P), dim3(KMEANS_UTHREADS), KMEANS_MAX_K * (KMEANS_UTILE * 8 + 4),
+                                         (size_t)k * (KMEANS_UTILE * 8 + 4), s, x, n, d, ldx, labels, k, psum, pcnt);
+  if (rc) return rc;
   hipLaunchKernelGGL(k_km_reduce, dim3(kmeans_tiles(k * d, PCA_THREADS)), dim3(PCA_THREADS), 0, s, psum, pcnt, w.split.P, k, d, centroids, counts);
   return check_launch("tmjx_kmeans_update");
 }
@@ -118,25 +97,25 @@ static int launch_update(const float *x, int n, int d, int64_t ldx, const int32_
 extern "C" {
 
 int tmjx_kmeans_workspace(int n, int d, int k, int64_t *floats) {
-  KM_TRY(kmeans_check_workspace(n, d, k, floats));
+  TM_TRY(kmeans_check_workspace(n, d, k, floats));
   *floats = kmeans_workspace(n, d, k).floats;
   return TMJX_OK;
 }
 
 int tmjx_kmeans_assign(const float *x, int n, int d, int64_t ldx, const float *centroids, int k, const int32_t *labels_prev, int32_t *labels, float *dist2,
                        double *inertia, int32_t *changed, float *workspace, void *stream) {
-  KM_TRY(kmeans_check_assign(x, n, d, ldx, centroids, k, labels, inertia, workspace));
+  TM_TRY(kmeans_check_assign(x, n, d, ldx, centroids, k, labels, inertia, workspace));
   return launch_assign(x, n, d, ldx, centroids, k, labels_prev, labels, dist2, inertia, changed, workspace, (hipStream_t)stream);
 }
 
 int tmjx_kmeans_update(const float *x, int n, int d, int64_t ldx, const int32_t *labels, int k, float *centroids, int32_t *counts, float *workspace,
                        void *stream) {
-  KM_TRY(kmeans_check_update(x, n, d, ldx, labels, k, centroids, counts, workspace));
+  TM_TRY(kmeans_check_update(x, n, d, ldx, labels, k, centroids, counts, workspace));
   return launch_update(x, n, d, ldx, labels, k, centroids, counts, workspace, (hipStream_t)stream);
 }
 
 int tmjx_kmeans_seed(const float *x, int n, int d, int64_t ldx, int k, const double *u, float *centroids, int32_t *index, float *workspace, void *stream) {
-  KM_TRY(kmeans_check_seed(x, n, d, ldx, k, u, centroids, index, workspace));
+  TM_TRY(kmeans_check_seed(x, n, d, ldx, k, u, centroids, index, workspace));
   const KmeansWorkspace w = kmeans_workspace(n, d, k);
   hipStream_t s = (hipStream_t)stream;
   float *d2 = workspace + w.d2;
@@ -149,21 +128,21 @@ int tmjx_kmeans_seed(const float *x, int n, int d, int64_t ldx, int k, const dou
   }
   int rc = check_launch("tmjx_kmeans_seed");
   if (rc) return rc;
-  KM_HIP("tmjx_kmeans_seed", hipMemcpyAsync(index, picks, sizeof(int32_t) * k, hipMemcpyDeviceToHost, s));
-  KM_HIP("tmjx_kmeans_seed", hipStreamSynchronize(s));
+  TM_HIP("tmjx_kmeans_seed", hipMemcpyAsync(index, picks, sizeof(int32_t) * k, hipMemcpyDeviceToHost, s));
+  TM_HIP("tmjx_kmeans_seed", hipStreamSynchronize(s));
   return TMJX_OK;
 }
 
 int tmjx_kmeans_fit(const float *x, int n, int d, int64_t ldx, int k, float *centroids, int32_t *labels, float *dist2, int max_iter, double tol,
                     tmjx_kmeans_info_t *info, float *workspace, void *stream) {
-  KM_TRY(kmeans_check_fit(x, n, d, ldx, k, centroids, labels, max_iter, tol, info, workspace));
+  TM_TRY(kmeans_check_fit(x, n, d, ldx, k, centroids, labels, max_iter, tol, info, workspace));
   const KmeansWorkspace w = kmeans_workspace(n, d, k);
   hipStream_t s = (hipStream_t)stream;
   struct Result { double inertia; int32_t changed, pad_; } host = {0.0, 0, 0};
   Result *dev = (Result *)(workspace + w.result);
   int32_t *buf[2] = {labels, (int32_t *)(workspace + w.labels2)}, *counts = (int32_t *)(workspace + w.picks);      // (the seeding's picks are dead by now)
   hipEvent_t ev[4];
-  for (int i = 0; i < 4; i++) KM_HIP("hipEventCreate", hipEventCreate(&ev[i]));
+  for (int i = 0; i < 4; i++) TM_HIP("hipEventCreate", hipEventCreate(&ev[i]));
   int rc = TMJX_OK, it = 0, cur = 0;
   bool update_pending = false;
   double previous = 0.0;

@@ -11,7 +11,6 @@
 #include "lstm_kernels.h"
 #include "lstm_decoder_act.h"
 
-static int fail(int code, const std::string &msg) { return tmjx_internal_fail(code, msg.c_str()); }
 static bool hidden_ok(int H) { return H == 32 || H == 64 || H == 128 || H == 256; }
 
 static const char *fwd_why(const tmjx_lstm_fwd_t *a) {

@@ -1,6 +1,6 @@
 // csrc/tmjx_pca.hip — PCA of recorded activations and the progression panel (include/tmjx.h: tmjx_pca_*, tmjx_plot_strips; DESIGN.md "PCA").
 // The bodies are csrc/pca_core.h (they also compile on the host); the argument checks csrc/pca_host.h.  Kernels:
-//   k_pca_colsum  one workgroup per PCA_ROWS_PER_WG rows: float64 column sums        k_pca_mean    the sums added in workgroup order
+//   k_moments_colsum  (csrc/moments_core.h) one workgroup per PCA_ROWS_PER_WG rows    k_pca_mean    the sums added in workgroup order
 //   k_pca_gram    one workgroup per PCA_ROWS_PER_WG rows: the centred partial Gram   k_pca_cov     the partials added in workgroup order, float64
 //   k_pca_jacobi  one workgroup: parallel-ordered cyclic Jacobi, A and V in LDS      k_pca_transform, k_plot_strips
 // The partial Gram tiles are plain float32 FMAs, not the fp32 MFMA: both run at the same 64 FLOP/clk/SIMD on gfx950, the fit of 210 000 x 128 is
@@ -15,17 +15,9 @@
 #include "host_launch.h"
 #include "pca_host.h"
 
-static int fail(int code, const std::string &msg) { return tmjx_internal_fail(code, msg.c_str()); }
-#define PCA_TRY(expr) do { const std::string e_ = (expr); if (!e_.empty()) return fail(TMJX_EINVAL, e_); } while (0)
-#define PCA_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(TMJX_EHIP, std::string(#expr ": ") + hipGetErrorString(e_)); } while (0)
 using namespace tmjx_host;
 
 // ----------------------------------------------------------------------------------------------- kernels
-__global__ __launch_bounds__(PCA_THREADS) void k_pca_colsum(const float *__restrict__ x, int64_t ldx, int n, int d, double *__restrict__ partial) {
-  __shared__ double s_sum[2 * PCA_MAX_D];
-  pca_colsum_wg(x, ldx, n, d, blockIdx.x, partial, s_sum);
-}
-
 __global__ __launch_bounds__(PCA_MAX_D) void k_pca_mean(const double *__restrict__ partial, int nwg, int d, int n, float *__restrict__ mean) {
   if ((int)threadIdx.x < d) mean[threadIdx.x] = pca_mean_col(partial, nwg, d, n, threadIdx.x);
 }
@@ -75,16 +67,6 @@ __global__ __launch_bounds__(PCA_THREADS) void k_plot_strips(PcaStrip s, const f
 }
 
 // ----------------------------------------------------------------------------------------------- launches
-// dynamic LDS beyond 64 KiB: the attribute is set once per kernel, to the largest size any accepted shape asks for
-template <class K>
-static int allow_lds(K kernel, const char *what, size_t max_bytes, bool &done) {
-  if (done) return TMJX_OK;
-  hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_bytes);
-  if (e != hipSuccess) return fail(TMJX_EHIP, std::string("hipFuncSetAttribute(") + what + "): " + hipGetErrorString(e));
-  done = true;
-  return TMJX_OK;
-}
-
 template <int NT>
 static void launch_gram(const float *x, int64_t ldx, int n, int d, const float *mean, float *partial, int nwg, hipStream_t s) {
   hipLaunchKernelGGL(k_pca_gram<NT>, dim3(nwg), dim3(PCA_THREADS), 0, s, x, ldx, n, d, mean, partial);
@@ -94,26 +76,23 @@ extern "C" {
 
 int tmjx_pca_workspace(int n, int d, int64_t *floats) {
   if (!floats) return fail(TMJX_EINVAL, "null argument");
-  PCA_TRY(pca_check_shape(n, d, d));
+  TM_TRY(pca_check_shape(n, d, d));
   *floats = pca_workspace(n, d).floats;
   return TMJX_OK;
 }
 
 int tmjx_pca_fit(const float *x, int n, int d, int64_t ldx, float *mean, float *components, float *variance, float *workspace, tmjx_pca_info_t *info,
                  void *stream) {
-  PCA_TRY(pca_check_fit(x, n, d, ldx, mean, components, variance, workspace, info));
+  TM_TRY(pca_check_fit(x, n, d, ldx, mean, components, variance, workspace, info));
   hipStream_t s = (hipStream_t)stream;
   const PcaWorkspace w = pca_workspace(n, d);
   double *colsum = (double *)(workspace + w.colsum);
   float *gram = workspace + w.gram, *cov = workspace + w.cov;
   PcaInfo *dinfo = (PcaInfo *)(workspace + w.info);
-  static bool lds_ok = false;
-  int rc = allow_lds(k_pca_jacobi, "k_pca_jacobi", sizeof(float) * pca_jacobi_lds_floats(PCA_MAX_D), lds_ok);
-  if (rc) return rc;
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  for (int i = 0; i < 3; i++) PCA_HIP(hipEventCreate(&ev[i]));
+  for (int i = 0; i < 3; i++) TM_HIP("hipEventCreate(&ev[i])", hipEventCreate(&ev[i]));
   hipEventRecord(ev[0], s);
-  hipLaunchKernelGGL(k_pca_colsum, dim3(w.nwg), dim3(PCA_THREADS), 0, s, x, ldx, n, d, colsum);
+  moments_launch_mean<true>(x, ldx, n, d, colsum, nullptr, s);
   hipLaunchKernelGGL(k_pca_mean, dim3(1), dim3(PCA_MAX_D), 0, s, colsum, w.nwg, d, n, mean);
   if (d <= 32) launch_gram<2>(x, ldx, n, d, mean, gram, w.nwg, s);
   else if (d <= 64) launch_gram<4>(x, ldx, n, d, mean, gram, w.nwg, s);
@@ -123,9 +102,9 @@ int tmjx_pca_fit(const float *x, int n, int d, int64_t ldx, float *mean, float *
   const int m = (d + 1) & ~1;
   int nt = ((m / 2) * m / 4 + 63) / 64 * 64;      // four (pair, element) items per thread and step, within [64, 1024] threads
   nt = nt < 64 ? 64 : (nt > 1024 ? 1024 : nt);
-  hipLaunchKernelGGL(k_pca_jacobi, dim3(1), dim3(nt), sizeof(float) * pca_jacobi_lds_floats(d), s, cov, d, components, variance, dinfo);
+  const int rc = launch_lds<k_pca_jacobi>("k_pca_jacobi", dim3(1), dim3(nt), sizeof(float) * pca_jacobi_lds_floats(PCA_MAX_D), sizeof(float) * pca_jacobi_lds_floats(d), s,
+                                    cov, d, components, variance, dinfo);      // (its check covers every launch of the fit)
   hipEventRecord(ev[2], s);
-  rc = check_launch("tmjx_pca_fit");
   PcaInfo hinfo = {0, 0, 0.f, 0};
   hipError_t e = rc ? hipSuccess : hipMemcpyAsync(&hinfo, dinfo, sizeof hinfo, hipMemcpyDeviceToHost, s);
   if (!rc && e == hipSuccess) e = hipStreamSynchronize(s);
@@ -142,19 +121,15 @@ int tmjx_pca_fit(const float *x, int n, int d, int64_t ldx, float *mean, float *
 }
 
 int tmjx_pca_transform(const float *x, int n, int d, int64_t ldx, const float *mean, const float *components, int k, float *out, int64_t ldo, void *stream) {
-  PCA_TRY(pca_check_transform(x, n, d, ldx, mean, components, k, out, ldo));
-  static bool lds_ok = false;
-  int rc = allow_lds(k_pca_transform, "k_pca_transform", sizeof(float) * (PCA_MAX_D + PCA_TROWS) * (PCA_MAX_D | 1), lds_ok);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_pca_transform, dim3((n + PCA_TROWS - 1) / PCA_TROWS), dim3(PCA_THREADS), sizeof(float) * (k + PCA_TROWS) * (d | 1), (hipStream_t)stream, x,
-                     n, d, ldx, mean, components, k, out, ldo);
-  return check_launch("k_pca_transform");
+  TM_TRY(pca_check_transform(x, n, d, ldx, mean, components, k, out, ldo));
+  return launch_lds<k_pca_transform>("k_pca_transform", dim3((n + PCA_TROWS - 1) / PCA_TROWS), dim3(PCA_THREADS), sizeof(float) * (PCA_MAX_D + PCA_TROWS) * (PCA_MAX_D | 1),
+                                     sizeof(float) * (k + PCA_TROWS) * (d | 1), (hipStream_t)stream, x, n, d, ldx, mean, components, k, out, ldo);
 }
 
 int tmjx_plot_strips(const float *proj, int T, int k, int64_t ldp, const int32_t *frame_idx, const uint8_t *flags, int F, float ymin, float ymax, int window,
                      const tmjx_strip_style_t *style, int W, int H, uint8_t *rgba, void *stream) {
   PcaStrip s;
-  PCA_TRY(pca_check_strips(proj, T, k, ldp, frame_idx, F, ymin, ymax, window, style, W, H, rgba, s));
+  TM_TRY(pca_check_strips(proj, T, k, ldp, frame_idx, F, ymin, ymax, window, style, W, H, rgba, s));
   if (F > 65535) return fail(TMJX_EINVAL, "F exceeds the 65535 frames of one launch: draw fewer frames per call");
   if ((long long)W * H > 0x7fffffffLL) return fail(TMJX_EINVAL, "W * H exceeds the pixels of one launch");
   hipLaunchKernelGGL(k_plot_strips, dim3((unsigned)(((long long)W * H + PCA_THREADS - 1) / PCA_THREADS), (unsigned)F), dim3(PCA_THREADS), 0, (hipStream_t)stream, s,

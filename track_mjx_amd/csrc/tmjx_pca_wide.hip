@@ -1,6 +1,6 @@
 // csrc/tmjx_pca_wide.hip — PCA of features 129 .. 1024 wide (include/tmjx.h: tmjx_pca_wide_workspace, tmjx_pca_fit_wide, tmjx_pca_transform_wide;
 // DESIGN.md "PCA", wide fit).  The bodies are csrc/pca_wide_core.h (they also compile on the host); the argument checks csrc/pca_wide_host.h.
-//   k_pcaw_colsum  one workgroup per (super-chunk, 128 columns): float64 column sums     k_pcaw_mean   the sums added in super-chunk order
+//   k_moments_colsum, k_moments_mean   the column mean by super-chunk (csrc/moments_core.h)
 //   k_pcaw_gram    one workgroup per (128 x 128 tile with j >= i, super-chunk)           k_pcaw_cov    the partials added in order, mirrored; V^T = I
 //   k_pcaw_rownorm, k_pcaw_norms   ||A||_F^2 and off(A)^2 in float64, fixed order
 //   k_pcaw_solve   one workgroup per pair of blocks: gathers the sub-matrix, pca_jacobi_wg in LDS
@@ -12,33 +12,19 @@
 
 #include <stdint.h>
 
-#include <atomic>
 #include <string>
 
 #include "../../include/tmjx.h"
 #include "host_launch.h"
 #include "pca_wide_host.h"
 
-static int fail(int code, const std::string &msg) { return tmjx_internal_fail(code, msg.c_str()); }
-#define PCA_TRY(expr) do { const std::string e_ = (expr); if (!e_.empty()) return fail(TMJX_EINVAL, e_); } while (0)
-#define PCA_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(TMJX_EHIP, std::string(#expr ": ") + hipGetErrorString(e_)); } while (0)
 using namespace tmjx_host;
 
 // ----------------------------------------------------------------------------------------------- kernels
-__global__ __launch_bounds__(PCA_THREADS) void k_pcaw_colsum(const float *__restrict__ x, int64_t ldx, int n, int d, double *__restrict__ partial) {
-  __shared__ double s_sum[2 * PCA_WIDE_TILE];
-  pca_wide_colsum_wg(x, ldx, n, d, blockIdx.y, blockIdx.x, partial, s_sum);
-}
-
-__global__ __launch_bounds__(PCA_THREADS) void k_pcaw_mean(const double *__restrict__ partial, int S, int d, int n, float *__restrict__ mean) {
-  const int c = blockIdx.x * PCA_THREADS + threadIdx.x;
-  if (c < d) mean[c] = pca_wide_mean_col(partial, S, d, n, c);
-}
-
 // blockIdx.x: the upper-triangle tile, row by row; blockIdx.y: the super-chunk
 __global__ __launch_bounds__(PCA_THREADS) void k_pcaw_gram(const float *__restrict__ x, int64_t ldx, int n, int d, const float *__restrict__ mean,
                                                            double *__restrict__ partial) {
-  __shared__ float s_tile[2 * PCA_KB * PCA_TILE_LD];
+  __shared__ float s_tile[2 * PCA_KB * PCA_WIDE_TILE];
   const int nt = pca_wide_tiles(d);
   int ti = 0, t = blockIdx.x;
   while (t >= nt - ti) { t -= nt - ti; ti++; }
@@ -95,20 +81,6 @@ __global__ __launch_bounds__(PCA_THREADS) void k_pcaw_transform(const float *__r
 }
 
 // ----------------------------------------------------------------------------------------------- launches
-// The inner solver's dynamic LDS goes beyond 64 KiB.  The attribute belongs to the device: it is set once per device, not once per process
-// (devices past 63 set it before every launch).
-static int allow_solve_lds() {
-  static std::atomic<uint64_t> done{0};
-  int dev = 0;
-  PCA_HIP(hipGetDevice(&dev));
-  const uint64_t bit = dev >= 0 && dev < 64 ? (uint64_t)1 << dev : 0;
-  if (bit && (done.load(std::memory_order_acquire) & bit)) return TMJX_OK;
-  hipError_t e = hipFuncSetAttribute((const void *)k_pcaw_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * pca_jacobi_lds_floats(PCA_MAX_D)));
-  if (e != hipSuccess) return fail(TMJX_EHIP, std::string("hipFuncSetAttribute(k_pcaw_solve): ") + hipGetErrorString(e));
-  done.fetch_or(bit, std::memory_order_release);
-  return TMJX_OK;
-}
-
 struct WideFit {
   const float *x; int n, d; int64_t ldx; float *mean, *components, *variance, *workspace; tmjx_pca_info_t *info; hipStream_t s;
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
@@ -121,8 +93,8 @@ static int wide_norms(const WideFit &f, const PcaWideWorkspace &w, double *norms
   hipLaunchKernelGGL(k_pcaw_norms, dim3(1), dim3(64), 0, f.s, (const double *)(ws + w.rowsum), f.d, (double *)(ws + w.norms));
   int rc = check_launch("tmjx_pca_fit_wide (norms)");
   if (rc) return rc;
-  PCA_HIP(hipMemcpyAsync(norms, ws + w.norms, 2 * sizeof(double), hipMemcpyDeviceToHost, f.s));
-  PCA_HIP(hipStreamSynchronize(f.s));
+  TM_HIP("hipMemcpyAsync(norms, ws + w.norms, 2 * sizeof(double), hipMemcpyDeviceToHost, f.s)", hipMemcpyAsync(norms, ws + w.norms, 2 * sizeof(double), hipMemcpyDeviceToHost, f.s));
+  TM_HIP("hipStreamSynchronize(f.s)", hipStreamSynchronize(f.s));
   return TMJX_OK;
 }
 
@@ -134,24 +106,23 @@ static int wide_fit(WideFit &f) {
   float *A = ws + w.cov, *Vt = ws + w.vt, *sub = ws + w.sub, *J = ws + w.rot, *lam = ws + w.lam;
   PcaInfo *pinfo = (PcaInfo *)(ws + w.info);
   const int tiles = pca_wide_tiles(d), S = w.split.S;
-  PCA_HIP(hipEventRecord(f.ev[0], f.s));
-  hipLaunchKernelGGL(k_pcaw_colsum, dim3(tiles, S), dim3(PCA_THREADS), 0, f.s, f.x, f.ldx, n, d, colsum);
-  hipLaunchKernelGGL(k_pcaw_mean, dim3((d + PCA_THREADS - 1) / PCA_THREADS), dim3(PCA_THREADS), 0, f.s, colsum, S, d, n, f.mean);
+  TM_HIP("hipEventRecord(f.ev[0], f.s)", hipEventRecord(f.ev[0], f.s));
+  moments_launch_mean<false>(f.x, f.ldx, n, d, colsum, f.mean, f.s);
   hipLaunchKernelGGL(k_pcaw_gram, dim3(tiles * (tiles + 1) / 2, S), dim3(PCA_THREADS), 0, f.s, f.x, f.ldx, n, d, f.mean, gram);
   hipLaunchKernelGGL(k_pcaw_cov, dim3((d * d + PCA_THREADS - 1) / PCA_THREADS), dim3(PCA_THREADS), 0, f.s, gram, S, d, n, A, Vt);
   int rc = check_launch("tmjx_pca_fit_wide (moments)");
   if (rc) return rc;
   double norms[2] = {0.0, 0.0};
   if ((rc = wide_norms(f, w, norms))) return rc;
-  PCA_HIP(hipEventRecord(f.ev[1], f.s));
+  TM_HIP("hipEventRecord(f.ev[1], f.s)", hipEventRecord(f.ev[1], f.s));
   if (!pca_wide_finite(norms)) return fail(TMJX_EINVAL, pca_wide_nonfinite_message());      // before any rotation launch
   const int players = pca_wide_players(d), slices = (d + PCA_WIDE_PASS - 1) / PCA_WIDE_PASS;
-  const size_t lds = sizeof(float) * pca_jacobi_lds_floats(PCA_MAX_D);
+  const size_t lds = sizeof(float) * pca_jacobi_lds_floats(PCA_MAX_D);      // (beyond 64 KiB)
   int sweeps = 0;
   bool converged = pca_wide_converged(norms);
   while (!converged && sweeps < PCA_SWEEP_LIMIT) {
     for (int r = 0; r < players - 1; r++) {
-      hipLaunchKernelGGL(k_pcaw_solve, dim3(w.pairs), dim3(1024), lds, f.s, A, d, r, sub, J, lam, pinfo);
+      if ((rc = launch_lds<k_pcaw_solve>("k_pcaw_solve", dim3(w.pairs), dim3(1024), lds, lds, f.s, A, d, r, sub, J, lam, pinfo))) return rc;
       hipLaunchKernelGGL(k_pcaw_rows, dim3(slices, w.pairs, 2), dim3(PCA_THREADS), 0, f.s, A, Vt, d, r, J);
       hipLaunchKernelGGL(k_pcaw_cols, dim3(slices, w.pairs), dim3(PCA_THREADS), 0, f.s, A, d, r, J, lam);
     }
@@ -162,9 +133,9 @@ static int wide_fit(WideFit &f) {
     converged = pca_wide_converged(norms);
   }
   hipLaunchKernelGGL(k_pcaw_finish, dim3((d + 63) / 64), dim3(64), 0, f.s, A, Vt, d, f.components, f.variance);
-  PCA_HIP(hipEventRecord(f.ev[2], f.s));
+  TM_HIP("hipEventRecord(f.ev[2], f.s)", hipEventRecord(f.ev[2], f.s));
   if ((rc = check_launch("tmjx_pca_fit_wide (finish)"))) return rc;
-  PCA_HIP(hipStreamSynchronize(f.s));
+  TM_HIP("hipStreamSynchronize(f.s)", hipStreamSynchronize(f.s));
   f.info->sweeps = sweeps; f.info->converged = converged ? 1 : 0; f.info->off_rel = pca_wide_off_rel(norms);
   hipEventElapsedTime(&f.info->moments_ms, f.ev[0], f.ev[1]);
   hipEventElapsedTime(&f.info->jacobi_ms, f.ev[1], f.ev[2]);
@@ -177,7 +148,7 @@ extern "C" {
 int tmjx_pca_wide_workspace(int n, int d, int64_t *floats) {
   if (d >= 1 && d <= PCA_MAX_D) return tmjx_pca_workspace(n, d, floats);
   if (!floats) return fail(TMJX_EINVAL, "null argument");
-  PCA_TRY(pca_wide_check_shape(n, d, d));
+  TM_TRY(pca_wide_check_shape(n, d, d));
   *floats = pca_wide_workspace(n, d).floats;
   return TMJX_OK;
 }
@@ -185,9 +156,7 @@ int tmjx_pca_wide_workspace(int n, int d, int64_t *floats) {
 int tmjx_pca_fit_wide(const float *x, int n, int d, int64_t ldx, float *mean, float *components, float *variance, float *workspace, tmjx_pca_info_t *info,
                       void *stream) {
   if (d >= 1 && d <= PCA_MAX_D) return tmjx_pca_fit(x, n, d, ldx, mean, components, variance, workspace, info, stream);
-  PCA_TRY(pca_wide_check_fit(x, n, d, ldx, mean, components, variance, workspace, info));
-  int rc = allow_solve_lds();
-  if (rc) return rc;
+  TM_TRY(pca_wide_check_fit(x, n, d, ldx, mean, components, variance, workspace, info));
   WideFit f{x, n, d, ldx, mean, components, variance, workspace, info, (hipStream_t)stream};
   for (int i = 0; i < 3; i++) {
     hipError_t e = hipEventCreate(&f.ev[i]);
@@ -198,7 +167,7 @@ int tmjx_pca_fit_wide(const float *x, int n, int d, int64_t ldx, float *mean, fl
   }
   info->sweeps = info->converged = 0;
   info->off_rel = info->moments_ms = info->jacobi_ms = 0.f;
-  rc = wide_fit(f);
+  const int rc = wide_fit(f);
   for (int i = 0; i < 3; i++) hipEventDestroy(f.ev[i]);
   return rc;
 }
@@ -206,7 +175,7 @@ int tmjx_pca_fit_wide(const float *x, int n, int d, int64_t ldx, float *mean, fl
 int tmjx_pca_transform_wide(const float *x, int n, int d, int64_t ldx, const float *mean, const float *components, int k, float *out, int64_t ldo,
                             void *stream) {
   if (d >= 1 && d <= PCA_MAX_D) return tmjx_pca_transform(x, n, d, ldx, mean, components, k, out, ldo, stream);
-  PCA_TRY(pca_wide_check_transform(x, n, d, ldx, mean, components, k, out, ldo));
+  TM_TRY(pca_wide_check_transform(x, n, d, ldx, mean, components, k, out, ldo));
   const unsigned row_groups = (unsigned)((n + PCA_TROWS - 1) / PCA_TROWS);
   if (k <= 16)
     hipLaunchKernelGGL(k_pcaw_transform<1>, dim3(row_groups, 1), dim3(PCA_THREADS), 0, (hipStream_t)stream, x, n, d, ldx, mean, components, k, out, ldo);

@@ -1,7 +1,7 @@
 // csrc/tmjx_readout.hip — the linear readout: ridge regression from recorded activations (include/tmjx.h: tmjx_readout_workspace, tmjx_readout_fit,
 // tmjx_readout_weights, tmjx_readout_predict, tmjx_readout_score; DESIGN.md "Readout").  The bodies are csrc/readout_core.h (they also compile on the
 // host); the argument checks and workspace layouts csrc/readout_host.h.  The eigen-decomposition is tmjx_pca_fit_wide's, called as it is.
-//   k_ro_colsum   one workgroup per (super-chunk, 128 targets): float64 column sums of y     k_ro_mean     the sums added in super-chunk order
+//   k_moments_colsum, k_moments_mean   the column mean of y by super-chunk (csrc/moments_core.h)
 //   k_ro_cross    one workgroup per (128 features x 64 targets, super-chunk)                  k_ro_c        the partials added in order, over n - 1
 //   k_ro_gemm<0>  Z = components . C                                                           k_ro_gemm<1>  W_l = components^T diag(1 / (s + lambda_l)) Z, every l
 //   k_ro_apply<0> predictions, 64 rows x 64 targets per workgroup                              k_ro_apply<1> the fused score: 256 rows x 64 of the L m columns
@@ -16,21 +16,9 @@
 #include "host_launch.h"
 #include "readout_host.h"
 
-static int fail(int code, const std::string &msg) { return tmjx_internal_fail(code, msg.c_str()); }
-#define RO_TRY(expr) do { const std::string e_ = (expr); if (!e_.empty()) return fail(TMJX_EINVAL, e_); } while (0)
 using namespace tmjx_host;
 
 // ----------------------------------------------------------------------------------------------- kernels
-__global__ __launch_bounds__(PCA_THREADS) void k_ro_colsum(const float *__restrict__ y, int64_t ldy, int n, int m, double *__restrict__ partial) {
-  __shared__ double s_sum[2 * PCA_WIDE_TILE];
-  pca_wide_colsum_wg(y, ldy, n, m, blockIdx.y, blockIdx.x, partial, s_sum);
-}
-
-__global__ __launch_bounds__(PCA_THREADS) void k_ro_mean(const double *__restrict__ partial, int S, int m, int n, float *__restrict__ mean) {
-  const int c = blockIdx.x * PCA_THREADS + threadIdx.x;
-  if (c < m) mean[c] = pca_wide_mean_col(partial, S, m, n, c);
-}
-
 // blockIdx.x: the feature tile; blockIdx.y: the target tile; blockIdx.z: the super-chunk
 __global__ __launch_bounds__(PCA_THREADS) void k_ro_cross(const float *__restrict__ x, int64_t ldx, const float *__restrict__ y, int64_t ldy, int n, int d, int m,
                                                           const float *__restrict__ mean_x, const float *__restrict__ mean_y, double *__restrict__ partial) {
@@ -83,7 +71,7 @@ __global__ __launch_bounds__(PCA_THREADS) void k_ro_totals(const double *__restr
 extern "C" {
 
 int tmjx_readout_workspace(int n, int d, int m, int n_lambda, int64_t *floats) {
-  RO_TRY(readout_check_workspace(n, d, m, n_lambda, floats));
+  TM_TRY(readout_check_workspace(n, d, m, n_lambda, floats));
   int64_t pca = 0, pca_widest = 0;
   int rc = tmjx_pca_wide_workspace(n, d, &pca);
   if (!rc) rc = tmjx_pca_wide_workspace(readout_widest_rows(n), d, &pca_widest);
@@ -94,7 +82,7 @@ int tmjx_readout_workspace(int n, int d, int m, int n_lambda, int64_t *floats) {
 
 int tmjx_readout_fit(const float *x, int n, int d, int64_t ldx, const float *y, int m, int64_t ldy, float *mean_x, float *components, float *variance,
                      float *mean_y, float *z, float *workspace, tmjx_pca_info_t *info, void *stream) {
-  RO_TRY(readout_check_fit(x, n, d, ldx, y, m, ldy, mean_x, components, variance, mean_y, z, workspace, info));
+  TM_TRY(readout_check_fit(x, n, d, ldx, y, m, ldy, mean_x, components, variance, mean_y, z, workspace, info));
   int64_t pca = 0;
   int rc = tmjx_pca_wide_workspace(n, d, &pca);
   if (rc) return rc;
@@ -104,8 +92,7 @@ int tmjx_readout_fit(const float *x, int n, int d, int64_t ldx, const float *y, 
   double *ysum = (double *)(workspace + w.ysum), *cross = (double *)(workspace + w.cross);
   float *c = workspace + w.c;
   const int S = w.split.S;
-  hipLaunchKernelGGL(k_ro_colsum, dim3(pca_wide_tiles(m), S), dim3(PCA_THREADS), 0, s, y, ldy, n, m, ysum);
-  hipLaunchKernelGGL(k_ro_mean, dim3(readout_tiles(m, PCA_THREADS)), dim3(PCA_THREADS), 0, s, ysum, S, m, n, mean_y);
+  moments_launch_mean<false>(y, ldy, n, m, ysum, mean_y, s);
   hipLaunchKernelGGL(k_ro_cross, dim3(pca_wide_tiles(d), readout_tiles(m, READOUT_TILE_M), S), dim3(PCA_THREADS), 0, s, x, ldx, y, ldy, n, d, m, mean_x, mean_y,
                      cross);
   hipLaunchKernelGGL(k_ro_c, dim3(readout_tiles(d * m, PCA_THREADS)), dim3(PCA_THREADS), 0, s, cross, S, d, m, n, c);
@@ -119,7 +106,7 @@ int tmjx_readout_fit(const float *x, int n, int d, int64_t ldx, const float *y, 
 
 int tmjx_readout_weights(const float *components, const float *variance, const float *z, int d, int m, const double *lambdas, int n_lambda, float *w,
                          void *stream) {
-  RO_TRY(readout_check_weights(components, variance, z, d, m, lambdas, n_lambda, w));
+  TM_TRY(readout_check_weights(components, variance, z, d, m, lambdas, n_lambda, w));
   ReadoutLambdas lam{};
   for (int i = 0; i < n_lambda; i++) lam.v[i] = (float)lambdas[i];
   hipLaunchKernelGGL(k_ro_gemm<true>, dim3(readout_tiles(d, READOUT_TILE), readout_tiles(m, READOUT_TILE), n_lambda), dim3(PCA_THREADS), 0, (hipStream_t)stream,
@@ -129,7 +116,7 @@ int tmjx_readout_weights(const float *components, const float *variance, const f
 
 int tmjx_readout_predict(const float *x, int n, int d, int64_t ldx, const float *mean_x, const float *w, const float *mean_y, int m, float *out, int64_t ldo,
                          void *stream) {
-  RO_TRY(readout_check_predict(x, n, d, ldx, mean_x, w, mean_y, m, out, ldo));
+  TM_TRY(readout_check_predict(x, n, d, ldx, mean_x, w, mean_y, m, out, ldo));
   hipLaunchKernelGGL(k_ro_apply<false>, dim3(readout_tiles(n, READOUT_ROWS), readout_tiles(m, READOUT_TILE)), dim3(PCA_THREADS), 0, (hipStream_t)stream, x, n, d,
                      ldx, mean_x, w, m, m, mean_y, (const float *)nullptr, (int64_t)0, out, ldo, (double *)nullptr);
   return check_launch("tmjx_readout_predict");
@@ -137,12 +124,12 @@ int tmjx_readout_predict(const float *x, int n, int d, int64_t ldx, const float 
 
 int tmjx_readout_score(const float *x, int n, int d, int64_t ldx, const float *y, int m, int64_t ldy, const float *mean_x, const float *w, const float *mean_y,
                        int n_lambda, double *sse, double *sst, float *workspace, void *stream) {
-  RO_TRY(readout_check_score(x, n, d, ldx, y, m, ldy, mean_x, w, mean_y, n_lambda, sse, sst, workspace));
+  TM_TRY(readout_check_score(x, n, d, ldx, y, m, ldy, mean_x, w, mean_y, n_lambda, sse, sst, workspace));
   const ReadoutScoreWorkspace ws = readout_score_workspace(n, m, n_lambda);
   hipStream_t s = (hipStream_t)stream;
   double *ysum = (double *)(workspace + ws.ysum), *sstp = (double *)(workspace + ws.sst), *ssep = (double *)(workspace + ws.sse);
   const int S = ws.split.S, Q = n_lambda * m, nblocks = ws.split.nchunks;
-  hipLaunchKernelGGL(k_ro_colsum, dim3(pca_wide_tiles(m), S), dim3(PCA_THREADS), 0, s, y, ldy, n, m, ysum);
+  moments_launch_mean<false>(y, ldy, n, m, ysum, nullptr, s);
   hipLaunchKernelGGL(k_ro_sst, dim3(pca_wide_tiles(m), S), dim3(PCA_THREADS), 0, s, y, ldy, n, m, ysum, sstp);
   hipLaunchKernelGGL(k_ro_apply<true>, dim3(nblocks, readout_tiles(Q, READOUT_TILE)), dim3(PCA_THREADS), 0, s, x, n, d, ldx, mean_x, w, m, Q, mean_y, y, ldy,
                      (float *)nullptr, (int64_t)0, ssep);

@@ -18,7 +18,6 @@
 #define TMJX_RENDER_TILE_X 16
 #endif
 
-static int fail(int code, const std::string &msg) { return tmjx_internal_fail(code, msg.c_str()); }
 
 struct RenderHandle {
   tmjx_host::RenderTables t;
@@ -94,7 +93,6 @@ __global__ __launch_bounds__(256) void k_render_rays(const float *__restrict__ p
 
 // ----------------------------------------------------------------------------------------------- C-ABI
 // (the argument checks are csrc/render_host.h's, shared with the host emulation)
-#define TMR_TRY(expr) do { const std::string e_ = (expr); if (!e_.empty()) return fail(TMJX_EINVAL, e_); } while (0)
 using namespace tmjx_host;
 
 static const RenderHandle *tables_of(const tmjx_model *m, int &rc) {
@@ -112,7 +110,7 @@ static int launch_pose(const RenderHandle *h, const float *qpos, const float *qp
 }
 
 static int launch_rays(const float *prims, const float *cams, int F, int P, int W, int H, uint8_t *rgba, float *depth, int32_t *geom_id, hipStream_t s) {
-  TMR_TRY(render_check_rays(prims, cams, F, P, W, H, rgba, depth, geom_id));
+  TM_TRY(render_check_rays(prims, cams, F, P, W, H, rgba, depth, geom_id));
   constexpr int WX = TMJX_RENDER_TILE_X, WY = 64 / TMJX_RENDER_TILE_X;
   const int tiles_x = (W + 2 * WX - 1) / (2 * WX), tiles_y = (H + 2 * WY - 1) / (2 * WY);
   const long long blocks = (long long)tiles_x * tiles_y * F;
@@ -139,7 +137,7 @@ int tmjx_render_camera(const tmjx_model *m, const char *name, tmjx_camera_t *out
   const RenderHandle *h = tables_of(m, rc);
   if (!h) return rc;
   if (!name || !out) return fail(TMJX_EINVAL, "null argument");
-  TMR_TRY(render_find_camera(h->t, name, out));
+  TM_TRY(render_find_camera(h->t, name, out));
   return TMJX_OK;
 }
 
@@ -149,8 +147,8 @@ int tmjx_render_pose(const tmjx_model *m, const float *qpos, const float *qpos_g
   const RenderHandle *h = tables_of(m, rc);
   if (!h) return rc;
   RCamera rcam;
-  TMR_TRY(render_check_frames(F, F_ghost, qpos, qpos_ghost));
-  TMR_TRY(render_check_camera(h->t.m, cam, rcam));
+  TM_TRY(render_check_frames(F, F_ghost, qpos, qpos_ghost));
+  TM_TRY(render_check_camera(h->t.m, cam, rcam));
   if (!workspace || !al16(workspace)) return fail(TMJX_EINVAL, "the workspace must be a 16-byte aligned device buffer of tmjx_render_info's size");
   return launch_pose(h, qpos, qpos_ghost, F, rcam, workspace, (hipStream_t)stream);
 }
@@ -165,11 +163,11 @@ int tmjx_render(const tmjx_model *m, const float *qpos, const float *qpos_ghost,
   const RenderHandle *h = tables_of(m, rc);
   if (!h) return rc;
   RCamera rcam;
-  TMR_TRY(render_check_frames(F, F_ghost, qpos, qpos_ghost));
-  TMR_TRY(render_check_camera(h->t.m, cam, rcam));
+  TM_TRY(render_check_frames(F, F_ghost, qpos, qpos_ghost));
+  TM_TRY(render_check_camera(h->t.m, cam, rcam));
   if (!workspace || !al16(workspace)) return fail(TMJX_EINVAL, "the workspace must be a 16-byte aligned device buffer of tmjx_render_info's size");
   const int P = h->t.m.ngeom + (qpos_ghost ? h->t.m.nghost : 0);
-  TMR_TRY(render_check_rays(workspace + (size_t)F * TMR_CAM, workspace, F, P, W, H, rgba, depth, geom_id));      // (before the first launch)
+  TM_TRY(render_check_rays(workspace + (size_t)F * TMR_CAM, workspace, F, P, W, H, rgba, depth, geom_id));      // (before the first launch)
   if ((rc = launch_pose(h, qpos, qpos_ghost, F, rcam, workspace, (hipStream_t)stream))) return rc;
   return launch_rays(workspace + (size_t)F * TMR_CAM, workspace, F, P, W, H, rgba, depth, geom_id, (hipStream_t)stream);
 }

@@ -12,7 +12,6 @@
 #include "rollout_kernels.h"
 
 static_assert(sizeof(tmjx_record_stream_t) == 176, "tmjx_record_stream_t: the layout hip.RecordStream declares");
-static int fail(int code, const std::string &msg) { return tmjx_internal_fail(code, msg.c_str()); }
 static int grid_of(long long total) { long long g = (total + 255) / 256; return (int)(g < 4096 ? (g > 0 ? g : 1) : 4096); }
 
 static std::string stream_why(const tmjx_record_stream_t &s, int n_env, int T) {

@@ -14,9 +14,6 @@
 #include "host_launch.h"
 #include "spectrogram_host.h"
 
-static int fail(int code, const std::string &msg) { return tmjx_internal_fail(code, msg.c_str()); }
-#define SPEC_TRY(expr) do { const std::string e_ = (expr); if (!e_.empty()) return fail(TMJX_EINVAL, e_); } while (0)
-#define SPEC_HIP(what, expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(TMJX_EHIP, std::string(what) + ": " + hipGetErrorString(e_)); } while (0)
 using namespace tmjx_host;
 
 __global__ __launch_bounds__(SPEC_THREADS) void k_spec_prepare(const int32_t *__restrict__ seq_start, int S, int tt, const float *__restrict__ bank,
@@ -48,21 +45,21 @@ __global__ __launch_bounds__(SPEC_THREADS) void k_spec_tile(const float *__restr
 extern "C" {
 
 int tmjx_wavelet_bank_size(double rate, const double *freqs, int F, double omega0, double support, int64_t *floats) {
-  SPEC_TRY(spec_check_bank(rate, freqs, F, omega0, support));
+  TM_TRY(spec_check_bank(rate, freqs, F, omega0, support));
   if (!floats) return fail(TMJX_EINVAL, "null argument");
   *floats = spec_bank_floats(rate, freqs, F, omega0, support);
   return TMJX_OK;
 }
 
 int tmjx_wavelet_bank(double rate, const double *freqs, int F, double omega0, double support, float *bank, int32_t *offset, int32_t *radius) {
-  SPEC_TRY(spec_check_bank(rate, freqs, F, omega0, support));
+  TM_TRY(spec_check_bank(rate, freqs, F, omega0, support));
   if (!bank || !offset || !radius) return fail(TMJX_EINVAL, "null argument");
   spec_build_bank(rate, freqs, F, omega0, support, bank, offset, radius);
   return TMJX_OK;
 }
 
 int tmjx_spectrogram_workspace(int n, int C, int F, int S, int64_t *floats) {
-  SPEC_TRY(spec_check_workspace(n, C, F, S, floats));
+  TM_TRY(spec_check_workspace(n, C, F, S, floats));
   *floats = spec_workspace(C, F, S).floats;
   return TMJX_OK;
 }
@@ -70,7 +67,7 @@ int tmjx_spectrogram_workspace(int n, int C, int F, int S, int64_t *floats) {
 int tmjx_spectrogram(const float *x, int n, int C, int64_t ldx, const int32_t *seq_start, int S, const float *bank, const int32_t *offset,
                      const int32_t *radius, int F, int detrend, int output_kind, float log_floor, float *out, int64_t ldo, float *coverage, float *workspace,
                      void *stream) {
-  SPEC_TRY(spec_check(x, n, C, ldx, seq_start, S, bank, offset, radius, F, output_kind, log_floor, out, ldo, coverage, workspace));
+  TM_TRY(spec_check(x, n, C, ldx, seq_start, S, bank, offset, radius, F, output_kind, log_floor, out, ldo, coverage, workspace));
   const SpecWorkspace w = spec_workspace(C, F, S);
   const SpecGeom g = spec_geom(C, spec_max_radius(radius, F));
   const int64_t tiles = spec_count_tiles(seq_start, S, g.tt);
@@ -79,9 +76,9 @@ int tmjx_spectrogram(const float *x, int n, int C, int64_t ldx, const int32_t *s
           *d_rad = (int32_t *)(workspace + w.radius);
   float *mean = workspace + w.mean;
   double *prefix = (double *)(workspace + w.prefix);
-  SPEC_HIP("tmjx_spectrogram", hipMemcpyAsync(d_seq, seq_start, sizeof(int32_t) * (size_t)(S + 1), hipMemcpyHostToDevice, s));
-  SPEC_HIP("tmjx_spectrogram", hipMemcpyAsync(d_off, offset, sizeof(int32_t) * (size_t)(F + 1), hipMemcpyHostToDevice, s));
-  SPEC_HIP("tmjx_spectrogram", hipMemcpyAsync(d_rad, radius, sizeof(int32_t) * (size_t)F, hipMemcpyHostToDevice, s));
+  TM_HIP("tmjx_spectrogram", hipMemcpyAsync(d_seq, seq_start, sizeof(int32_t) * (size_t)(S + 1), hipMemcpyHostToDevice, s));
+  TM_HIP("tmjx_spectrogram", hipMemcpyAsync(d_off, offset, sizeof(int32_t) * (size_t)(F + 1), hipMemcpyHostToDevice, s));
+  TM_HIP("tmjx_spectrogram", hipMemcpyAsync(d_rad, radius, sizeof(int32_t) * (size_t)F, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_spec_prepare, dim3(1), dim3(SPEC_THREADS), 0, s, d_seq, S, g.tt, bank, d_off, d_rad, F, d_tile, prefix);
   if (detrend) hipLaunchKernelGGL(k_spec_mean, dim3(S, kmeans_tiles(C, 64)), dim3(SPEC_THREADS), 0, s, x, C, ldx, d_seq, mean);
   hipLaunchKernelGGL(k_spec_tile, dim3((unsigned)tiles, g.cblocks), dim3(g.threads), sizeof(float) * (size_t)g.lds_floats, s, x, C, ldx, d_seq, d_tile, S,

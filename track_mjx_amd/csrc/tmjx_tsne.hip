@@ -2,7 +2,7 @@
 // gradient and step, and out-of-sample placement (include/tmjx.h: tmjx_tsne_workspace, tmjx_knn, tmjx_tsne_affinities, tmjx_tsne_gradient,
 // tmjx_tsne_update, tmjx_tsne_fit, tmjx_tsne_place; DESIGN.md "Behaviour map").  The bodies are csrc/tsne_core.h (they also compile on the host);
 // the argument checks and the workspace layout csrc/tsne_host.h.
-//   k_km_colsum / k_km_mean  the column mean of x, as the k-means forms it        k_ts_norms    ||row - mean||^2, one thread per row
+//   k_moments_colsum / _mean the column mean of x, as the k-means forms it        k_ts_norms    ||row - mean||^2, one thread per row
 //   k_ts_knn      the fused search: 128 queries per workgroup, the k best in LDS    k_ts_affinity the perplexity search, one thread per row
 //   k_ts_rep      all-pairs repulsion: (256 points, part of the walk) per workgroup k_ts_rowsum   the parts in part order, Z per block
 //   k_ts_attr     the CSR attraction, the gradient and kl per block                 k_ts_kl       kl: the blocks in block order
@@ -19,23 +19,9 @@
 #include "host_launch.h"
 #include "tsne_host.h"
 
-static int fail(int code, const std::string &msg) { return tmjx_internal_fail(code, msg.c_str()); }
-#define TS_TRY(expr) do { const std::string e_ = (expr); if (!e_.empty()) return fail(TMJX_EINVAL, e_); } while (0)
-#define TS_HIP(what, expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(TMJX_EHIP, std::string(what) + ": " + hipGetErrorString(e_)); } while (0)
 using namespace tmjx_host;
 
 // ----------------------------------------------------------------------------------------------- kernels
-// (this unit's own copies of the k-means' column-sum kernels: the bodies are shared, a kernel belongs to its translation unit)
-__global__ __launch_bounds__(PCA_THREADS) void k_ts_colsum(const float *__restrict__ x, int64_t ldx, int n, int d, double *__restrict__ partial) {
-  __shared__ double s_sum[2 * PCA_WIDE_TILE];
-  kmeans_colsum_wg(x, ldx, n, d, blockIdx.x, blockIdx.y, partial, s_sum);
-}
-
-__global__ __launch_bounds__(PCA_THREADS) void k_ts_mean(const double *__restrict__ partial, int nchunks, int d, int n, float *__restrict__ mean) {
-  const int c = blockIdx.x * PCA_THREADS + threadIdx.x;
-  if (c < d) mean[c] = kmeans_mean_col(partial, nchunks, d, n, c);
-}
-
 __global__ __launch_bounds__(PCA_THREADS) void k_ts_norms(const float *__restrict__ x, int64_t rows, int d, int64_t ldx, const float *__restrict__ mean,
                                                           float *__restrict__ out) {
   const int64_t r = (int64_t)blockIdx.x * PCA_THREADS + threadIdx.x;
@@ -125,60 +111,53 @@ static int launch_update(float *y, const float *grad, float *velocity, float *ga
 extern "C" {
 
 int tmjx_tsne_workspace(int n, int64_t m, int d, int k, int64_t *floats) {
-  TS_TRY(tsne_check_workspace(n, m, d, k, floats));
+  TM_TRY(tsne_check_workspace(n, m, d, k, floats));
   *floats = tsne_workspace(n, m, d, k).floats;
   return TMJX_OK;
 }
 
 int tmjx_knn(const float *x, int n, int d, int64_t ldx, const float *q, int64_t m, int64_t ldq, int exclude_self, int k, int32_t *idx, float *dist2,
              float *workspace, void *stream) {
-  TS_TRY(tsne_check_knn(x, n, d, ldx, q, m, ldq, exclude_self, k, idx, dist2, workspace));
+  TM_TRY(tsne_check_knn(x, n, d, ldx, q, m, ldq, exclude_self, k, idx, dist2, workspace));
   const TsneWorkspace w = tsne_workspace(n, m, d, k);
   hipStream_t s = (hipStream_t)stream;
   double *colsum = (double *)(workspace + w.colsum);
   float *mean = workspace + w.mean, *xnorm = workspace + w.xnorm, *qnorm = workspace + w.qnorm;
   const int self = tsne_knn_self(x, n, ldx, q, m, ldq, exclude_self) ? 1 : 0;
-  hipLaunchKernelGGL(k_ts_colsum, dim3(w.nchunks, pca_wide_tiles(d)), dim3(PCA_THREADS), 0, s, x, ldx, n, d, colsum);
-  hipLaunchKernelGGL(k_ts_mean, dim3(kmeans_tiles(d, PCA_THREADS)), dim3(PCA_THREADS), 0, s, colsum, w.nchunks, d, n, mean);
+  moments_launch_mean<true>(x, ldx, n, d, colsum, mean, s);
   hipLaunchKernelGGL(k_ts_norms, dim3(blocks_of(n, PCA_THREADS)), dim3(PCA_THREADS), 0, s, x, (int64_t)n, d, ldx, mean, xnorm);
   hipLaunchKernelGGL(k_ts_norms, dim3(blocks_of(m, PCA_THREADS)), dim3(PCA_THREADS), 0, s, q, m, d, ldq, mean, qnorm);
   int rc = check_launch("tmjx_knn");
   if (rc) return rc;
-  static bool attr_set = false;      // more than 64 KiB of dynamic LDS needs the attribute once: set for the largest k
-  if (!attr_set) {
-    TS_HIP("hipFuncSetAttribute(k_ts_knn)", hipFuncSetAttribute((const void *)k_ts_knn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tsne_knn_lds(TSNE_MAX_K)));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(k_ts_knn, dim3(blocks_of(m, TSNE_ROWS)), dim3(PCA_THREADS), tsne_knn_lds(k), s, x, n, d, ldx, q, m, ldq, self, k, mean, xnorm, qnorm, idx,
-                     dist2);
-  return check_launch("tmjx_knn");
+  return launch_lds<k_ts_knn>("tmjx_knn", dim3(blocks_of(m, TSNE_ROWS)), dim3(PCA_THREADS), tsne_knn_lds(TSNE_MAX_K), tsne_knn_lds(k), s, x, n, d, ldx, q, m, ldq, self, k,
+                              mean, xnorm, qnorm, idx, dist2);
 }
 
 int tmjx_tsne_affinities(const float *dist2, int64_t m, int k, double perplexity, float *p, float *beta, void *stream) {
-  TS_TRY(tsne_check_affinities(dist2, m, k, perplexity, p, beta));
+  TM_TRY(tsne_check_affinities(dist2, m, k, perplexity, p, beta));
   hipLaunchKernelGGL(k_ts_affinity, dim3(blocks_of(m, PCA_THREADS)), dim3(PCA_THREADS), 0, (hipStream_t)stream, dist2, m, k, log(perplexity), p, beta);
   return check_launch("tmjx_tsne_affinities");
 }
 
 int tmjx_tsne_gradient(const float *y, int n, const int32_t *row_ptr, const int32_t *col, const float *val, int64_t nnz, double exaggeration, float *grad,
                        double *z, double *kl, float *workspace, void *stream) {
-  TS_TRY(tsne_check_gradient(y, n, row_ptr, col, val, nnz, exaggeration, grad, z, kl, workspace));
+  TM_TRY(tsne_check_gradient(y, n, row_ptr, col, val, nnz, exaggeration, grad, z, kl, workspace));
   const TsneWorkspace w = tsne_workspace(n, 1, 1, 1);
   hipStream_t s = (hipStream_t)stream;
-  TS_HIP("tmjx_tsne_gradient", hipMemcpyAsync(workspace + w.row_ptr, row_ptr, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, s));
+  TM_HIP("tmjx_tsne_gradient", hipMemcpyAsync(workspace + w.row_ptr, row_ptr, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, s));
   return launch_gradient(y, n, col, val, exaggeration, grad, z, kl, workspace, w, s);
 }
 
 int tmjx_tsne_update(float *y, const float *grad, float *velocity, float *gains, int n, float momentum, float eta, float min_gain, float *workspace,
                      void *stream) {
-  TS_TRY(tsne_check_update(y, grad, velocity, gains, n, momentum, eta, min_gain, workspace));
+  TM_TRY(tsne_check_update(y, grad, velocity, gains, n, momentum, eta, min_gain, workspace));
   return launch_update(y, grad, velocity, gains, n, momentum, eta, min_gain, workspace, tsne_workspace(n, 1, 1, 1), (hipStream_t)stream);
 }
 
 int tmjx_tsne_fit(float *y, int n, const int32_t *row_ptr, const int32_t *col, const float *val, int64_t nnz, int n_iter, double exaggeration,
                   int exaggeration_iters, float momentum_early, float momentum_late, float eta, float min_gain, float *velocity, float *gains,
                   tmjx_tsne_info_t *info, float *workspace, void *stream) {
-  TS_TRY(tsne_check_fit(y, n, row_ptr, col, val, nnz, n_iter, exaggeration, exaggeration_iters, momentum_early, momentum_late, eta, min_gain, velocity, gains,
+  TM_TRY(tsne_check_fit(y, n, row_ptr, col, val, nnz, n_iter, exaggeration, exaggeration_iters, momentum_early, momentum_late, eta, min_gain, velocity, gains,
                         info, workspace));
   const TsneWorkspace w = tsne_workspace(n, 1, 1, 1);
   hipStream_t s = (hipStream_t)stream;
@@ -190,9 +169,9 @@ int tmjx_tsne_fit(float *y, int n, const int32_t *row_ptr, const int32_t *col, c
   auto finish = [&](int code) { for (hipEvent_t e : ev) (void)hipEventDestroy(e); return code; };
   auto mark = [&]() -> int {
     hipEvent_t e;
-    TS_HIP("hipEventCreate", hipEventCreate(&e));
+    TM_HIP("hipEventCreate", hipEventCreate(&e));
     ev.push_back(e);
-    TS_HIP("hipEventRecord", hipEventRecord(e, s));
+    TM_HIP("hipEventRecord", hipEventRecord(e, s));
     return TMJX_OK;
   };
   int rc = TMJX_OK;
@@ -221,7 +200,7 @@ int tmjx_tsne_fit(float *y, int n, const int32_t *row_ptr, const int32_t *col, c
 }
 
 int tmjx_tsne_place(const int32_t *idx, const float *p, int64_t m, int k, const float *y_train, int n, float *y_out, void *stream) {
-  TS_TRY(tsne_check_place(idx, p, m, k, y_train, n, y_out));
+  TM_TRY(tsne_check_place(idx, p, m, k, y_train, n, y_out));
   hipLaunchKernelGGL(k_ts_place, dim3(blocks_of(m, PCA_THREADS)), dim3(PCA_THREADS), 0, (hipStream_t)stream, idx, p, m, k, y_train, n, y_out);
   return check_launch("tmjx_tsne_place");
 }

@@ -1,13 +1,14 @@
 // csrc/tsne_core.h — the bodies of the behaviour-map kernels (DESIGN.md "Behaviour map"; include/tmjx.h: tmjx_knn, tmjx_tsne_*): a brute-force
 // k-nearest-neighbour search with a fused top-k, the perplexity search, the exact t-SNE gradient (all-pairs repulsion, CSR attraction), the
-// delta-bar-delta step and the out-of-sample placement.  Written with the PCA_WG / PCA_PAR / PCA_SYNC / PCA_PRIVATE discipline of csrc/pca_core.h,
-// so that they also compile on the host (tests/hostemu/tsne_emu.cpp).  Every pair is a chain of float32 operations in a fixed order, every
+// delta-bar-delta step and the out-of-sample placement.  Written with the PCA_WG / PCA_PAR / PCA_SYNC / PCA_PRIVATE discipline of csrc/wg_core.h,
+// so that they also compile on the host (tests/hostemu/tsne_emu.cpp); the column mean is csrc/moments_core.h, km_f4 and kmeans_inf the k-means'.  Every pair is a chain of float32 operations in a fixed order, every
 // division is a correctly rounded one, every sum across points, tiles or workgroups is float64 in a fixed order: no atomics of any kind, the same
 // bits on every run.
 #pragma once
 #include <string.h>
 
 #include "kmeans_core.h"
+#include "moments_core.h"
 
 #define TSNE_MAX_D 1024
 #define TSNE_MAX_N 65536         // reference / training rows: a neighbour's index fits 16 bits of LDS
@@ -374,11 +375,7 @@ PCA_WG void tsne_attr_wg(const float *y, int n, const int32_t *row_ptr, const in
 }
 
 // the blocks' sums in block order
-TM_DEV double tsne_total(const double *block, int nb) {
-  double s = 0.0;
-  for (int t = 0; t < nb; t++) s += block[t];
-  return s;
-}
+TM_DEV double tsne_total(const double *block, int nb) { return wg_sum(block, nb, 1); }
 
 // ----------------------------------------------------------------------------------------------- update
 TM_DEV int tsne_sign(float v) { return (v > 0.f) - (v < 0.f); }
