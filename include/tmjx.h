@@ -1125,6 +1125,45 @@ int tmjx_decoder_jacobian(const tmjx_jacobian_desc_t *desc, const float *x, int 
                           int64_t ld_scale, int mode, float *ctrl_out, float *jac, float *gain, float *col2, float *row2, float *action_var, double *sums,
                           float *workspace, void *stream);
 
+/* ---- The LSTM decoder's Jacobian at recorded steps: the local linearisation of one step of the stacked-LSTM decoder, ctrl = tanh(loc), with
+ * respect to columns of its input row and to the carry (h, c) entering the step (csrc/tmjx_lstm_jacobian.hip, csrc/lstm_jacobian_core.h; DESIGN.md
+ * "LSTM decoder Jacobian").  The conventions of tmjx_decoder_jacobian word for word: no model handle; all device memory is the caller's; everything
+ * runs on the caller's stream; the list is worked through in passes of 1024 rows; fixed-order arithmetic, no atomics: the same bits on every run,
+ * and the bits of a row's outputs depend neither on m nor on where the row stands in the list.
+ *   The descriptor: L stacked cells of H units (1 <= L <= 4, H one of 32, 64, 128, 256; layer k: W_ih [4H][in_k] with row stride ldwi >= in_k,
+ *     in_0 = d_in (1 <= d_in <= 1024) and in_k = H above, W_hh [4H][H] with row stride ldwh >= H, b_hh [4H]; gate rows i | f | g | o), the
+ *     projection Wp [2A][H] with row stride ldwp whose first A rows are loc (1 <= A <= 64; only they are read), bp, and the differentiated input
+ *     columns [wrt_col0, wrt_col0 + wrt_cols), 1 <= wrt_cols <= 128 inside d_in.
+ *   tmjx_lstm_jacobian_workspace: *floats = the scratch a call with this descriptor and m rows takes (it stops growing at 1024 rows).
+ *   tmjx_lstm_decoder_jacobian: x [n][d_in] (row stride ldx); h_in, c_in [n][L H] (row stride ld_carry >= L H): the carry ENTERING the step, layer k
+ *     in the columns [k H, (k + 1) H); row_index, m, mode, scale, ld_scale as in tmjx_decoder_jacobian (an index outside 0 .. n - 1 reads x and the
+ *     carry as zeros); carry_scale (optional) [2 L H]: one factor per carry column, the h columns then the c columns (null: ones).  Forward per
+ *     row: x_0 = the row; pre = (W_ih[k] x_k + b_hh[k]) + W_hh[k] h_k (each product the chain fmaf from 0 in ascending index), c'_k = sig(f) c_k +
+ *     sig(i) tanh(g), h'_k = sig(o) tanh(c'_k), x_{k+1} = h'_k; loc = Wp[:A] h'_{L-1} + bp[:A].  Reverse for the A rows at once: G = diag(1 -
+ *     ctrl^2) Wp[:A] (mode 1: Wp[:A]); per layer from the top, Gc = Gh sig(o) (1 - tanh(c')^2), D = [Gc tanh(g) sig'(i) | Gc c_k sig'(f) | Gc sig(i)
+ *     (1 - tanh(g)^2) | Gh tanh(c') sig'(o)], d / d c_k = Gc sig(f), d / d h_k = D W_hh[k], d / d x_k = D W_ih[k] (the next Gh; at k = 0 over the
+ *     wrt columns only).  Outputs, each optional by null except sums: ctrl_out, jac, gain, col2, row2, action_var with the meaning they have in
+ *     tmjx_decoder_jacobian; carry_jac [m][A][2 L H]: the h blocks of every layer, then the c blocks, unscaled; carry_gain [m][2 L]: the squared
+ *     Frobenius norm of each layer's block of carry_jac diag(carry_scale), the h layers then the c layers; sums: device float64 [A wrt_cols |
+ *     wrt_cols^2 | A^2 | A 2 L H] = the sums over the m rows of J, J^T J, J J^T and carry_jac (across rows float64: groups of 32 rows in row order,
+ *     the groups in order).  The bits of the input-side outputs do not depend on which carry outputs are asked for.
+ * Each returns TMJX_EINVAL before any launch, with a message that names the value, for a limit above exceeded, a null required pointer, ldx < d_in,
+ * ld_carry < L H, a weight stride below its width, ld_scale < wrt_cols, m < 1, n < 1, m > n without row_index, a mode outside 0 .. 1, action_var
+ * without scale, a workspace that is not 16-byte aligned, or a misaligned array. */
+#define TMJX_LSTM_JACOBIAN_MAX_LAYERS 4
+typedef struct { const float *W_ih, *W_hh, *b_hh; int32_t ldwi, ldwh; } tmjx_lstm_jacobian_layer_t;
+typedef struct {
+  int32_t L, H, d_in, A;
+  tmjx_lstm_jacobian_layer_t layer[TMJX_LSTM_JACOBIAN_MAX_LAYERS];
+  const float *Wp, *bp;
+  int32_t ldwp, wrt_col0, wrt_cols, pad_;
+} tmjx_lstm_jacobian_desc_t;
+int tmjx_lstm_jacobian_workspace(const tmjx_lstm_jacobian_desc_t *desc, int m, int64_t *floats);
+int tmjx_lstm_decoder_jacobian(const tmjx_lstm_jacobian_desc_t *desc, const float *x, int n, int64_t ldx, const float *h_in, const float *c_in, int64_t ld_carry,
+                               const int32_t *row_index, int m, const float *scale, int64_t ld_scale, const float *carry_scale, int mode, float *ctrl_out,
+                               float *jac, float *gain, float *col2, float *row2, float *action_var, float *carry_jac, float *carry_gain, double *sums,
+                               float *workspace, void *stream);
+
 /* ---- Morlet wavelet spectrograms of recorded signals x [n][C] (1 <= C <= 1024) at 1 <= F <= 64 centre frequencies (csrc/tmjx_spectrogram.hip,
  * csrc/spectrogram_core.h; DESIGN.md "Spectrogram").  The conventions of tmjx_hmm_*: no model handle; all device memory is the caller's; everything
  * runs on the caller's stream; x is float32 and may be a column slice of a wider buffer (ldx >= C); the rows form S sequences given by

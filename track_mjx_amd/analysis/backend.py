@@ -1,5 +1,5 @@
 """The analysis entry points of the C-ABI (include/tmjx.h: tmjx_pca_*, tmjx_plot_strips, tmjx_readout_*, tmjx_kmeans_*, tmjx_hmm_*, tmjx_arhmm_*,
-tmjx_wavelet_bank*, tmjx_spectrogram*, tmjx_knn, tmjx_tsne_*, tmjx_cka_linear, tmjx_rdm_corr, tmjx_cca, tmjx_compare_svd, tmjx_decoder_jacobian) as methods on
+tmjx_wavelet_bank*, tmjx_spectrogram*, tmjx_knn, tmjx_tsne_*, tmjx_cka_linear, tmjx_rdm_corr, tmjx_cca, tmjx_compare_svd, tmjx_decoder_jacobian, tmjx_lstm_decoder_jacobian) as methods on
 arrays.
 
 `Backend` marshals every call once, against a small provider of arrays: what differs between the device and a host is how an array is uploaded,
@@ -466,6 +466,62 @@ class Backend:
         res = {k: p.to_numpy(v) for k, v in out.items()}
         s = p.to_numpy(sums)
         res["mean_sum"], res["gram_in"], res["gram_out"] = s[:A * cols].reshape(A, cols), s[A * cols:A * cols + cols * cols].reshape(cols, cols), s[A * cols + cols * cols:].reshape(A, A)
+        return res
+
+    # the LSTM decoder's Jacobian (analysis/jacobian.py; tmjx_lstm_jacobian_workspace, tmjx_lstm_decoder_jacobian): x, h_in, c_in from asarray
+    def lstm_decoder_jacobian(self, x, h_in, c_in, layers, head, wrt, row_index=None, scale=None, carry_scale=None, mode=0,
+                              want=("ctrl", "jac", "gain", "col2", "row2", "carry_jac", "carry_gain")):
+        """The Jacobian of one step of the stacked-LSTM decoder, ctrl = tanh(loc) (mode 0) or loc (mode 1), with respect to the columns wrt = (col0, cols)
+        of the rows of x [n, d_in] and to the carry h_in, c_in [n, L H] entering the step (layer k in the columns [k H, (k + 1) H)).  layers:
+        [(W_ih [4H, in_k], W_hh [4H, H], b_hh [4H])]; head: (Wp [>= A, H], bp, A); row_index, scale, mode as in decoder_jacobian; carry_scale: numpy
+        [2 L H], one factor per carry column (h then c) for carry_gain.  -> the dict of decoder_jacobian plus those of `want` among carry_jac
+        [m, A, 2 L H] (the h blocks of every layer, then the c blocks) and carry_gain [m, 2 L], and the float64 carry_sum [A, 2 L H]."""
+        p = self._p
+        n, d_in = x.shape
+        (col0, cols), (wp, bp, A) = (int(v) for v in wrt), head
+        L, H = len(layers), int(layers[0][1].shape[1]) if len(layers) else 0
+        if not 1 <= L <= _hip.LSTM_JACOBIAN_MAX_LAYERS:
+            raise ValueError(f"{L} LSTM layers: the Jacobian takes 1 to {_hip.LSTM_JACOBIAN_MAX_LAYERS}")
+        for name, a in (("h_in", h_in), ("c_in", c_in)):
+            if tuple(a.shape) != (n, L * H):
+                raise ValueError(f"{name} has shape {tuple(a.shape)}: expected the carry entering every row of x, [{n}, {L * H}]")
+        if p.ld(h_in) != p.ld(c_in):
+            raise ValueError(f"h_in and c_in have the row strides {p.ld(h_in)} and {p.ld(c_in)}: the call takes one")
+        desc, keep = _hip.LstmJacobianDesc(), []
+
+        def up(a):
+            keep.append(p.upload(a, f32))
+            return keep[-1]
+        desc.L, desc.H, desc.d_in, desc.A, desc.wrt_col0, desc.wrt_cols = L, H, d_in, int(A), col0, cols
+        for k, (slot, (w_ih, w_hh, b_hh)) in enumerate(zip(desc.layer, layers)):
+            if tuple(w_hh.shape) != (4 * H, H) or tuple(w_ih.shape) != (4 * H, d_in if k == 0 else H) or tuple(b_hh.shape) != (4 * H,):
+                raise ValueError(f"LSTM layer {k}: W_ih {tuple(w_ih.shape)}, W_hh {tuple(w_hh.shape)}, b_hh {tuple(b_hh.shape)} are not those of {H} units behind "
+                                 f"{d_in if k == 0 else H} inputs")
+            wi, wh = up(w_ih), up(w_hh)
+            slot.W_ih, slot.W_hh, slot.b_hh, slot.ldwi, slot.ldwh = p.ptr(wi), p.ptr(wh), p.ptr(up(b_hh)), p.ld(wi), p.ld(wh)
+        w = up(wp)
+        desc.Wp, desc.bp, desc.ldwp = p.ptr(w), p.ptr(up(bp)), p.ld(w)
+        idx = None if row_index is None else p.upload(row_index, i32, copy=True)
+        cs = None if carry_scale is None else up(np.asarray(carry_scale).reshape(-1))
+        if cs is not None and cs.shape[0] != 2 * L * H:
+            raise ValueError(f"carry_scale holds {cs.shape[0]} factors: expected one per carry column, {2 * L * H}")
+        m = n if idx is None else int(idx.shape[0])
+        ws = self._workspace("tmjx_lstm_jacobian_workspace", C.byref(desc), m)
+        W = 2 * L * H
+        shapes = {"ctrl": (m, A), "jac": (m, A, cols), "gain": (m,), "col2": (m, cols), "row2": (m, A), "carry_jac": (m, A, W), "carry_gain": (m, 2 * L)}
+        out = {k: p.empty(shapes[k], f32) for k in shapes if k in want}
+        if scale is not None:
+            out["action_var"] = p.empty((m, A), f32)
+        E = A * cols + cols * cols + A * A
+        sums = p.empty((E + A * W,), f64)
+        arg = lambda k: p.ptr(out[k]) if k in out else None      # noqa: E731
+        self._call("tmjx_lstm_decoder_jacobian", C.byref(desc), p.ptr(x), n, p.ld(x), p.ptr(h_in), p.ptr(c_in), p.ld(h_in), None if idx is None else p.ptr(idx), m,
+                   None if scale is None else p.ptr(scale), 0 if scale is None else p.ld(scale), None if cs is None else p.ptr(cs), int(mode), arg("ctrl"), arg("jac"),
+                   arg("gain"), arg("col2"), arg("row2"), arg("action_var"), arg("carry_jac"), arg("carry_gain"), p.ptr(sums), p.ptr(ws), p.stream())
+        res = {k: p.to_numpy(v) for k, v in out.items()}
+        s = p.to_numpy(sums)
+        res["mean_sum"], res["gram_in"], res["gram_out"] = s[:A * cols].reshape(A, cols), s[A * cols:A * cols + cols * cols].reshape(cols, cols), s[A * cols + cols * cols:E].reshape(A, A)
+        res["carry_sum"] = s[E:].reshape(A, W)
         return res
 
     # the wavelet spectrogram (analysis/spectrogram.py; tmjx_wavelet_bank*, tmjx_spectrogram*): x from asarray, the bank as wavelet_bank returns it

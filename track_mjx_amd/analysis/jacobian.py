@@ -18,8 +18,21 @@ max_rows= evaluates a sorted random sample (the other rows of the per-clip serie
 adds motif_mean_jacobian [K, A, Z], motif_gram_in [K, Z, Z], motif_gain [K] and motif_rows [K]; store=true adds jacobian/clip_<i> [T-1, A, Z]
 (refused above 2^31 bytes); features_out= writes a directory of clip_<i>.h5 with activations/latent_sensitivity, activations/actuator_sensitivity,
 activations/jacobian_gain [T-1, 1] and the clip's meta, which analysis.cluster, hmm, pca, readout, spectrogram and embed take like a roll-out
-directory.  Limits: the MLP decoder only (a use_lstm checkpoint is refused: the recurrent decoder's Jacobian is not built), up to 8 blocks of up to
-1024 units, 64 actuators, 128 differentiated columns a call."""
+directory.
+
+A use_lstm checkpoint (the stacked-LSTM decoder; csrc/tmjx_lstm_jacobian.hip, DESIGN.md "LSTM decoder Jacobian") is taken the same way, on roll-outs
+made with `analysis.rollout ... log_activations=true log_decoder_input=true` (an LSTM roll-out records egocentric_obs only with that option; a
+replay_latents= directory records neither the carry nor the input and is refused).  The step is linearised at its recorded input row AND at the carry
+(h, c) entering it: the recorded hidden_state of row t - 1, zeros at t = 0 and behind a step whose `aligned` flag is set (the roll-out zeroes the
+carry of a re-aligned env).  Beyond the above it writes memory_sensitivity/clip_<i> [T-1, 2 L] (the squared Frobenius norm of d ctrl / d h_k, then
+of d ctrl / d c_k, per layer, each carry column scaled by its standard deviation over the evaluated rows: how much of the action comes from memory
+rather than from the current input, comparable with action_var), carry_std [2 L H] (that scale), mean_carry_jacobian [A, 2 L H] (the h blocks of
+every layer, then the c blocks), with labels= motif_mean_carry_jacobian [K, A, 2 L H] and motif_memory_sensitivity [K, 2 L], with store=true
+carry_jacobian/clip_<i> [T-1, A, 2 L H], with features_out= activations/memory_sensitivity, and hidden_state_size, hidden_layer_num; `model` says
+which decoder (mlp | lstm) the file is of.
+
+Limits: the MLP decoder up to 8 blocks of up to 1024 units, the LSTM decoder up to 4 layers of 32, 64, 128 or 256 units behind up to 1024 inputs; 64
+actuators, 128 differentiated columns a call; one time step (not the Jacobian of the new carry with respect to the old one)."""
 from __future__ import annotations
 
 import os
@@ -37,8 +50,14 @@ USAGE = ("usage: python -m track_mjx_amd.analysis.jacobian checkpoint=<run dir |
 MODES = {"ctrl": _hip.JACOBIAN_CTRL, "loc": _hip.JACOBIAN_LOC}
 MISMATCH_WARN = 1e-3
 STORE_MAX_BYTES = 2 ** 31
-LSTM_REFUSAL = ("the checkpoint holds an LSTM decoder (train_config.use_lstm): the Jacobian is built for the MLP decoder (Dense -> SiLU -> LayerNorm blocks) "
-                "only; the recurrent decoder's Jacobian is not built")
+LSTM_REFUSAL = ("the checkpoint holds an LSTM decoder (train_config.use_lstm): decoder_weights reads the MLP decoder (Dense -> SiLU -> LayerNorm blocks); "
+                "the LSTM decoder's weights come from lstm_decoder_weights")
+LSTM_NO_CARRY = ("the checkpoint holds an LSTM decoder and {where} has no activations/hidden_state: the recorded carry is missing; roll the LSTM checkpoint out "
+                 "with `analysis.rollout ... log_activations=true log_decoder_input=true`")
+LSTM_NO_INPUT = ("{where} has no activations/egocentric_obs: an LSTM roll-out records the decoder's input only with `analysis.rollout ... "
+                 "log_decoder_input=true`")
+LSTM_REPLAY = ("{where} is a replay_latents= roll-out: it records neither the LSTM decoder's carry nor its input, so the Jacobian cannot be placed at its "
+               "steps; use the roll-out the latents came from")
 
 
 def decoder_weights(source):
@@ -65,6 +84,101 @@ def decoder_weights(source):
     layers = [(num(b.dense.weight), num(b.dense.bias), num(b.norm.weight), num(b.norm.bias)) for b in blocks]
     wh, bh = num(net.head.weight), num(net.head.bias)
     return layers, (wh, bh, wh.shape[0] // 2), eps.pop()
+
+
+def is_lstm_decoder(source) -> bool:
+    net = getattr(source, "net", source)
+    return hasattr(net, "w_hh") and hasattr(net, "w_ih")
+
+
+def lstm_decoder_weights(source):
+    """-> (layers [(W_ih [4H, in_k], W_hh [4H, H], b_hh [4H])], (Wp [2A, H], bp, A)) as float32 numpy.  `source`: a use_lstm checkpoint (loaded as
+    agent.checkpoint.make_lstm_decoder_policy_fn loads it), an LSTMDecoderPolicy or an LSTMIntentionPolicy."""
+    if isinstance(source, (str, os.PathLike)):
+        from ..agent import checkpoint as ckpt
+        source = ckpt.make_lstm_decoder_policy_fn(source, device="cpu")
+    if not is_lstm_decoder(source):
+        raise ValueError(f"{type(source).__name__} has no LSTM decoder (w_ih, w_hh, b_hh and a projection)")
+    num = lambda t: np.ascontiguousarray(t.detach().cpu().numpy(), np.float32)      # noqa: E731
+    wp, bp = (source.w_p, source.b_p) if hasattr(source, "w_p") else (source.projection.weight, source.projection.bias)
+    layers = [(num(a), num(b), num(c)) for a, b, c in zip(source.w_ih, source.w_hh, source.b_hh)]
+    if not layers:
+        raise ValueError("the LSTM decoder has no layer")
+    wp = num(wp)
+    return layers, (wp, num(bp), wp.shape[0] // 2)
+
+
+def load_decoder(source):
+    """-> ("mlp", layers, head, eps) as decoder_weights gives them, or ("lstm", layers, head, None) as lstm_decoder_weights does: whichever decoder
+    the checkpoint (or the module, or the policy object) holds."""
+    if isinstance(source, (str, os.PathLike)):
+        from ..agent import checkpoint as ckpt
+        try:
+            source = ckpt.make_decoder_policy_fn(source, device="cpu")
+        except NotImplementedError:
+            source = ckpt.make_lstm_decoder_policy_fn(source, device="cpu")
+    if is_lstm_decoder(source):
+        return ("lstm", *lstm_decoder_weights(source), None)
+    return ("mlp", *decoder_weights(source))
+
+
+def _carry_of(r, where):
+    """(h, c) [T-1, L, H] of a roll-out's activations/hidden_state (written as the pair (h, c): members 0 and 1; a group h, c is taken too), or None."""
+    try:
+        node = r["activations"]["hidden_state"]
+    except (KeyError, IndexError, TypeError):
+        return None
+    out = []
+    for names in (("h", "0", 0), ("c", "1", 1)):
+        for k in names:
+            try:
+                v = node[k]
+            except (KeyError, IndexError, TypeError):
+                continue
+            out.append(np.asarray(v if isinstance(v, np.ndarray) else v[()], np.float32))
+            break
+    if len(out) != 2 or out[0].ndim != 3 or out[0].shape != out[1].shape:
+        raise ValueError(f"{where}: activations/hidden_state is not the pair (h, c) of [T-1, L, H] arrays")
+    return out[0], out[1]
+
+
+def _read_lstm_clip(r, clip, where):
+    """_read_clip for an LSTM roll-out, plus the carry ENTERING every step [T-1, L H] twice (h, c) and its (L, H): the recorded carry of the row
+    before, zeros at t = 0 and behind a step whose `aligned` flag is set."""
+    from .. import h5lite
+    from .spectrogram import _tree
+    if isinstance(r, h5lite.File):
+        meta = _tree(r["meta"]) if "meta" in r else None
+    else:
+        meta = r.get("meta") if hasattr(r, "get") else None
+    if meta is not None and "replay_latents" in meta:
+        raise ValueError(LSTM_REPLAY.format(where=where))
+    carry = _carry_of(r, where)
+    if carry is None:
+        raise ValueError(LSTM_NO_CARRY.format(where=where))
+    try:
+        _pca._feature_of(r, "egocentric_obs", where)
+    except KeyError:
+        raise ValueError(LSTM_NO_INPUT.format(where=where)) from None
+    x, Z, logvar, ctrl, meta = _read_clip(r, clip, where)
+    h, c = carry
+    T1, L, H = h.shape
+    if T1 != x.shape[0]:
+        raise ValueError(f"{where}: hidden_state has {T1} rows, intention {x.shape[0]}")
+    keep = np.ones(T1, bool)
+    keep[0] = False
+    try:
+        node = r["aligned"]
+        aligned = np.asarray(node if isinstance(node, np.ndarray) else node[()]).reshape(-1) != 0
+        if aligned.shape[0] != T1:
+            raise ValueError(f"{where}: aligned has {aligned.shape[0]} rows, intention {T1}")
+        keep[1:] &= ~aligned[:-1]
+    except (KeyError, IndexError, TypeError):
+        pass
+    h_in, c_in = np.zeros((T1, L * H), np.float32), np.zeros((T1, L * H), np.float32)
+    h_in[1:], c_in[1:] = h.reshape(T1, -1)[:-1], c.reshape(T1, -1)[:-1]
+    h_in[~keep], c_in[~keep] = 0.0, 0.0
+    return x, Z, logvar, ctrl, meta, h_in, c_in, (L, H)
 
 
 def _read_clip(r, clip, where):
@@ -131,14 +245,20 @@ def jacobian_rollouts(checkpoint, rollouts, wrt="intention", mode="ctrl", max_ro
     writes.  -> the dict the command line writes."""
     if mode not in MODES:
         raise ValueError(f"mode = {mode!r}: ctrl (through the tanh) or loc")
-    layers, head, eps = decoder_weights(checkpoint)
+    model, layers, head, eps = load_decoder(checkpoint)
+    lstm = model == "lstm"
     d_in, A = layers[0][0].shape[1], head[2]
-    ids, items = rollout_features(rollouts, _read_clip, "the decoder's input", "differentiate")
+    ids, items = rollout_features(rollouts, _read_lstm_clip if lstm else _read_clip, "the decoder's input", "differentiate")
     width = items[0][0].shape[1]
     if width != d_in:
         raise ValueError(f"the roll-outs' decoder input [intention | egocentric_obs] is {width} wide, the checkpoint's decoder takes {d_in}: "
                          "this checkpoint did not make these roll-outs")
     Z = items[0][1]
+    Lk, H = (len(layers), layers[0][1].shape[1]) if lstm else (0, 0)
+    W = 2 * Lk * H
+    if lstm and any(it[7] != (Lk, H) for it in items):
+        raise ValueError(f"the roll-outs' hidden_state is [T-1, L, H] with (L, H) = {sorted({it[7] for it in items})}, the checkpoint's decoder has "
+                         f"{Lk} layers of {H} units: this checkpoint did not make these roll-outs")
     col0, cols = _parse_wrt(wrt, Z, d_in)
     lens = [it[0].shape[0] for it in items]
     n = int(sum(lens))
@@ -154,7 +274,8 @@ def jacobian_rollouts(checkpoint, rollouts, wrt="intention", mode="ctrl", max_ro
     if max_rows < 0:
         raise ValueError(f"max_rows must be >= 0 (got {max_rows})")
     # a row that is not finite (a roll-out whose physics diverged is recorded to its end) is never evaluated: its series stay NaN
-    finite = np.flatnonzero(np.isfinite(x).all(1) & (np.isfinite(scale).all(1) if scale is not None else True))
+    carry = np.ascontiguousarray(np.concatenate([np.concatenate([it[5], it[6]], 1) for it in items], 0), np.float32) if lstm else None      # [n, h | c]
+    finite = np.flatnonzero(np.isfinite(x).all(1) & (np.isfinite(scale).all(1) if scale is not None else True) & (np.isfinite(carry).all(1) if lstm else True))
     if finite.shape[0] < 1:
         raise ValueError("no recorded step has a finite decoder input")
     sampled = 0 < max_rows < finite.shape[0]
@@ -168,14 +289,27 @@ def jacobian_rollouts(checkpoint, rollouts, wrt="intention", mode="ctrl", max_ro
     m = n if index is None else int(index.shape[0])
     if store and m * A * cols * 4 > STORE_MAX_BYTES:
         raise ValueError(f"store=true: {m} rows x {A} x {cols} float32 exceed 2^31 bytes; sample with max_rows= or differentiate fewer columns")
+    if store and lstm and m * A * W * 4 > STORE_MAX_BYTES:
+        raise ValueError(f"store=true: {m} rows x {A} x {W} float32 of the carry Jacobian exceed 2^31 bytes; sample with max_rows=")
     bk = _pca.HipBackend(device) if backend is None else backend
     xa, sa = bk.asarray(x), None if scale is None else bk.asarray(scale)
     want = ("ctrl", "gain", "col2", "row2") + (("jac",) if store else ())
+    rows = np.arange(n) if index is None else index.astype(np.int64)
+    if lstm:
+        # the scale of the memory's sensitivity: the standard deviation of every carry column over the evaluated rows
+        carry_std = carry[rows].astype(np.float64).std(0).astype(np.float32)
+        ha, ca = bk.asarray(carry[:, :W // 2]), bk.asarray(carry[:, W // 2:])
+        want = want + ("carry_gain",) + (("carry_jac",) if store else ())
+
+        def evaluate(idx, sc, wanted):
+            return bk.lstm_decoder_jacobian(xa, ha, ca, layers, head, (col0, cols), idx, sc, carry_std, MODES[mode], wanted)
+    else:
+        def evaluate(idx, sc, wanted):
+            return bk.decoder_jacobian(xa, layers, head, (col0, cols), eps, idx, sc, MODES[mode], wanted)
     try:
-        res = bk.decoder_jacobian(xa, layers, head, (col0, cols), eps, index, sa, MODES[mode], want)
+        res = evaluate(index, sa, want)
     except _hip.TmjxError as e:
         raise ValueError(str(e)) from None
-    rows = np.arange(n) if index is None else index.astype(np.int64)
     ends = np.cumsum(lens)
 
     def per_clip(a):
@@ -187,6 +321,11 @@ def jacobian_rollouts(checkpoint, rollouts, wrt="intention", mode="ctrl", max_ro
         out["action_var"] = per_clip(res["action_var"])
     if store:
         out["jacobian"] = per_clip(res["jac"])
+    if lstm:
+        out.update({"memory_sensitivity": per_clip(res["carry_gain"]), "carry_std": carry_std, "mean_carry_jacobian": res["carry_sum"] / m,
+                    "hidden_state_size": np.int64(H), "hidden_layer_num": np.int64(Lk)})
+        if store:
+            out["carry_jacobian"] = per_clip(res["carry_jac"])
     gram_in = res["gram_in"] / m
     values, vectors = eigen(gram_in, bk)
     total = float(values.sum())
@@ -196,7 +335,7 @@ def jacobian_rollouts(checkpoint, rollouts, wrt="intention", mode="ctrl", max_ro
                 "explained_variance": values.astype(np.float32),
                 "explained_variance_ratio": (values / total if total > 0.0 else np.zeros_like(values)).astype(np.float32),
                 "forward_mismatch": np.float64(np.abs(res["ctrl"].astype(np.float64) - recorded[rows]).max()) if recorded is not None else np.float64(np.nan),
-                "rows": np.int64(m), "wrt": f"{col0}:{col0 + cols}", "mode": mode, "clips": np.asarray(ids, np.int64)})
+                "rows": np.int64(m), "wrt": f"{col0}:{col0 + cols}", "mode": mode, "clips": np.asarray(ids, np.int64), "model": model})
     if index is not None:
         out["row_index"] = index.astype(np.int64)
     if labels is not None:
@@ -212,18 +351,25 @@ def jacobian_rollouts(checkpoint, rollouts, wrt="intention", mode="ctrl", max_ro
         picked = np.zeros(n, bool)
         picked[rows] = True
         mj, mg, gain, count = np.full((K, A, cols), np.nan), np.full((K, cols, cols), np.nan), np.full(K, np.nan), np.zeros(K, np.int64)
+        mcj, mms = np.full((K, A, W), np.nan), np.full((K, 2 * Lk), np.nan)
         for k in range(K):
             mine = np.flatnonzero((flat == k) & picked).astype(np.int32)
             count[k] = mine.shape[0]
             if mine.shape[0]:
-                r = bk.decoder_jacobian(xa, layers, head, (col0, cols), eps, mine, None, MODES[mode], ("gain",))
+                r = evaluate(mine, None, ("gain", "carry_gain") if lstm else ("gain",))
                 mj[k], mg[k], gain[k] = r["mean_sum"] / mine.shape[0], r["gram_in"] / mine.shape[0], float(r["gain"].astype(np.float64).mean())
+                if lstm:
+                    mcj[k], mms[k] = r["carry_sum"] / mine.shape[0], r["carry_gain"].astype(np.float64).mean(0)
         out.update({"motif_mean_jacobian": mj, "motif_gram_in": mg, "motif_gain": gain, "motif_rows": count})
+        if lstm:
+            out.update({"motif_mean_carry_jacobian": mcj, "motif_memory_sensitivity": mms})
     if features:
         out["features"] = {}
         for j, c in enumerate(ids):
             tree = {"activations": {"latent_sensitivity": out["latent_sensitivity"][f"clip_{c}"], "actuator_sensitivity": out["actuator_sensitivity"][f"clip_{c}"],
                                     "jacobian_gain": out["gain"][f"clip_{c}"].reshape(-1, 1)}}
+            if lstm:
+                tree["activations"]["memory_sensitivity"] = out["memory_sensitivity"][f"clip_{c}"]
             if items[j][4] is not None:
                 tree["meta"] = items[j][4]
             out["features"][c] = tree
@@ -238,7 +384,8 @@ def _flag(opts, name):
 
 
 def main(argv=None, backend=None, policy=None) -> int:
-    """The command line; `policy`: a module in place of checkpoint= (DecoderNet, IntentionPolicy), `backend`: a stand-in for HipBackend."""
+    """The command line; `policy`: a module or policy object in place of checkpoint= (DecoderNet, IntentionPolicy, DecoderPolicy; LSTMIntentionPolicy,
+    LSTMDecoderPolicy), `backend`: a stand-in for HipBackend."""
     from .. import h5lite
     argv = list(sys.argv[1:] if argv is None else argv)
     opts = dict(a.split("=", 1) for a in argv if "=" in a and a.split("=", 1)[0] in CLI_OPTIONS)
@@ -267,6 +414,11 @@ def main(argv=None, backend=None, policy=None) -> int:
     print(f"[jacobian] d {res['mode']} / d input[{res['wrt']}]: {int(res['rows'])} rows of {len(res['clips'])} clips, {res['mean_jacobian'].shape[0]} actuators; "
           f"mean gain {float(np.trace(res['gram_in'])):.4g}, the leading sensitive directions carry {ratio}; forward mismatch {mismatch:.3g}; wrote {opts['out']}",
           flush=True)
+    if res["model"] == "lstm":
+        mem = np.nanmean(np.concatenate(list(res["memory_sensitivity"].values()), 0), 0)
+        L = int(res["hidden_layer_num"])
+        print(f"[jacobian] LSTM decoder, {L} layers of {int(res['hidden_state_size'])} units: mean memory sensitivity per layer, d ctrl / d h "
+              f"{', '.join(f'{v:.4g}' for v in mem[:L])}; d ctrl / d c {', '.join(f'{v:.4g}' for v in mem[L:])} (carry columns scaled by carry_std)", flush=True)
     return 0
 
 

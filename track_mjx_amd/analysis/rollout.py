@@ -31,8 +31,10 @@ zeroed where an alignment happened (tmjx_lstm_seq_fwd's reset flags = the env's 
 they were.
 
 CLI:  python -m track_mjx_amd.analysis.rollout checkpoint=<run dir | step dir> [data_path=...] [clips=all|a:b|i,j,k] [seed=42] [out=<dir>]
-      [log_activations=true] [log_metrics=true] [log_sensor_data=false] [align_on_fail=false]
+      [log_activations=true] [log_metrics=true] [log_sensor_data=false] [log_decoder_input=false] [align_on_fail=false]
       ->  <out>/clip_<idx>.h5 (save_to_h5py layout + a `meta` group)
+      log_decoder_input=true: an LSTM roll-out also records activations/egocentric_obs, the normalised proprioceptive columns of the decoder's input
+      row (an MLP roll-out always does), which analysis.jacobian needs to place the LSTM decoder's Jacobian at the recorded steps.
       replay_latents=<dir of clip_<i>.h5> [latent_scale=1.0] [path=auto|fused|layers]: instead of running the encoder, re-run the clips of those files
       through a HighLevelWrapper env (environment/wrappers.py: the checkpoint's decoder inside the env) fed their recorded activations/intention
       (times latent_scale), and write the same clip_<i>.h5 layout (activations: the intention that was fed).
@@ -140,8 +142,10 @@ class _PolicyStep:
     buffer obs_soa [W][n]."""
 
     def __init__(self, rp: RolloutPolicy, n: int, obs_soa: torch.Tensor, record: bool = True, carry_reset: torch.Tensor | None = None,
-                 intervention=None, gates=None):
+                 intervention=None, gates=None, decoder_input: bool = False):
         """`carry_reset` [n] float32 (LSTM policy): where it is non-zero when the step is launched, the row's (h, c) are zeroed first.
+        `decoder_input` (LSTM policy): the normalised proprioceptive columns of the decoder's input row are an activation, egocentric_obs, as they
+        always are for the MLP policy.
         `intervention` (analysis.intervene.Intervention) with `gates` = (window [n, 2], dose [n]): one tmjx_intervene call directly behind the
         launch that produces its target; without one the list is what it always was."""
         pol, dev = rp.policy, rp.device
@@ -184,6 +188,8 @@ class _PolicyStep:
             _, self.logits, self.ctrl, self.action_t = ll.decoder(self.x, (), pol.projection.weight, pol.projection.bias,
                                                                   lstm=(pol.w_ih, pol.w_hh, pol.b_hh, self.h, self.c, carry_reset))
             self.acts["decoder"] = {"lstm_projection": (self.logits, 0, 2 * A, 2 * A)}
+            if decoder_input:
+                self.acts["egocentric_obs"] = (self.x, Z, prop, self.x.shape[1])
         else:
             ys, self.logits, self.ctrl, self.action_t = ll.decoder(self.x, pol.decoder, pol.head.weight, pol.head.bias)
             self.acts["decoder"] = {f"layer_{i}": (y, 0, y.shape[1], y.shape[1]) for i, y in enumerate(ys)}
@@ -235,7 +241,7 @@ def _upload_table(streams: Sequence, n: int, T: int, dev) -> torch.Tensor:
 def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, model: str = "mlp", log_activations: bool = False,
                              log_metrics: bool = False, log_sensor_data: bool = False, clips_per_batch: int = CLIPS_PER_BATCH,
                              align_on_fail: bool = False, friction_scale=None, actuator_scale=None, damping_scale=None,
-                             gravity_scale=None, slope_deg=None, intervention=None):
+                             gravity_scale=None, slope_deg=None, intervention=None, log_decoder_input: bool = False):
     """rollout.py:73-269.  Returns generate_rollout(clip_idx=None, seed=42): one clip (int / None) -> dict of arrays; a sequence of clips -> the
     same dict with a leading [N] axis (batches larger than `clips_per_batch` run in chunks).
 
@@ -251,7 +257,11 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
     the one that produces the target); its window and dose are one value, or one per clip of a generate_rollout call (a clip may be repeated in
     clip_idx with different doses).  The result gains the group `intervention` (target, mode, directions | units, center, gain, offset, window [2],
     dose and, in subspace mode, projection [T - 1, K]: the pre-edit coordinates of every step, ON or OFF), and the recorded activation of the
-    target is its value after the edit."""
+    target is its value after the edit.
+
+    `log_decoder_input`: with log_activations, an LSTM roll-out also records activations/egocentric_obs [T - 1, prop], the normalised proprioceptive
+    columns of the decoder's input row, which an MLP roll-out always records (analysis.jacobian places the LSTM decoder's Jacobian there).  On an
+    MLP policy it changes nothing."""
     if intervention is not None:
         from .intervene import Intervention
         if not isinstance(intervention, Intervention):
@@ -361,7 +371,7 @@ def create_rollout_generator(cfg: dict, environment, inference_fn: Callable, mod
                       qpos_noise=torch.from_numpy(qn), qvel_noise=torch.from_numpy(vn))
             # align_on_fail: the LSTM carry of an env is zeroed in the policy step that follows its alignment (done_buf is 0 after reset)
             step = _PolicyStep(inference_fn, n, env.obs_buf, carry_reset=env.done_buf if align_on_fail and inference_fn.model == "lstm" else None,
-                               intervention=intervention, gates=gates)
+                               intervention=intervention, gates=gates, decoder_input=bool(log_decoder_input))
             f32 = dict(dtype=torch.float32, device=dev)
             rec: dict = {}
             state_streams, step_streams = [], []
@@ -546,7 +556,7 @@ def _parse_clips(spec: str, n_clips: int) -> list:
     return [int(c) for c in spec.split(",") if c.strip()]
 
 
-CLI_OPTIONS = ("checkpoint", "clips", "seed", "out", "log_activations", "log_metrics", "log_sensor_data", "align_on_fail", "step",
+CLI_OPTIONS = ("checkpoint", "clips", "seed", "out", "log_activations", "log_metrics", "log_sensor_data", "log_decoder_input", "align_on_fail", "step",
                "replay_latents", "latent_scale", "path", "friction_scale", "actuator_scale", "damping_scale", "gravity_scale", "slope_deg",
                "intervene_pca", "intervene_components", "intervene_readout", "intervene_centroids", "intervene_columns", "intervene_units", "intervene_mean", "intervene_gain",
                "intervene_offset", "intervene_window", "intervene_dose")
@@ -680,7 +690,7 @@ def main(argv=None) -> int:
     opts, rest = _split_argv(argv)
     if "checkpoint" not in opts:
         print("usage: python -m track_mjx_amd.analysis.rollout checkpoint=<run dir | step dir> [data_path=...] [clips=all|a:b|i,j,k] [seed=42] "
-              "[out=<dir>] [log_activations=true] [log_metrics=true] [log_sensor_data=false] [align_on_fail=false] "
+              "[out=<dir>] [log_activations=true] [log_metrics=true] [log_sensor_data=false] [log_decoder_input=false] [align_on_fail=false] "
               "[friction_scale=<s | s0,s1,..>] [actuator_scale=..] [damping_scale=..] [gravity_scale=<s | s0,s1,..>] [slope_deg=<a | a0,a1,..>] "
               "[replay_latents=<dir of clip_<i>.h5> [latent_scale=1.0] [path=auto|fused|layers]] "
               "[intervene_pca=<pca.h5> [intervene_components=a:b] | intervene_readout=<readout.h5> [intervene_columns=a:b] | intervene_centroids=<clusters.h5> [intervene_columns=a:b] | "
@@ -726,6 +736,7 @@ def main(argv=None) -> int:
     log_act, log_met = yes(opts.get("log_activations", "true")), yes(opts.get("log_metrics", "true"))
     log_sens = yes(opts.get("log_sensor_data", "false"))
     align = yes(opts.get("align_on_fail", "false"))
+    log_dec_in = yes(opts.get("log_decoder_input", "false"))
     clips = _parse_clips(opts.get("clips", "all"), env._n_clips)
 
     def scale_opt(name):          # one float, or a comma list with one value per clip
@@ -745,7 +756,8 @@ def main(argv=None) -> int:
             return 2
     gen = create_rollout_generator(cfg, env, fn, model=fn.model, log_activations=log_act, log_metrics=log_met, log_sensor_data=log_sens,
                                    align_on_fail=align, **{k: (None if v is None else 1.0) for k, v in scale_lists.items()},
-                                   **{k: (1.0 if k == "gravity_scale" else 0.0) for k in gravity_lists}, intervention=intervention)
+                                   **{k: (1.0 if k == "gravity_scale" else 0.0) for k in gravity_lists}, intervention=intervention,
+                                   log_decoder_input=log_dec_in)
     print(f"[rollout] done-policy: {gen.done_policy}" + (" (a done env is re-aligned to the clip frame it has reached; `aligned` / `n_alignments` "
                                                         "are recorded)" if align else " (the env keeps stepping after done)"), flush=True)
     out_dir = opts.get("out", os.path.join(step_dir, "rollouts"))

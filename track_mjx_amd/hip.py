@@ -15,12 +15,13 @@ _PKG = Path(__file__).resolve().parent
 SO_PATH = Path(os.environ.get("TMJX_SO", str(_PKG / "libtmjx_hip.so")))  # TMJX_SO: alternative build (profiling)
 CSRC = _PKG / "csrc"
 SOURCES = (CSRC / "tmjx_hip.hip", CSRC / "tmjx_bf16.hip", CSRC / "tmjx_wave.hip", CSRC / "tmjx_chain.hip", CSRC / "tmjx_lstm.hip",
-           CSRC / "tmjx_rollout.hip", CSRC / "tmjx_wave_sensors.hip", CSRC / "tmjx_wave_align.hip", CSRC / "tmjx_wave_rand.hip", CSRC / "tmjx_render.hip", CSRC / "tmjx_act.hip", CSRC / "tmjx_pca.hip", CSRC / "tmjx_pca_wide.hip", CSRC / "tmjx_readout.hip", CSRC / "tmjx_intervene.hip", CSRC / "tmjx_kmeans.hip", CSRC / "tmjx_hmm.hip", CSRC / "tmjx_spectrogram.hip", CSRC / "tmjx_arhmm.hip", CSRC / "tmjx_tsne.hip", CSRC / "tmjx_compare.hip", CSRC / "tmjx_jacobian.hip")
+           CSRC / "tmjx_rollout.hip", CSRC / "tmjx_wave_sensors.hip", CSRC / "tmjx_wave_align.hip", CSRC / "tmjx_wave_rand.hip", CSRC / "tmjx_render.hip", CSRC / "tmjx_act.hip", CSRC / "tmjx_pca.hip", CSRC / "tmjx_pca_wide.hip", CSRC / "tmjx_readout.hip", CSRC / "tmjx_intervene.hip", CSRC / "tmjx_kmeans.hip", CSRC / "tmjx_hmm.hip", CSRC / "tmjx_spectrogram.hip", CSRC / "tmjx_arhmm.hip", CSRC / "tmjx_tsne.hip", CSRC / "tmjx_compare.hip", CSRC / "tmjx_jacobian.hip", CSRC / "tmjx_lstm_jacobian.hip")
 # per-source compiler flags: the physics kernel's unit is built without machine LICM (csrc/tmjx_wave.hip says why)
 SOURCE_FLAGS = {"tmjx_wave.hip": ("-mllvm", "-disable-machine-licm"),
                 "tmjx_wave_sensors.hip": ("-mllvm", "-disable-machine-licm"),      # (the recording kernel: the same loop body)
                 "tmjx_wave_rand.hip": ("-mllvm", "-disable-machine-licm"),         # (the domain-randomisation kernel: likewise)
-                "tmjx_jacobian.hip": ("-ffp-contract=off",)}      # (the Jacobian states its order: only the fmaf it writes is fused, as on the host)
+                "tmjx_jacobian.hip": ("-ffp-contract=off",),      # (the Jacobian states its order: only the fmaf it writes is fused, as on the host)
+                "tmjx_lstm_jacobian.hip": ("-ffp-contract=off",)}      # (the LSTM decoder's likewise)
 
 
 class TmjxError(RuntimeError):
@@ -237,6 +238,20 @@ class JacobianDesc(C.Structure):
                 ("bh", C.c_void_p), ("ldwh", C.c_int32), ("wrt_col0", C.c_int32), ("wrt_cols", C.c_int32), ("pad_", C.c_int32)]
 
 
+LSTM_JACOBIAN_MAX_LAYERS, LSTM_JACOBIAN_MAX_DIN = 4, 1024      # csrc/lstm_jacobian_core.h (H: agent.lstm.LSTM_HIDDEN_SIZES; A, wrt, the pass: the MLP's)
+
+
+class LstmJacobianLayer(C.Structure):
+    """tmjx_lstm_jacobian_layer_t (include/tmjx.h)."""
+    _fields_ = [(k, C.c_void_p) for k in ("W_ih", "W_hh", "b_hh")] + [("ldwi", C.c_int32), ("ldwh", C.c_int32)]
+
+
+class LstmJacobianDesc(C.Structure):
+    """tmjx_lstm_jacobian_desc_t (include/tmjx.h)."""
+    _fields_ = [("L", C.c_int32), ("H", C.c_int32), ("d_in", C.c_int32), ("A", C.c_int32), ("layer", LstmJacobianLayer * LSTM_JACOBIAN_MAX_LAYERS), ("Wp", C.c_void_p),
+                ("bp", C.c_void_p), ("ldwp", C.c_int32), ("wrt_col0", C.c_int32), ("wrt_cols", C.c_int32), ("pad_", C.c_int32)]
+
+
 INTERVENE_SUBSPACE, INTERVENE_UNITS, INTERVENE_MAX_W, INTERVENE_MAX_K = 0, 1, 1024, 16      # include/tmjx.h, csrc/intervene_core.h
 
 
@@ -430,6 +445,8 @@ SIGNATURES = {
     "tmjx_compare_svd": ([_vp, _i, _i, _i64, _vp, _vp, _vp, _P(_i), _vp, _vp], _i),
     "tmjx_jacobian_workspace": ([_P(JacobianDesc), _i, _P(_i64)], _i),
     "tmjx_decoder_jacobian": ([_P(JacobianDesc), _vp, _i, _i64, _vp, _i, _vp, _i64, _i] + [_vp] * 9, _i),
+    "tmjx_lstm_jacobian_workspace": ([_P(LstmJacobianDesc), _i, _P(_i64)], _i),
+    "tmjx_lstm_decoder_jacobian": ([_P(LstmJacobianDesc), _vp, _i, _i64, _vp, _vp, _i64, _vp, _i, _vp, _i64, _vp, _i] + [_vp] * 11, _i),
     "tmjx_wavelet_bank_size": ([_d, _P(_d), _i, _d, _d, _P(_i64)], _i),
     "tmjx_wavelet_bank": ([_d, _P(_d), _i, _d, _d, _vp, _P(_i), _P(_i)], _i),
     "tmjx_spectrogram_workspace": ([_i] * 4 + [_P(_i64)], _i),
