@@ -1164,6 +1164,46 @@ int tmjx_lstm_decoder_jacobian(const tmjx_lstm_jacobian_desc_t *desc, const floa
                                float *jac, float *gain, float *col2, float *row2, float *action_var, float *carry_jac, float *carry_gain, double *sums,
                                float *workspace, void *stream);
 
+/* ---- The LSTM decoder's recurrent dynamics at recorded steps: the carry-to-carry map J_t = d (h', c') / d (h, c) of one step of the stacked-LSTM
+ * decoder, applied to tangent rows, and the Lyapunov spectrum of its product along recorded sequences (csrc/tmjx_lstm_tangent.hip,
+ * csrc/lstm_tangent_core.h; DESIGN.md "LSTM decoder dynamics").  The conventions of tmjx_lstm_decoder_jacobian: no model handle; all device memory
+ * is the caller's; everything runs on the caller's stream; fixed-order float32 chains (a product: fmaf from 0 in ascending index), no atomics: the
+ * same bits on every run.  The descriptor is tmjx_lstm_jacobian_desc_t with the same limits on L, H, d_in and the layers; Wp, bp, ldwp, A and the
+ * wrt columns are not read.  The input row is held as recorded: these are the CONDITIONAL dynamics of the decoder driven by its recorded input.
+ *   The carry space has W = 2 L H columns: the h blocks of every layer, then the c blocks (the layout of carry_jac).  A tangent is a row [W].
+ *   The tangent map at a row (x, h, c), for a tangent (dh_k, dc_k per layer): the forward is tmjx_lstm_decoder_jacobian's, with gi, gf, gg, go the
+ *     gates, tc = tanh(c'), and per unit ka = go (1 - tc^2), ki = gg gi (1 - gi), kf = c gf (1 - gf), kg = gi (1 - gg^2), ko = tc go (1 - go).  For
+ *     k = 0 .. L - 1:  dpre = W_ih[k] dh'_(k-1) + W_hh[k] dh_k (the input product first, the recurrent product added to it; at k = 0 the recurrent
+ *     product alone: dx_0 = 0);  dc'_k = fmaf(kg, dpre_g, fmaf(kf, dpre_f, fmaf(ki, dpre_i, gf dc_k)));  dh'_k = fmaf(ka, dc'_k, ko dpre_o).
+ *   tmjx_lstm_tangent_workspace: *floats = the scratch for S rows a step (the S sequences of tmjx_lstm_lyapunov; min(n, 1024) rows for
+ *     tmjx_lstm_tangent_step) and K tangents each.  It grows with S, K, H and L only, not with n.
+ *   tmjx_lstm_tangent_step: x [n][d_in] (row stride ldx); h_in, c_in [n][L H] (row stride ld_carry): the carry ENTERING the step; v [n][K][W]:
+ *     K tangents a row; out [n][K][W] = J_row v, row by row, in passes of 1024 rows.  The bits of a row depend neither on n nor on its place.
+ *   tmjx_lstm_lyapunov: the n rows form S sequences given by seq_start [S + 1] (HOST int32: seq_start[0] = 0, ascending, no empty sequence,
+ *     seq_start[S] = n; the host schedules by length, and the array must stay valid until the queued work has run); 1 <= K <= 32 tangents; q0
+ *     [q0_per_seq ? S : 1][K][W]: the first basis of every sequence (of all of them), meant to be orthonormal and not checked.  Per sequence
+ *     Q := q0; then for each of its rows t in order V = J_t Q, V = Q' R, Q := Q'.  The factorisation is modified Gram-Schmidt twice: two sweeps over
+ *     the columns j in order, in each  r = sqrtf(sum v_j^2),  q_j = v_j / r,  and for every later i:  v_i = fmaf(-(q_j . v_i), q_j, v_i); the dots
+ *     and norms are the chains of 256 threads over the elements tid, tid + 256, ... and a fixed tree; column j never reads a later column.
+ *     R_jj = r1 r2 and the local exponent is logf(r1) + logf(r2).  A column whose norm is not at least FLT_MIN in either sweep (zero, subnormal, not
+ *     a number) becomes a zero column and stays one: its local exponent is -inf from there on and the sequence's status is 1.  Outputs, each
+ *     optional by null except sums: local [n][K] = the local exponents at that row; energy [n][K][2 L] = the squared norm of each column of Q'
+ *     inside each layer's h block, then each c block; q_out [S][K][W] = the basis behind each sequence's last row; status int32 [S] (0: every
+ *     column alive); sums, device float64 [S][K]: per sequence the sum of `local` over its rows t >= warmup (t counted inside the sequence), in row
+ *     order, -inf counted as it is; the rows before are propagated and not summed.  The sequences advance in lockstep, ordered by descending
+ *     length inside the call only: a sequence's outputs have the same bits alone, among others and at any position of seq_start.
+ * Each returns TMJX_EINVAL before any launch, with a message that names the value, for L, H, d_in outside the descriptor's limits, K outside
+ * 1 .. 32, S < 1, S > 65536, n < 1, a seq_start that breaks the rules, warmup < 0, q0_per_seq outside 0 .. 1, ldx < d_in,
+ * ld_carry < L H, a weight stride below its width, a null required pointer, a workspace, v, out, q0 or q_out that is not 16-byte aligned, sums that
+ * is not 8-byte aligned, or another array that is not 4-byte aligned. */
+#define TMJX_LSTM_TANGENT_MAX_K 32
+int tmjx_lstm_tangent_workspace(const tmjx_lstm_jacobian_desc_t *desc, int S, int K, int64_t *floats);
+int tmjx_lstm_tangent_step(const tmjx_lstm_jacobian_desc_t *desc, const float *x, int n, int64_t ldx, const float *h_in, const float *c_in, int64_t ld_carry,
+                           const float *v, int K, float *out, float *workspace, void *stream);
+int tmjx_lstm_lyapunov(const tmjx_lstm_jacobian_desc_t *desc, const float *x, int n, int64_t ldx, const float *h_in, const float *c_in, int64_t ld_carry,
+                       const int32_t *seq_start, int S, const float *q0, int q0_per_seq, int K, int warmup, float *local, float *energy, float *q_out,
+                       int32_t *status, double *sums, float *workspace, void *stream);
+
 /* ---- Morlet wavelet spectrograms of recorded signals x [n][C] (1 <= C <= 1024) at 1 <= F <= 64 centre frequencies (csrc/tmjx_spectrogram.hip,
  * csrc/spectrogram_core.h; DESIGN.md "Spectrogram").  The conventions of tmjx_hmm_*: no model handle; all device memory is the caller's; everything
  * runs on the caller's stream; x is float32 and may be a column slice of a wider buffer (ldx >= C); the rows form S sequences given by

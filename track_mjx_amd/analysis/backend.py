@@ -1,5 +1,5 @@
 """The analysis entry points of the C-ABI (include/tmjx.h: tmjx_pca_*, tmjx_plot_strips, tmjx_readout_*, tmjx_kmeans_*, tmjx_hmm_*, tmjx_arhmm_*,
-tmjx_wavelet_bank*, tmjx_spectrogram*, tmjx_knn, tmjx_tsne_*, tmjx_cka_linear, tmjx_rdm_corr, tmjx_cca, tmjx_compare_svd, tmjx_decoder_jacobian, tmjx_lstm_decoder_jacobian) as methods on
+tmjx_wavelet_bank*, tmjx_spectrogram*, tmjx_knn, tmjx_tsne_*, tmjx_cka_linear, tmjx_rdm_corr, tmjx_cca, tmjx_compare_svd, tmjx_decoder_jacobian, tmjx_lstm_decoder_jacobian, tmjx_lstm_tangent_step, tmjx_lstm_lyapunov) as methods on
 arrays.
 
 `Backend` marshals every call once, against a small provider of arrays: what differs between the device and a host is how an array is uploaded,
@@ -493,12 +493,7 @@ class Backend:
             keep.append(p.upload(a, f32))
             return keep[-1]
         desc.L, desc.H, desc.d_in, desc.A, desc.wrt_col0, desc.wrt_cols = L, H, d_in, int(A), col0, cols
-        for k, (slot, (w_ih, w_hh, b_hh)) in enumerate(zip(desc.layer, layers)):
-            if tuple(w_hh.shape) != (4 * H, H) or tuple(w_ih.shape) != (4 * H, d_in if k == 0 else H) or tuple(b_hh.shape) != (4 * H,):
-                raise ValueError(f"LSTM layer {k}: W_ih {tuple(w_ih.shape)}, W_hh {tuple(w_hh.shape)}, b_hh {tuple(b_hh.shape)} are not those of {H} units behind "
-                                 f"{d_in if k == 0 else H} inputs")
-            wi, wh = up(w_ih), up(w_hh)
-            slot.W_ih, slot.W_hh, slot.b_hh, slot.ldwi, slot.ldwh = p.ptr(wi), p.ptr(wh), p.ptr(up(b_hh)), p.ld(wi), p.ld(wh)
+        self._lstm_cells(desc, layers, up)
         w = up(wp)
         desc.Wp, desc.bp, desc.ldwp = p.ptr(w), p.ptr(up(bp)), p.ld(w)
         idx = None if row_index is None else p.upload(row_index, i32, copy=True)
@@ -522,6 +517,81 @@ class Backend:
         s = p.to_numpy(sums)
         res["mean_sum"], res["gram_in"], res["gram_out"] = s[:A * cols].reshape(A, cols), s[A * cols:A * cols + cols * cols].reshape(cols, cols), s[A * cols + cols * cols:E].reshape(A, A)
         res["carry_sum"] = s[E:].reshape(A, W)
+        return res
+
+    def _lstm_cells(self, desc, layers, up):
+        """The cells of a tmjx_lstm_jacobian_desc_t (L, H, d_in set) from layers [(W_ih, W_hh, b_hh)], uploaded through `up`."""
+        p, H, d_in = self._p, desc.H, desc.d_in
+        for k, (slot, (w_ih, w_hh, b_hh)) in enumerate(zip(desc.layer, layers)):
+            if tuple(w_hh.shape) != (4 * H, H) or tuple(w_ih.shape) != (4 * H, d_in if k == 0 else H) or tuple(b_hh.shape) != (4 * H,):
+                raise ValueError(f"LSTM layer {k}: W_ih {tuple(w_ih.shape)}, W_hh {tuple(w_hh.shape)}, b_hh {tuple(b_hh.shape)} are not those of {H} units behind "
+                                 f"{d_in if k == 0 else H} inputs")
+            wi, wh = up(w_ih), up(w_hh)
+            slot.W_ih, slot.W_hh, slot.b_hh, slot.ldwi, slot.ldwh = p.ptr(wi), p.ptr(wh), p.ptr(up(b_hh)), p.ld(wi), p.ld(wh)
+
+    # the LSTM decoder's recurrent dynamics (analysis/dynamics.py; tmjx_lstm_tangent_workspace, tmjx_lstm_tangent_step, tmjx_lstm_lyapunov): x, h_in,
+    # c_in from asarray, the weights and the tangents float32 numpy.  The carry space has W = 2 L H columns: the h blocks of every layer, then the c blocks
+    def _lstm_dynamics(self, x, h_in, c_in, layers):
+        """-> (desc, keep, n, L, H, W) of a dynamics call: the descriptor's cells (no projection, no wrt columns) and the checks on the carry."""
+        p = self._p
+        n, d_in = x.shape
+        L, H = len(layers), int(layers[0][1].shape[1]) if len(layers) else 0
+        if not 1 <= L <= _hip.LSTM_JACOBIAN_MAX_LAYERS:
+            raise ValueError(f"{L} LSTM layers: the dynamics take 1 to {_hip.LSTM_JACOBIAN_MAX_LAYERS}")
+        for name, a in (("h_in", h_in), ("c_in", c_in)):
+            if tuple(a.shape) != (n, L * H):
+                raise ValueError(f"{name} has shape {tuple(a.shape)}: expected the carry entering every row of x, [{n}, {L * H}]")
+        if p.ld(h_in) != p.ld(c_in):
+            raise ValueError(f"h_in and c_in have the row strides {p.ld(h_in)} and {p.ld(c_in)}: the call takes one")
+        desc, keep = _hip.LstmJacobianDesc(), []
+
+        def up(a):
+            keep.append(p.upload(a, f32))
+            return keep[-1]
+        desc.L, desc.H, desc.d_in = L, H, d_in
+        self._lstm_cells(desc, layers, up)
+        return desc, keep, n, L, H, 2 * L * H
+
+    def lstm_tangent_step(self, x, h_in, c_in, layers, v):
+        """v [n, K, W] -> J_row v [n, K, W] float32 numpy: K tangents of the carry pushed through the carry-to-carry map d (h', c') / d (h, c) of one step
+        of the stacked-LSTM decoder at every row of x [n, d_in] with the carry h_in, c_in [n, L H] entering it; the input row is held as recorded
+        (tmjx_lstm_tangent_step)."""
+        p = self._p
+        desc, keep, n, L, H, W = self._lstm_dynamics(x, h_in, c_in, layers)
+        if np.ndim(v) != 3 or np.shape(v)[0] != n or np.shape(v)[2] != W:
+            raise ValueError(f"v has shape {tuple(np.shape(v))}: expected K tangents of the {W} carry columns for every row, [{n}, K, {W}]")
+        K = int(np.shape(v)[1])
+        vv, out = p.upload(v, f32, copy=True), p.empty((n, max(K, 1), W), f32)
+        ws = self._workspace("tmjx_lstm_tangent_workspace", C.byref(desc), min(n, _hip.JACOBIAN_CHUNK), K)
+        self._call("tmjx_lstm_tangent_step", C.byref(desc), p.ptr(x), n, p.ld(x), p.ptr(h_in), p.ptr(c_in), p.ld(h_in), p.ptr(vv), K, p.ptr(out), p.ptr(ws), p.stream())
+        return p.to_numpy(out)
+
+    def lstm_lyapunov(self, x, h_in, c_in, layers, seq_start, q0, warmup=0, want=("local", "energy", "q_out", "status")):
+        """The Lyapunov spectrum of the carry-to-carry map along the sequences seq_start int32 [S + 1] of the rows of x: per sequence Q = q0 ([K, W]: one
+        basis for all, or [S, K, W]), then at every row V = J_t Q, V = Q' R by modified Gram-Schmidt twice, Q = Q'.  -> a dict of numpy arrays: those of
+        `want` among local [n, K] (log R_jj at that row), energy [n, K, 2 L] (the squared norm of each column of Q' in each layer's h block, then c
+        block), q_out [S, K, W] (the basis behind each sequence's last row), status int32 [S] (1: a column died), and sums float64 [S, K]: the sum of
+        local over each sequence's rows from `warmup` on (tmjx_lstm_lyapunov)."""
+        p = self._p
+        desc, keep, n, L, H, W = self._lstm_dynamics(x, h_in, c_in, layers)
+        seq, seq_p, S = self._seq(seq_start)
+        q0 = np.asarray(q0)
+        if q0.ndim not in (2, 3) or q0.shape[-1] != W or (q0.ndim == 3 and q0.shape[0] != S):
+            raise ValueError(f"q0 has shape {tuple(q0.shape)}: expected one basis [K, {W}] or one a sequence [{S}, K, {W}]")
+        K = int(q0.shape[-2])
+        qq = p.upload(q0, f32, copy=True)
+        ws = self._workspace("tmjx_lstm_tangent_workspace", C.byref(desc), S, K)
+        shapes = {"local": ((n, K), f32), "energy": ((n, K, 2 * L), f32), "q_out": ((S, K, W), f32), "status": ((S,), i32)}
+        out = {k: p.empty(*shapes[k]) for k in shapes if k in want}
+        sums = p.empty((S, max(K, 1)), f64)
+        arg = lambda k: p.ptr(out[k]) if k in out else None      # noqa: E731
+        with p.guard():
+            p.check(p.lib.tmjx_lstm_lyapunov(C.byref(desc), p.ptr(x), n, p.ld(x), p.ptr(h_in), p.ptr(c_in), p.ld(h_in), seq_p, S, p.ptr(qq), int(q0.ndim == 3), K,
+                                             int(warmup), arg("local"), arg("energy"), arg("q_out"), arg("status"), p.ptr(sums), p.ptr(ws), p.stream()),
+                    "tmjx_lstm_lyapunov")
+            p.sync()      # (the host offsets must outlive the queued copy)
+        res = {k: p.to_numpy(v) for k, v in out.items()}
+        res["sums"] = p.to_numpy(sums)
         return res
 
     # the wavelet spectrogram (analysis/spectrogram.py; tmjx_wavelet_bank*, tmjx_spectrogram*): x from asarray, the bank as wavelet_bank returns it

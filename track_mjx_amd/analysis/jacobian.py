@@ -32,7 +32,8 @@ carry_jacobian/clip_<i> [T-1, A, 2 L H], with features_out= activations/memory_s
 which decoder (mlp | lstm) the file is of.
 
 Limits: the MLP decoder up to 8 blocks of up to 1024 units, the LSTM decoder up to 4 layers of 32, 64, 128 or 256 units behind up to 1024 inputs; 64
-actuators, 128 differentiated columns a call; one time step (not the Jacobian of the new carry with respect to the old one)."""
+actuators, 128 differentiated columns a call; one time step (the Jacobian of the new carry with respect to the old one, followed through time, is
+analysis.dynamics)."""
 from __future__ import annotations
 
 import os

@@ -15,13 +15,14 @@ _PKG = Path(__file__).resolve().parent
 SO_PATH = Path(os.environ.get("TMJX_SO", str(_PKG / "libtmjx_hip.so")))  # TMJX_SO: alternative build (profiling)
 CSRC = _PKG / "csrc"
 SOURCES = (CSRC / "tmjx_hip.hip", CSRC / "tmjx_bf16.hip", CSRC / "tmjx_wave.hip", CSRC / "tmjx_chain.hip", CSRC / "tmjx_lstm.hip",
-           CSRC / "tmjx_rollout.hip", CSRC / "tmjx_wave_sensors.hip", CSRC / "tmjx_wave_align.hip", CSRC / "tmjx_wave_rand.hip", CSRC / "tmjx_render.hip", CSRC / "tmjx_act.hip", CSRC / "tmjx_pca.hip", CSRC / "tmjx_pca_wide.hip", CSRC / "tmjx_readout.hip", CSRC / "tmjx_intervene.hip", CSRC / "tmjx_kmeans.hip", CSRC / "tmjx_hmm.hip", CSRC / "tmjx_spectrogram.hip", CSRC / "tmjx_arhmm.hip", CSRC / "tmjx_tsne.hip", CSRC / "tmjx_compare.hip", CSRC / "tmjx_jacobian.hip", CSRC / "tmjx_lstm_jacobian.hip")
+           CSRC / "tmjx_rollout.hip", CSRC / "tmjx_wave_sensors.hip", CSRC / "tmjx_wave_align.hip", CSRC / "tmjx_wave_rand.hip", CSRC / "tmjx_render.hip", CSRC / "tmjx_act.hip", CSRC / "tmjx_pca.hip", CSRC / "tmjx_pca_wide.hip", CSRC / "tmjx_readout.hip", CSRC / "tmjx_intervene.hip", CSRC / "tmjx_kmeans.hip", CSRC / "tmjx_hmm.hip", CSRC / "tmjx_spectrogram.hip", CSRC / "tmjx_arhmm.hip", CSRC / "tmjx_tsne.hip", CSRC / "tmjx_compare.hip", CSRC / "tmjx_jacobian.hip", CSRC / "tmjx_lstm_jacobian.hip", CSRC / "tmjx_lstm_tangent.hip")
 # per-source compiler flags: the physics kernel's unit is built without machine LICM (csrc/tmjx_wave.hip says why)
 SOURCE_FLAGS = {"tmjx_wave.hip": ("-mllvm", "-disable-machine-licm"),
                 "tmjx_wave_sensors.hip": ("-mllvm", "-disable-machine-licm"),      # (the recording kernel: the same loop body)
                 "tmjx_wave_rand.hip": ("-mllvm", "-disable-machine-licm"),         # (the domain-randomisation kernel: likewise)
                 "tmjx_jacobian.hip": ("-ffp-contract=off",),      # (the Jacobian states its order: only the fmaf it writes is fused, as on the host)
-                "tmjx_lstm_jacobian.hip": ("-ffp-contract=off",)}      # (the LSTM decoder's likewise)
+                "tmjx_lstm_jacobian.hip": ("-ffp-contract=off",),      # (the LSTM decoder's likewise)
+                "tmjx_lstm_tangent.hip": ("-ffp-contract=off",)}      # (and its recurrent dynamics)
 
 
 class TmjxError(RuntimeError):
@@ -239,6 +240,7 @@ class JacobianDesc(C.Structure):
 
 
 LSTM_JACOBIAN_MAX_LAYERS, LSTM_JACOBIAN_MAX_DIN = 4, 1024      # csrc/lstm_jacobian_core.h (H: agent.lstm.LSTM_HIDDEN_SIZES; A, wrt, the pass: the MLP's)
+LSTM_TANGENT_MAX_K = 32      # csrc/lstm_tangent_core.h: the tangents of a sequence (tmjx_lstm_tangent_step, tmjx_lstm_lyapunov)
 
 
 class LstmJacobianLayer(C.Structure):
@@ -447,6 +449,9 @@ SIGNATURES = {
     "tmjx_decoder_jacobian": ([_P(JacobianDesc), _vp, _i, _i64, _vp, _i, _vp, _i64, _i] + [_vp] * 9, _i),
     "tmjx_lstm_jacobian_workspace": ([_P(LstmJacobianDesc), _i, _P(_i64)], _i),
     "tmjx_lstm_decoder_jacobian": ([_P(LstmJacobianDesc), _vp, _i, _i64, _vp, _vp, _i64, _vp, _i, _vp, _i64, _vp, _i] + [_vp] * 11, _i),
+    "tmjx_lstm_tangent_workspace": ([_P(LstmJacobianDesc), _i, _i, _P(_i64)], _i),
+    "tmjx_lstm_tangent_step": ([_P(LstmJacobianDesc), _vp, _i, _i64, _vp, _vp, _i64, _vp, _i, _vp, _vp, _vp], _i),
+    "tmjx_lstm_lyapunov": ([_P(LstmJacobianDesc), _vp, _i, _i64, _vp, _vp, _i64, _P(_i), _i, _vp, _i, _i, _i] + [_vp] * 7, _i),
     "tmjx_wavelet_bank_size": ([_d, _P(_d), _i, _d, _d, _P(_i64)], _i),
     "tmjx_wavelet_bank": ([_d, _P(_d), _i, _d, _d, _vp, _P(_i), _P(_i)], _i),
     "tmjx_spectrogram_workspace": ([_i] * 4 + [_P(_i64)], _i),
