@@ -477,6 +477,7 @@ def check_tool(tmp_path, backend, capsys):
     from track_mjx_amd import h5lite
     from track_mjx_amd.analysis import jacobian as JT
     from track_mjx_amd.analysis import pca as PCA
+    from track_mjx_amd.analysis.recorded import feature_of
     from track_mjx_amd.analysis.utils import load_from_h5py
     tmp = str(tmp_path)
     n, A, Z = sum(TOOL_ROWS), 5, 6
@@ -500,7 +501,7 @@ def check_tool(tmp_path, backend, capsys):
     assert np.abs(f["gram_in"] @ comp.T - comp.T * ev).max() <= 1e-6 * ev[0] and abs(float(f["explained_variance_ratio"].sum()) - 1) < 1e-6
     # the stored Jacobians are the call's, and the means are theirs
     layers, head, eps = JT.decoder_weights(pol)
-    x = np.concatenate([np.concatenate([JT._pca._feature_of(r, k, "") for k in ("intention", "egocentric_obs")], 1)
+    x = np.concatenate([np.concatenate([feature_of(r, k, "") for k in ("intention", "egocentric_obs")], 1)
                         for r in (load_from_h5py(os.path.join(rollouts, f"clip_{c}.h5")) for c in range(3))], 0)
     direct = backend.decoder_jacobian(backend.asarray(x), layers, head, (0, Z), eps)
     stored = np.concatenate([f["jacobian"][f"clip_{c}"] for c in range(3)], 0)

@@ -62,6 +62,7 @@ def step():
     import torch
     from track_mjx_amd import hip
     from track_mjx_amd.analysis import embed as EM
+    from track_mjx_amd.analysis.pca import HipBackend
     Lb = hip.lib()
     print(f"# behaviour map: median of {REPEATS} repeats (min .. max); build {hip.build_id()}, {torch.cuda.get_device_name(0)}")
     dev = dict(device="cuda")
@@ -105,7 +106,7 @@ def step():
         torch.cuda.empty_cache()
 
     # ------------------------------------------------------------------ gradient and fit
-    b = EM._pca.HipBackend("cuda")
+    b = HipBackend("cuda")
     for n in FIT_NS:
         x = blobs(n, FIT_D, 300 + n)
         idx, dist2 = b.knn(x, None, FIT_K, exclude_self=True)

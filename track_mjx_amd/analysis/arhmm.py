@@ -19,16 +19,14 @@ descending modulus: whether the motif oscillates, and at what rate.
 """
 from __future__ import annotations
 
-import os
 import sys
 
 import numpy as np
 
 from .. import hip as _hip
-from . import cluster as _cluster
+from . import cli
 from . import hmm as _hmm
-from . import pca as _pca
-from .utils import rollout_features
+from .recorded import feature_of, rollout_features, seq_start, signals
 
 CLI_OPTIONS = ("rollouts", "out", "feature", "projections", "n_components", "k", "lags", "warmup", "ridge", "kappa", "prior", "seed", "n_init", "max_iter", "tol",
                "holdout", "rate", "posteriors")
@@ -82,7 +80,7 @@ class ARHMM(_hmm.GaussianHMM):
         b, k, L, R = self._b, self.n_states, self.lags, self.warmup
         xa = b.asarray(x)
         n, d = (int(v) for v in xa.shape)
-        seq = _hmm._seq_start(lengths, n)
+        seq = seq_start(lengths, n)
         if k > n:
             raise ValueError(f"n_states = {k} exceeds the {n} rows")
         if d > _hip.ARHMM_MAX_D:
@@ -95,17 +93,10 @@ class ARHMM(_hmm.GaussianHMM):
         self.ridge_ = self.ridge * colvar
         center = x64.mean(0).astype(np.float32)
         p = L * d + 1
-        km = _cluster.KMeans(k, n_init=self.n_init, seed=self.seed, backend=b).fit(xa)
-        lab0 = km.labels_
-        cut = [lab0[s:e] for s, e in zip(seq[:-1], seq[1:])]
-        onehot = np.zeros((n, k), np.float32)
-        onehot[np.arange(n), lab0] = 1.0
+        km, onehot, A, pi = self._start(xa, seq)
         moments, weight = b.arhmm_moments(xa, seq, L, R, center, onehot)
         W, var, _, _ = b.arhmm_solve(moments, weight, d, L, center, np.zeros((k, d, p), np.float32),
                                      np.full((k, d), max(colvar, self.min_var_, 1e-30), np.float32), self.ridge_, self.min_var_, 0.5)
-        _, trans, _ = _cluster.segment_summary(cut, k)
-        first = np.bincount(lab0[seq[:-1]], minlength=k).astype(np.float64)
-        A, pi = b.hmm_transitions(trans.astype(np.float64), first, self.prior, self.kappa, np.full((k, k), 1.0 / k, np.float32), np.full(k, 1.0 / k, np.float32))
         W, var, A, pi, gamma, labels, status, info = b.arhmm_fit(xa, seq, L, R, center, W, var, A, pi, self.max_iter, self.tol, self.prior, self.kappa, self.ridge_,
                                                                  self.min_var_, _hmm.MIN_WEIGHT)
         # every state's weighted mean of x over the scored rows, from the moments of the final posteriors (a state without weight: the centre)
@@ -113,16 +104,9 @@ class ARHMM(_hmm.GaussianHMM):
         with np.errstate(divide="ignore", invalid="ignore"):
             shift = np.where(weight[:, None] > 0, moments[:, p:, p - 1] / weight[:, None], 0.0)
         mu = (center.astype(np.float64)[None, :] + shift).astype(np.float32)
-        counts = np.bincount(labels, minlength=k)
-        order = np.argsort(-counts, kind="stable")      # descending count, equal counts in their original order
-        rank = np.empty(k, np.int64)
-        rank[order] = np.arange(k)
-        self.weights_, self.vars_, self.means_ = np.ascontiguousarray(W[order]), np.ascontiguousarray(var[order]), np.ascontiguousarray(mu[order])
-        self.transmat_, self.startprob_ = np.ascontiguousarray(A[order][:, order]), np.ascontiguousarray(pi[order])
-        self.labels_, self.counts_, self.gamma_ = rank[labels].astype(np.int32), counts[order].astype(np.int64), np.ascontiguousarray(gamma[:, order])
-        self.status_, self.n_singular_, self.center_ = np.ascontiguousarray(status[order]), int(info.n_singular), center
-        self.loglik_, self.n_iter_, self.converged_ = float(info.loglik), int(info.n_iter), bool(info.converged)
-        self.init_labels_, self.n_samples_, self.n_features_, self.seq_start_, self.n_scored_ = lab0, n, d, seq, self._scored(seq)
+        order = self._fitted(mu, var, A, pi, gamma, labels, info, km.labels_, seq, d)
+        self.weights_, self.status_, self.n_singular_, self.center_ = np.ascontiguousarray(W[order]), np.ascontiguousarray(status[order]), int(info.n_singular), center
+        self.n_scored_ = self._scored(seq)
         return self
 
     def _logb(self, x, lengths):
@@ -131,8 +115,11 @@ class ARHMM(_hmm.GaussianHMM):
         xa = self._b.asarray(x)
         if xa.shape[1] != self.n_features_:
             raise ValueError(f"expected {self.n_features_} features, got {xa.shape[1]}")
-        seq = _hmm._seq_start(lengths, int(xa.shape[0]))
+        seq = seq_start(lengths, int(xa.shape[0]))
         return self._b.arhmm_emission(xa, seq, self.lags, self.warmup, self.center_, self.weights_, self.vars_), seq
+
+    def scored_rows(self, lengths) -> int:
+        return max(self._scored(seq_start(lengths, sum(lengths))), 1)
 
     def eigenvalues(self):
         """[K, L D] complex: the eigenvalues of every state's companion matrix, by descending modulus."""
@@ -140,19 +127,19 @@ class ARHMM(_hmm.GaussianHMM):
 
 
 def _read(rollouts, feature, projections, n_components):
-    """-> (clip numbers, [T_j, D] float32 signals): the recorded feature, or the leading n_components of the projections of a pca.h5."""
+    """-> (clip numbers, [T_j, D] float32 signals, the name they go by): the recorded feature, or the leading n_components of the projections of a
+    pca.h5."""
     if projections is None:
-        ids, feats = rollout_features(rollouts, lambda r, _, where: _pca._feature_of(r, feature, where), feature, "fit")
+        ids, feats = rollout_features(rollouts, lambda r, _, where: feature_of(r, feature, where), feature, "fit")
         if feats[0].shape[1] > _hip.ARHMM_MAX_D:
             raise ValueError(f"{feature}: " + _too_wide(feats[0].shape[1]))
-        return ids, [np.ascontiguousarray(f, np.float32) for f in feats]
-    from .spectrogram import _signals
+        return ids, [np.ascontiguousarray(f, np.float32) for f in feats], feature
     if not 1 <= int(n_components) <= _hip.ARHMM_MAX_D:
         raise ValueError(f"n_components must be in 1 .. {_hip.ARHMM_MAX_D} (got {n_components})")
-    ids, sigs, _ = _signals(rollouts, "projections", None, projections)
+    ids, sigs, _ = signals(rollouts, "projections", None, projections)
     if sigs[0].shape[1] < int(n_components):
         raise ValueError(f"{projections} holds {sigs[0].shape[1]} components, n_components = {n_components} asked")
-    return ids, [np.ascontiguousarray(s[:, :int(n_components)], np.float32) for s in sigs]
+    return ids, [np.ascontiguousarray(s[:, :int(n_components)], np.float32) for s in sigs], "projections"
 
 
 def fit_rollouts(rollouts, feature: str = "intention", k: int = 32, lags: int = 3, warmup=None, ridge: float = 1.0, max_iter: int = 50, tol: float = 1e-4,
@@ -161,78 +148,36 @@ def fit_rollouts(rollouts, feature: str = "intention", k: int = 32, lags: int = 
     """Fit `feature` (up to 32 wide), or the leading n_components of `projections` (a pca.h5), over the roll-outs, each one sequence.  With
     holdout = h >= 2 the clips at the positions p, p % h == h - 1, are left out of the fit and scored.
     -> (arhmm, feats): as analysis.hmm.fit_rollouts; the likelihoods per step are per SCORED row."""
-    holdout = int(holdout)
-    if holdout < 0 or holdout == 1:
-        raise ValueError(f"holdout must be 0 (no clip held out) or >= 2 (got {holdout})")
-    ids, feats = _read(rollouts, feature, projections, n_components)
-    held = [p for p in range(len(ids)) if holdout and p % holdout == holdout - 1]
-    train = [p for p in range(len(ids)) if p not in held]
-    if not train or (holdout and not held):
-        raise ValueError(f"holdout = {holdout} over {len(ids)} clips leaves no {'training' if not train else 'held-out'} clip")
-    m = ARHMM(k, lags=lags, warmup=warmup, ridge=ridge, max_iter=max_iter, tol=tol, prior=prior, kappa=kappa, n_init=n_init, seed=seed, device=device,
-              backend=backend)
-    m.fit(np.concatenate([feats[p] for p in train], 0), [feats[p].shape[0] for p in train])
-    m.clips_, m.feature_, m.train_, m.heldout_ = ids, feature if projections is None else "projections", train, held
-    m.loglik_per_step_train_ = m.loglik_ / max(m.n_scored_, 1)
-    m.loglik_per_step_heldout_ = None
-    if held:
-        lens = [feats[p].shape[0] for p in held]
-        m.loglik_per_step_heldout_ = m.score(np.concatenate([feats[p] for p in held], 0), lens) / max(m._scored(_hmm._seq_start(lens, sum(lens))), 1)
-    return m, feats
+    return _hmm.fit_split(lambda: _read(rollouts, feature, projections, n_components),
+                          lambda: ARHMM(k, lags=lags, warmup=warmup, ridge=ridge, max_iter=max_iter, tol=tol, prior=prior, kappa=kappa, n_init=n_init, seed=seed,
+                                        device=device, backend=backend), holdout)
 
 
 def main(argv=None, backend=None) -> int:
-    from .. import h5lite
-    argv = list(sys.argv[1:] if argv is None else argv)
-    opts = dict(a.split("=", 1) for a in argv if "=" in a and a.split("=", 1)[0] in CLI_OPTIONS)
-    if any(o not in opts for o in ("rollouts", "out", "k")) or len(opts) != len(argv) or ("feature" in opts and "projections" in opts):
-        print(USAGE, file=sys.stderr)
+    opts = cli.parse(argv, CLI_OPTIONS, ("rollouts", "out", "k"), USAGE, lambda o: not ("feature" in o and "projections" in o))
+    if opts is None:
         return 2
-    feature = opts.get("feature", "intention")
     try:
         k, seed, lags = int(opts["k"]), int(opts.get("seed", 0)), int(opts.get("lags", 3))
         warmup = int(opts["warmup"]) if opts.get("warmup", "") != "" else None
         rate = float(opts["rate"]) if opts.get("rate", "") != "" else None
         if rate is not None and not rate > 0.0:
             raise ValueError(f"rate must be > 0 (got {rate})")
-        posteriors = opts.get("posteriors", "false").lower()
-        if posteriors not in ("true", "false"):
-            raise ValueError(f"posteriors must be true or false (got {opts['posteriors']})")
-        m, feats = fit_rollouts(opts["rollouts"], feature, k, lags, warmup, float(opts.get("ridge", 1.0)), int(opts.get("max_iter", 50)), float(opts.get("tol", 1e-4)),
-                                float(opts.get("prior", 0.1)), float(opts.get("kappa", 0.0)), int(opts.get("n_init", 4)), seed, int(opts.get("holdout", 0)),
-                                opts.get("projections"), int(opts.get("n_components", 10)), backend=backend)
-        lens = [f.shape[0] for f in feats]
-        allx = np.concatenate(feats, 0)
-        labels, gamma = m.predict(allx, lens), m.predict_proba(allx, lens)
+        posteriors = cli.flag(opts, "posteriors")
+        m, feats = fit_rollouts(opts["rollouts"], opts.get("feature", "intention"), k, lags, warmup, float(opts.get("ridge", 1.0)), int(opts.get("max_iter", 50)),
+                                float(opts.get("tol", 1e-4)), float(opts.get("prior", 0.1)), float(opts.get("kappa", 0.0)), int(opts.get("n_init", 4)), seed,
+                                int(opts.get("holdout", 0)), opts.get("projections"), int(opts.get("n_components", 10)), backend=backend)
+        tree = _hmm.fitted_tree(m, feats, seed, posteriors)
     except (KeyError, ValueError) as e:
-        print(f"[arhmm] {e.args[0] if e.args else e}", file=sys.stderr)
-        return 2
-    ends = np.cumsum(lens)
-    cut = lambda a: [a[e - t:e] for e, t in zip(ends, lens)]      # noqa: E731
-    lab, gam = cut(labels), cut(gamma)
-    counts, trans, dwell = _cluster.segment_summary(lab, k)
-    _, _, dwell0 = _cluster.segment_summary([m.init_labels_[s:e] for s, e in zip(m.seq_start_[:-1], m.seq_start_[1:])], k)
-    tree = {"means": m.means_, "variances": m.vars_, "transmat": m.transmat_, "startprob": m.startprob_, "centroids": m.means_, "weights": m.weights_,
-            "center": m.center_, "lags": np.int64(m.lags), "warmup": np.int64(m.warmup), "status": np.asarray(m.status_, np.int32),
-            "n_singular": np.int64(m.n_singular_), "loglik": np.float64(m.loglik_), "loglik_per_step_train": np.float64(m.loglik_per_step_train_),
-            "n_iter": np.int64(m.n_iter_), "converged": np.int64(m.converged_), "feature": m.feature_, "clips": np.asarray(m.clips_, np.int64),
-            "seed": np.int64(seed), "counts": counts, "transitions": trans, "dwell_mean": dwell, "init_dwell_mean": dwell0,
-            "labels": {f"clip_{c}": np.asarray(v, np.int32) for c, v in zip(m.clips_, lab)},
-            "confidence": {f"clip_{c}": np.ascontiguousarray(g[np.arange(len(v)), v], np.float32) for c, v, g in zip(m.clips_, lab, gam)}}
-    if m.loglik_per_step_heldout_ is not None:
-        tree["loglik_per_step_heldout"] = np.float64(m.loglik_per_step_heldout_)
-    if posteriors == "true":
-        tree["gamma"] = {f"clip_{c}": np.ascontiguousarray(g, np.float32) for c, g in zip(m.clips_, gam)}
+        return cli.report("arhmm", e)
+    tree.update({"weights": m.weights_, "center": m.center_, "lags": np.int64(m.lags), "warmup": np.int64(m.warmup), "status": np.asarray(m.status_, np.int32),
+                 "n_singular": np.int64(m.n_singular_)})
     if rate is not None:
         ev = m.eigenvalues()
         tree["eig_modulus"], tree["eig_freq_hz"] = np.abs(ev), np.abs(np.angle(ev)) * rate / (2.0 * np.pi)
-    os.makedirs(os.path.dirname(os.path.abspath(opts["out"])), exist_ok=True)
-    h5lite.write_tree(opts["out"], tree)
-    occ, occ0 = counts > 0, dwell0 > 0
-    held = "" if m.loglik_per_step_heldout_ is None else f", {m.loglik_per_step_heldout_:.4f} on {len(m.heldout_)} held-out clips"
-    print(f"[arhmm] {m.feature_}: {m.n_samples_} samples x {m.n_features_} features from {len(m.train_)} clips into {k} states of {m.lags} lags, {m.n_iter_} "
-          f"iterations{'' if m.converged_ else ' (not converged)'}, loglik per scored step {m.loglik_per_step_train_:.4f}{held}; mean dwell "
-          f"{float(dwell[occ].mean()):.2f} steps (k-means start: {float(dwell0[occ0].mean()):.2f}); wrote {opts['out']}", flush=True)
+    cli.write(opts["out"], tree)
+    print(f"[arhmm] {m.feature_}: {m.n_samples_} samples x {m.n_features_} features from {len(m.train_)} clips into {k} states of {m.lags} lags, "
+          + _hmm.summary_tail(m, tree, "scored step", opts["out"]), flush=True)
     return 0
 
 

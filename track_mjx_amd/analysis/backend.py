@@ -698,3 +698,8 @@ class HipBackend(Backend):
     def __init__(self, device="cuda", lib=None):
         super().__init__(TorchArrays(device, lib))
         self.device = self._p.device
+
+
+def resolve(backend=None, device="cuda"):
+    """The backend a tool runs on: the stand-in it was handed, or the HIP library on `device`."""
+    return HipBackend(device) if backend is None else backend

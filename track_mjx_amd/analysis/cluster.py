@@ -10,16 +10,18 @@ commonest.  `python -m track_mjx_amd.analysis.rollout ... intervene_centroids=<c
 """
 from __future__ import annotations
 
-import os
 import sys
 
 import numpy as np
 
 from .. import hip as _hip
-from . import pca as _pca
-from .utils import rollout_features
+from . import cli
+from .backend import resolve
+from .recorded import by_clip, feature_of, number_by_count, rollout_features, split
 
 CLI_OPTIONS = ("rollouts", "out", "feature", "k", "seed", "n_init", "max_iter", "tol")
+USAGE = ("usage: python -m track_mjx_amd.analysis.cluster rollouts=<dir of clip_<i>.h5> [feature=intention] k=32 [seed=0] [n_init=4] [max_iter=100] "
+         "[tol=1e-4] out=<clusters.h5>")
 
 
 class KMeans:
@@ -35,7 +37,7 @@ class KMeans:
         if int(n_init) < 1 or int(max_iter) < 1 or not float(tol) >= 0.0:
             raise ValueError(f"n_init and max_iter must be >= 1 and tol >= 0 (got {n_init}, {max_iter}, {tol})")
         self.n_clusters, self.n_init, self.max_iter, self.tol, self.seed = int(n_clusters), int(n_init), int(max_iter), float(tol), int(seed)
-        self._b = _pca.HipBackend(device) if backend is None else backend
+        self._b = resolve(backend, device)
 
     def fit(self, x):
         xa = self._b.asarray(x)
@@ -53,11 +55,8 @@ class KMeans:
             if best is None or float(info.inertia) < best[3]:
                 best = (cen, labels, dist2, float(info.inertia), int(info.n_iter), r)
         cen, labels, dist2, self.inertia_, self.n_iter_, self.best_init_ = best
-        counts = np.bincount(labels, minlength=k)
-        order = np.argsort(-counts, kind="stable")      # descending count, equal counts in their original order
-        rank = np.empty(k, np.int64)
-        rank[order] = np.arange(k)
-        self.cluster_centers_, self.counts_ = np.ascontiguousarray(cen[order]), counts[order].astype(np.int64)
+        order, rank, self.counts_ = number_by_count(labels, k)
+        self.cluster_centers_ = np.ascontiguousarray(cen[order])
         self.labels_, self.distances_ = rank[labels].astype(np.int32), dist2
         self.n_samples_, self.n_features_ = n, d
         return self
@@ -96,22 +95,17 @@ def fit_rollouts(rollouts, feature: str = "intention", k: int = 32, n_init: int 
                  backend=None):
     """Cluster `feature` (up to 1024 wide) over every roll-out.  `rollouts`: a directory of clip_<i>.h5, or a list of roll-out dicts.
     -> (kmeans, labels, distances): labels[j] int32 [T_j] and distances[j] float32 [T_j] of roll-out j; kmeans.clips_ are the clip numbers."""
-    ids, feats = rollout_features(rollouts, lambda r, _, where: _pca._feature_of(r, feature, where), feature, "cluster")
+    ids, feats = rollout_features(rollouts, lambda r, _, where: feature_of(r, feature, where), feature, "cluster")
     km = KMeans(k, n_init=n_init, max_iter=max_iter, tol=tol, seed=seed, device=device, backend=backend)
     km.fit(km._b.asarray(np.concatenate(feats, 0)))
     km.clips_, km.feature_ = ids, feature
-    ends = np.cumsum([f.shape[0] for f in feats])
-    cut = lambda a: [a[e - f.shape[0]:e] for e, f in zip(ends, feats)]      # noqa: E731
-    return km, cut(km.labels_), cut(km.distances_)
+    lens = [f.shape[0] for f in feats]
+    return km, split(km.labels_, lens), split(km.distances_, lens)
 
 
 def main(argv=None, backend=None) -> int:
-    from .. import h5lite
-    argv = list(sys.argv[1:] if argv is None else argv)
-    opts = dict(a.split("=", 1) for a in argv if "=" in a and a.split("=", 1)[0] in CLI_OPTIONS)
-    if any(o not in opts for o in ("rollouts", "out", "k")) or len(opts) != len(argv):
-        print("usage: python -m track_mjx_amd.analysis.cluster rollouts=<dir of clip_<i>.h5> [feature=intention] k=32 [seed=0] [n_init=4] [max_iter=100] "
-              "[tol=1e-4] out=<clusters.h5>", file=sys.stderr)
+    opts = cli.parse(argv, CLI_OPTIONS, ("rollouts", "out", "k"), USAGE)
+    if opts is None:
         return 2
     feature = opts.get("feature", "intention")
     try:
@@ -119,15 +113,11 @@ def main(argv=None, backend=None) -> int:
         km, labels, dists = fit_rollouts(opts["rollouts"], feature, k, int(opts.get("n_init", 4)), int(opts.get("max_iter", 100)), float(opts.get("tol", 1e-4)),
                                          seed, backend=backend)
     except (KeyError, ValueError) as e:
-        print(f"[cluster] {e.args[0] if e.args else e}", file=sys.stderr)
-        return 2
+        return cli.report("cluster", e)
     counts, trans, dwell = segment_summary(labels, k)
-    os.makedirs(os.path.dirname(os.path.abspath(opts["out"])), exist_ok=True)
-    h5lite.write_tree(opts["out"], {"centroids": km.cluster_centers_, "counts": counts, "transitions": trans, "dwell_mean": dwell,
-                                    "inertia": np.float64(km.inertia_), "n_iter": np.int64(km.n_iter_), "feature": feature,
-                                    "clips": np.asarray(km.clips_, np.int64), "seed": np.int64(seed),
-                                    "labels": {f"clip_{c}": np.asarray(v, np.int32) for c, v in zip(km.clips_, labels)},
-                                    "distances": {f"clip_{c}": np.asarray(v, np.float32) for c, v in zip(km.clips_, dists)}})
+    cli.write(opts["out"], {"centroids": km.cluster_centers_, "counts": counts, "transitions": trans, "dwell_mean": dwell, "inertia": np.float64(km.inertia_),
+                            "n_iter": np.int64(km.n_iter_), "feature": feature, "clips": np.asarray(km.clips_, np.int64), "seed": np.int64(seed),
+                            "labels": by_clip(km.clips_, labels, np.int32), "distances": by_clip(km.clips_, dists, np.float32)})
     top = ", ".join(f"{c}" for c in counts[:5])
     print(f"[cluster] {feature}: {km.n_samples_} samples x {km.n_features_} features from {len(labels)} clips into {k} motifs, {km.n_iter_} iterations "
           f"(restart {km.best_init_} of {km.n_init}), inertia {km.inertia_:.6g}; the commonest motifs hold {top} steps; mean dwell "

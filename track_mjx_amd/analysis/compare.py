@@ -25,11 +25,13 @@ import warnings
 import numpy as np
 
 from .. import hip as _hip
-from . import pca as _pca
-from . import readout as _readout
-from .utils import rollout_features
+from . import cli
+from .backend import resolve
+from .recorded import columns, feature_of, labels_file, rollout_features, target_of
 
 CLI_OPTIONS = ("a", "b", "features_a", "features_b", "cols_a", "cols_b", "labels", "metric", "max_rows", "seed", "cca", "var_keep", "out")
+USAGE = ("usage: python -m track_mjx_amd.analysis.compare a=<dir of clip_<i>.h5> [b=<dir>] features_a=<f1,f2,...> [features_b=...] [cols_a=a:b] [cols_b=a:b] "
+         "[labels=<clusters.h5>] [metric=correlation|euclidean|sqeuclidean] [max_rows=20000] [seed=0] [cca=<fa>:<fb>] [var_keep=0.99] out=<compare.h5>")
 METRICS = {"sqeuclidean": _hip.COMPARE_SQEUCLIDEAN, "euclidean": _hip.COMPARE_EUCLIDEAN, "correlation": _hip.COMPARE_CORRELATION, "labels": _hip.COMPARE_LABEL}
 LABELS = "labels"      # the name of the motif-label feature that labels= adds to side a
 
@@ -75,7 +77,7 @@ class Comparison:
     `sweeps_` set.  Inputs: numpy arrays, or torch device tensors (a row stride is kept)."""
 
     def __init__(self, device="cuda", backend=None):
-        self._b = _pca.HipBackend(device) if backend is None else backend
+        self._b = resolve(backend, device)
 
     def _rows(self, x):
         return self._b.asarray(x[:, None] if getattr(x, "ndim", 2) == 1 else x)
@@ -108,10 +110,10 @@ class Comparison:
 def _series_of(rollout, name: str, where: str) -> np.ndarray:
     """A feature of analysis.pca or a target of analysis.readout of one roll-out, [rows, D] float32."""
     try:
-        return _pca._feature_of(rollout, name, where)
+        return feature_of(rollout, name, where)
     except KeyError as first:
         try:
-            return _readout._target_of(rollout, name, where)
+            return target_of(rollout, name, where)
         except KeyError:
             raise first from None
 
@@ -134,16 +136,10 @@ def _side(rollouts, names, cols, labels_of=None):
                 out.append(np.asarray(labels_of[clip], np.float32).reshape(-1, 1))
                 continue
             a = _series_of(r, name, where)
-            out.append(np.ascontiguousarray(a[:, _readout._cols(cols, a.shape[1])]))
+            out.append(np.ascontiguousarray(a[:, columns(cols, a.shape[1])]))
         return out
     ids, items = rollout_features(rollouts, read, None, "compare")
     return dict(zip(ids, items))
-
-
-def _labels_file(path):
-    from .. import h5lite
-    with h5lite.File(str(path)) as h:
-        return {int(k.split("_", 1)[1]): np.asarray(h["labels"][k][()]) for k in h["labels"].keys()}
 
 
 def compare_rollouts(a, b=None, features_a=("intention",), features_b=None, cols_a=None, cols_b=None, labels=None, metric="correlation", max_rows=20000,
@@ -164,7 +160,7 @@ def compare_rollouts(a, b=None, features_a=("intention",), features_b=None, cols
         fa = fa + [LABELS]
     if not fa or not fb:
         raise ValueError("no feature to compare")
-    lab = None if labels is None else (_labels_file(labels) if isinstance(labels, (str, os.PathLike)) else dict(labels))
+    lab = None if labels is None else (labels_file(labels) if isinstance(labels, (str, os.PathLike)) else dict(labels))
     side_a = _side(a, fa, cols_a, lab)
     side_b = side_a if b is None and fb == fa and cols_b == cols_a else _side(a if b is None else b, fb, cols_b, lab)
     clips = sorted(set(side_a) & set(side_b))
@@ -214,23 +210,16 @@ def compare_rollouts(a, b=None, features_a=("intention",), features_b=None, cols
 
 
 def main(argv=None, backend=None) -> int:
-    from .. import h5lite
-    argv = list(sys.argv[1:] if argv is None else argv)
-    opts = dict(a.split("=", 1) for a in argv if "=" in a and a.split("=", 1)[0] in CLI_OPTIONS)
-    if any(k not in opts for k in ("a", "features_a", "out")) or len(opts) != len(argv):
-        print("usage: python -m track_mjx_amd.analysis.compare a=<dir of clip_<i>.h5> [b=<dir>] features_a=<f1,f2,...> [features_b=...] [cols_a=a:b] [cols_b=a:b] "
-              "[labels=<clusters.h5>] [metric=correlation|euclidean|sqeuclidean] [max_rows=20000] [seed=0] [cca=<fa>:<fb>] [var_keep=0.99] out=<compare.h5>",
-              file=sys.stderr)
+    opts = cli.parse(argv, CLI_OPTIONS, ("a", "features_a", "out"), USAGE)
+    if opts is None:
         return 2
     try:
         res = compare_rollouts(opts["a"], opts.get("b"), opts["features_a"].split(","), opts["features_b"].split(",") if "features_b" in opts else None,
                                opts.get("cols_a"), opts.get("cols_b"), opts.get("labels"), opts.get("metric", "correlation"), int(opts.get("max_rows", 20000)),
                                int(opts.get("seed", 0)), opts.get("cca"), float(opts.get("var_keep", 0.99)), backend=backend)
     except (KeyError, ValueError) as e:
-        print(f"[compare] {e.args[0] if e.args else e}", file=sys.stderr)
-        return 2
-    os.makedirs(os.path.dirname(os.path.abspath(opts["out"])), exist_ok=True)
-    h5lite.write_tree(opts["out"], res)
+        return cli.report("compare", e)
+    cli.write(opts["out"], res)
     fa, fb = res["features_a"].split(","), res["features_b"].split(",")
     best = ", ".join(f"{a} ~ {fb[int(np.nanargmax(res['cka'][i]))]} {np.nanmax(res['cka'][i]):.3f}" for i, a in enumerate(fa) if np.isfinite(res["cka"][i]).any())
     tail = f"; cca {res['cca_features']}: {res['kx']} x {res['ky']} kept, svcca {float(res['svcca']):.4f}" if "rho" in res else ""

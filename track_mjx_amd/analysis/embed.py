@@ -12,17 +12,19 @@ feature and clips.  Regions are numbered by descending count of time steps: regi
 """
 from __future__ import annotations
 
-import os
 import sys
 
 import numpy as np
 
 from .. import hip as _hip
-from . import pca as _pca
+from . import cli
+from .backend import resolve
 from .cluster import segment_summary
-from .utils import rollout_features
+from .recorded import by_clip, feature_of, rollout_features, split
 
 CLI_OPTIONS = ("rollouts", "out", "feature", "perplexity", "max_train", "n_iter", "grid", "sigma")
+USAGE = ("usage: python -m track_mjx_amd.analysis.embed rollouts=<dir of clip_<i>.h5> [feature=intention] [perplexity=30] [max_train=20000] [n_iter=750] "
+         "[grid=256] [sigma=<in map units>] out=<map.h5>")
 INIT_STD = 1e-4
 
 
@@ -68,7 +70,7 @@ class TSNE:
         self.perplexity, self.n_iter, self.exaggeration, self.exaggeration_iters = float(perplexity), int(n_iter), float(exaggeration), int(exaggeration_iters)
         self.eta, self.max_train, self.min_gain = eta, int(max_train), float(min_gain)
         self.momentum_early, self.momentum_late = float(momentum_early), float(momentum_late)
-        self._b = _pca.HipBackend(device) if backend is None else backend
+        self._b = resolve(backend, device)
 
     def _neighbours(self, n_train):
         k = min(int(3 * self.perplexity), n_train - 1, _hip.TSNE_MAX_K)
@@ -219,45 +221,36 @@ def map_rollouts(rollouts, feature: str = "intention", perplexity: float = 30, m
     """Embed `feature` (up to 1024 wide) over every roll-out and cut the map into regions.  `rollouts`: a directory of clip_<i>.h5, or a list of
     roll-out dicts.  -> (tsne, result): result has embedding[j] [T_j, 2] and labels[j] int32 [T_j] of roll-out j, density, regions, extent, counts,
     transitions, dwell_mean and centroids; tsne.clips_ are the clip numbers."""
-    ids, feats = rollout_features(rollouts, lambda r, _, where: _pca._feature_of(r, feature, where), feature, "embed")
-    x = np.concatenate(feats, 0)
+    ids, feats = rollout_features(rollouts, lambda r, _, where: feature_of(r, feature, where), feature, "embed")
+    x, lens = np.concatenate(feats, 0), [f.shape[0] for f in feats]
     tsne = TSNE(perplexity, n_iter=n_iter, max_train=max_train, device=device, backend=backend)
-    emb = np.asarray(tsne.fit_transform(x, [f.shape[0] for f in feats]), np.float32)
+    emb = np.asarray(tsne.fit_transform(x, lens), np.float32)
     tsne.clips_, tsne.feature_ = ids, feature
     density, extent, hist = density_map(emb, grid, sigma)
     regions = watershed(density, hist)
     labels = region_labels(regions, emb, extent)
     K = int(regions.max()) + 1
-    ends = np.cumsum([f.shape[0] for f in feats])
-    cut = lambda a: [a[e - f.shape[0]:e] for e, f in zip(ends, feats)]      # noqa: E731
-    counts, trans, dwell = segment_summary(cut(labels), K)
+    counts, trans, dwell = segment_summary(split(labels, lens), K)
     x64 = np.asarray(x, np.float64)
     centroids = np.stack([x64[labels == j].mean(0) if counts[j] else np.zeros(x.shape[1]) for j in range(K)]).astype(np.float32)
-    return tsne, {"embedding": cut(emb), "labels": cut(labels), "density": density, "regions": regions, "extent": np.asarray(extent, np.float64),
+    return tsne, {"embedding": split(emb, lens), "labels": split(labels, lens), "density": density, "regions": regions, "extent": np.asarray(extent, np.float64),
                   "counts": counts, "transitions": trans, "dwell_mean": dwell, "centroids": centroids}
 
 
 def main(argv=None, backend=None) -> int:
-    from .. import h5lite
-    argv = list(sys.argv[1:] if argv is None else argv)
-    opts = dict(a.split("=", 1) for a in argv if "=" in a and a.split("=", 1)[0] in CLI_OPTIONS)
-    if any(o not in opts for o in ("rollouts", "out")) or len(opts) != len(argv):
-        print("usage: python -m track_mjx_amd.analysis.embed rollouts=<dir of clip_<i>.h5> [feature=intention] [perplexity=30] [max_train=20000] [n_iter=750] "
-              "[grid=256] [sigma=<in map units>] out=<map.h5>", file=sys.stderr)
+    opts = cli.parse(argv, CLI_OPTIONS, ("rollouts", "out"), USAGE)
+    if opts is None:
         return 2
     feature = opts.get("feature", "intention")
     try:
         tsne, res = map_rollouts(opts["rollouts"], feature, float(opts.get("perplexity", 30)), int(opts.get("max_train", 20000)), int(opts.get("n_iter", 750)),
                                  int(opts.get("grid", 256)), float(opts["sigma"]) if "sigma" in opts else None, backend=backend)
     except (KeyError, ValueError) as e:
-        print(f"[embed] {e.args[0] if e.args else e}", file=sys.stderr)
-        return 2
-    os.makedirs(os.path.dirname(os.path.abspath(opts["out"])), exist_ok=True)
-    h5lite.write_tree(opts["out"], {"embedding": {f"clip_{c}": np.asarray(v, np.float32) for c, v in zip(tsne.clips_, res["embedding"])},
-                                    "train_index": tsne.train_index_, "kl": np.float64(tsne.kl_), "density": res["density"], "regions": res["regions"],
-                                    "extent": res["extent"], "labels": {f"clip_{c}": np.asarray(v, np.int32) for c, v in zip(tsne.clips_, res["labels"])},
-                                    "counts": res["counts"], "transitions": res["transitions"], "dwell_mean": res["dwell_mean"], "centroids": res["centroids"],
-                                    "feature": feature, "clips": np.asarray(tsne.clips_, np.int64), "perplexity": np.float64(tsne.perplexity)})
+        return cli.report("embed", e)
+    cli.write(opts["out"], {"embedding": by_clip(tsne.clips_, res["embedding"], np.float32), "train_index": tsne.train_index_, "kl": np.float64(tsne.kl_),
+                            "density": res["density"], "regions": res["regions"], "extent": res["extent"], "labels": by_clip(tsne.clips_, res["labels"], np.int32),
+                            "counts": res["counts"], "transitions": res["transitions"], "dwell_mean": res["dwell_mean"], "centroids": res["centroids"],
+                            "feature": feature, "clips": np.asarray(tsne.clips_, np.int64), "perplexity": np.float64(tsne.perplexity)})
     print(f"[embed] {feature}: {tsne.n_samples_} samples x {tsne.n_features_} features from {len(res['labels'])} clips, {len(tsne.train_index_)} trained "
           f"({tsne.n_neighbours_} neighbours, {tsne.n_iter_} iterations, kl {tsne.kl_:.4f}); {len(res['counts'])} regions, the commonest hold "
           f"{', '.join(str(c) for c in res['counts'][:5])} steps; wrote {opts['out']}", flush=True)

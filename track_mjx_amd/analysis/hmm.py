@@ -15,25 +15,20 @@ the commonest.
 """
 from __future__ import annotations
 
-import os
 import sys
 
 import numpy as np
 
 from .. import hip as _hip
-from . import cluster as _cluster
-from . import pca as _pca
-from .utils import rollout_features
+from . import cli
+from .backend import resolve
+from .cluster import KMeans, segment_summary
+from .recorded import by_clip, feature_of, number_by_count, rollout_features, seq_start, split
 
 CLI_OPTIONS = ("rollouts", "out", "feature", "k", "kappa", "prior", "seed", "n_init", "max_iter", "tol", "holdout", "posteriors")
+USAGE = ("usage: python -m track_mjx_amd.analysis.hmm rollouts=<dir of clip_<i>.h5> [feature=intention] k=32 [kappa=0] [prior=0.1] [seed=0] [n_init=4] "
+         "[max_iter=50] [tol=1e-4] [holdout=0] [posteriors=false] out=<hmm.h5>")
 MIN_WEIGHT = 1e-3      # a state holding less than this many expected rows keeps its emission parameters
-
-
-def _seq_start(lengths, n):
-    lengths = np.asarray(lengths, np.int64).reshape(-1)
-    if lengths.size == 0 or (lengths < 1).any() or int(lengths.sum()) != n:
-        raise ValueError(f"lengths must be positive and sum to the {n} rows (got {lengths.size} lengths summing to {int(lengths.sum())})")
-    return np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
 
 
 class GaussianHMM:
@@ -55,38 +50,46 @@ class GaussianHMM:
             raise ValueError(f"min_var must be >= 0 (got {min_var})")
         self.n_states, self.max_iter, self.tol, self.prior, self.kappa = int(n_states), int(max_iter), float(tol), float(prior), float(kappa)
         self.min_var, self.n_init, self.seed = None if min_var is None else float(min_var), int(n_init), int(seed)
-        self._b = _pca.HipBackend(device) if backend is None else backend
+        self._b = resolve(backend, device)
+
+    def _start(self, xa, seq):
+        """The deterministic start both models share: -> (the k-means, its labels as one-hot posteriors [n, K], the transition matrix and start
+        probabilities from its label counts)."""
+        b, k, n = self._b, self.n_states, int(xa.shape[0])
+        km = KMeans(k, n_init=self.n_init, seed=self.seed, backend=b).fit(xa)
+        lab0 = km.labels_
+        onehot = np.zeros((n, k), np.float32)
+        onehot[np.arange(n), lab0] = 1.0
+        _, trans, _ = segment_summary([lab0[s:e] for s, e in zip(seq[:-1], seq[1:])], k)
+        first = np.bincount(lab0[seq[:-1]], minlength=k).astype(np.float64)
+        A, pi = b.hmm_transitions(trans.astype(np.float64), first, self.prior, self.kappa, np.full((k, k), 1.0 / k, np.float32), np.full(k, 1.0 / k, np.float32))
+        return km, onehot, A, pi
+
+    def _fitted(self, mu, var, A, pi, gamma, labels, info, lab0, seq, d):
+        """Keep a fit's result with the states numbered by descending Viterbi count; -> the permutation `order`."""
+        order, rank, self.counts_ = number_by_count(labels, self.n_states)
+        self.means_, self.vars_ = np.ascontiguousarray(mu[order]), np.ascontiguousarray(var[order])
+        self.transmat_, self.startprob_ = np.ascontiguousarray(A[order][:, order]), np.ascontiguousarray(pi[order])
+        self.labels_, self.gamma_ = rank[labels].astype(np.int32), np.ascontiguousarray(gamma[:, order])
+        self.loglik_, self.n_iter_, self.converged_ = float(info.loglik), int(info.n_iter), bool(info.converged)
+        self.init_labels_, self.n_samples_, self.n_features_, self.seq_start_ = lab0, int(labels.shape[0]), d, seq
+        return order
 
     def fit(self, x, lengths):
         b, k = self._b, self.n_states
         xa = b.asarray(x)
         n, d = (int(v) for v in xa.shape)
-        seq = _seq_start(lengths, n)
+        seq = seq_start(lengths, n)
         if k > n:
             raise ValueError(f"n_states = {k} exceeds the {n} rows")
         if d > _hip.HMM_MAX_D:
             raise ValueError(f"{d} features: the HMM takes up to {_hip.HMM_MAX_D}")
         colvar = float(np.asarray(b.to_numpy(xa), np.float64).var(0).mean())
         self.min_var_ = 1e-3 * colvar if self.min_var is None else self.min_var
-        km = _cluster.KMeans(k, n_init=self.n_init, seed=self.seed, backend=b).fit(xa)
-        lab0 = km.labels_
-        cut = [lab0[s:e] for s, e in zip(seq[:-1], seq[1:])]
-        onehot = np.zeros((n, k), np.float32)
-        onehot[np.arange(n), lab0] = 1.0
+        km, onehot, A, pi = self._start(xa, seq)
         mu, var, _ = b.hmm_mstep(xa, onehot, km.cluster_centers_, np.full((k, d), max(colvar, self.min_var_, 1e-30), np.float32), self.min_var_, 0.5)
-        _, trans, _ = _cluster.segment_summary(cut, k)
-        first = np.bincount(lab0[seq[:-1]], minlength=k).astype(np.float64)
-        A, pi = b.hmm_transitions(trans.astype(np.float64), first, self.prior, self.kappa, np.full((k, k), 1.0 / k, np.float32), np.full(k, 1.0 / k, np.float32))
         mu, var, A, pi, gamma, labels, info = b.hmm_fit(xa, seq, mu, var, A, pi, self.max_iter, self.tol, self.prior, self.kappa, self.min_var_, MIN_WEIGHT)
-        counts = np.bincount(labels, minlength=k)
-        order = np.argsort(-counts, kind="stable")      # descending count, equal counts in their original order
-        rank = np.empty(k, np.int64)
-        rank[order] = np.arange(k)
-        self.means_, self.vars_ = np.ascontiguousarray(mu[order]), np.ascontiguousarray(var[order])
-        self.transmat_, self.startprob_ = np.ascontiguousarray(A[order][:, order]), np.ascontiguousarray(pi[order])
-        self.labels_, self.counts_, self.gamma_ = rank[labels].astype(np.int32), counts[order].astype(np.int64), np.ascontiguousarray(gamma[:, order])
-        self.loglik_, self.n_iter_, self.converged_ = float(info.loglik), int(info.n_iter), bool(info.converged)
-        self.init_labels_, self.n_samples_, self.n_features_, self.seq_start_ = lab0, n, d, seq
+        self._fitted(mu, var, A, pi, gamma, labels, info, km.labels_, seq, d)
         return self
 
     def _logb(self, x, lengths):
@@ -95,7 +98,7 @@ class GaussianHMM:
         xa = self._b.asarray(x)
         if xa.shape[1] != self.n_features_:
             raise ValueError(f"expected {self.n_features_} features, got {xa.shape[1]}")
-        return self._b.hmm_emission(xa, self.means_, self.vars_), _seq_start(lengths, int(xa.shape[0]))
+        return self._b.hmm_emission(xa, self.means_, self.vars_), seq_start(lengths, int(xa.shape[0]))
 
     def predict(self, x, lengths):
         logb, seq = self._logb(x, lengths)
@@ -113,6 +116,34 @@ class GaussianHMM:
         logb, seq = self._logb(x, lengths)
         return self._b.hmm_forward_backward(logb, seq, self.transmat_, self.startprob_)[4]
 
+    def scored_rows(self, lengths) -> int:
+        """The rows of sequences of `lengths` that a likelihood counts: what a likelihood per step is divided by."""
+        return int(sum(lengths))
+
+
+def fit_split(read, make, holdout):
+    """The fit both sequence models run over roll-outs: `read()` -> (clip numbers, features, the feature's name), `make()` -> the model.  With
+    holdout = h >= 2 the clips at the positions p, p % h == h - 1, are left out of the fit and scored.  -> (model, feats); the model gains
+    clips_, feature_, train_, heldout_ and loglik_per_step_train_ / _heldout_ (None without held-out clips), per row of model.scored_rows."""
+    holdout = int(holdout)
+    if holdout < 0 or holdout == 1:
+        raise ValueError(f"holdout must be 0 (no clip held out) or >= 2 (got {holdout})")
+    ids, feats, feature = read()
+    held = [p for p in range(len(ids)) if holdout and p % holdout == holdout - 1]
+    train = [p for p in range(len(ids)) if p not in held]
+    if not train or (holdout and not held):
+        raise ValueError(f"holdout = {holdout} over {len(ids)} clips leaves no {'training' if not train else 'held-out'} clip")
+    model = make()
+    lens = [feats[p].shape[0] for p in train]
+    model.fit(np.concatenate([feats[p] for p in train], 0), lens)
+    model.clips_, model.feature_, model.train_, model.heldout_ = ids, feature, train, held
+    model.loglik_per_step_train_ = model.loglik_ / model.scored_rows(lens)
+    model.loglik_per_step_heldout_ = None
+    if held:
+        lens = [feats[p].shape[0] for p in held]
+        model.loglik_per_step_heldout_ = model.score(np.concatenate([feats[p] for p in held], 0), lens) / model.scored_rows(lens)
+    return model, feats
+
 
 def fit_rollouts(rollouts, feature: str = "intention", k: int = 32, max_iter: int = 50, tol: float = 1e-4, prior: float = 0.1, kappa: float = 0.0,
                  n_init: int = 4, seed: int = 0, holdout: int = 0, device="cuda", backend=None):
@@ -120,69 +151,53 @@ def fit_rollouts(rollouts, feature: str = "intention", k: int = 32, max_iter: in
     With holdout = h >= 2 the clips at the positions p, p % h == h - 1, are left out of the fit and scored.
     -> (hmm, feats): feats[j] float32 [T_j, D] of roll-out j; hmm.clips_ are the clip numbers, hmm.train_ / hmm.heldout_ the positions fitted / scored,
     hmm.loglik_per_step_train_ / hmm.loglik_per_step_heldout_ (None without held-out clips)."""
-    holdout = int(holdout)
-    if holdout < 0 or holdout == 1:
-        raise ValueError(f"holdout must be 0 (no clip held out) or >= 2 (got {holdout})")
-    ids, feats = rollout_features(rollouts, lambda r, _, where: _pca._feature_of(r, feature, where), feature, "fit")
-    held = [p for p in range(len(ids)) if holdout and p % holdout == holdout - 1]
-    train = [p for p in range(len(ids)) if p not in held]
-    if not train or (holdout and not held):
-        raise ValueError(f"holdout = {holdout} over {len(ids)} clips leaves no {'training' if not train else 'held-out'} clip")
-    hmm = GaussianHMM(k, max_iter=max_iter, tol=tol, prior=prior, kappa=kappa, n_init=n_init, seed=seed, device=device, backend=backend)
-    hmm.fit(np.concatenate([feats[p] for p in train], 0), [feats[p].shape[0] for p in train])
-    hmm.clips_, hmm.feature_, hmm.train_, hmm.heldout_ = ids, feature, train, held
-    hmm.loglik_per_step_train_ = hmm.loglik_ / hmm.n_samples_
-    hmm.loglik_per_step_heldout_ = None
-    if held:
-        lens = [feats[p].shape[0] for p in held]
-        hmm.loglik_per_step_heldout_ = hmm.score(np.concatenate([feats[p] for p in held], 0), lens) / sum(lens)
-    return hmm, feats
+    return fit_split(lambda: (*rollout_features(rollouts, lambda r, _, where: feature_of(r, feature, where), feature, "fit"), feature),
+                     lambda: GaussianHMM(k, max_iter=max_iter, tol=tol, prior=prior, kappa=kappa, n_init=n_init, seed=seed, device=device, backend=backend), holdout)
+
+
+def fitted_tree(model, feats, seed, posteriors: bool):
+    """What hmm.h5 and arhmm.h5 share, from a fitted model and the features of every clip."""
+    k, lens = model.n_states, [f.shape[0] for f in feats]
+    allx = np.concatenate(feats, 0)
+    lab, gam = split(model.predict(allx, lens), lens), split(model.predict_proba(allx, lens), lens)
+    counts, trans, dwell = segment_summary(lab, k)
+    _, _, dwell0 = segment_summary([model.init_labels_[s:e] for s, e in zip(model.seq_start_[:-1], model.seq_start_[1:])], k)
+    tree = {"means": model.means_, "variances": model.vars_, "transmat": model.transmat_, "startprob": model.startprob_, "centroids": model.means_,
+            "loglik": np.float64(model.loglik_), "loglik_per_step_train": np.float64(model.loglik_per_step_train_), "n_iter": np.int64(model.n_iter_),
+            "converged": np.int64(model.converged_), "feature": model.feature_, "clips": np.asarray(model.clips_, np.int64), "seed": np.int64(seed),
+            "counts": counts, "transitions": trans, "dwell_mean": dwell, "init_dwell_mean": dwell0, "labels": by_clip(model.clips_, lab, np.int32),
+            "confidence": by_clip(model.clips_, [g[np.arange(len(v)), v] for v, g in zip(lab, gam)], np.float32)}
+    if model.loglik_per_step_heldout_ is not None:
+        tree["loglik_per_step_heldout"] = np.float64(model.loglik_per_step_heldout_)
+    if posteriors:
+        tree["gamma"] = by_clip(model.clips_, gam, np.float32)
+    return tree
+
+
+def summary_tail(model, tree, per: str, out) -> str:
+    """The end of the summary line both tools print: the likelihoods per step, the dwell times, the file."""
+    dwell, dwell0 = tree["dwell_mean"], tree["init_dwell_mean"]
+    held = "" if model.loglik_per_step_heldout_ is None else f", {model.loglik_per_step_heldout_:.4f} on {len(model.heldout_)} held-out clips"
+    return (f"{model.n_iter_} iterations{'' if model.converged_ else ' (not converged)'}, loglik per {per} {model.loglik_per_step_train_:.4f}{held}; mean dwell "
+            f"{float(dwell[tree['counts'] > 0].mean()):.2f} steps (k-means start: {float(dwell0[dwell0 > 0].mean()):.2f}); wrote {out}")
 
 
 def main(argv=None, backend=None) -> int:
-    from .. import h5lite
-    argv = list(sys.argv[1:] if argv is None else argv)
-    opts = dict(a.split("=", 1) for a in argv if "=" in a and a.split("=", 1)[0] in CLI_OPTIONS)
-    if any(o not in opts for o in ("rollouts", "out", "k")) or len(opts) != len(argv):
-        print("usage: python -m track_mjx_amd.analysis.hmm rollouts=<dir of clip_<i>.h5> [feature=intention] k=32 [kappa=0] [prior=0.1] [seed=0] [n_init=4] "
-              "[max_iter=50] [tol=1e-4] [holdout=0] [posteriors=false] out=<hmm.h5>", file=sys.stderr)
+    opts = cli.parse(argv, CLI_OPTIONS, ("rollouts", "out", "k"), USAGE)
+    if opts is None:
         return 2
-    feature = opts.get("feature", "intention")
     try:
         k, seed = int(opts["k"]), int(opts.get("seed", 0))
-        posteriors = opts.get("posteriors", "false").lower()
-        if posteriors not in ("true", "false"):
-            raise ValueError(f"posteriors must be true or false (got {opts['posteriors']})")
-        hmm, feats = fit_rollouts(opts["rollouts"], feature, k, int(opts.get("max_iter", 50)), float(opts.get("tol", 1e-4)), float(opts.get("prior", 0.1)),
-                                  float(opts.get("kappa", 0.0)), int(opts.get("n_init", 4)), seed, int(opts.get("holdout", 0)), backend=backend)
-        lens = [f.shape[0] for f in feats]
-        allx = np.concatenate(feats, 0)
-        labels, gamma = hmm.predict(allx, lens), hmm.predict_proba(allx, lens)
+        posteriors = cli.flag(opts, "posteriors")
+        hmm, feats = fit_rollouts(opts["rollouts"], opts.get("feature", "intention"), k, int(opts.get("max_iter", 50)), float(opts.get("tol", 1e-4)),
+                                  float(opts.get("prior", 0.1)), float(opts.get("kappa", 0.0)), int(opts.get("n_init", 4)), seed, int(opts.get("holdout", 0)),
+                                  backend=backend)
+        tree = fitted_tree(hmm, feats, seed, posteriors)
     except (KeyError, ValueError) as e:
-        print(f"[hmm] {e.args[0] if e.args else e}", file=sys.stderr)
-        return 2
-    ends = np.cumsum(lens)
-    cut = lambda a: [a[e - t:e] for e, t in zip(ends, lens)]      # noqa: E731
-    lab, gam = cut(labels), cut(gamma)
-    counts, trans, dwell = _cluster.segment_summary(lab, k)
-    _, _, dwell0 = _cluster.segment_summary([hmm.init_labels_[s:e] for s, e in zip(hmm.seq_start_[:-1], hmm.seq_start_[1:])], k)
-    tree = {"means": hmm.means_, "variances": hmm.vars_, "transmat": hmm.transmat_, "startprob": hmm.startprob_, "centroids": hmm.means_,
-            "loglik": np.float64(hmm.loglik_), "loglik_per_step_train": np.float64(hmm.loglik_per_step_train_), "n_iter": np.int64(hmm.n_iter_),
-            "converged": np.int64(hmm.converged_), "feature": feature, "clips": np.asarray(hmm.clips_, np.int64), "seed": np.int64(seed),
-            "counts": counts, "transitions": trans, "dwell_mean": dwell, "init_dwell_mean": dwell0,
-            "labels": {f"clip_{c}": np.asarray(v, np.int32) for c, v in zip(hmm.clips_, lab)},
-            "confidence": {f"clip_{c}": np.ascontiguousarray(g[np.arange(len(v)), v], np.float32) for c, v, g in zip(hmm.clips_, lab, gam)}}
-    if hmm.loglik_per_step_heldout_ is not None:
-        tree["loglik_per_step_heldout"] = np.float64(hmm.loglik_per_step_heldout_)
-    if posteriors == "true":
-        tree["gamma"] = {f"clip_{c}": np.ascontiguousarray(g, np.float32) for c, g in zip(hmm.clips_, gam)}
-    os.makedirs(os.path.dirname(os.path.abspath(opts["out"])), exist_ok=True)
-    h5lite.write_tree(opts["out"], tree)
-    occ, occ0 = counts > 0, dwell0 > 0
-    held = "" if hmm.loglik_per_step_heldout_ is None else f", {hmm.loglik_per_step_heldout_:.4f} on {len(hmm.heldout_)} held-out clips"
-    print(f"[hmm] {feature}: {hmm.n_samples_} samples x {hmm.n_features_} features from {len(hmm.train_)} clips into {k} states, {hmm.n_iter_} iterations"
-          f"{'' if hmm.converged_ else ' (not converged)'}, loglik per step {hmm.loglik_per_step_train_:.4f}{held}; mean dwell "
-          f"{float(dwell[occ].mean()):.2f} steps (k-means start: {float(dwell0[occ0].mean()):.2f}); wrote {opts['out']}", flush=True)
+        return cli.report("hmm", e)
+    cli.write(opts["out"], tree)
+    print(f"[hmm] {hmm.feature_}: {hmm.n_samples_} samples x {hmm.n_features_} features from {len(hmm.train_)} clips into {k} states, "
+          + summary_tail(hmm, tree, "step", opts["out"]), flush=True)
     return 0
 
 

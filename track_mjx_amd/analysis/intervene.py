@@ -305,20 +305,17 @@ def effect_summary(baseline: str, perturbed: str) -> dict:
 
 
 def main(argv=None) -> int:
-    from .. import h5lite
-    argv = list(sys.argv[1:] if argv is None else argv)
-    opts = dict(a.split("=", 1) for a in argv if "=" in a and a.split("=", 1)[0] in ("baseline", "perturbed", "out"))
-    if len(opts) != 3 or len(argv) != 3:
-        print("usage: python -m track_mjx_amd.analysis.intervene baseline=<dir of clip_<i>.h5> perturbed=<dir of clip_<i>.h5> out=<effect.h5>", file=sys.stderr)
+    from . import cli
+    from .utils import to_tree
+    opts = cli.parse(argv, ("baseline", "perturbed", "out"), ("baseline", "perturbed", "out"),
+                     "usage: python -m track_mjx_amd.analysis.intervene baseline=<dir of clip_<i>.h5> perturbed=<dir of clip_<i>.h5> out=<effect.h5>")
+    if opts is None:
         return 2
     try:
         tree = effect_summary(opts["baseline"], opts["perturbed"])
     except (OSError, KeyError, ValueError) as e:
-        print(f"[intervene] {e.args[0] if e.args else e}", file=sys.stderr)
-        return 2
-    os.makedirs(os.path.dirname(os.path.abspath(opts["out"])), exist_ok=True)
-    from .utils import _to_tree
-    h5lite.write_tree(opts["out"], _to_tree(tree))
+        return cli.report("intervene", e)
+    cli.write(opts["out"], to_tree(tree))
     d = [int(v["first_divergence"]) for v in tree.values()]
     dr = [float(v["reward_mean_difference"]) for v in tree.values()]
     print(f"[intervene] {len(tree)} clips; diverged: {sum(x >= 0 for x in d)} (first step: {min([x for x in d if x >= 0], default=-1)}); "

@@ -38,12 +38,14 @@ from __future__ import annotations
 
 import os
 import sys
+from typing import NamedTuple
 
 import numpy as np
 
 from .. import hip as _hip
-from . import pca as _pca
-from .utils import rollout_features
+from . import cli
+from .backend import resolve
+from .recorded import aligned_of, feature_of, labels_for_rows, meta_of, rollout_features, scatter_per_clip
 
 CLI_OPTIONS = ("checkpoint", "rollouts", "wrt", "mode", "max_rows", "seed", "labels", "store", "out", "features_out")
 USAGE = ("usage: python -m track_mjx_amd.analysis.jacobian checkpoint=<run dir | step dir> rollouts=<dir of clip_<i>.h5> [wrt=intention | input:a:b] "
@@ -143,64 +145,94 @@ def _carry_of(r, where):
     return out[0], out[1]
 
 
-def _read_lstm_clip(r, clip, where):
-    """_read_clip for an LSTM roll-out, plus the carry ENTERING every step [T-1, L H] twice (h, c) and its (L, H): the recorded carry of the row
-    before, zeros at t = 0 and behind a step whose `aligned` flag is set."""
-    from .. import h5lite
-    from .spectrogram import _tree
-    if isinstance(r, h5lite.File):
-        meta = _tree(r["meta"]) if "meta" in r else None
-    else:
-        meta = r.get("meta") if hasattr(r, "get") else None
+class Clip(NamedTuple):
+    """What the decoder tools read of one roll-out.  The last four are an LSTM roll-out's."""
+    x: np.ndarray                  # [T-1, d_in]: the decoder's input rows [intention | egocentric_obs]
+    Z: int                         # the width of the intention
+    logvar: np.ndarray | None      # encoder/logvar [T-1, Z], where recorded
+    ctrl: np.ndarray | None        # the recorded ctrl [T-1, A], where recorded
+    meta: dict | None              # the roll-out's meta tree
+    h_in: np.ndarray | None = None       # [T-1, L H]: the carry ENTERING every step: the recorded one of the row before, zeros at t = 0 and behind a
+    c_in: np.ndarray | None = None       # step whose `aligned` flag is set
+    shape: tuple | None = None           # (L, H) of the recorded carry
+    aligned: np.ndarray | None = None    # bool [T-1]: the step ended with a re-alignment (the roll-out zeroed the carry behind it)
+
+
+def read_clip(r, clip, where) -> Clip:
+    z, prop = feature_of(r, "intention", where), feature_of(r, "egocentric_obs", where)
+    if z.shape[0] != prop.shape[0]:
+        raise ValueError(f"{where}: intention has {z.shape[0]} rows, egocentric_obs {prop.shape[0]}")
+    try:
+        logvar = feature_of(r, "encoder/logvar", where)
+    except KeyError:
+        logvar = None
+    try:
+        ctrl = feature_of(r, "ctrl", where)[:z.shape[0]]
+    except KeyError:
+        ctrl = None
+    return Clip(np.concatenate([z, prop], 1), z.shape[1], logvar, ctrl, meta_of(r))
+
+
+def read_lstm_clip(r, clip, where) -> Clip:
+    """read_clip for an LSTM roll-out, with the carry placed at every step; a roll-out without the carry or the input, or a replay, is refused by name."""
+    meta = meta_of(r)
     if meta is not None and "replay_latents" in meta:
         raise ValueError(LSTM_REPLAY.format(where=where))
     carry = _carry_of(r, where)
     if carry is None:
         raise ValueError(LSTM_NO_CARRY.format(where=where))
     try:
-        _pca._feature_of(r, "egocentric_obs", where)
+        feature_of(r, "egocentric_obs", where)
     except KeyError:
         raise ValueError(LSTM_NO_INPUT.format(where=where)) from None
-    x, Z, logvar, ctrl, meta = _read_clip(r, clip, where)
+    one = read_clip(r, clip, where)
     h, c = carry
     T1, L, H = h.shape
-    if T1 != x.shape[0]:
-        raise ValueError(f"{where}: hidden_state has {T1} rows, intention {x.shape[0]}")
+    if T1 != one.x.shape[0]:
+        raise ValueError(f"{where}: hidden_state has {T1} rows, intention {one.x.shape[0]}")
+    aligned = aligned_of(r, T1, where)
+    aligned = np.zeros(T1, bool) if aligned is None else aligned
     keep = np.ones(T1, bool)
     keep[0] = False
-    try:
-        node = r["aligned"]
-        aligned = np.asarray(node if isinstance(node, np.ndarray) else node[()]).reshape(-1) != 0
-        if aligned.shape[0] != T1:
-            raise ValueError(f"{where}: aligned has {aligned.shape[0]} rows, intention {T1}")
-        keep[1:] &= ~aligned[:-1]
-    except (KeyError, IndexError, TypeError):
-        pass
+    keep[1:] &= ~aligned[:-1]
     h_in, c_in = np.zeros((T1, L * H), np.float32), np.zeros((T1, L * H), np.float32)
     h_in[1:], c_in[1:] = h.reshape(T1, -1)[:-1], c.reshape(T1, -1)[:-1]
     h_in[~keep], c_in[~keep] = 0.0, 0.0
-    return x, Z, logvar, ctrl, meta, h_in, c_in, (L, H)
+    return one._replace(h_in=h_in, c_in=c_in, shape=(L, H), aligned=aligned)
 
 
-def _read_clip(r, clip, where):
-    z, prop = _pca._feature_of(r, "intention", where), _pca._feature_of(r, "egocentric_obs", where)
-    if z.shape[0] != prop.shape[0]:
-        raise ValueError(f"{where}: intention has {z.shape[0]} rows, egocentric_obs {prop.shape[0]}")
-    try:
-        logvar = _pca._feature_of(r, "encoder/logvar", where)
-    except KeyError:
-        logvar = None
-    try:
-        ctrl = _pca._feature_of(r, "ctrl", where)[:z.shape[0]]
-    except KeyError:
-        ctrl = None
-    from .. import h5lite
-    from .spectrogram import _tree
-    if isinstance(r, h5lite.File):
-        meta = _tree(r["meta"]) if "meta" in r else None
-    else:
-        meta = r.get("meta") if hasattr(r, "get") else None
-    return np.concatenate([z, prop], 1), z.shape[1], logvar, ctrl, meta
+def read_clips(rollouts, layers, lstm: bool, verb: str):
+    """-> (clip numbers, the Clip of every roll-out), read for the decoder `layers` belong to; roll-outs another checkpoint made are refused."""
+    d_in = layers[0][0].shape[1]
+    ids, clips = rollout_features(rollouts, read_lstm_clip if lstm else read_clip, "the decoder's input", verb)
+    width = clips[0].x.shape[1]
+    if width != d_in:
+        raise ValueError(f"the roll-outs' decoder input [intention | egocentric_obs] is {width} wide, the checkpoint's decoder takes {d_in}: "
+                         "this checkpoint did not make these roll-outs")
+    Lk, H = (len(layers), layers[0][1].shape[1]) if lstm else (0, 0)
+    if lstm and any(c.shape != (Lk, H) for c in clips):
+        raise ValueError(f"the roll-outs' hidden_state is [T-1, L, H] with (L, H) = {sorted({c.shape for c in clips})}, the checkpoint's decoder has "
+                         f"{Lk} layers of {H} units: this checkpoint did not make these roll-outs")
+    return ids, clips
+
+
+def forward_mismatch(ctrl, clips, A: int, rows) -> np.float64:
+    """The largest |recomputed ctrl - recorded ctrl| over the evaluated `rows`; NaN where a roll-out did not record ctrl [T-1, A]."""
+    if not all(c.ctrl is not None and c.ctrl.shape[1] == A for c in clips):
+        return np.float64(np.nan)
+    return np.float64(np.abs(ctrl.astype(np.float64) - np.concatenate([c.ctrl for c in clips], 0)[rows]).max())
+
+
+def warn_mismatch(tool: str, mismatch: float) -> None:
+    if mismatch > MISMATCH_WARN:
+        print(f"[{tool}] warning: the recomputed ctrl differs from the recorded one by up to {mismatch:.3g} (> {MISMATCH_WARN}): did this checkpoint make "
+              "these roll-outs, and without an intervention downstream of the intention?", file=sys.stderr)
+
+
+def feature_trees(ids, clips, series: dict) -> dict:
+    """What features_out= writes, {clip: tree}: activations/<name> of every per-clip series {name: {clip_<c>: [T-1, ...]}} and the clip's meta."""
+    return {c: {"activations": {name: per[f"clip_{c}"] for name, per in series.items()}, **({} if clip.meta is None else {"meta": clip.meta})}
+            for c, clip in zip(ids, clips)}
 
 
 def _parse_wrt(wrt: str, Z: int, d_in: int) -> tuple:
@@ -219,14 +251,6 @@ def _parse_wrt(wrt: str, Z: int, d_in: int) -> tuple:
     if b - a > _hip.JACOBIAN_MAX_WRT:
         raise ValueError(f"wrt = {wrt}: {b - a} columns exceed the {_hip.JACOBIAN_MAX_WRT} one call differentiates; pick a range with wrt=input:a:b")
     return a, b - a
-
-
-def _labels_file(path):
-    from .. import h5lite
-    with h5lite.File(str(path)) as h:
-        if "labels" not in h:
-            raise KeyError(f"{path} has no labels group (write it with analysis.cluster, hmm, arhmm or embed)")
-        return {int(k.split("_", 1)[1]): np.asarray(h["labels"][k][()]).reshape(-1) for k in h["labels"].keys()}
 
 
 def eigen(gram, backend):
@@ -249,33 +273,25 @@ def jacobian_rollouts(checkpoint, rollouts, wrt="intention", mode="ctrl", max_ro
     model, layers, head, eps = load_decoder(checkpoint)
     lstm = model == "lstm"
     d_in, A = layers[0][0].shape[1], head[2]
-    ids, items = rollout_features(rollouts, _read_lstm_clip if lstm else _read_clip, "the decoder's input", "differentiate")
-    width = items[0][0].shape[1]
-    if width != d_in:
-        raise ValueError(f"the roll-outs' decoder input [intention | egocentric_obs] is {width} wide, the checkpoint's decoder takes {d_in}: "
-                         "this checkpoint did not make these roll-outs")
-    Z = items[0][1]
+    ids, clips = read_clips(rollouts, layers, lstm, "differentiate")
+    Z = clips[0].Z
     Lk, H = (len(layers), layers[0][1].shape[1]) if lstm else (0, 0)
     W = 2 * Lk * H
-    if lstm and any(it[7] != (Lk, H) for it in items):
-        raise ValueError(f"the roll-outs' hidden_state is [T-1, L, H] with (L, H) = {sorted({it[7] for it in items})}, the checkpoint's decoder has "
-                         f"{Lk} layers of {H} units: this checkpoint did not make these roll-outs")
     col0, cols = _parse_wrt(wrt, Z, d_in)
-    lens = [it[0].shape[0] for it in items]
+    lens = [c.x.shape[0] for c in clips]
     n = int(sum(lens))
     if n < 1:
         raise ValueError("the roll-outs hold no recorded step")
-    x = np.ascontiguousarray(np.concatenate([it[0] for it in items], 0), np.float32)
+    x = np.ascontiguousarray(np.concatenate([c.x for c in clips], 0), np.float32)
     scale = None
-    if all(it[2] is not None for it in items) and col0 + cols <= Z:
-        lv = np.concatenate([it[2] for it in items], 0)[:, col0:col0 + cols]
+    if all(c.logvar is not None for c in clips) and col0 + cols <= Z:
+        lv = np.concatenate([c.logvar for c in clips], 0)[:, col0:col0 + cols]
         scale = np.ascontiguousarray(np.exp(0.5 * lv.astype(np.float64)), np.float32)
-    recorded = np.concatenate([it[3] for it in items], 0) if all(it[3] is not None and it[3].shape[1] == A for it in items) else None
     max_rows = int(max_rows)
     if max_rows < 0:
         raise ValueError(f"max_rows must be >= 0 (got {max_rows})")
     # a row that is not finite (a roll-out whose physics diverged is recorded to its end) is never evaluated: its series stay NaN
-    carry = np.ascontiguousarray(np.concatenate([np.concatenate([it[5], it[6]], 1) for it in items], 0), np.float32) if lstm else None      # [n, h | c]
+    carry = np.ascontiguousarray(np.concatenate([np.concatenate([c.h_in, c.c_in], 1) for c in clips], 0), np.float32) if lstm else None      # [n, h | c]
     finite = np.flatnonzero(np.isfinite(x).all(1) & (np.isfinite(scale).all(1) if scale is not None else True) & (np.isfinite(carry).all(1) if lstm else True))
     if finite.shape[0] < 1:
         raise ValueError("no recorded step has a finite decoder input")
@@ -292,7 +308,7 @@ def jacobian_rollouts(checkpoint, rollouts, wrt="intention", mode="ctrl", max_ro
         raise ValueError(f"store=true: {m} rows x {A} x {cols} float32 exceed 2^31 bytes; sample with max_rows= or differentiate fewer columns")
     if store and lstm and m * A * W * 4 > STORE_MAX_BYTES:
         raise ValueError(f"store=true: {m} rows x {A} x {W} float32 of the carry Jacobian exceed 2^31 bytes; sample with max_rows=")
-    bk = _pca.HipBackend(device) if backend is None else backend
+    bk = resolve(backend, device)
     xa, sa = bk.asarray(x), None if scale is None else bk.asarray(scale)
     want = ("ctrl", "gain", "col2", "row2") + (("jac",) if store else ())
     rows = np.arange(n) if index is None else index.astype(np.int64)
@@ -311,12 +327,9 @@ def jacobian_rollouts(checkpoint, rollouts, wrt="intention", mode="ctrl", max_ro
         res = evaluate(index, sa, want)
     except _hip.TmjxError as e:
         raise ValueError(str(e)) from None
-    ends = np.cumsum(lens)
 
     def per_clip(a):
-        full = np.full((n, *a.shape[1:]), np.nan, np.float32)
-        full[rows] = a
-        return {f"clip_{c}": full[e - t:e] for c, e, t in zip(ids, ends, lens)}
+        return scatter_per_clip(a, rows, n, ids, lens)
     out = {"gain": per_clip(res["gain"]), "latent_sensitivity": per_clip(res["col2"]), "actuator_sensitivity": per_clip(res["row2"])}
     if "action_var" in res:
         out["action_var"] = per_clip(res["action_var"])
@@ -335,19 +348,11 @@ def jacobian_rollouts(checkpoint, rollouts, wrt="intention", mode="ctrl", max_ro
                 "mean": x[rows, col0:col0 + cols].astype(np.float64).mean(0).astype(np.float32), "components": vectors.astype(np.float32),
                 "explained_variance": values.astype(np.float32),
                 "explained_variance_ratio": (values / total if total > 0.0 else np.zeros_like(values)).astype(np.float32),
-                "forward_mismatch": np.float64(np.abs(res["ctrl"].astype(np.float64) - recorded[rows]).max()) if recorded is not None else np.float64(np.nan),
-                "rows": np.int64(m), "wrt": f"{col0}:{col0 + cols}", "mode": mode, "clips": np.asarray(ids, np.int64), "model": model})
+                "forward_mismatch": forward_mismatch(res["ctrl"], clips, A, rows), "rows": np.int64(m), "wrt": f"{col0}:{col0 + cols}", "mode": mode, "clips": np.asarray(ids, np.int64), "model": model})
     if index is not None:
         out["row_index"] = index.astype(np.int64)
     if labels is not None:
-        lab = _labels_file(labels) if isinstance(labels, (str, os.PathLike)) else {int(k): np.asarray(v).reshape(-1) for k, v in dict(labels).items()}
-        flat = np.full(n, -1, np.int64)
-        for c, e, t in zip(ids, ends, lens):
-            if c not in lab:
-                raise KeyError(f"the labels file has no clip_{c}")
-            if lab[c].shape[0] < t:
-                raise ValueError(f"the labels of clip_{c} hold {lab[c].shape[0]} rows, the roll-out {t}")
-            flat[e - t:e] = lab[c][:t]
+        flat = labels_for_rows(labels, ids, lens)
         K = int(flat.max()) + 1
         picked = np.zeros(n, bool)
         picked[rows] = True
@@ -365,52 +370,32 @@ def jacobian_rollouts(checkpoint, rollouts, wrt="intention", mode="ctrl", max_ro
         if lstm:
             out.update({"motif_mean_carry_jacobian": mcj, "motif_memory_sensitivity": mms})
     if features:
-        out["features"] = {}
-        for j, c in enumerate(ids):
-            tree = {"activations": {"latent_sensitivity": out["latent_sensitivity"][f"clip_{c}"], "actuator_sensitivity": out["actuator_sensitivity"][f"clip_{c}"],
-                                    "jacobian_gain": out["gain"][f"clip_{c}"].reshape(-1, 1)}}
-            if lstm:
-                tree["activations"]["memory_sensitivity"] = out["memory_sensitivity"][f"clip_{c}"]
-            if items[j][4] is not None:
-                tree["meta"] = items[j][4]
-            out["features"][c] = tree
+        series = {"latent_sensitivity": out["latent_sensitivity"], "actuator_sensitivity": out["actuator_sensitivity"],
+                  "jacobian_gain": {key: v.reshape(-1, 1) for key, v in out["gain"].items()}}
+        if lstm:
+            series["memory_sensitivity"] = out["memory_sensitivity"]
+        out["features"] = feature_trees(ids, clips, series)
     return out
-
-
-def _flag(opts, name):
-    v = opts.get(name, "false").lower()
-    if v not in ("true", "false"):
-        raise ValueError(f"{name} must be true or false (got {opts[name]})")
-    return v == "true"
 
 
 def main(argv=None, backend=None, policy=None) -> int:
     """The command line; `policy`: a module or policy object in place of checkpoint= (DecoderNet, IntentionPolicy, DecoderPolicy; LSTMIntentionPolicy,
     LSTMDecoderPolicy), `backend`: a stand-in for HipBackend."""
-    from .. import h5lite
-    argv = list(sys.argv[1:] if argv is None else argv)
-    opts = dict(a.split("=", 1) for a in argv if "=" in a and a.split("=", 1)[0] in CLI_OPTIONS)
-    if ("checkpoint" not in opts and policy is None) or "rollouts" not in opts or "out" not in opts or len(opts) != len(argv):
-        print(USAGE, file=sys.stderr)
+    opts = cli.parse(argv, CLI_OPTIONS, ("rollouts", "out"), USAGE, lambda o: "checkpoint" in o or policy is not None)
+    if opts is None:
         return 2
     try:
         res = jacobian_rollouts(opts["checkpoint"] if policy is None else policy, opts["rollouts"], opts.get("wrt", "intention"), opts.get("mode", "ctrl"),
-                                int(opts.get("max_rows", 0)), int(opts.get("seed", 0)), opts.get("labels"), _flag(opts, "store"), "features_out" in opts,
+                                int(opts.get("max_rows", 0)), int(opts.get("seed", 0)), opts.get("labels"), cli.flag(opts, "store"), "features_out" in opts,
                                 backend=backend)
     except (KeyError, ValueError, OSError) as e:
-        print(f"[jacobian] {e.args[0] if e.args else e}", file=sys.stderr)
-        return 2
+        return cli.report("jacobian", e)
     feats = res.pop("features", None)
-    os.makedirs(os.path.dirname(os.path.abspath(opts["out"])), exist_ok=True)
-    h5lite.write_tree(opts["out"], res)
+    cli.write(opts["out"], res)
     if feats is not None:
-        os.makedirs(opts["features_out"], exist_ok=True)
-        for c, tree in feats.items():
-            h5lite.write_tree(os.path.join(opts["features_out"], f"clip_{c}.h5"), tree)
+        cli.write_clips(opts["features_out"], feats)
     mismatch = float(res["forward_mismatch"])
-    if mismatch > MISMATCH_WARN:
-        print(f"[jacobian] warning: the recomputed ctrl differs from the recorded one by up to {mismatch:.3g} (> {MISMATCH_WARN}): did this checkpoint make "
-              "these roll-outs, and without an intervention downstream of the intention?", file=sys.stderr)
+    warn_mismatch("jacobian", mismatch)
     ratio = ", ".join(f"{100 * r:.1f}%" for r in res["explained_variance_ratio"][:4])
     print(f"[jacobian] d {res['mode']} / d input[{res['wrt']}]: {int(res['rows'])} rows of {len(res['clips'])} clips, {res['mean_jacobian'].shape[0]} actuators; "
           f"mean gain {float(np.trace(res['gram_in'])):.4g}, the leading sensitive directions carry {ratio}; forward mismatch {mismatch:.3g}; wrote {opts['out']}",

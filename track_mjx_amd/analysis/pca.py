@@ -12,16 +12,17 @@ writes mean, components, explained_variance, explained_variance_ratio, feature, 
 """
 from __future__ import annotations
 
-import os
 import sys
 
 import numpy as np
 
 from .. import hip as _hip
-from .backend import HipBackend      # (analysis/backend.py: the calls of every analysis; importers find it here)
-from .utils import rollout_features
+from . import cli
+from .backend import HipBackend, resolve      # noqa: F401  (analysis/backend.py: the calls of every analysis; tests and tools take pca.HipBackend)
+from .recorded import by_clip, feature_of, rollout_features, split
 
 CLI_OPTIONS = ("rollouts", "out", "feature", "n_components")
+USAGE = "usage: python -m track_mjx_amd.analysis.pca rollouts=<dir of clip_<i>.h5> [feature=intention] [n_components=4] out=<pca.h5>"
 # the first eight of matplotlib's default colour cycle (what the reference's curves get), then background, axes, "terminated" line
 STRIP_COLOURS = ((31, 119, 180), (255, 127, 14), (44, 160, 44), (214, 39, 40), (148, 103, 189), (140, 86, 75), (227, 119, 194), (127, 127, 127))
 
@@ -50,7 +51,7 @@ class PCA:
         if n_components is not None and int(n_components) < 1:
             raise ValueError(f"n_components must be >= 1 (got {n_components})")
         self.n_components = None if n_components is None else int(n_components)
-        self._b = HipBackend(device) if backend is None else backend
+        self._b = resolve(backend, device)
 
     def fit(self, x):
         xa = self._b.asarray(x)
@@ -81,51 +82,29 @@ class PCA:
         return self.fit(x).transform(x)
 
 
-def _feature_of(rollout, feature: str, where: str) -> np.ndarray:
-    """The recorded feature of one roll-out as [T, D]: `ctrl`, or a path under activations/ (intention, decoder/layer_0, hidden_state/h, ...)."""
-    node, path = rollout, ([feature] if feature == "ctrl" else ["activations", *[p for p in feature.split("/") if p]])
-    for part in path:
-        try:
-            node = node[part]
-        except (KeyError, IndexError, TypeError):
-            raise KeyError(f"{where} has no {'/'.join(path)}" + (" (roll it out with log_activations=true)" if feature != "ctrl" else "")) from None
-    if hasattr(node, "keys"):
-        raise KeyError(f"{where}: {'/'.join(path)} is a group ({', '.join(node.keys())}), not a recorded array")
-    a = np.asarray(node if isinstance(node, (np.ndarray, list, tuple)) else node[()], np.float32)      # (an h5lite dataset reads with [()])
-    if a.ndim < 2:
-        raise ValueError(f"{where}: {'/'.join(path)} has shape {a.shape}, expected [T, D]")
-    return a.reshape(-1, a.shape[-1])
-
-
 def fit_rollouts(rollouts, feature: str = "intention", n_components: int | None = None, device="cuda", backend=None):
     """Fit one PCA on `feature` (up to 1024 wide) over every roll-out and project each.  `rollouts`: a directory of clip_<i>.h5, or a list of roll-out dicts.
     -> (pca, projections): projections[j] float32 [T_j, K] of roll-out j; pca.clips_ are the clip numbers (the list positions for dicts)."""
-    ids, feats = rollout_features(rollouts, lambda r, _, where: _feature_of(r, feature, where), feature, "fit")
+    ids, feats = rollout_features(rollouts, lambda r, _, where: feature_of(r, feature, where), feature, "fit")
     pca = PCA(n_components, device=device, backend=backend)
     x = pca._b.asarray(np.concatenate(feats, 0))
     proj = pca._b.to_numpy(pca.fit(x).transform(x))
     pca.clips_, pca.feature_ = ids, feature
-    ends = np.cumsum([f.shape[0] for f in feats])
-    return pca, [proj[e - f.shape[0]:e] for e, f in zip(ends, feats)]
+    return pca, split(proj, [f.shape[0] for f in feats])
 
 
 def main(argv=None, backend=None) -> int:
-    from .. import h5lite
-    argv = list(sys.argv[1:] if argv is None else argv)
-    opts = dict(a.split("=", 1) for a in argv if "=" in a and a.split("=", 1)[0] in CLI_OPTIONS)
-    if "rollouts" not in opts or "out" not in opts or len(opts) != len(argv):
-        print("usage: python -m track_mjx_amd.analysis.pca rollouts=<dir of clip_<i>.h5> [feature=intention] [n_components=4] out=<pca.h5>", file=sys.stderr)
+    opts = cli.parse(argv, CLI_OPTIONS, ("rollouts", "out"), USAGE)
+    if opts is None:
         return 2
     feature = opts.get("feature", "intention")
     try:
         pca, proj = fit_rollouts(opts["rollouts"], feature, int(opts.get("n_components", 4)), backend=backend)
     except (KeyError, ValueError) as e:
-        print(f"[pca] {e.args[0] if e.args else e}", file=sys.stderr)
-        return 2
-    os.makedirs(os.path.dirname(os.path.abspath(opts["out"])), exist_ok=True)
-    h5lite.write_tree(opts["out"], {"mean": pca.mean_, "components": pca.components_, "explained_variance": pca.explained_variance_,
-                                    "explained_variance_ratio": pca.explained_variance_ratio_, "feature": feature, "n_samples": np.int64(pca.n_samples_),
-                                    "clips": np.asarray(pca.clips_, np.int64), "projections": {f"clip_{c}": p for c, p in zip(pca.clips_, proj)}})
+        return cli.report("pca", e)
+    cli.write(opts["out"], {"mean": pca.mean_, "components": pca.components_, "explained_variance": pca.explained_variance_,
+                            "explained_variance_ratio": pca.explained_variance_ratio_, "feature": feature, "n_samples": np.int64(pca.n_samples_),
+                            "clips": np.asarray(pca.clips_, np.int64), "projections": by_clip(pca.clips_, proj)})
     ratio = ", ".join(f"{100 * r:.1f}%" for r in pca.explained_variance_ratio_)
     print(f"[pca] {feature}: {pca.n_samples_} samples x {pca.n_features_} features from {len(proj)} clips, {pca.n_sweeps_} sweeps; explained variance "
           f"{ratio}; wrote {opts['out']}", flush=True)

@@ -12,19 +12,19 @@ test_clips and predictions/clip_<i> [T', M] of the held-out clips.
 """
 from __future__ import annotations
 
-import os
-import re
 import sys
 
 import numpy as np
 
 from .. import hip as _hip
-from . import pca as _pca
-from .utils import rollout_features
+from . import cli
+from .backend import resolve
+from .recorded import by_clip, columns, feature_of, rollout_features, target_of
 
 CLI_OPTIONS = ("rollouts", "out", "feature", "target", "target_cols", "alphas", "holdout", "lag")
+USAGE = ("usage: python -m track_mjx_amd.analysis.readout rollouts=<dir of clip_<i>.h5> feature=<layer> target=<recorded array> [target_cols=a:b] "
+         "[alphas=1e-3,1e-2,1e-1,1] [holdout=5] [lag=0] out=<readout.h5>")
 DEFAULT_ALPHAS = (1e-3, 1e-2, 1e-1, 1.0, 10.0)
-PLAIN_TARGETS = ("ctrl", "qposes_rollout", "qposes_ref", "state_rewards", "joint_forces", "sensor_readings")
 
 
 class Ridge:
@@ -41,7 +41,7 @@ class Ridge:
         if not (np.isfinite(a) & (a > 0)).all():
             raise ValueError(f"every alpha must be finite and > 0 (got {a.tolist()}): alpha = 0 is not a ridge, and a rank-deficient layer needs one")
         self.alphas_ = a
-        self._b = _pca.HipBackend(device) if backend is None else backend
+        self._b = resolve(backend, device)
 
     @staticmethod
     def _columns(y):
@@ -94,39 +94,6 @@ class Ridge:
         return self._b.to_numpy(out) if isinstance(x, np.ndarray) else out
 
 
-def _target_of(rollout, target: str, where: str) -> np.ndarray:
-    """The recorded target of one roll-out as [rows, M] float32."""
-    if target.startswith("activations/"):
-        return _pca._feature_of(rollout, target[len("activations/"):], where)
-    parts = [p for p in target.split("/") if p]
-    if not (target in PLAIN_TARGETS or (len(parts) == 2 and parts[0] == "rollout_metrics")):
-        raise KeyError(f"unknown target {target!r}: one of {', '.join(PLAIN_TARGETS)}, rollout_metrics/<name> or activations/<path>")
-    node = rollout
-    for part in parts:
-        try:
-            node = node[part]
-        except (KeyError, IndexError, TypeError):
-            raise KeyError(f"{where} has no {target}" + (" (roll it out with log_sensors=true)" if target in ("joint_forces", "sensor_readings") else "")) from None
-    if hasattr(node, "keys"):
-        raise KeyError(f"{where}: {target} is a group ({', '.join(node.keys())}), not a recorded array")
-    a = np.asarray(node if isinstance(node, (np.ndarray, list, tuple)) else node[()], np.float32)
-    if a.ndim < 1:
-        raise ValueError(f"{where}: {target} is a scalar")
-    return a.reshape(a.shape[0], -1)      # (joint_forces [T - 1, nbody, 6] -> [T - 1, 6 nbody]; a [T] series -> [T, 1])
-
-
-def _cols(spec, width: int) -> slice:
-    if spec is None or spec == "":
-        return slice(0, width)
-    m = re.fullmatch(r"(-?\d*):(-?\d*)", str(spec))
-    if not m:
-        raise ValueError(f"target_cols = {spec!r}: expected a:b")
-    sl = slice(int(m.group(1)) if m.group(1) else None, int(m.group(2)) if m.group(2) else None)
-    if len(range(*sl.indices(width))) < 1:
-        raise ValueError(f"target_cols = {spec} selects no column of {width}")
-    return sl
-
-
 def _align(feat, targ, lag: int, where: str):
     """Rows of one roll-out: activation row t is paired with target[t + lag], and the rows without a partner are dropped.  A per-frame series (T rows
     against the T - 1 steps) has a partner for every row at either lag; a per-step one (T - 1 rows) is used as it is at lag 0 and loses its last
@@ -139,7 +106,7 @@ def _align(feat, targ, lag: int, where: str):
 
 
 def fit_rollouts(rollouts, feature: str, target: str, alphas=DEFAULT_ALPHAS, holdout: int = 5, lag: int = 0, target_cols=None, device="cuda", backend=None):
-    """Fit a `Ridge` from `feature` (as analysis.pca resolves it) to `target` over the training clips and score it on the held-out ones: of the sorted
+    """Fit a `Ridge` from `feature` (as recorded.feature_of resolves it) to `target` over the training clips and score it on the held-out ones: of the sorted
     clip list, the positions p with p % holdout == holdout - 1.  `rollouts`: a directory of clip_<i>.h5, or a list of roll-out dicts.
     -> the fitted Ridge with r2_ [L, M], best_index_, train_clips_, test_clips_ (clip numbers; list positions for dicts), feature_, target_, and
     test_features_ (the held-out clips' feature rows, for predictions)."""
@@ -148,12 +115,12 @@ def fit_rollouts(rollouts, feature: str, target: str, alphas=DEFAULT_ALPHAS, hol
         raise ValueError(f"holdout must be >= 2 (got {holdout})")
     if lag not in (0, 1):
         raise ValueError(f"lag must be 0 or 1 (got {lag})")
-    ids, pairs = rollout_features(rollouts, lambda r, _, where: (_pca._feature_of(r, feature, where), _target_of(r, target, where)))
+    ids, pairs = rollout_features(rollouts, lambda r, _, where: (feature_of(r, feature, where), target_of(r, target, where)))
     if len(ids) < 2:
         raise ValueError(f"a held-out score needs at least two clips (got {len(ids)})")
     if len({f.shape[1] for f, _ in pairs}) != 1 or len({t.shape[1] for _, t in pairs}) != 1:
         raise ValueError(f"{feature} or {target} has different widths across roll-outs")
-    sl = _cols(target_cols, pairs[0][1].shape[1])
+    sl = columns(target_cols, pairs[0][1].shape[1])
     width = len(range(*sl.indices(pairs[0][1].shape[1])))
     if width > _hip.READOUT_MAX_M:
         raise ValueError(f"{target} is {width} wide: a readout takes up to {_hip.READOUT_MAX_M} targets, pick columns with target_cols=a:b")
@@ -172,28 +139,21 @@ def fit_rollouts(rollouts, feature: str, target: str, alphas=DEFAULT_ALPHAS, hol
 
 
 def main(argv=None, backend=None) -> int:
-    from .. import h5lite
-    argv = list(sys.argv[1:] if argv is None else argv)
-    opts = dict(a.split("=", 1) for a in argv if "=" in a and a.split("=", 1)[0] in CLI_OPTIONS)
-    if any(k not in opts for k in ("rollouts", "out", "feature", "target")) or len(opts) != len(argv):
-        print("usage: python -m track_mjx_amd.analysis.readout rollouts=<dir of clip_<i>.h5> feature=<layer> target=<recorded array> [target_cols=a:b] "
-              "[alphas=1e-3,1e-2,1e-1,1] [holdout=5] [lag=0] out=<readout.h5>", file=sys.stderr)
+    opts = cli.parse(argv, CLI_OPTIONS, ("rollouts", "out", "feature", "target"), USAGE)
+    if opts is None:
         return 2
     try:
         alphas = tuple(float(v) for v in opts["alphas"].split(",")) if "alphas" in opts else DEFAULT_ALPHAS
         r = fit_rollouts(opts["rollouts"], opts["feature"], opts["target"], alphas, int(opts.get("holdout", 5)), int(opts.get("lag", 0)),
                          opts.get("target_cols"), backend=backend)
     except (KeyError, ValueError) as e:
-        print(f"[readout] {e.args[0] if e.args else e}", file=sys.stderr)
-        return 2
+        return cli.report("readout", e)
     best = r.best_index_
     r2_mean = np.array([np.nanmean(v) if np.isfinite(v).any() else np.nan for v in r.r2_])
-    os.makedirs(os.path.dirname(os.path.abspath(opts["out"])), exist_ok=True)
-    h5lite.write_tree(opts["out"], {"alphas": r.alphas_, "lambdas": r.lambdas_, "r2": r.r2_, "r2_mean": r2_mean, "best_index": np.int64(best),
-                                    "coef": r.coef_[best], "intercept": r.intercept_[best], "mean_x": r.mean_, "mean_y": r.mean_y_,
-                                    "feature": r.feature_, "target": r.target_, "train_clips": np.asarray(r.train_clips_, np.int64),
-                                    "test_clips": np.asarray(r.test_clips_, np.int64),
-                                    "predictions": {f"clip_{c}": r.predict(f) for c, f in zip(r.test_clips_, r.test_features_)}})
+    cli.write(opts["out"], {"alphas": r.alphas_, "lambdas": r.lambdas_, "r2": r.r2_, "r2_mean": r2_mean, "best_index": np.int64(best), "coef": r.coef_[best],
+                            "intercept": r.intercept_[best], "mean_x": r.mean_, "mean_y": r.mean_y_, "feature": r.feature_, "target": r.target_,
+                            "train_clips": np.asarray(r.train_clips_, np.int64), "test_clips": np.asarray(r.test_clips_, np.int64),
+                            "predictions": by_clip(r.test_clips_, [r.predict(f) for f in r.test_features_])})
     print(f"[readout] {r.feature_} -> {r.target_}: {r.n_samples_} samples x {r.n_features_} features -> {r.n_targets_} targets, {len(r.train_clips_)} training and "
           f"{len(r.test_clips_)} held-out clips; held-out R2 by alpha " + ", ".join(f"{a:g}: {v:.4f}" for a, v in zip(r.alphas_, r2_mean)) +
           f"; best alpha {r.alphas_[best]:g}; wrote {opts['out']}", flush=True)

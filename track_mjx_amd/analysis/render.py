@@ -22,6 +22,8 @@ import numpy as np
 
 from .. import hip as _hip
 from .. import walker as _walker
+from . import cli
+from .backend import resolve
 
 CLI_OPTIONS = ("rollouts", "out", "camera", "size", "ghost", "every", "checkpoint", "step", "pca", "pca_window")
 MAX_FRAMES_PER_CALL = 64      # frames rendered per launch pair: bounds the output buffers (64 frames of 640 x 480: 79 MB rgba)
@@ -196,7 +198,7 @@ def plot_pca_progression(projections, frame_idx, n_components: int = 4, window_s
     terminated line.  The y limits are min - 0.2 / max + 0.2 over those columns of the whole clip, as the reference takes them.  Drawn in batches of
     MAX_FRAMES_PER_CALL frames; `backend`: a stand-in for pca.HipBackend."""
     from . import pca as _pca
-    b = _pca.HipBackend(device) if backend is None else backend
+    b = resolve(backend, device)
     width, height = int(size[0]), int(size[1])
     host = projections if isinstance(projections, np.ndarray) else None
     p = b.asarray(projections)
@@ -251,9 +253,7 @@ def _write_gif(path, frames, fps) -> bool:
 def main(argv=None, renderer_cls=None, pca_backend=None) -> int:
     from .. import config as _config
     from .. import h5lite
-    argv = list(sys.argv[1:] if argv is None else argv)
-    opts = dict(a.split("=", 1) for a in argv if "=" in a and a.split("=", 1)[0] in CLI_OPTIONS)
-    rest = [a for a in argv if not ("=" in a and a.split("=", 1)[0] in opts)]
+    opts, rest = cli.split(list(sys.argv[1:] if argv is None else argv), CLI_OPTIONS)      # (the rest: config overrides)
     if "rollouts" not in opts or "out" not in opts:
         print("usage: python -m track_mjx_amd.analysis.render rollouts=<dir of clip_<i>.h5> out=<dir> [camera=close_profile] [size=640x480] "
               "[ghost=true] [every=1] [checkpoint=<run dir | step dir>] [pca=<pca.h5>] [pca_window=530] [key=value config overrides ...]", file=sys.stderr)

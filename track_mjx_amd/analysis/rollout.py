@@ -677,9 +677,8 @@ def _main_replay(opts: dict, cfg: dict, step_dir: str, intervention=None) -> int
 
 def _split_argv(argv) -> tuple:
     """(the roll-out's own key=value options, everything else: config overrides in train's syntax)."""
-    opts = dict(a.split("=", 1) for a in argv if "=" in a and a.split("=", 1)[0] in CLI_OPTIONS)
-    rest = [a for a in argv if not ("=" in a and a.split("=", 1)[0] in opts)]
-    return opts, rest
+    from . import cli
+    return cli.split(argv, CLI_OPTIONS)
 
 
 def main(argv=None) -> int:

@@ -25,10 +25,9 @@ import sys
 import numpy as np
 
 from .. import hip as _hip
-from . import hmm as _hmm
-from . import pca as _pca
-from . import readout as _readout
-from .utils import rollout_features
+from . import cli
+from .backend import resolve
+from .recorded import seq_start, signals, split
 
 CLI_OPTIONS = ("rollouts", "out", "source", "cols", "rate", "f_min", "f_max", "n_freqs", "omega0", "support", "detrend", "output", "floor", "projections")
 MAX_TOOL_WIDTH = 1024      # analysis.cluster, analysis.hmm and the wide PCA stop here
@@ -70,7 +69,7 @@ class Spectrogram:
             raise ValueError(f"every frequency must lie in (0, rate / 2 = {0.5 * rate}] (got {freqs.min():.6g} .. {freqs.max():.6g})")
         freqs = np.minimum(freqs, 0.5 * rate)      # (the last step of a dyadic grid may exceed f_max by a rounding)
         self.rate, self.omega0, self.support, self.detrend, self.output, self.floor = rate, float(omega0), float(support), bool(detrend), output, float(floor)
-        self._b = _pca.HipBackend(device) if backend is None else backend
+        self._b = resolve(backend, device)
         try:
             self._bank, self._offset, self.radius_ = self._b.wavelet_bank(rate, freqs, self.omega0, self.support)
         except _hip.TmjxError as e:
@@ -86,65 +85,12 @@ class Spectrogram:
         n, C = (int(v) for v in xa.shape)
         if C > _hip.SPECTROGRAM_MAX_C:
             raise ValueError(f"{C} channels: the spectrogram takes up to {_hip.SPECTROGRAM_MAX_C}")
-        seq = _hmm._seq_start(lengths, n)
+        seq = seq_start(lengths, n)
         out, cov = self._b.spectrogram(xa, seq, self._bank, self._offset, self.radius_, self.detrend, self.output == "log", self.floor)
         self.columns_ = self.columns(C)
         if isinstance(x, np.ndarray):
             return self._b.to_numpy(out), self._b.to_numpy(cov)
         return out, cov
-
-
-def _signals(rollouts, source: str, cols, projections):
-    """-> (clip numbers, [T_j, C] float32 signals, the roll-outs' meta trees or None)."""
-    from .. import h5lite
-    if projections is None:
-        parts = [p for p in str(source).split("/") if p]
-        if not (source in _readout.PLAIN_TARGETS or str(source).startswith("activations/") or (len(parts) == 2 and parts[0] == "rollout_metrics")):
-            raise KeyError(f"unknown source {source!r}: one of {', '.join(_readout.PLAIN_TARGETS)}, rollout_metrics/<name> or activations/<path>")
-    proj = None
-    if projections is not None:
-        with h5lite.File(projections) as h:
-            if "projections" not in h:
-                raise KeyError(f"{projections} has no projections group (write it with analysis.pca)")
-            proj = {int(k.split("_")[1]): np.asarray(h["projections"][k][()], np.float32) for k in h["projections"].keys()}
-
-    def one(r, clip, where):
-        if proj is not None:
-            if clip not in proj:
-                raise KeyError(f"{projections} has no projections/clip_{clip}")
-            a = proj[clip]
-        else:
-            a = _readout._target_of(r, source, where)
-            node = r
-            for part in [p for p in source.split("/") if p]:
-                node = node[part]
-            raw = np.shape(node if isinstance(node, (np.ndarray, list, tuple)) else node[()])
-            if len(raw) < 2:      # (as analysis.pca resolves a feature: a [T] series is not a set of channels)
-                raise ValueError(f"{where}: {source} has shape {tuple(raw)}, expected [T, C]")
-        try:
-            sl = _readout._cols(cols, a.shape[1])
-        except ValueError as e:
-            raise ValueError(str(e).replace("target_cols", "cols")) from None
-        return np.ascontiguousarray(a[:, sl], np.float32)
-
-    def meta(r):
-        if isinstance(r, h5lite.File):
-            return _tree(r["meta"]) if "meta" in r else None
-        return r.get("meta") if hasattr(r, "get") else None
-
-    ids, items = rollout_features(rollouts, lambda r, clip, where: (one(r, clip, where), meta(r)), source, "transform")
-    sigs, metas = [s for s, _ in items], [m for _, m in items]
-    if any(s.ndim != 2 or s.shape[0] < 1 for s in sigs):
-        raise ValueError(f"{source}: expected [T, C] with T >= 1")
-    return ids, sigs, metas
-
-
-def _tree(node):
-    """An h5lite group as nested dicts of numpy arrays."""
-    if hasattr(node, "keys"):
-        return {k: _tree(node[k]) for k in node.keys()}
-    v = node[()]
-    return bytes(v) if isinstance(v, (bytes, bytearray, np.bytes_)) else np.asarray(v)
 
 
 def transform_rollouts(rollouts, source: str, cols=None, projections=None, rate: float = 50.0, device="cuda", backend=None, max_width=None, **spectrogram_args):
@@ -153,7 +99,7 @@ def transform_rollouts(rollouts, source: str, cols=None, projections=None, rate:
     -> (spec, features, coverage): features[j] float32 [T_j, F C] and coverage[j] [T_j, F] of roll-out j; spec.clips_ are the clip numbers (the
     list positions for dicts), spec.source_, spec.cols_, spec.n_channels_, spec.metas_ (the roll-outs' meta trees).  max_width: refuse more columns
     than this (the command line's 1024)."""
-    ids, sigs, metas = _signals(rollouts, source, cols, projections)
+    ids, sigs, metas = signals(rollouts, source, cols, projections)
     spec = Spectrogram(rate, device=device, backend=backend, **spectrogram_args)
     width = spec.n_freqs_ * sigs[0].shape[1]
     if max_width is not None and width > max_width:
@@ -162,49 +108,32 @@ def transform_rollouts(rollouts, source: str, cols=None, projections=None, rate:
                          f"projections=<pca.h5>")
     lens = [s.shape[0] for s in sigs]
     feats, cov = spec.transform(np.concatenate(sigs, 0), lens)
-    ends = np.cumsum(lens)
-    cut = lambda a: [a[e - t:e] for e, t in zip(ends, lens)]      # noqa: E731
     spec.clips_, spec.source_, spec.cols_, spec.n_channels_, spec.metas_ = ids, source, "" if cols is None else str(cols), sigs[0].shape[1], metas
-    return spec, cut(feats), cut(cov)
-
-
-def _flag(opts, name, default):
-    v = opts.get(name, default).lower()
-    if v not in ("true", "false"):
-        raise ValueError(f"{name} must be true or false (got {opts[name]})")
-    return v == "true"
+    return spec, split(feats, lens), split(cov, lens)
 
 
 def main(argv=None, backend=None) -> int:
-    from .. import h5lite
-    argv = list(sys.argv[1:] if argv is None else argv)
-    opts = dict(a.split("=", 1) for a in argv if "=" in a and a.split("=", 1)[0] in CLI_OPTIONS)
-    if any(o not in opts for o in ("rollouts", "out", "rate")) or ("source" not in opts and "projections" not in opts) or len(opts) != len(argv):
-        print(USAGE, file=sys.stderr)
+    opts = cli.parse(argv, CLI_OPTIONS, ("rollouts", "out", "rate"), USAGE, lambda o: "source" in o or "projections" in o)
+    if opts is None:
         return 2
     source = opts.get("source", "projections")
     try:
         rate, n_freqs = float(opts["rate"]), int(opts.get("n_freqs", 25))
         args = dict(f_min=float(opts.get("f_min", 1.0)), f_max=float(opts["f_max"]) if "f_max" in opts else None, n_freqs=n_freqs,
-                    omega0=float(opts.get("omega0", 5.0)), support=float(opts.get("support", 4.0)), detrend=_flag(opts, "detrend", "true"),
+                    omega0=float(opts.get("omega0", 5.0)), support=float(opts.get("support", 4.0)), detrend=cli.flag(opts, "detrend", "true"),
                     output=opts.get("output", "amplitude"), floor=float(opts.get("floor", 1e-3)))
         if args["f_max"] is not None and args["f_max"] > 0.5 * rate:
             raise ValueError(f"f_max = {args['f_max']} exceeds rate / 2 = {0.5 * rate}")
         spec, feats, cov = transform_rollouts(opts["rollouts"], source, opts.get("cols"), opts.get("projections"), rate, backend=backend, max_width=MAX_TOOL_WIDTH, **args)
     except (KeyError, ValueError, OSError) as e:
-        print(f"[spectrogram] {e.args[0] if e.args else e}", file=sys.stderr)
-        return 2
-    os.makedirs(opts["out"], exist_ok=True)
+        return cli.report("spectrogram", e)
     meta = {"source": spec.source_, "cols": spec.cols_, "rate": np.float64(rate), "omega0": np.float64(spec.omega0), "support": np.float64(spec.support),
             "detrend": np.int64(spec.detrend), "output": spec.output, "floor": np.float64(spec.floor), "n_channels": np.int64(spec.n_channels_)}
     if "projections" in opts:
         meta["projections"] = os.path.basename(opts["projections"])
-    for c, f, cv, m in zip(spec.clips_, feats, cov, spec.metas_):
-        tree = {"activations": {"spectrogram": np.ascontiguousarray(f, np.float32)}, "spectrogram_coverage": np.ascontiguousarray(cv, np.float32),
-                "frequencies": np.asarray(spec.frequencies_, np.float64), "spectrogram_meta": meta}
-        if m is not None:
-            tree["meta"] = m
-        h5lite.write_tree(os.path.join(opts["out"], f"clip_{c}.h5"), tree)
+    cli.write_clips(opts["out"], {c: {"activations": {"spectrogram": np.ascontiguousarray(f, np.float32)}, "spectrogram_coverage": np.ascontiguousarray(cv, np.float32),
+                                      "frequencies": np.asarray(spec.frequencies_, np.float64), "spectrogram_meta": meta, **({} if m is None else {"meta": m})}
+                                  for c, f, cv, m in zip(spec.clips_, feats, cov, spec.metas_)})
     print(f"[spectrogram] {source}{'[' + spec.cols_ + ']' if spec.cols_ else ''}: {sum(f.shape[0] for f in feats)} rows x {spec.n_channels_} channels from "
           f"{len(feats)} clips at {spec.n_freqs_} frequencies {spec.frequencies_[0]:.3g} .. {spec.frequencies_[-1]:.3g} Hz (radii {int(spec.radius_.max())} .. "
           f"{int(spec.radius_.min())} samples, output {spec.output}) -> {spec.n_freqs_ * spec.n_channels_} columns; wrote {opts['out']}/clip_<i>.h5", flush=True)

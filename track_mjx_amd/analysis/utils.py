@@ -5,8 +5,6 @@ Mapping (recursive_dict_to_h5py): dict -> group, list / tuple -> group with memb
 dataset, None -> skipped.  Loading turns a group whose members are all digits back into a list (an empty group too, as the reference does)."""
 from __future__ import annotations
 
-import os
-import re
 from pathlib import Path
 
 import numpy as np
@@ -14,32 +12,7 @@ import numpy as np
 from .. import h5lite
 
 
-def rollout_features(rollouts, read, name=None, verb=None):
-    """What the analysis tools take of a set of roll-outs.  `rollouts`: a directory of clip_<i>.h5 (read in numeric order), or a list of roll-out
-    dicts; `read(rollout, clip, where)` -> the [T, D] feature of one (an open h5lite file or a dict), or a tuple that starts with it.
-    -> (clip numbers: the list positions for dicts, [what `read` returned]).  With `verb` ("fit", "cluster", ...) an empty set is an error; with
-    `name` the features must all have one width."""
-    if isinstance(rollouts, (str, os.PathLike)):
-        ids = sorted(int(m.group(1)) for m in (re.fullmatch(r"clip_(\d+)\.h5", f) for f in os.listdir(rollouts)) if m)
-        if verb is not None and not ids:
-            raise ValueError(f"no clip_<i>.h5 in {rollouts}")
-        items = []
-        for c in ids:
-            with h5lite.File(os.path.join(rollouts, f"clip_{c}.h5")) as h:
-                items.append(read(h, c, f"clip_{c}.h5"))
-    else:
-        ids = list(range(len(rollouts)))
-        if verb is not None and not ids:
-            raise ValueError(f"no roll-outs to {verb}")
-        items = [read(r, j, f"roll-out {j}") for j, r in enumerate(rollouts)]
-    if name is not None:
-        widths = {(i[0] if isinstance(i, tuple) else i).shape[1] for i in items}
-        if len(widths) != 1:
-            raise ValueError(f"{name} has different widths across roll-outs: {sorted(widths)}")
-    return ids, items
-
-
-def _to_tree(data):
+def to_tree(data):
     if data is None:
         return None
     if isinstance(data, tuple):
@@ -47,14 +20,14 @@ def _to_tree(data):
     if isinstance(data, dict):
         out = {}
         for k, v in data.items():
-            t = _to_tree(v)
+            t = to_tree(v)
             if t is not None:
                 out[str(k)] = t
         return out
     if isinstance(data, list):
         out = {}
         for i, v in enumerate(data):
-            t = _to_tree(v)
+            t = to_tree(v)
             if t is not None:
                 out[str(i)] = t
         return out
@@ -73,7 +46,7 @@ def _nest(tree: dict, group_path: str) -> dict:
 
 def save_to_h5py(file_path: str | Path, data, group_path: str = "/") -> None:
     """Write `data` (a pytree) to a new file, rooted at `group_path`."""
-    tree = _to_tree(data)
+    tree = to_tree(data)
     if not isinstance(tree, dict):
         parts = [p for p in group_path.split("/") if p]
         if not parts:
